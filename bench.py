@@ -16,6 +16,10 @@ barrier / max-reduce of the timing and for one final all_gather of the results.
     --config 3   configs[3]: 65 536 dynamic bicycles over all seven data/ tracks, sharded (per-GPU share 8192; N = 8 is the whole of it)
     --config 4   configs[4]: the MiL loop, 4096 cars x 200 control steps, sharded (per-GPU share 512)
 
+    --dump-outputs DIR   config 1: after the timed steps, what the timed path computed in its last step (u0, qp_iter, status, x0, x, u of
+                         every instance) as DIR/<name>.npy in float64 -- a fixed, seeded sample of the instances past 64 MB -- so that two builds
+                         can be compared output for output (the inputs are seeded: the same arguments give the same inputs)
+
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (live HIP-event time on the solver's stream);
 `cpu_baseline` is the CPU oracle (own restatement, NOT acados) on the host cores; `configs2` / `live_options` are short runs of
 BASELINE.json configs[2] and of the reference's live solver options, measured after the timed region of the headline (N = 1 only).
@@ -39,6 +43,7 @@ FP64_PEAK_TFLOPS = 78.6      # MI355X fp64 vector peak = fp64 matrix peak (guide
 HBM_PEAK_GBS = 8000.0
 CONFIG3_TOTAL, CONFIG4_TOTAL, NODE_GPUS = 65536, 4096, 8
 TRAFFIC_JSON = os.path.join("profiles", "r4", "bench_traffic.json")
+DUMP_LIMIT_BYTES, DUMP_SAMPLE_SEED = 64 << 20, 20240607
 
 
 def build_problem(batch):
@@ -79,6 +84,26 @@ def monte_carlo_batch(plans, total, seed=20240607):
         sel = tid == t
         x0[sel] = sample_x0(p, int(sel.sum()), seed=seed + t)
     return x0, tid
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, suffix=""):
+    """Writes every array of ``arrays`` (name -> per-instance array, instances first) as ``out_dir/<name><suffix>.npy`` in float64.  If they
+    come to more than ``limit`` bytes, the same fixed, seeded sample of instances is taken from each, and its row indices are written as
+    ``sample_index``.  Returns the names written."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = {a.shape[0] for a in arrays.values()}
+    assert len(B) == 1, "one row per instance in every array"
+    B = B.pop()
+    per_row = sum(a[:1].nbytes for a in arrays.values())
+    if per_row * B > limit:
+        k = max(1, (limit - 4096) // (per_row + 8))      # 4 kB for the .npy headers, 8 B per row for sample_index
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    return sorted(arrays)
 
 
 def flops_per_solve(n_ipm):
@@ -346,6 +371,9 @@ def parse_args(argv=None):
     ap.add_argument("--global-batch", type=int, default=0,
                     help="shard ONE global batch of this many instances over the ranks (contiguous block split, ihm2_amd/dist.py::shard_bounds: "
                          "strong scaling) instead of --batch instances per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 1: write what the timed path computed in its last step as DIR/<name>.npy (float64; u0, qp_iter, status, x0, x, u per "
+                         "instance; a fixed, seeded sample of the instances past 64 MB in all; with N > 1 ranks every rank writes <name>_rank<r>.npy)")
     return ap.parse_args(argv)
 
 
@@ -366,6 +394,12 @@ def main():
     if args.gpus > 1 and (args.config == 2 or args.live_options):
         # one-GPU workloads: N processes would each run the whole of it on the same device and print N lines
         raise SystemExit("--config 2 and --live-options are one-GPU measurements: run them with --gpus 1 (configs 1, 3 and 4 shard over --gpus N)")
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        raise SystemExit("--warmup must not be negative")
+    if args.dump_outputs and (args.config != 1 or args.live_options):
+        raise SystemExit("--dump-outputs writes the outputs of config 1's timed path: run it without --config 2/3/4 and --live-options")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: bench.py starts one process per GPU itself -- BEFORE anything here touches the GPU -- and rank 0 prints the line.
         # Every rank opens device LOCAL_RANK: on a node with fewer GPUs the rank fails in ihm2mpc_create and so does the run (never a silent
@@ -466,6 +500,13 @@ def main_config1(args, ranks):
         ranks.barrier(solver)
         elapsed = time.perf_counter() - t0
         qp_iters_timed = None
+    if args.dump_outputs:
+        # the last timed step's results, read back before the latency section below steps the solver on
+        last = {"u0": u0_hist[steps - 1] if persistent else u0_ring[(steps - 1) % SYNC_EVERY],
+                "qp_iter": it_hist[steps - 1] if persistent else solver.get_qp_iter(),
+                "status": solver.get_status(), "x0": solver.get_x0(), "x": solver.get_x(), "u": solver.get_u()}
+        names = dump_outputs(args.dump_outputs, last, limit=DUMP_LIMIT_BYTES // world, suffix="" if world == 1 else f"_rank{rank}")
+        print(f"bench.py: rank {rank} wrote {', '.join(names)} of the last of {steps} timed steps to {args.dump_outputs}", file=sys.stderr, flush=True)
     # per-step latency of a batch (step + read-back + wait), outside the timed region: 24 synchronous steps
     step_ms = []
     t_lin_s = t_qp_s = 0.0
@@ -605,8 +646,8 @@ def main_config2(args):
     422 k against 368 k with the collocation integrator, profiles/r4/dyn_persistent_vs_perstep.jsonl).  Both the model as written (quirk Q3:
     crossed slip angles, open-loop unstable -- most QPs are infeasible) and the named deviation fdyn6u are run and reported."""
     B = 8192 if args.batch is None else args.batch
-    steps = 20 if args.steps is None else min(args.steps, 50)
-    warmup = 5 if args.warmup is None else min(args.warmup, 10)
+    steps = 20 if args.steps is None else args.steps
+    warmup = 5 if args.warmup is None else args.warmup
     var = configs2_record(B=B, steps=steps, warmup=warmup, device=args.device or 0)
     r = var["fdyn6"]
     print(json.dumps({

@@ -63,7 +63,11 @@ def _worker(rank, world, port, total, q):
 
 
 def test_two_rank_gloo_shard_and_gather(track):
-    import torch.multiprocessing as mp
+    # the standard library's spawn, not torch.multiprocessing: torch stays out of the test process.  Importing it there maps torch's own
+    # HIP runtime and librccl beside the product's, and the native communicator of a later GPU test in the same process would pick up
+    # that foreign RCCL (libihm2mpc.so reuses a librccl the process has already mapped)
+    import multiprocessing as mp
+
     from conftest import make_ocp, sample_x0
 
     from oracle import oracle as orc

@@ -81,6 +81,41 @@ def test_a_rank_without_a_device_fails_the_run():
     assert r.returncode != 0 and not any(l.startswith("{") for l in r.stdout.splitlines())
 
 
+def test_dump_outputs_writes_the_last_timed_step_and_repeats_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's arrays of every instance in float64; the same arguments give the same arrays, another
+    `--steps` another step.  Both timed paths (one launch, launches per step)."""
+    import numpy as np
+
+    B, names = 64, ("u0", "qp_iter", "status", "x0", "x", "u")
+    shapes = {"u0": (B, 2), "qp_iter": (B,), "status": (B,), "x0": (B, 8), "x": (B, 41, 8), "u": (B, 40, 2)}
+    common = ["--warmup", "2", "--batch", str(B), "--no-cpu-baseline", "--no-extras"]
+
+    def run(tag, steps, *extra):
+        d = _run("--steps", str(steps), *common, *extra, "--dump-outputs", str(tmp_path / tag))
+        assert d["steps"] == steps
+        assert sorted(os.listdir(tmp_path / tag)) == sorted(n + ".npy" for n in names)
+        got = {n: np.load(tmp_path / tag / f"{n}.npy") for n in names}
+        for n in names:
+            assert got[n].dtype == np.float64 and got[n].shape == shapes[n], n
+        assert np.all(np.isfinite(got["x"])) and np.all(np.isin(got["status"], range(5)))
+        np.testing.assert_array_equal(got["u0"], got["u"][:, 0])         # u0 is the first control of the returned trajectory
+        return got
+
+    for extra in ((), ("--per-step-launches",)):
+        a, b, c = run("a", 5, *extra), run("b", 5, *extra), run("c", 4, *extra)
+        for n in names:
+            np.testing.assert_array_equal(a[n], b[n], err_msg=n)
+        assert not np.array_equal(a["x0"], c["x0"])                     # one plant step fewer
+        for t in ("a", "b", "c"):
+            for f in os.listdir(tmp_path / t):
+                os.remove(tmp_path / t / f)
+    # N > 1 ranks (rehearsed on one device over gloo): every rank writes its own instances
+    _run("--gpus", "2", "--device", "0", "--dist-backend", "gloo", "--steps", "3", *common, "--dump-outputs", str(tmp_path / "r"))
+    assert sorted(os.listdir(tmp_path / "r")) == sorted(f"{n}_rank{r}.npy" for n in names for r in (0, 1))
+    for r in (0, 1):
+        assert np.load(tmp_path / "r" / f"x_rank{r}.npy").shape == shapes["x"]
+
+
 def test_the_launch_line_of_the_driver_prints_one_line_and_nothing_else():
     """`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 ...` as the driver
     starts it, both ranks on the one device of the box (`--device 0`, a declared rehearsal): the default carrier finds RCCL refusing the duplicate

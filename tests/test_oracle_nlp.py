@@ -27,7 +27,7 @@ def problem(track):
 def _sqp(problem):
     P, x0 = problem["P"], problem["x0"]
     x = np.tile(x0, (1, NF + 1, 1)).copy(); u = np.tile(x0[6:8], (1, NF, 1)).copy()
-    out = P.sqp_solve(x, u, x0[None], np.zeros((1, NF, 12)), np.zeros((1, 8)), max_iter=60, tol=1e-7)
+    out = P.sqp_solve(x, u, x0[None], np.zeros((1, NF, 12)), np.zeros((1, 8)), max_iter=60, tol=1e-7, nthreads=1)
     return x[0], u[0], out
 
 
@@ -56,8 +56,10 @@ def test_converged_sqp_is_the_slsqp_solution_of_the_written_out_programme(proble
         return float(np.einsum("ki,ij,kj->", X[:-1], Q, X[:-1]) + np.einsum("ki,ij,kj->", U, R, U) + X[-1] @ Qf @ X[-1])
 
     def shooting(w):
+        # one thread for three intervals: SLSQP calls this thousands of times, and the default OpenMP team is every core the process may
+        # run on -- on a many-core host with a small CPU share each call would wait for the whole team
         X, U = split(w)
-        return np.concatenate(((P.sim_step(X[:-1].copy(), U.copy(), 0, 25) - X[1:]).reshape(-1), X[0] - x0))
+        return np.concatenate(((P.sim_step(X[:-1].copy(), U.copy(), 0, 25, nthreads=1) - X[1:]).reshape(-1), X[0] - x0))
 
     def rates(w):                                     # ulin - |x_act - u| >= 0
         X, U = split(w)
