@@ -25,6 +25,106 @@ from .solver import BatchedOcpSolver
 from .track import NUMBER_SPLINE_INTERVALS
 
 
+# the limits of IHM2Controller that may be given per instance, in get_acados_ocp's order, and its 18 weights (default_weights' order)
+LIMIT_NAMES = ("n_max", "v_x_max", "T_max", "delta_max", "T_dot_max", "delta_dot_max")
+WEIGHT_NAMES = ("q_s", "q_n", "q_psi", "q_v_x", "q_v_y", "q_r", "q_T", "q_delta", "q_s_f", "q_n_f", "q_psi_f", "q_v_x_f", "q_v_y_f",
+                "q_r_f", "q_T_f", "q_delta_f", "q_T_dot", "q_delta_dot")
+
+
+def controller_ocp(nknots: int, Nf: int, limits: dict, a_lat_max: float = 5.0, terminal_bounds: str = "reference",
+                   soft_state_bounds: tuple | None = None, track_rows: bool = False, track_rows_penalty: tuple | None = (100.0, 100.0),
+                   lateral_acceleration_row: bool = False):
+    """The OCP of :class:`IHM2Controller` for scalar ``limits`` (``LIMIT_NAMES``), without solver options and weights."""
+    n_max, v_x_max, T_max, delta_max, T_dot_max, delta_dot_max = (limits[k] for k in LIMIT_NAMES)
+    model = get_acados_model_from_explicit_dynamics(
+        name="ihm2_fkin6", continuous_model_fn=fkin6_model, x=NX, u=NU, p=2 * nknots)
+    ocp = get_acados_ocp(model, Nf, n_max, v_x_max, T_max, delta_max, T_dot_max, delta_dot_max)
+    if terminal_bounds == "stage":
+        # quirk Q1: python/mpc.py:82-84 puts the T/delta limits on (v_y, r) at the terminal stage; with a plant
+        # whose yaw rate is real (|r| = |v kappa| > delta_max) that box is infeasible.  "stage" repeats the
+        # stage box [n, v_x, T, delta] at the terminal stage instead.
+        c = ocp.constraints
+        c.idxbx_e, c.lbx_e, c.ubx_e = c.idxbx.copy(), c.lbx.copy(), c.ubx.copy()
+    elif terminal_bounds != "reference":
+        raise ValueError("terminal_bounds must be 'reference' or 'stage'")
+    if soft_state_bounds is not None:
+        # not in the reference (python/mpc.py:58-90 has hard sides only): soften the path constraints on the
+        # PLANT states -- the n and v_x boxes of every stage and the whole terminal box -- with the penalty
+        # z s + 1/2 Z s^2, soft_state_bounds = (z, Z).  The actuator-state boxes, the input boxes and the rate rows
+        # stay hard and can always be met, so the QP is feasible from any plant state.
+        z_pen, Z_pen = (float(v) for v in soft_state_bounds)
+        c = ocp.constraints
+        pos = np.flatnonzero(np.isin(np.asarray(c.idxbx), (1, 3)))
+        nsb, nsb_e = len(pos), len(c.idxbx_e)
+        c.idxsbx, c.idxsbx_e = pos, np.arange(nsb_e)
+        ocp.cost.zl = ocp.cost.zu = np.full(nsb, z_pen)
+        ocp.cost.Zl = ocp.cost.Zu = np.full(nsb, Z_pen)
+        ocp.cost.zl_e = ocp.cost.zu_e = np.full(nsb_e, z_pen)
+        ocp.cost.Zl_e = ocp.cost.Zu_e = np.full(nsb_e, Z_pen)
+    if track_rows:
+        # the nonlinear track-boundary rows of old/generate_acaods_interface.py:191-212,411-449 (footprint of the car
+        # against the right / left width), soft with L1 + L2 weights (:380-395) unless track_rows_penalty is None
+        model.con_h_expr = "track"
+        c = ocp.constraints
+        c.lh = c.lh_e = np.array([-1e3, -1e3])
+        c.uh = c.uh_e = np.array([0.0, 0.0])
+        if track_rows_penalty is not None:
+            z_pen, Z_pen = (float(v) for v in track_rows_penalty)
+            c.idxsh, c.idxsh_e = np.arange(2), np.arange(2)
+            for name in ("zl", "zu"):
+                setattr(ocp.cost, name, np.concatenate([getattr(ocp.cost, name), np.full(2, z_pen)]))
+                setattr(ocp.cost, name + "_e", np.concatenate([getattr(ocp.cost, name + "_e"), np.full(2, z_pen)]))
+            for name in ("Zl", "Zu"):
+                setattr(ocp.cost, name, np.concatenate([getattr(ocp.cost, name), np.full(2, Z_pen)]))
+                setattr(ocp.cost, name + "_e", np.concatenate([getattr(ocp.cost, name + "_e"), np.full(2, Z_pen)]))
+        if lateral_acceleration_row:
+            # the kinematic set's fifth row, |a_lat| <= ModelBounds.a_lat_max (old/generate_acaods_interface.py:198-209,
+            # :424, :433), at the stages only; softened like the track rows (idxsh = all, :436)
+            model.con_h_expr = "track+a_lat"
+            c.lh = np.concatenate([c.lh, [-a_lat_max]]); c.uh = np.concatenate([c.uh, [a_lat_max]])
+            if track_rows_penalty is not None:
+                c.idxsh = np.arange(3)
+                for name, v in (("zl", z_pen), ("zu", z_pen), ("Zl", Z_pen), ("Zu", Z_pen)):
+                    setattr(ocp.cost, name, np.concatenate([getattr(ocp.cost, name), [v]]))
+    elif lateral_acceleration_row:
+        raise ValueError("lateral_acceleration_row comes with the track rows (track_widths): old/generate_acaods_interface.py:198-209")
+    return model, ocp
+
+
+def instance_tuning(B: int, weights: dict, limits: dict, nknots: int, Nf: int, **ocp_kw):
+    """Per-instance tuning from ``(B,)`` arrays among the 18 weights and the 6 limits of :class:`IHM2Controller` (scalars broadcast).
+    Returns ``(W, W_e)`` -- ``(B,12,12)``, ``(B,8,8)`` -- or ``None`` when every weight is a scalar, and ``{lbx, ubx, lbu, ubu, lg, ug}`` --
+    ``(B,N+1,8)``, ``(B,N,2)`` x 4 -- or ``None`` when every limit is a scalar: for instance b exactly the tables the scalar path builds from
+    b's values (``default_weights`` / ``controller_ocp``; one OCP per distinct set of limits)."""
+    def per_instance(d):
+        vals = {k: np.asarray(v, dtype=np.float64) for k, v in d.items()}
+        for k, v in vals.items():
+            if v.ndim > 1 or (v.ndim == 1 and v.shape != (B,)):
+                raise ValueError(f"{k} must be a scalar or have shape ({B},), got {v.shape}")
+        if all(v.ndim == 0 for v in vals.values()):
+            return None
+        return {k: np.broadcast_to(v, (B,)) for k, v in vals.items()}
+
+    wt, lt = per_instance(weights), per_instance(limits)
+    inst_w = inst_b = None
+    if wt is not None:
+        W, W_e = np.empty((B, 12, 12)), np.empty((B, 8, 8))
+        for b in range(B):
+            W[b], W_e[b] = default_weights(*(float(wt[k][b]) for k in WEIGHT_NAMES))
+        inst_w = (W, W_e)
+    if lt is not None:
+        cache, out = {}, {k: [] for k in ("lbx", "ubx", "lbu", "ubu", "lg", "ug")}
+        for b in range(B):
+            key = tuple(float(lt[k][b]) for k in LIMIT_NAMES)
+            if key not in cache:
+                d = controller_ocp(nknots, Nf, dict(zip(LIMIT_NAMES, key)), **ocp_kw)[1].flatten()
+                cache[key] = {k: np.asarray(getattr(d, k), dtype=np.float64) for k in out}
+            for k in out:
+                out[k].append(cache[key][k])
+        inst_b = {k: np.stack(v) for k, v in out.items()}
+    return inst_w, inst_b
+
+
 class Controller(ABC):
     """``new_python/controller.py:134-159``."""
 
@@ -121,58 +221,18 @@ class IHM2Controller(Controller):
         self.model_bounds = ModelBounds(n_max=n_max, v_x_min=0.0, v_x_max=v_x_max, T_max=T_max, delta_max=delta_max,
                                         T_dot_max=T_dot_max, delta_dot_max=delta_dot_max, a_lat_max=a_lat_max)
         s_ref = np.atleast_2d(np.asarray(s_ref, dtype=np.float64))
-        model = get_acados_model_from_explicit_dynamics(
-            name="ihm2_fkin6", continuous_model_fn=fkin6_model, x=self.nx, u=self.nu, p=2 * s_ref.shape[1])
-        ocp = get_acados_ocp(model, Nf, n_max, v_x_max, T_max, delta_max, T_dot_max, delta_dot_max)
-        if terminal_bounds == "stage":
-            # quirk Q1: python/mpc.py:82-84 puts the T/delta limits on (v_y, r) at the terminal stage; with a plant
-            # whose yaw rate is real (|r| = |v kappa| > delta_max) that box is infeasible.  "stage" repeats the
-            # stage box [n, v_x, T, delta] at the terminal stage instead.
-            c = ocp.constraints
-            c.idxbx_e, c.lbx_e, c.ubx_e = c.idxbx.copy(), c.lbx.copy(), c.ubx.copy()
-        elif terminal_bounds != "reference":
-            raise ValueError("terminal_bounds must be 'reference' or 'stage'")
-        if soft_state_bounds is not None:
-            # not in the reference (python/mpc.py:58-90 has hard sides only): soften the path constraints on the
-            # PLANT states -- the n and v_x boxes of every stage and the whole terminal box -- with the penalty
-            # z s + 1/2 Z s^2, soft_state_bounds = (z, Z).  The actuator-state boxes, the input boxes and the rate rows
-            # stay hard and can always be met, so the QP is feasible from any plant state.
-            z_pen, Z_pen = (float(v) for v in soft_state_bounds)
-            c = ocp.constraints
-            pos = np.flatnonzero(np.isin(np.asarray(c.idxbx), (1, 3)))
-            nsb, nsb_e = len(pos), len(c.idxbx_e)
-            c.idxsbx, c.idxsbx_e = pos, np.arange(nsb_e)
-            ocp.cost.zl = ocp.cost.zu = np.full(nsb, z_pen)
-            ocp.cost.Zl = ocp.cost.Zu = np.full(nsb, Z_pen)
-            ocp.cost.zl_e = ocp.cost.zu_e = np.full(nsb_e, z_pen)
-            ocp.cost.Zl_e = ocp.cost.Zu_e = np.full(nsb_e, Z_pen)
-        if track_widths is not None:
-            # the nonlinear track-boundary rows of old/generate_acaods_interface.py:191-212,411-449 (footprint of the car
-            # against the right / left width), soft with L1 + L2 weights (:380-395) unless track_rows_penalty is None
-            model.con_h_expr = "track"
-            c = ocp.constraints
-            c.lh = c.lh_e = np.array([-1e3, -1e3])
-            c.uh = c.uh_e = np.array([0.0, 0.0])
-            if track_rows_penalty is not None:
-                z_pen, Z_pen = (float(v) for v in track_rows_penalty)
-                c.idxsh, c.idxsh_e = np.arange(2), np.arange(2)
-                for name in ("zl", "zu"):
-                    setattr(ocp.cost, name, np.concatenate([getattr(ocp.cost, name), np.full(2, z_pen)]))
-                    setattr(ocp.cost, name + "_e", np.concatenate([getattr(ocp.cost, name + "_e"), np.full(2, z_pen)]))
-                for name in ("Zl", "Zu"):
-                    setattr(ocp.cost, name, np.concatenate([getattr(ocp.cost, name), np.full(2, Z_pen)]))
-                    setattr(ocp.cost, name + "_e", np.concatenate([getattr(ocp.cost, name + "_e"), np.full(2, Z_pen)]))
-            if lateral_acceleration_row:
-                # the kinematic set's fifth row, |a_lat| <= ModelBounds.a_lat_max (old/generate_acaods_interface.py:198-209,
-                # :424, :433), at the stages only; softened like the track rows (idxsh = all, :436)
-                model.con_h_expr = "track+a_lat"
-                c.lh = np.concatenate([c.lh, [-a_lat_max]]); c.uh = np.concatenate([c.uh, [a_lat_max]])
-                if track_rows_penalty is not None:
-                    c.idxsh = np.arange(3)
-                    for name, v in (("zl", z_pen), ("zu", z_pen), ("Zl", Z_pen), ("Zu", Z_pen)):
-                        setattr(ocp.cost, name, np.concatenate([getattr(ocp.cost, name), [v]]))
-        elif lateral_acceleration_row:
-            raise ValueError("lateral_acceleration_row comes with the track rows (track_widths): old/generate_acaods_interface.py:198-209")
+        if np.ndim(a_lat_max) != 0:
+            raise ValueError("a_lat_max is batch-shared: per-instance a_lat bounds are not supported")
+        # any of the 18 weights and the 6 limits may be a (B,) array (per-instance tuning, BatchedOcpSolver.set_instance_*):
+        # the batch-shared tables then hold instance 0's values
+        weights = dict(zip(WEIGHT_NAMES, (q_s, q_n, q_psi, q_v_x, q_v_y, q_r, q_T, q_delta, q_s_f, q_n_f, q_psi_f, q_v_x_f, q_v_y_f,
+                                          q_r_f, q_T_f, q_delta_f, q_T_dot, q_delta_dot)))
+        limits = dict(zip(LIMIT_NAMES, (n_max, v_x_max, T_max, delta_max, T_dot_max, delta_dot_max)))
+        ocp_kw = dict(a_lat_max=a_lat_max, terminal_bounds=terminal_bounds, soft_state_bounds=soft_state_bounds,
+                      track_rows=track_widths is not None, track_rows_penalty=track_rows_penalty, lateral_acceleration_row=lateral_acceleration_row)
+        inst_w, inst_b = instance_tuning(self.B, weights, limits, s_ref.shape[1], Nf, **ocp_kw)
+        first = lambda v: v if np.ndim(v) == 0 else float(np.asarray(v).reshape(-1)[0])      # noqa: E731
+        model, ocp = controller_ocp(s_ref.shape[1], Nf, {k: first(v) for k, v in limits.items()}, **ocp_kw)
         opts = AcadosOcpOptions()                      # python/main.py:227-238, with ERK x M for IRK
         opts.tf = Nf * dt
         opts.nlp_solver_type = nlp_solver_type
@@ -185,14 +245,17 @@ class IHM2Controller(Controller):
         opts.integrator_type = integrator_type
         opts.sim_integrator_type, opts.sim_collocation_type = sim_integrator_type, "GAUSS_RADAU_IIA"
         ocp.solver_options = opts
-        ocp.cost.W, ocp.cost.W_e = default_weights(q_s, q_n, q_psi, q_v_x, q_v_y, q_r, q_T, q_delta, q_s_f, q_n_f, q_psi_f,
-                                                   q_v_x_f, q_v_y_f, q_r_f, q_T_f, q_delta_f, q_T_dot, q_delta_dot)
+        ocp.cost.W, ocp.cost.W_e = default_weights(*(first(weights[k]) for k in WEIGHT_NAMES))
         self.solver = BatchedOcpSolver(ocp, self.B, s_ref, kappa_ref, track_id=track_id, device=device, track_widths=track_widths)
+        if inst_w is not None:
+            self.solver.set_instance_weights(*inst_w)
+        if inst_b is not None:
+            self.solver.set_instance_bounds(**inst_b)
         # cold start of the prediction arrays (python/main.py:242-246)
         x_pred = np.zeros((self.B, Nf + 1, NX))
         x_pred[:, :, 0] = -6.0 + np.arange(Nf + 1) * dt
         u_pred = np.zeros((self.B, Nf, NU))
-        u_pred[:, :, 0] = T_max
+        u_pred[:, :, 0] = T_max if np.ndim(T_max) == 0 else np.asarray(T_max, dtype=np.float64)[:, None]
         self.solver.set_x(x_pred)
         self.solver.set_u(u_pred)
         self.last_status = np.zeros(self.B, dtype=np.int32)

@@ -85,11 +85,135 @@ void cost_selector(double V[NY][NZ])
     V[10][8] = -1.0; V[11][9] = -1.0;
 }
 
+// The QP's weight tables of one stage k < N (cost_scale * V'W_k V, cost_scale * V'W_k) and of the terminal stage (W_e padded with I, W_e).
+// ihm2mpc_set_weights and ihm2mpc_set_instance_weights both expand through these: one instance's tables are then those of a batch-shared
+// table with its weights bit for bit.
+void stage_weight_tables(const double *Wk, double cs, double *Hk, double *Gk)
+{
+    double V[NY][NZ];
+    cost_selector(V);
+    double VtW[NZ][NY];
+    for (int i = 0; i < NZ; i++)
+        for (int j = 0; j < NY; j++) {
+            double acc = 0;
+            for (int l = 0; l < NY; l++) acc += V[l][i] * Wk[l * NY + j];
+            VtW[i][j] = acc;
+            Gk[i * 12 + j] = cs * acc;
+        }
+    for (int i = 0; i < NZ; i++)
+        for (int j = 0; j < NZ; j++) {
+            double acc = 0;
+            for (int l = 0; l < NY; l++) acc += VtW[i][l] * V[l][j];
+            Hk[i * 10 + j] = cs * acc;
+        }
+}
+
+void terminal_weight_tables(const double *W_e, double *HN, double *GN)
+{
+    for (int i = 0; i < NX; i++)
+        for (int j = 0; j < NX; j++) {
+            HN[i * 10 + j] = W_e[i * NX + j];
+            GN[i * 12 + j] = W_e[i * NX + j];
+        }
+    HN[8 * 10 + 8] = 1.0;
+    HN[9 * 10 + 9] = 1.0;
+}
+
+// true if the 10x10 Hessian of a stage is symmetric (to rounding)
+bool symmetric10(const double *Hk)
+{
+    for (int i = 0; i < NZ; i++)
+        for (int j = 0; j < i; j++)
+            if (fabs(Hk[i * 10 + j] - Hk[j * 10 + i]) > 1e-12 * (1 + fabs(Hk[i * 10 + j]))) return false;
+    return true;
+}
+
+const char *row_name(int c)
+{
+    static const char *names[NC] = {"lbx/ubx[0]", "lbx/ubx[1]", "lbx/ubx[2]", "lbx/ubx[3]", "lbx/ubx[4]", "lbx/ubx[5]", "lbx/ubx[6]", "lbx/ubx[7]",
+                                    "lbu/ubu[0]", "lbu/ubu[1]", "lg/ug[0]", "lg/ug[1]", "lh/uh[0]", "lh/uh[1]"};
+    return (c >= 0 && c < NC) ? names[c] : "?";
+}
+
+// Per-instance bounds -> the slot table of the batch-shared pattern: the values of instance b sit where the shared table has a finite
+// side (rows 0..11; the track rows and the a_lat row stay batch-shared), and the SQP mode's (NS,NC) bounds alike.  Refuses when the
+// stored values' finite sides differ from the shared table's (a later shared setter may have changed them).
+int check_instance_pattern(const ihm2mpc_handle *h, const double *il, const double *iu)
+{
+    const int NS = h->NS;
+    for (int b = 0; b < h->B; b++)
+        for (int k = 0; k < NS; k++)
+            for (int c = 0; c < 12; c++) {
+                const double lb = il[((size_t)b * NS + k) * 12 + c], ub = iu[((size_t)b * NS + k) * 12 + c];
+                const double slb = h->host_lb[k * NC + c], sub = h->host_ub[k * NC + c];
+                if (std::isfinite(lb) != std::isfinite(slb) || std::isfinite(ub) != std::isfinite(sub))
+                    return fail("instance %d, stage %d, row %d (%s): the finite sides (%s, %s) differ from the batch-shared table's (%s, %s)", b, k, c,
+                                row_name(c), std::isfinite(lb) ? "lower" : "-", std::isfinite(ub) ? "upper" : "-",
+                                std::isfinite(slb) ? "lower" : "-", std::isfinite(sub) ? "upper" : "-");
+            }
+    return 0;
+}
+
+int scatter_instance_bounds(ihm2mpc_handle *h)
+{
+    const int B = h->B, NS = h->NS;
+    h->inst_b_ok = false;
+    if (check_instance_pattern(h, h->ih_lb, h->ih_ub)) return -1;
+    const size_t n = (size_t)h->nslot_lane * 64;
+    if (n > h->i_slot_cap) {
+        if (h->i_slot_lb) { (void)hipFree(h->i_slot_lb); (void)hipFree(h->i_slot_ub); h->i_slot_lb = h->i_slot_ub = nullptr; }
+        h->i_slot_cap = 0;
+        if (dalloc(&h->i_slot_lb, (size_t)B * n) || dalloc(&h->i_slot_ub, (size_t)B * n)) return -1;
+        h->i_slot_cap = n;
+    }
+    std::vector<double> slb((size_t)B * n), sub((size_t)B * n), stl((size_t)B * NS * NC), stu((size_t)B * NS * NC);
+    for (int b = 0; b < B; b++) {
+        const double *il = h->ih_lb + (size_t)b * NS * 12, *iu = h->ih_ub + (size_t)b * NS * 12;
+        for (size_t e = 0; e < n; e++) {
+            const int kc = h->host_kc[e], k = kc >> 4, c = kc & 15;
+            double lo = h->host_slb[e], up = h->host_sub[e];
+            if (kc >= 0 && c < 12) {     // a split (soft) row's halves keep their absent side
+                if (std::isfinite(lo)) lo = il[k * 12 + c];
+                if (std::isfinite(up)) up = iu[k * 12 + c];
+            }
+            slb[(size_t)b * n + e] = lo; sub[(size_t)b * n + e] = up;
+        }
+        for (int k = 0; k < NS; k++)
+            for (int c = 0; c < NC; c++) {
+                stl[((size_t)b * NS + k) * NC + c] = (c < 12) ? il[k * 12 + c] : h->host_lb[k * NC + c];
+                stu[((size_t)b * NS + k) * NC + c] = (c < 12) ? iu[k * 12 + c] : h->host_ub[k * NC + c];
+            }
+    }
+    if (n && (upload_shared(h, slb.data(), h->i_slot_lb, slb.size()) || upload_shared(h, sub.data(), h->i_slot_ub, sub.size()))) return -1;
+    if (upload_shared(h, stl.data(), h->i_st_lb, stl.size()) || upload_shared(h, stu.data(), h->i_st_ub, stu.size())) return -1;
+    h->inst_b_ok = true;
+    return 0;
+}
+
+void free_instance_weights(ihm2mpc_handle *h)
+{
+    for (double *p : {h->iHs, h->iGy, h->iWd}) if (p) (void)hipFree(p);
+    h->iHs = h->iGy = h->iWd = nullptr;
+    h->inst_w = false;
+}
+
+void free_instance_bounds(ihm2mpc_handle *h)
+{
+    for (double *p : {h->i_slot_lb, h->i_slot_ub, h->i_st_lb, h->i_st_ub, h->i_lbu, h->i_ubu, h->i_lg, h->i_ug}) if (p) (void)hipFree(p);
+    h->i_slot_lb = h->i_slot_ub = h->i_st_lb = h->i_st_ub = h->i_lbu = h->i_ubu = h->i_lg = h->i_ug = nullptr;
+    h->i_slot_cap = 0;
+    delete[] h->ih_lb; delete[] h->ih_ub;
+    h->ih_lb = h->ih_ub = nullptr;
+    h->inst_b = false; h->inst_b_ok = false;
+}
+
 int ready(ihm2mpc_handle *h)
 {
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
     if (!h->weights_set) return fail("ihm2mpc_set_weights has not been called");
     if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called");
+    if (h->inst_w && !h->uniform_CD) return fail("per-instance weights need stage-independent general rows C, D (the QP keeps one copy of them)");
+    if (h->inst_b && !h->inst_b_ok) return fail("the per-instance bounds do not fit the batch-shared constraint pattern any more: set them again, or pass NULL");
     if (!h->slots_fit) return fail("the constraint rows fit no QP kernel: at most 10 slots per lane of 64 (a two-sided hard row is one slot, a row with a soft side two), of which at most 4 soft; with soft sides the hard two-sided rows get 10 - 4 or 8 - 3 (8 - 2 without track rows) of them");
     if (h->alat_on) {
         // the row belongs to the kinematic constraint set of old/generate_acaods_interface.py:198-209, which comes with the track rows and SQP_RTI (old/generate.py:21)
@@ -190,6 +314,7 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
     for (int i = 0; i < 4; i++) h->sqp_tol[i] = cfg->nlp_tol;
     h->host_lb = new double[NS * NC]; h->host_ub = new double[NS * NC];
     h->host_sz = new double[NS * NLAM]; h->host_sZ = new double[NS * NLAM];
+    h->host_kc = new int32_t[MAX_SLOTS]; h->host_slb = new double[MAX_SLOTS]; h->host_sub = new double[MAX_SLOTS];
     for (size_t i = 0; i < NS * NC; i++) { h->host_lb[i] = -INFINITY; h->host_ub[i] = INFINITY; }
     for (size_t i = 0; i < NS * NLAM; i++) { h->host_sz[i] = 0.0; h->host_sZ[i] = -1.0; }
     DA(x, B * NS * 8); DA(u, B * N * 2); DA(x0, B * 8); DA(yref, B * N * 12); DA(yref_e, B * 8);
@@ -214,7 +339,10 @@ int ihm2mpc_free(ihm2mpc_handle *h)
                     h->ls_x, h->ls_u, h->ls_pi, h->ls_lam, h->ls_slk, h->ls_wpi, h->ls_wlam, h->ls_alpha, h->ls_args, h->ls_done, h->ls_status, h->ls_iter, h->ls_qp_acc, h->ls_pending, h->irk_tab, h->sim_irk_tab,
                     h->hist_u0, h->hist_x0, h->hist_st, h->hist_it};
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    free_instance_weights(h);
+    free_instance_bounds(h);
     delete[] h->host_lb; delete[] h->host_ub; delete[] h->host_sz; delete[] h->host_sZ;
+    delete[] h->host_kc; delete[] h->host_slb; delete[] h->host_sub;
     for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (int i = 0; i < 2; i++) { if (h->args_host[i]) (void)hipHostFree(h->args_host[i]); if (h->args_ev[i]) (void)hipEventDestroy(h->args_ev[i]); }
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
@@ -349,49 +477,64 @@ int ihm2mpc_set_weights(ihm2mpc_handle *h, const double *W, const double *W_e)
     CHECK_H(h);
     if (!W || !W_e) return fail("null argument");
     const int N = h->N, NS = h->NS;
-    double V[NY][NZ];
-    cost_selector(V);
     std::vector<double> Hs((size_t)NS * 100, 0.0), Gy((size_t)NS * 120, 0.0);
     const double cs = h->cfg.cost_scale_stage;
-    for (int k = 0; k < N; k++) {
-        const double *Wk = W + (size_t)k * NY * NY;
-        double VtW[NZ][NY];
-        for (int i = 0; i < NZ; i++)
-            for (int j = 0; j < NY; j++) {
-                double acc = 0;
-                for (int l = 0; l < NY; l++) acc += V[l][i] * Wk[l * NY + j];
-                VtW[i][j] = acc;
-                Gy[((size_t)k * 10 + i) * 12 + j] = cs * acc;
-            }
-        for (int i = 0; i < NZ; i++)
-            for (int j = 0; j < NZ; j++) {
-                double acc = 0;
-                for (int l = 0; l < NY; l++) acc += VtW[i][l] * V[l][j];
-                Hs[((size_t)k * 10 + i) * 10 + j] = cs * acc;
-            }
-    }
-    for (int i = 0; i < NX; i++)
-        for (int j = 0; j < NX; j++) {
-            Hs[((size_t)N * 10 + i) * 10 + j] = W_e[i * NX + j];
-            Gy[((size_t)N * 10 + i) * 12 + j] = W_e[i * NX + j];
-        }
-    Hs[((size_t)N * 10 + 8) * 10 + 8] = 1.0;
-    Hs[((size_t)N * 10 + 9) * 10 + 9] = 1.0;
+    for (int k = 0; k < N; k++) stage_weight_tables(W + (size_t)k * NY * NY, cs, &Hs[(size_t)k * 100], &Gy[(size_t)k * 120]);
+    terminal_weight_tables(W_e, &Hs[(size_t)N * 100], &Gy[(size_t)N * 120]);
     for (int k = 0; k < NS; k++)
-        for (int i = 0; i < NZ; i++)
-            for (int j = 0; j < i; j++)
-                if (fabs(Hs[((size_t)k * 10 + i) * 10 + j] - Hs[((size_t)k * 10 + j) * 10 + i]) > 1e-12 * (1 + fabs(Hs[((size_t)k * 10 + i) * 10 + j])))
-                    return fail("weight matrix of stage %d is not symmetric", k);
-    h->uniform_H = true;
-    for (int k = 1; k < N && h->uniform_H; k++)
+        if (!symmetric10(&Hs[(size_t)k * 100])) return fail("weight matrix of stage %d is not symmetric", k);
+    bool uni = true;
+    for (int k = 1; k < N && uni; k++)
         for (int i = 0; i < 100; i++)
-            if (Hs[(size_t)k * 100 + i] != Hs[i]) { h->uniform_H = false; break; }
-    for (int k = 1; k < N && h->uniform_H; k++)       // "uniform" covers the gradient map as well: the QP kernel keeps one copy of both
+            if (Hs[(size_t)k * 100 + i] != Hs[i]) { uni = false; break; }
+    for (int k = 1; k < N && uni; k++)       // "uniform" covers the gradient map as well: the QP kernel keeps one copy of both
         for (int i = 0; i < 120; i++)
-            if (Gy[(size_t)k * 120 + i] != Gy[i]) { h->uniform_H = false; break; }
+            if (Gy[(size_t)k * 120 + i] != Gy[i]) { uni = false; break; }
     if (upload_shared(h, Hs.data(), h->Hs, Hs.size()) || upload_shared(h, Gy.data(), h->Gy, Gy.size())) return -1;
     if (upload_shared(h, W, h->Wd, (size_t)N * 144) || upload_shared(h, W_e, h->Wd + (size_t)N * 144, 64)) return -1;
+    h->shared_uniform_H = uni;
+    h->uniform_H = h->inst_w || uni;       // per-instance weights are stage-independent whatever the shared table holds
     h->weights_set = true;
+    return 0;
+}
+
+// One weight set per instance: W (B,12,12) for every stage k < N, W_e (B,8,8) -- acados' per-solver
+// cost_set(k, "W", W) / cost_set(N, "W", W_e) (python/main.py:248-292).  Expanded by the code of ihm2mpc_set_weights.
+int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const double *W_e)
+{
+    CHECK_H(h);
+    if (!W && !W_e) {
+        free_instance_weights(h);
+        h->uniform_H = h->shared_uniform_H;
+        return 0;
+    }
+    if (!W || !W_e) return fail("W and W_e must both be given, or both be NULL (batch-shared weights again)");
+    if (!h->weights_set) return fail("ihm2mpc_set_weights has not been called (the batch-shared weights come first)");
+    if (h->bounds_set && !h->uniform_CD) return fail("per-instance weights need stage-independent general rows C, D");
+    const int B = h->B;
+    std::vector<double> Hs((size_t)B * 200, 0.0), Gy((size_t)B * 240, 0.0), Wd((size_t)B * 208);
+    const double cs = h->cfg.cost_scale_stage;
+    for (int b = 0; b < B; b++) {
+        const double *Wb = W + (size_t)b * 144, *Web = W_e + (size_t)b * 64;
+        for (int i = 0; i < 144; i++) if (Wb[i] != Wb[i]) return fail("instance %d: W[%d][%d] is NaN", b, i / 12, i % 12);
+        for (int i = 0; i < 64; i++) if (Web[i] != Web[i]) return fail("instance %d: W_e[%d][%d] is NaN", b, i / 8, i % 8);
+        double *Hb = &Hs[(size_t)b * 200], *Gb = &Gy[(size_t)b * 240];
+        stage_weight_tables(Wb, cs, Hb, Gb);
+        terminal_weight_tables(Web, Hb + 100, Gb + 120);
+        if (!symmetric10(Hb)) return fail("instance %d: the weight matrix of the stages 0..%d is not symmetric", b, h->N - 1);
+        if (!symmetric10(Hb + 100)) return fail("instance %d: the weight matrix of stage %d (terminal) is not symmetric", b, h->N);
+        std::memcpy(&Wd[(size_t)b * 208], Wb, 144 * sizeof(double));
+        std::memcpy(&Wd[(size_t)b * 208 + 144], Web, 64 * sizeof(double));
+    }
+    if (!h->iHs && (dalloc(&h->iHs, (size_t)B * 200) || dalloc(&h->iGy, (size_t)B * 240) || dalloc(&h->iWd, (size_t)B * 208))) {
+        free_instance_weights(h);
+        return -1;
+    }
+    if (upload_shared(h, Hs.data(), h->iHs, Hs.size()) || upload_shared(h, Gy.data(), h->iGy, Gy.size()) ||
+        upload_shared(h, Wd.data(), h->iWd, Wd.size()))
+        return -1;
+    h->inst_w = true;
+    h->uniform_H = true;
     return 0;
 }
 
@@ -520,6 +663,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
     if (upload_shared(h, h->host_lb, h->st_lb, (size_t)NS * NC) || upload_shared(h, h->host_ub, h->st_ub, (size_t)NS * NC) ||
         upload_shared(h, h->host_sz, h->st_sz, (size_t)NS * NLAM) || upload_shared(h, h->host_sZ, h->st_sZ, (size_t)NS * NLAM))
         return -1;
+    for (size_t e = 0; e < n; e++) { h->host_kc[e] = kc[e]; h->host_slb[e] = slb[e]; h->host_sub[e] = sub[e]; }
     if (n) {
         HIP_TRY(hipMemcpyAsync(h->slot_kc, kc.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -527,6 +671,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
             upload_shared(h, zw.data(), h->slot_zw, n) || upload_shared(h, Zw.data(), h->slot_Zw, n))
             return -1;
     }
+    if (h->inst_b) return scatter_instance_bounds(h);      // the per-instance values into the new table (or a refusal: ready() then reports it)
     return 0;
 }
 
@@ -565,6 +710,53 @@ int ihm2mpc_set_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, 
         upload_shared(h, ug, h->ug, (size_t)N * 2))
         return -1;
     h->bounds_set = true;
+    return 0;
+}
+
+// The bound values per instance: lbx/ubx (B,N+1,8) (stage 0 unused: x_0 is fixed), lbu/ubu (B,N,2), lg/ug (B,N,2) -- acados' per-solver
+// constraints_set(k, "lbx" / "ubx" / "lbu" / "ubu" / "lg" / "ug", ...) (python/main.py:248-292).  The finite sides must be those of the
+// batch-shared table (|v| >= 1e20: absent); C, D, soft penalties, track rows and the a_lat row stay batch-shared.
+int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, const double *lbu, const double *ubu,
+                                const double *lg, const double *ug)
+{
+    CHECK_H(h);
+    const bool none = !lbx && !ubx && !lbu && !ubu && !lg && !ug;
+    if (none) { free_instance_bounds(h); return 0; }
+    if (!lbx || !ubx || !lbu || !ubu || !lg || !ug) return fail("lbx, ubx, lbu, ubu, lg, ug must all be given, or all be NULL (batch-shared bounds again)");
+    if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called (the batch-shared table gives the pattern)");
+    const int B = h->B, N = h->N, NS = h->NS;
+    double *il = new double[(size_t)B * NS * 12], *iu = new double[(size_t)B * NS * 12];
+    auto bad = [&](int rc) { delete[] il; delete[] iu; return rc; };
+    for (int b = 0; b < B; b++)
+        for (int k = 0; k < NS; k++)
+            for (int c = 0; c < 12; c++) {
+                double lb = -INFINITY, ub = INFINITY;
+                if (c < 8) { if (k >= 1) { lb = lbx[((size_t)b * NS + k) * 8 + c]; ub = ubx[((size_t)b * NS + k) * 8 + c]; } }
+                else if (c < 10) { if (k < N) { lb = lbu[((size_t)b * N + k) * 2 + c - 8]; ub = ubu[((size_t)b * N + k) * 2 + c - 8]; } }
+                else { if (k < N) { lb = lg[((size_t)b * N + k) * 2 + c - 10]; ub = ug[((size_t)b * N + k) * 2 + c - 10]; } }
+                if (lb != lb || ub != ub) return bad(fail("instance %d, stage %d, row %d (%s): bound is NaN", b, k, c, row_name(c)));
+                if (lb > ub) return bad(fail("instance %d, stage %d, row %d (%s): lower bound %g > upper bound %g", b, k, c, row_name(c), lb, ub));
+                il[((size_t)b * NS + k) * 12 + c] = (std::fabs(lb) < 1e20) ? lb : -INFINITY;      // as ihm2mpc_set_bounds
+                iu[((size_t)b * NS + k) * 12 + c] = (std::fabs(ub) < 1e20) ? ub : INFINITY;
+            }
+    // the pattern check before anything of the handle changes
+    if (check_instance_pattern(h, il, iu)) return bad(-1);
+    if (!h->i_st_lb) {
+        const size_t nb = (size_t)B;
+        if (dalloc(&h->i_st_lb, nb * NS * NC) || dalloc(&h->i_st_ub, nb * NS * NC) || dalloc(&h->i_lbu, nb * N * 2) || dalloc(&h->i_ubu, nb * N * 2) ||
+            dalloc(&h->i_lg, nb * N * 2) || dalloc(&h->i_ug, nb * N * 2)) {
+            bad(0);
+            free_instance_bounds(h);
+            return -1;
+        }
+    }
+    delete[] h->ih_lb; delete[] h->ih_ub;
+    h->ih_lb = il; h->ih_ub = iu;
+    if (upload_shared(h, lbu, h->i_lbu, (size_t)B * N * 2) || upload_shared(h, ubu, h->i_ubu, (size_t)B * N * 2) ||
+        upload_shared(h, lg, h->i_lg, (size_t)B * N * 2) || upload_shared(h, ug, h->i_ug, (size_t)B * N * 2))
+        return -1;
+    h->inst_b = true;
+    if (scatter_instance_bounds(h)) return -1;
     return 0;
 }
 

@@ -132,6 +132,21 @@ struct ihm2mpc_handle {
     hipEvent_t args_ev[2];          // recorded after a slot's upload: the slot is free again once it has passed
     int args_idx;
 
+    // ---- per-instance tuning (ihm2mpc_set_instance_weights / _bounds): allocated while the mode is on ----
+    // Weights: one stage weight and one terminal weight per instance, expanded on the host by the code of ihm2mpc_set_weights.
+    // Bounds: the VALUES of the rows 0..11 per instance; which sides are finite or soft stays batch-shared (the slot table's pattern).
+    bool inst_w, inst_b;
+    bool inst_b_ok;                // false: a later setter changed the shared pattern and the stored values no longer fit it
+    bool shared_uniform_H;         // uniform_H of the batch-shared weights (restored when the per-instance weights go)
+    double *iHs, *iGy, *iWd;       // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
+    double *ih_lb, *ih_ub;         // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
+    double *i_slot_lb, *i_slot_ub; // (B,nslot_lane*64) the slot table's bounds per instance
+    size_t i_slot_cap;             // entries per instance the two arrays hold
+    double *i_st_lb, *i_st_ub;     // (B,NS,NC) the SQP mode's bounds per instance
+    double *i_lbu, *i_ubu, *i_lg, *i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
+    int32_t *host_kc;              // host copies of the slot table (MAX_SLOTS): the per-instance values are scattered into its pattern
+    double *host_slb, *host_sub;
+
     // ---- history of ihm2mpc_run_steps, grown on demand ----
     size_t hist_cap;                // steps the buffers hold
     double *hist_u0, *hist_x0;      // (steps,B,2), (steps,B,8)

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64) void k_init_guess(int B, int N, int M, double d
                                                    const double *__restrict__ s_ref, const double *__restrict__ kappa_ref,
                                                    const int32_t *__restrict__ track_id, const double *__restrict__ x0,
                                                    const double *__restrict__ lbu, const double *__restrict__ ubu,
-                                                   const double *__restrict__ lg, const double *__restrict__ ug,
+                                                   const double *__restrict__ lg, const double *__restrict__ ug, int clamp_bs,
                                                    double *__restrict__ xs, double *__restrict__ us,
                                                    const int32_t *__restrict__ only_failed, double *__restrict__ pi,
                                                    double *__restrict__ lam, int exact_lags)
@@ -65,6 +65,8 @@ __global__ __launch_bounds__(64) void k_init_guess(int B, int N, int M, double d
     const double eT2 = exact_lags ? exp(-0.5 * h / k_tT) : 1.0, eT = eT2 * eT2, eD2 = exact_lags ? exp(-0.5 * h / k_tdelta) : 1.0, eD = eD2 * eD2;
     double J[8][10];
     double *xb = xs + (size_t)b * (N + 1) * 8, *ub = us + (size_t)b * N * 2;
+    // the clamps of this instance: clamp_bs = N * 2 with per-instance bounds, 0 with the batch-shared table
+    lbu += (size_t)b * clamp_bs; ubu += (size_t)b * clamp_bs; lg += (size_t)b * clamp_bs; ug += (size_t)b * clamp_bs;
     for (int k = 0; k < N; k++) {
 #pragma unroll
         for (int i = 0; i < 8; i++) xb[k * 8 + i] = x[i];
@@ -133,10 +135,12 @@ void ihm2_launch_init_guess(ihm2mpc_handle *h, double v_ref_scale, int only_fail
     // waits for the rollouts of its few failed instances -- 3.3 ms of a 19-26 ms step of configs[2] with 25 sub-steps per interval -- so they take the
     // actuator lags in closed form and sub-steps of at most 12.5 ms (0.55 ms)
     const int exact_lags = only_failed ? 1 : 0;
+    const bool ib = h->inst_b;
     if (exact_lags) M_roll = std::max(4, (int)std::ceil(h->cfg.dt / 12.5e-3));
 #define LAUNCH_IG(MD)                                                                                                          \
     hipLaunchKernelGGL(k_init_guess<MD>, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->B, h->N, M_roll, h->cfg.dt,      \
-                       v_ref_scale, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x0, h->lbu, h->ubu, h->lg, h->ug,    \
+                       v_ref_scale, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x0, ib ? h->i_lbu : h->lbu,          \
+                       ib ? h->i_ubu : h->ubu, ib ? h->i_lg : h->lg, ib ? h->i_ug : h->ug, ib ? h->N * 2 : 0,                 \
                        h->x, h->u, mask, h->pi, h->lam, exact_lags)
     // recovery of a few failed instances: the kinematic rollout is 5x cheaper and its defects are what one RTI step absorbs
     if (h->cfg.model == IHM2MPC_MODEL_FDYN6U && !only_failed) LAUNCH_IG(IHM2MPC_MODEL_FDYN6U);

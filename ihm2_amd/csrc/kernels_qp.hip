@@ -52,6 +52,9 @@ struct QpArgs {
     // shared
     const double *Hs, *Gy, *CD, *slot_lb, *slot_ub, *slot_zw, *slot_Zw;
     const int32_t *slot_kc;
+    // per-instance tuning (api.hip: ihm2mpc_set_instance_weights / _bounds): doubles of Hs / Gy / slot_lb, slot_ub per instance (0: batch-shared)
+    // and the offset of the terminal stage's Hs / Gy block (N * 100, N * 120 batch-shared; 100, 120 per instance: (B,2,100), (B,2,120))
+    int hs_bs, hs_te, gy_bs, gy_te, sl_bs;
     // per instance
     double *x, *u;
     const double *x0, *yref, *yref_e;
@@ -256,6 +259,11 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     // constraint rows per stage held in LDS: 8 x boxes, 2 u boxes, 2 general rows (+ 2 track rows (+ the lateral-acceleration row, PATH == 2)); the
     // multiplier arrays in HBM always have the full NLAM = 28 columns (14 lower sides, then 14 upper sides); row 14 keeps its two in lam_a / slk_a
     constexpr int NCK = (PATH == 2) ? 15 : PATH ? 14 : 12;
+    // the instance's weight tables and slot bounds: wave-uniform bases (batch-shared tables: stride 0, terminal at stage N).  Per-instance weights
+    // are stage-independent (UNI), and UNI reads stage 0 for every k < N -- which a batch-shared UNI table holds bit for bit as well
+    const double *Hs0 = a.Hs + (size_t)b * a.hs_bs, *HsT = Hs0 + a.hs_te;
+    const double *Gy0 = a.Gy + (size_t)b * a.gy_bs, *GyT = Gy0 + a.gy_te;
+    const double *slot_lbb = a.slot_lb + (size_t)b * a.sl_bs, *slot_ubb = a.slot_ub + (size_t)b * a.sl_bs;
     constexpr bool ALAT = PATH == 2;
     // UNI: the stage Hessians H_0..H_{N-1} and the general rows [C D]_k do not depend on k (the reference's OCP: one W, one C, D
     // for all stages, python/mpc.py:49-99).  They are then kept in LDS (H only where the budget of 40 KB per instance allows)
@@ -281,7 +289,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     double *CDl = Hl + (HL ? 200 : 0);       // 20   general rows (CL only)
     double *spv = CDl + (CL ? 20 : 0);       // 60   the (up to three) non-zeros of every row of the two Hessians (HL only) ...
     int *spc = reinterpret_cast<int *>(spv + 60);      // 60 ints: ... and their columns
-#define HS(k, i, l) (HL ? Hl[(((k) == N) ? 100 : 0) + (i) * 10 + (l)] : a.Hs[((k) * 10 + (i)) * 10 + (l)])
+#define HS(k, i, l) (HL ? Hl[(((k) == N) ? 100 : 0) + (i) * 10 + (l)] : ((k) == N ? HsT : Hs0 + (UNI ? 0 : (k)) * 100)[(i) * 10 + (l)])
 #define CDV(k, r, j) (CL ? CDl[(r) * 10 + (j)] : a.CD[((k) * 2 + (r)) * 10 + (j)])
 
     // reductions over the instance's threads: wave butterfly, then (NW > 1) one LDS word per wave -- the transpose tile of the factor
@@ -320,7 +328,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 
     // ------------------------------------------------------------------ QP data + NLP residuals
     // gradient g_k = H_k z_k - Gy_k yref_k, and the stationarity of the NLP with the incoming multipliers
-    if (HL) for (int e = tid; e < 200; e += NT) Hl[e] = a.Hs[(e < 100) ? e : N * 100 + (e - 100)];
+    if (HL) for (int e = tid; e < 200; e += NT) Hl[e] = (e < 100) ? Hs0[e] : HsT[e - 100];
     if (CL && tid < 20) CDl[tid] = a.CD[tid];
     if (UNI) BSYNC();
     // Rows of the batch-shared Hessians with at most three non-zeros each (the reference's cost y = [x; u; x_act - u], python/mpc.py:49-58,
@@ -374,11 +382,11 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             acc = fma(HS(k, j, 9), ub[k * 2 + 1], acc);
             const double *yr = a.yref + ((size_t)b * N + k) * 12;
 #pragma unroll
-            for (int l = 0; l < 12; l++) acc = fma(-a.Gy[(k * 10 + j) * 12 + l], yr[l], acc);
+            for (int l = 0; l < 12; l++) acc = fma(-Gy0[((UNI ? 0 : k) * 10 + j) * 12 + l], yr[l], acc);
         } else {
             const double *yr = a.yref_e + (size_t)b * 8;
 #pragma unroll
-            for (int l = 0; l < 8; l++) acc = fma(-a.Gy[(k * 10 + j) * 12 + l], yr[l], acc);
+            for (int l = 0; l < 8; l++) acc = fma(-GyT[j * 12 + l], yr[l], acc);
         }
         gb[e] = acc;
         const bool counted = !((k == 0 && j < 8) || (k == N && j >= 8));
@@ -471,7 +479,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 cz = fma(CDV(k, c - 10, 8), ub[k * 2 + 0], cz);
                 cz = fma(CDV(k, c - 10, 9), ub[k * 2 + 1], cz);
             }
-            const double lb = a.slot_lb[s], ubd = a.slot_ub[s];
+            const double lb = slot_lbb[s], ubd = slot_ubb[s];
             bool soft = false;
             if (r < NSOFT) { so_zw[r < NSOFT ? r : 0] = a.slot_zw[s]; so_Zw[r < NSOFT ? r : 0] = a.slot_Zw[s]; soft = a.slot_Zw[s] >= 0.0; }
             // soft sides may be violated: they do not count as infeasibility of the iterate
@@ -745,7 +753,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             RicLds L;
             L.gt = NS * 10; L.pv = NS * 28; L.gam = NS * 36 + N * 8; L.dz = L.gam + 2 * NS * NCK; L.kff = L.dz + NS * 10; L.Kl = L.kff + N * 4;
             L.Ginv = L.Kl + N * 16; L.hv = L.Ginv + N * 8; L.tile = L.hv + N * 8; L.hc = L.tile + 136; L.ha = L.hc + NS * 2;
-            riccati_sweep_mfma<NCK, PATH != 0, UNI != 0, RIC_RING, ALAT>(N, lane, linb, a.Hs, a.CD, L, Pg, Mg, LIN_REC, a.m_act == 0, a.symmetrize != 0);
+            riccati_sweep_mfma<NCK, PATH != 0, UNI != 0, RIC_RING, ALAT>(N, lane, linb, Hs0, HsT, a.CD, L, Pg, Mg, LIN_REC, a.m_act == 0, a.symmetrize != 0);
             if (lane < 8) dz[lane] = 0.0;
         }
         BSYNC();
@@ -1401,6 +1409,9 @@ static QpArgs qp_args(ihm2mpc_handle *h)
     a.nslots_can = h->nslot_lane * 64;
     a.tol = h->cfg.ipm_tol; a.mu0 = h->cfg.ipm_mu0; a.tau0 = h->cfg.ipm_tau0;
     a.Hs = h->Hs; a.Gy = h->Gy; a.CD = h->CD; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.slot_kc = h->slot_kc;
+    a.hs_bs = 0; a.hs_te = h->N * 100; a.gy_bs = 0; a.gy_te = h->N * 120; a.sl_bs = 0;
+    if (h->inst_w) { a.Hs = h->iHs; a.Gy = h->iGy; a.hs_bs = 200; a.hs_te = 100; a.gy_bs = 240; a.gy_te = 120; }
+    if (h->inst_b) { a.sl_bs = h->nslot_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }
     a.x = h->x; a.u = h->u; a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e;
     a.pi = h->pi; a.lam = h->lam; a.res = h->res; a.qp_res = h->qp_res; a.u0 = h->u0; a.status = h->status; a.qp_iter = h->qp_iter;
     a.lin = h->lin; a.g = h->q_g; a.rg = h->q_rg; a.P = h->q_P; a.M = h->q_M + (size_t)QM_PAD * 64;
@@ -1571,7 +1582,8 @@ int ihm2_launch_qp(ihm2mpc_handle *h)
     } while (0)
 #if QP_SET == 0
     // few instances (at most one per CU): four wavefronts per instance, slots from the 256-lane table
-    if (h->block_qp && nsoft == 0 && !h->path_on && h->nslot_lane_blk >= 1 && h->nslot_lane_blk <= 2 && h->B <= h->n_cu && h->nslot_lane * 64 <= (h->N + 1) * 12) {
+    // (per-instance bounds: the 64-lane table alone carries them -- k_qp_wave's results are the four-wave kernel's bit for bit)
+    if (h->block_qp && !h->inst_b && nsoft == 0 && !h->path_on && h->nslot_lane_blk >= 1 && h->nslot_lane_blk <= 2 && h->B <= h->n_cu && h->nslot_lane * 64 <= (h->N + 1) * 12) {
         a.slot_kc = h->slot_kc_blk; a.slot_lb = h->slot_lb_blk; a.slot_ub = h->slot_ub_blk; a.nslots = h->nslot_lane_blk * 256;
         if (uni) {
             (void)hipFuncSetAttribute((const void *)k_qp_block<2, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

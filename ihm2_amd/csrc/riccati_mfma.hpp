@@ -152,10 +152,11 @@ __device__ __forceinline__ void dyn_residual(const int N, const int lane, double
 
 // Backward sweep.  In (LDS): gam, hc, gt = the predictor's gradient incl. [A B]'pi; in the records: A, B and rb (slot 88).
 // Out: LDS arrays of RicLds; HBM: Pg (NS,64), Mg (N,64) in the RIC_IDX layout.  store_p (wave-uniform): also keep p_k, k < N.
-// Hs (NS,10,10), CD (N,2,10): batch-shared; UNI: the same for all k < N.  D: depth of the record prefetch ring.
+// Hs (NS,10,10), CD (N,2,10): batch-shared; UNI: the same for all k < N (only stage 0 is read).  HsT: the terminal stage's 10x10.  D: depth of the record prefetch ring.
 // ALAT: a fifteenth row per stage, gam[k][14] a a' with a = the four non-zeros in L.ha (stages 1..N-1).
 template <int NCK, bool PATH, bool UNI, int D, bool ALAT = false>
 __device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, const double *__restrict__ linb, const double *__restrict__ Hs,
+                                                   const double *__restrict__ HsT,
                                                    const double *__restrict__ CD, const RicLds L, double *__restrict__ Pg, double *__restrict__ Mg,
                                                    const int lin_rec, const bool store_p, const bool symmetrize)
 {
@@ -216,7 +217,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, 
         for (int r = 0; r < 2; r++) {
             double v = 0.0;
             if (j < 8) {
-                v = Hs[(N * 10 + row[r]) * 10 + j];
+                v = HsT[row[r] * 10 + j];
                 if (row[r] == j) v += sm[L.gam + N * NCK + j];
             } else if (j == 10) v = sm[L.gt + N * 10 + row[r]];
             if (PATH && r == 0) v += p11 * (g12 + g13) + p12 * (g12 * a0 - g13 * a1) + p22 * (g12 * a0 * a0 + g13 * a1 * a1);

@@ -19,6 +19,9 @@ struct LsArgs {
     const double *st_lb, *st_ub;     // (NS,14) bounds per (stage, row), -+inf = absent
     const double *st_sz, *st_sZ;     // (NS,28) slack penalties per side, sZ < 0 = hard
     const double *CD, *Hs, *widths;
+    // per-instance tuning: doubles per instance of W (B,144+64), Hs (B,2,100), st_lb / st_ub (0: batch-shared); W's stage stride (144 shared, 0:
+    // one stage weight per instance) and the offset of W_e (N * 144 shared, 144 per instance)
+    int w_bs, w_ks, w_te, hs_bs, st_bs;
     const double *x0, *yref, *yref_e, *g, *lin;
     double *x, *u, *pi, *lam, *slk;  // in: the QP's full step; out: the accepted iterate
     const double *xp, *up, *pip, *lamp, *slkp;   // the iterate the QP was built at
@@ -82,6 +85,9 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
     const double *lampb = a.lamp + (size_t)b * NS * 28, *slpb = a.slkp + (size_t)b * NS * 28;
     double *wpib = a.wpi + (size_t)b * NS * 8, *wlamb = a.wlam + (size_t)b * NS * 28;
     const double *x0b = a.x0 + (size_t)b * 8;
+    // the instance's tuning (kernels_qp.hip: QpArgs::wi); batch-shared: the tables themselves
+    const double *Wb = a.W + (size_t)b * a.w_bs, *Hsb = a.Hs + (size_t)b * a.hs_bs;
+    const double *st_lbb = a.st_lb + (size_t)b * a.st_bs, *st_ubb = a.st_ub + (size_t)b * a.st_bs;
 
     auto restore = [&](bool primal_dual) {
         if (primal_dual) {
@@ -134,7 +140,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
             const int j = lane;
             const double *gb = a.g + (size_t)b * NS * 10, *rec = a.lin + (size_t)b * N * LIN_REC;
             pi0 = gb[j];
-            for (int l = 0; l < 10; l++) pi0 = fma(a.Hs[j * 10 + l], (l < 8) ? xb[l] - xpb[l] : ub[l - 8] - upb[l - 8], pi0);
+            for (int l = 0; l < 10; l++) pi0 = fma(Hsb[j * 10 + l], (l < 8) ? xb[l] - xpb[l] : ub[l - 8] - upb[l - 8], pi0);
             for (int l = 0; l < 8; l++) pi0 = fma(rec[l * 8 + j], pib[8 + l], pi0);
             for (int r = 0; r < 2; r++) pi0 = fma(-a.CD[r * 10 + j], lamb[10 + r] - lamb[24 + r], pi0);
         }
@@ -170,7 +176,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
                 for (int i = 0; i < 8; i++) inf += wpib[i] * fabs(x0b[i] - xk[i]);
             if (k < N) {
                 const double uT = upb[k * 2] + al * (ub[k * 2] - upb[k * 2]), ud = upb[k * 2 + 1] + al * (ub[k * 2 + 1] - upb[k * 2 + 1]);
-                const double *yr = a.yref + ((size_t)b * N + k) * 12, *Wk = a.W + (size_t)k * 144;
+                const double *yr = a.yref + ((size_t)b * N + k) * 12, *Wk = Wb + (size_t)k * a.w_ks;
                 double e[12];
 #pragma unroll
                 for (int i = 0; i < 8; i++) e[i] = xk[i] - yr[i];
@@ -213,7 +219,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
                     cv[10 + r] = acc;
                 }
             } else {
-                const double *ye = a.yref_e + (size_t)b * 8, *We = a.W + (size_t)N * 144;
+                const double *ye = a.yref_e + (size_t)b * 8, *We = Wb + a.w_te;
                 double q = 0.0;
                 for (int i = 0; i < 8; i++) {
                     double acc = 0.0;
@@ -230,7 +236,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
             }
 #pragma unroll
             for (int c = 0; c < 14; c++) {
-                const double lb = a.st_lb[k * 14 + c], ubd = a.st_ub[k * 14 + c];
+                const double lb = st_lbb[k * 14 + c], ubd = st_ubb[k * 14 + c];
                 if (lb > -INFINITY) {
                     double viol = lb - cv[c];
                     const double Z = a.st_sZ[k * 28 + c];
@@ -329,6 +335,9 @@ static inline LsArgs make_ls_args(ihm2mpc_handle *h)
     a.s_ref = h->s_ref; a.kappa_ref = h->kappa_ref; a.track_id = h->track_id;
     a.W = h->Wd; a.st_lb = h->st_lb; a.st_ub = h->st_ub; a.st_sz = h->st_sz; a.st_sZ = h->st_sZ;
     a.CD = h->CD; a.Hs = h->Hs; a.widths = h->widths;
+    a.w_bs = 0; a.w_ks = 144; a.w_te = h->N * 144; a.hs_bs = 0; a.st_bs = 0;
+    if (h->inst_w) { a.W = h->iWd; a.Hs = h->iHs; a.w_bs = 208; a.w_ks = 0; a.w_te = 144; a.hs_bs = 200; }
+    if (h->inst_b) { a.st_bs = h->NS * NC; a.st_lb = h->i_st_lb; a.st_ub = h->i_st_ub; }
     a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e; a.g = h->q_g; a.lin = h->lin;
     a.x = h->x; a.u = h->u; a.pi = h->pi; a.lam = h->lam; a.slk = h->slk;
     a.xp = h->ls_x; a.up = h->ls_u; a.pip = h->ls_pi; a.lamp = h->ls_lam; a.slkp = h->ls_slk;

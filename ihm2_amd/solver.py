@@ -167,6 +167,34 @@ class BatchedOcpSolver:
             self.data.W_e = np.asarray(W_e, dtype=np.float64)
         self._push_weights()
 
+    # ---- per-instance tuning ----
+    def set_instance_weights(self, W=None, W_e=None):
+        """One weight set per instance: W ``(B,12,12)`` for every stage, W_e ``(B,8,8)``.  Instance b then gives what a
+        batch whose shared weights are ``(W[b], W_e[b])`` gives, bit for bit.  ``None, None``: the shared weights again."""
+        if W is None and W_e is None:
+            self._inst_W = None
+            _lib.check(self.lib.ihm2mpc_set_instance_weights(self._h, None, None))
+            return
+        if W is None or W_e is None:
+            raise ValueError("W and W_e must both be given, or both be None")
+        W = _f64(W, (self.B, NY, NY), "W"); W_e = _f64(W_e, (self.B, NX, NX), "W_e")
+        _lib.check(self.lib.ihm2mpc_set_instance_weights(self._h, _ptr(W), _ptr(W_e)))
+        self._inst_W = (W, W_e)
+
+    def set_instance_bounds(self, lbx=None, ubx=None, lbu=None, ubu=None, lg=None, ug=None):
+        """Bound values per instance: lbx/ubx ``(B,N+1,8)`` (stage 0 unused), lbu/ubu ``(B,N,2)``, lg/ug ``(B,N,2)``.  The finite
+        sides must be the shared table's; C, D, soft penalties, track rows and the a_lat row stay shared.  All ``None``: shared again."""
+        arrs = (lbx, ubx, lbu, ubu, lg, ug)
+        if all(a is None for a in arrs):
+            _lib.check(self.lib.ihm2mpc_set_instance_bounds(self._h, None, None, None, None, None, None))
+            return
+        if any(a is None for a in arrs):
+            raise ValueError("lbx, ubx, lbu, ubu, lg, ug must all be given, or all be None")
+        B, N = self.B, self.N
+        shapes = ((B, N + 1, NX), (B, N + 1, NX), (B, N, NU), (B, N, NU), (B, N, 2), (B, N, 2))
+        arrs = [_f64(a, sh, n) for a, sh, n in zip(arrs, shapes, ("lbx", "ubx", "lbu", "ubu", "lg", "ug"))]
+        _lib.check(self.lib.ihm2mpc_set_instance_bounds(self._h, *[_ptr(a) for a in arrs]))
+
     # ---- per-instance data, batched ----
     def set_x0(self, x0):
         _lib.check(self.lib.ihm2mpc_set_x0(self._h, _ptr(_f64(x0, (self.B, NX), "x0"))))
@@ -529,6 +557,8 @@ class AcadosOcpSolver:
             raise Exception(f"AcadosOcpSolver.set(): '{field}' is not a valid argument.")
 
     def cost_set(self, stage: int, field: str, value, api: str = "warn") -> None:
+        """Writes the batch-SHARED weight table (every instance of the batch sees it); per-instance weights go through
+        ``BatchedOcpSolver.set_instance_weights``."""
         if field != "W":
             raise Exception(f"AcadosOcpSolver.cost_set(): '{field}' is not a valid argument.")
         b = self.batch
@@ -544,6 +574,8 @@ class AcadosOcpSolver:
         b._push_weights()
 
     def constraints_set(self, stage: int, field: str, value, api: str = "warn") -> None:
+        """Stage 0's lbx/ubx set this instance's x0; every other field writes the batch-SHARED bound table.  Per-instance
+        bounds go through ``BatchedOcpSolver.set_instance_bounds``."""
         b, d, c = self.batch, self.batch.data, self.batch.ocp.constraints
         v = np.asarray(value, dtype=np.float64)
         if field in ("lbx", "ubx") and stage == 0:

@@ -12,6 +12,8 @@
  *                                ihm2_fkin6_acados_update_params                mpc_control_node.cpp:360-364
  *   ihm2mpc_set_weights       <- solver.cost_set(i, "W", W)                     python/main.py:253-295; mpc_control_node.cpp:287-293
  *   ihm2mpc_set_bounds        <- ocp.constraints.* / constraints_set(i,"lbx"..) python/mpc.py:79-99; dpc/main.py:226-227,259-261
+ *   ihm2mpc_set_instance_weights <- solver_b.cost_set(i, "W", W_b), one solver per tuning  python/main.py:248-292
+ *   ihm2mpc_set_instance_bounds  <- solver_b.constraints_set(i, "lbx".."ug", ..) per tuning python/main.py:248-292
  *   ihm2mpc_set_x0            <- solver.set(0,"lbx",x); set(0,"ubx",x)          python/main.py:299-300; mpc_control_node.cpp:177-179
  *   ihm2mpc_set_yref(_e)      <- solver.set(j,"yref",..)                        python/main.py:303-314; mpc_control_node.cpp:183-186
  *   ihm2mpc_set_x / _set_u    <- solver.set(j,"x"/"u",..) (warm start)          python/main.py:317-322
@@ -145,6 +147,16 @@ int ihm2mpc_set_weights(ihm2mpc_handle *h, const double *W, const double *W_e); 
 int ihm2mpc_set_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, const double *lbu,
                        const double *ubu, const double *C, const double *D, const double *lg,
                        const double *ug);
+/* Per-instance tuning: instance b carries its own weights and bound values; its results are those of a handle whose
+ * batch-shared tables hold b's tuning, bit for bit.  NULL (all arguments) = batch-shared again.
+ * Weights: W (B,12,12) for every stage k < N, W_e (B,8,8); needs stage-independent C, D; ihm2mpc_set_weights first.
+ * Bounds: lbx/ubx (B,N+1,8) [row 0 unused], lbu/ubu (B,N,2), lg/ug (B,N,2); ihm2mpc_set_bounds first.  Which sides are
+ * finite (|v| < 1e20) must match the batch-shared table; C, D, soft penalties, track rows and the a_lat row stay shared.
+ * A later ihm2mpc_set_bounds / _set_soft / _set_path_constraints / _set_alat_constraint re-applies the stored values (or the
+ * next solve refuses, if the pattern no longer matches).  Errors name the instance, stage and row. */
+int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const double *W_e);
+int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, const double *lbu,
+                                const double *ubu, const double *lg, const double *ug);
 /* SOFT constraint sides (AcadosOcpConstraints idxsbx / idxsbx_e / idxsg with AcadosOcpCost zl, zu, Zl, Zu --
  * declared by the reference's OCP class, python/mpc.py:58-90 uses hard sides only): soft_z, soft_Z (N+1,28) per
  * one-sided constraint, 14 lower sides [x(8) u(2) g(2) h(2)] then 14 upper sides.  A side with soft_Z >= 0 carries a
