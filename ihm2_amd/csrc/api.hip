@@ -1091,6 +1091,14 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n)
     return 0;
 }
 
+int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec)
+{
+    CHECK_H(h);
+    if (!rec) return fail("null argument");
+    for (int i = 0; i < 16; i++) rec[i] = h->launch_rec[i];
+    return 0;
+}
+
 int ihm2mpc_get_linearization(ihm2mpc_handle *h, double *A, double *Bm, double *b)
 {
     CHECK_H(h);
@@ -1338,6 +1346,9 @@ int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_
     }
     if (rc != 0) {
         if (freeze) return fail("no persistent loop for this configuration (needs batch-shared weights and rows for soft tables or the collocation integrator, and a batch of at most %d): call ihm2mpc_step per control period", 4 * h->n_cu);
+        // the record of the fallback (a k_steps launch writes its own): the per-step QP launches below update [0..4]
+        for (int i = 6; i < 13; i++) h->launch_rec[i] = 0;
+        h->launch_rec[5] = 2; h->launch_rec[13] = resident ? 1 : 2;
         for (size_t i = 0; i < n; i++) {      // launches per step, histories by device-to-device copies in stream order
             if (ihm2mpc_step(h, model, M_sim, s_target)) return -1;
             HIP_TRY(hipMemcpyAsync(h->hist_u0 + i * B * 2, h->u0, B * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));

@@ -151,6 +151,9 @@ struct ihm2mpc_handle {
     size_t hist_cap;                // steps the buffers hold
     double *hist_u0, *hist_x0;      // (steps,B,2), (steps,B,8)
     int32_t *hist_st, *hist_it;     // (steps,B)
+
+    // ---- what the launchers last launched (ihm2mpc_get_launch_record), written at the launch sites ----
+    int32_t launch_rec[16];
 };
 
 // --- launchers (each defined in one .hip file) ---

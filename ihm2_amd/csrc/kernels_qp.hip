@@ -1422,6 +1422,19 @@ static QpArgs qp_args(ihm2mpc_handle *h)
     return a;
 }
 
+// ihm2mpc_get_launch_record: the launch sites below note what they launch (host-side stores, include/ihm2mpc.h)
+static inline void record_qp(ihm2mpc_handle *h, int kind, int ns, int no, int pt, int un)
+{
+    int32_t *r = h->launch_rec;
+    r[0] = kind; r[1] = ns; r[2] = no; r[3] = pt; r[4] = un;
+}
+
+static inline void record_steps(ihm2mpc_handle *h, int ns, int no, int pt, int un, int sq, int ir, int dy)
+{
+    int32_t *r = h->launch_rec;
+    r[5] = 1; r[6] = ns; r[7] = no; r[8] = pt; r[9] = un; r[10] = sq; r[11] = ir; r[12] = dy; r[13] = 0;
+}
+
 // n_steps control steps in one launch (k_steps).  Returns 0 launched, 1 the configuration has no persistent instantiation
 // (the caller then runs ihm2mpc_step n_steps times, which gives the same results).  The all-hard tables are launched from the
 // QP_SET = 0 object, the soft / track-row tables from the QP_SET = 1 object.
@@ -1502,6 +1515,7 @@ int ihm2_launch_steps_dyn(ihm2mpc_handle *h, int model, int M_sim, double s_targ
     do {                                                                                                                                    \
         (void)hipFuncSetAttribute((const void *)k_steps<NS_, NO_, PT_, UN_, SQ_, IR_, DY_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((k_steps<NS_, NO_, PT_, UN_, SQ_, IR_, DY_>), dim3(h->B), dim3(64), lds, h->stream, sdev, a, ls);                \
+        record_steps(h, NS_, NO_, PT_, UN_, SQ_, IR_, DY_);                                                                                \
     } while (0)
     // SQP mode and integrator at run time
 #if QP_SET == 2
@@ -1575,9 +1589,11 @@ int ihm2_launch_qp(ihm2mpc_handle *h)
         if (uni) {                                                                                                        \
             (void)hipFuncSetAttribute((const void *)k_qp_wave<NS_, NO_, PT_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             hipLaunchKernelGGL((k_qp_wave<NS_, NO_, PT_, 1>), dim3(h->B), dim3(64), lds, h->stream, a);                   \
+            record_qp(h, 1, NS_, NO_, PT_, 1);                                                                            \
         } else {                                                                                                          \
             (void)hipFuncSetAttribute((const void *)k_qp_wave<NS_, NO_, PT_, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             hipLaunchKernelGGL((k_qp_wave<NS_, NO_, PT_, 0>), dim3(h->B), dim3(64), lds, h->stream, a);                   \
+            record_qp(h, 1, NS_, NO_, PT_, 0);                                                                            \
         }                                                                                                                 \
     } while (0)
 #if QP_SET == 0
@@ -1588,9 +1604,11 @@ int ihm2_launch_qp(ihm2mpc_handle *h)
         if (uni) {
             (void)hipFuncSetAttribute((const void *)k_qp_block<2, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL((k_qp_block<2, 1, 4>), dim3(h->B), dim3(256), lds, h->stream, a);
+            record_qp(h, 2, 2, 0, 0, 1);
         } else {
             (void)hipFuncSetAttribute((const void *)k_qp_block<2, 0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL((k_qp_block<2, 0, 4>), dim3(h->B), dim3(256), lds, h->stream, a);
+            record_qp(h, 2, 2, 0, 0, 0);
         }
         return 0;
     }
@@ -1605,9 +1623,11 @@ int ihm2_launch_qp(ihm2mpc_handle *h)
         if (nsoft == 0) {       // all sides hard
             (void)hipFuncSetAttribute((const void *)k_qp_wave<8, 0, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL((k_qp_wave<8, 0, 2, 1>), dim3(h->B), dim3(64), lds, h->stream, a);
+            record_qp(h, 1, 8, 0, 2, 1);
         } else {
             (void)hipFuncSetAttribute((const void *)k_qp_wave<10, 4, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL((k_qp_wave<10, 4, 2, 1>), dim3(h->B), dim3(64), lds, h->stream, a);
+            record_qp(h, 1, 10, 4, 2, 1);
         }
     } else if (!h->path_on) {
         if (nsoft <= 2 && per_lane <= 8) LAUNCH_QP(8, 2, 0);

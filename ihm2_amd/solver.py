@@ -404,6 +404,27 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_get_timings(self._h, _ptr(ms), 3))
         return {"total_ms": ms[0], "linearize_ms": ms[1], "qp_ms": ms[2]}
 
+    def get_launch_record(self):
+        """Which instantiations the launchers last launched (``ihm2mpc_get_launch_record``), as they launched them:
+
+        ``qp``: the last per-step QP launch, e.g. ``"k_qp_wave<8,2,0,1>"`` (NSLOT, NSOFT, PATH, UNI) or ``"k_qp_block<2,1,4>"``
+        (slots per thread, UNI, wavefronts); ``steps``: the last ``run_steps``, ``"k_steps<...>"`` (NSLOT, NSOFT, PATH, UNI, SQP, IRK,
+        DYN) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` / ``"not_resident"``.  ``None`` where nothing was launched yet."""
+        rec = np.zeros(16, dtype=np.int32)
+        _lib.check(self.lib.ihm2mpc_get_launch_record(self._h, rec.ctypes.data_as(_lib.c_int32_p)))
+        r = [int(v) for v in rec]
+        qp = None
+        if r[0] == 1:
+            qp = "k_qp_wave<%d,%d,%d,%d>" % tuple(r[1:5])
+        elif r[0] == 2:
+            qp = "k_qp_block<%d,%d,4>" % (r[1], r[4])
+        steps, fallback = None, None
+        if r[5] == 1:
+            steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13])
+        elif r[5] == 2:
+            steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
+        return {"qp": qp, "steps": steps, "steps_fallback": fallback}
+
     # ---- device-pointer variants (zero copy; dptr = integer device address, instance-major layout) ----
     def set_x0_device(self, dptr: int):
         _lib.check(self.lib.ihm2mpc_set_x0_device(self._h, C.c_void_p(dptr)))

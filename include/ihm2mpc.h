@@ -249,6 +249,15 @@ int ihm2mpc_set_slacks(ihm2mpc_handle *h, const double *sl);     /* (B,N+1,28) *
 int ihm2mpc_get_slacks(ihm2mpc_handle *h, double *sl);         /* (B,N+1,28) slack of each soft side after the last QP */
 /* milliseconds of the last solve(): [0] total, [1] linearize, [2] qp+update (HIP events) */
 int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
+/* Which kernel instantiations the handle's launchers last launched, written by the launch sites themselves (host side, no device work).
+ * rec (16 int32):
+ *   [0] last per-step QP launch: 0 none yet, 1 k_qp_wave, 2 k_qp_block;  [1..4] its NSLOT, NSOFT, PATH, UNI
+ *       (k_qp_block: NSLOT = slots per thread of its 256-lane table, NSOFT = PATH = 0)
+ *   [5] last ihm2mpc_run_steps: 0 none yet, 1 one k_steps launch, 2 launches per step (ihm2mpc_step n_steps times);
+ *       [6..12] the k_steps parameters NSLOT, NSOFT, PATH, UNI, SQP, IRK, DYN (0 when [5] != 1);
+ *       [13] why it went per step: 0 it did not, 1 the configuration has no k_steps instantiation, 2 the batch exceeds the resident limit
+ *   [14..15] 0 (reserved) */
+int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */

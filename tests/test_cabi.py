@@ -84,3 +84,20 @@ def test_oracle_and_library_share_the_interior_point_constants():
 
     assert define("include/ihm2mpc.h", "IHM2MPC_IPM_STEP_FRACTION") == define("oracle/ihm2_oracle.h", "ORC_IPM_STEP_FRACTION")
     assert define("include/ihm2mpc.h", "IHM2MPC_IRK_NEWTON_ITER") == define("oracle/ihm2_oracle.h", "ORC_IRK_NEWTON_ITER")
+
+
+def test_launch_record_getter_is_declared_documented_and_bound():
+    """ihm2mpc_get_launch_record (which instantiation the launchers last launched): declared with a comment that names the fields the
+    tests read, in the ctypes table with the header's signature, and wrapped by BatchedOcpSolver.get_launch_record."""
+    from ihm2_amd import _lib
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hdr = open(os.path.join(ROOT, "include", "ihm2mpc.h")).read()
+    m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int ihm2mpc_get_launch_record\(ihm2mpc_handle \*h, int32_t \*rec\);", hdr, flags=re.S)
+    assert m, "ihm2mpc_get_launch_record is not declared right after its comment"
+    doc = m.group(1)
+    for word in ("k_qp_wave", "k_qp_block", "k_steps", "NSLOT", "NSOFT", "PATH", "UNI", "SQP", "IRK", "DYN", "rec (16 int32)"):
+        assert word in doc, f"the comment of ihm2mpc_get_launch_record does not mention {word}"
+    assert "ihm2mpc_get_launch_record" in _declared_symbols()
+    assert _lib.SYMBOLS["ihm2mpc_get_launch_record"] == (ctypes.c_int, [ctypes.c_void_p, _lib.c_int32_p])
+    assert callable(getattr(BatchedOcpSolver, "get_launch_record", None))

@@ -113,6 +113,7 @@ def test_alat_instantiation_on_4096_instances_matches_oracle(track, soft, build)
         s, P, x0, yref, yref_e = _setup(track, soft, B, 4321, 2.5 if soft else 3.0)
     x, u = s.get_x(), s.get_u()
     status = s.solve()
+    assert s.get_launch_record()["qp"] == ("k_qp_wave<10,4,2,1>" if soft else "k_qp_wave<8,0,2,1>")
     out = P.rti_step(x, u, x0, yref, yref_e)
     np.testing.assert_array_equal(status, out["status"])
     ok = status == 0

@@ -329,6 +329,7 @@ def test_block_qp_kernel_matches_the_single_wave_kernel_and_the_oracle(track, B,
         s.set_yref(yref); s.set_yref_e(yref_e); s.set_multipliers(None, None)
         x_in, u_in = s.get_x(), s.get_u()
         st = s.solve()
+        assert s.get_launch_record()["qp"] == ("k_qp_block<2,1,4>" if mode == "1" else "k_qp_wave<5,0,0,1>")
         first = dict(status=st.copy(), it=s.get_qp_iter().copy(), x=s.get_x(), u=s.get_u(), res=s.get_qp_residuals())
         hist = []
         for _ in range(6):

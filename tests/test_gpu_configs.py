@@ -286,7 +286,8 @@ def _build(which):
 @pytest.mark.parametrize("build", ["default", "ilp"])
 @pytest.mark.parametrize("soft", [True, False])
 def test_track_row_instantiations_on_4096_instances_match_oracle(track, soft, build):
-    """The track-row instantiations of the QP kernel (`<8,3,1,1>` soft, `<8,2,1,1>` hard) on a large batch, in both builds: every
+    """The track-row instantiations of the QP kernel (`<10,4,1,1>` soft: both sides of both rows soft put 4 soft sides on some lanes;
+    `<8,0,1,1>` hard) on a large batch, in both builds: every
     status, every IPM iteration count of the solved instances, states and controls against the oracle."""
     from test_gpu_parity import _path_setup
 
@@ -295,6 +296,8 @@ def test_track_row_instantiations_on_4096_instances_match_oracle(track, soft, bu
         s, P, x0, yref, yref_e = _path_setup(track, "fkin6", soft, B, 1234, 1.2 if soft else 1.6)
     x, u = s.get_x(), s.get_u()
     status = s.solve()
+    # the instantiation that ran (launch record): both sides of both track rows soft give more than 3 soft sides on some lanes
+    assert s.get_launch_record()["qp"] == ("k_qp_wave<10,4,1,1>" if soft else "k_qp_wave<8,0,1,1>")
     out = P.rti_step(x, u, x0, yref, yref_e)
     np.testing.assert_array_equal(status, out["status"])
     ok = status == 0
@@ -306,7 +309,7 @@ def test_track_row_instantiations_on_4096_instances_match_oracle(track, soft, bu
 
 def _soft_ocp(kind):
     """OCPs that select the instantiations without track rows: all-hard `<5,0,0>`; soft sides on n, v_x and the steering-rate row
-    (the OCP of test_gpu_parity.py::setup_soft) for the soft tables `<8,2,0>` / `<10,4,0>`."""
+    (the OCP of test_gpu_parity.py::setup_soft): 238 soft sides, the soft table `<10,4,0>`."""
     if kind == "hard":
         return make_ocp()
     ocp = make_ocp(n_max=0.3)           # the sampled |n| <= 0.5 violates the track bound: slacks are active
@@ -338,6 +341,7 @@ def test_both_builds_agree_on_4096_instances(track, kind):
         s.set_yref(yref); s.set_yref_e(yref_e)
         x, u = s.get_x(), s.get_u()
         st = s.solve()
+        assert s.get_launch_record()["qp"] == {"hard": "k_qp_wave<5,0,0,1>", "soft_rows": "k_qp_wave<10,4,0,1>"}[kind]
         r = dict(status=st.copy(), it=s.get_qp_iter().copy(), u=s.get_u().copy())
         if build == "default":
             P = orc.OracleProblem(ocp.flatten().as_dict(track.s_ref, track.kappa_ref))
@@ -351,6 +355,9 @@ def test_both_builds_agree_on_4096_instances(track, kind):
             assert _rel(r["u"][ok & same], u[ok & same]) < 1e-6                           # tolerance 1e-6 relative (where both sides stopped at the same iterate)
         s.set_lap_wrap(True)
         h = s.run_steps(40.0, 4, model=0, M_sim=25, u0_hist=True, status_hist=True, qp_iter_hist=True)
+        rec = s.get_launch_record()         # B = 4096 > 4 per CU: launches per step
+        assert rec["steps"] == "per_step" and rec["steps_fallback"] == "not_resident"
+        assert rec["qp"] == {"hard": "k_qp_wave<5,0,0,1>", "soft_rows": "k_qp_wave<10,4,0,1>"}[kind]
         r.update(h_u0=h["u0"].copy(), h_st=h["status"].copy(), h_it=h["qp_iter"].copy())
         res[build] = r
     a, b = res["default"], res["ilp"]
