@@ -33,7 +33,9 @@ __global__ __launch_bounds__(64) void k_wrap_lap(int B, int N, int nknots, const
 // MODEL: the model the rollout integrates -- the OCP's own model where that is usable as a simulator (fkin6, fdyn6u), the
 // kinematic one for fdyn6 as written (open-loop unstable over the horizon).
 // only_failed != nullptr: re-initialise only the instances whose last solve failed (status other than 0 and 2 = max-iter of
-// the SQP mode, as python/main.py:326 accepts), and clear their multipliers.
+// the SQP mode, as python/main.py:326 accepts), and clear everything the next solve starts from besides (x, u): pi, lam, the slacks of
+// the SQP mode (a failed QP leaves those of the iterate before it, sqp_body.hpp: restore(false)) and the a_lat row's multipliers and
+// slacks (a failed QP does not rewrite them).
 template <int MODEL>
 __global__ __launch_bounds__(64) void k_init_guess(int B, int N, int M, double dt, double v_ref_scale, int nknots,
                                                    const double *__restrict__ s_ref, const double *__restrict__ kappa_ref,
@@ -42,14 +44,16 @@ __global__ __launch_bounds__(64) void k_init_guess(int B, int N, int M, double d
                                                    const double *__restrict__ lg, const double *__restrict__ ug, int clamp_bs,
                                                    double *__restrict__ xs, double *__restrict__ us,
                                                    const int32_t *__restrict__ only_failed, double *__restrict__ pi,
-                                                   double *__restrict__ lam, int exact_lags)
+                                                   double *__restrict__ lam, double *__restrict__ slk, double *__restrict__ lam_a,
+                                                   double *__restrict__ slk_a, int exact_lags)
 {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     if (only_failed) {
         if (only_failed[b] == 0 || only_failed[b] == 2) return;
         for (int e = 0; e < (N + 1) * 8; e++) pi[(size_t)b * (N + 1) * 8 + e] = 0.0;
-        for (int e = 0; e < (N + 1) * NLAM; e++) lam[(size_t)b * (N + 1) * NLAM + e] = 0.0;
+        for (int e = 0; e < (N + 1) * NLAM; e++) { lam[(size_t)b * (N + 1) * NLAM + e] = 0.0; slk[(size_t)b * (N + 1) * NLAM + e] = 0.0; }
+        for (int e = 0; e < (N + 1) * 2; e++) { lam_a[(size_t)b * (N + 1) * 2 + e] = 0.0; slk_a[(size_t)b * (N + 1) * 2 + e] = 0.0; }
     }
     double x[8];
 #pragma unroll
@@ -141,7 +145,7 @@ void ihm2_launch_init_guess(ihm2mpc_handle *h, double v_ref_scale, int only_fail
     hipLaunchKernelGGL(k_init_guess<MD>, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->B, h->N, M_roll, h->cfg.dt,      \
                        v_ref_scale, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x0, ib ? h->i_lbu : h->lbu,          \
                        ib ? h->i_ubu : h->ubu, ib ? h->i_lg : h->lg, ib ? h->i_ug : h->ug, ib ? h->N * 2 : 0,                 \
-                       h->x, h->u, mask, h->pi, h->lam, exact_lags)
+                       h->x, h->u, mask, h->pi, h->lam, h->slk, h->lam_a, h->slk_a, exact_lags)
     // recovery of a few failed instances: the kinematic rollout is 5x cheaper and its defects are what one RTI step absorbs
     if (h->cfg.model == IHM2MPC_MODEL_FDYN6U && !only_failed) LAUNCH_IG(IHM2MPC_MODEL_FDYN6U);
     else LAUNCH_IG(IHM2MPC_MODEL_FKIN6);

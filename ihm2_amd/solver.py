@@ -222,7 +222,9 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_init_guess(self._h, float(v_ref_scale)))
 
     def reinit_failed(self, v_ref_scale: float = 1.0):
-        """Re-roll the warm start of the instances whose last solve failed (status != 0) from their current ``x0``."""
+        """Re-roll the warm start of the instances whose last solve failed (status not 0 and not 2) from their current ``x0``: the
+        kinematic rollout (``fkin6`` whatever the OCP's model) with the actuator lags in closed form, and zero multipliers and slacks
+        (``pi``, ``lam``, ``slk`` and the a_lat row's pair).  The other instances keep everything."""
         _lib.check(self.lib.ihm2mpc_reinit_failed(self._h, float(v_ref_scale)))
 
     def prepare_step(self, s_target: float):

@@ -46,10 +46,10 @@ def lat_pacejka(alpha):
 
 
 def kappa_interp(s, s_ref, kappa_ref):
-    """casadi 'linear' interpolant, exact lookup, linear extrapolation; complex-safe in s."""
+    """casadi 'linear' interpolant, exact lookup, linear extrapolation; complex-safe in s, elementwise for an array s."""
     sr = np.real(s)
     n = len(s_ref)
-    i = int(np.clip(np.searchsorted(s_ref, sr, side="right") - 1, 0, n - 2))
+    i = np.clip(np.searchsorted(s_ref, sr, side="right") - 1, 0, n - 2)
     slope = (kappa_ref[i + 1] - kappa_ref[i]) / (s_ref[i + 1] - s_ref[i])
     return kappa_ref[i] + slope * (s - s_ref[i])
 
