@@ -2,6 +2,7 @@
 // copy-out getters, and the launch sequence of one RTI iteration on the handle's HIP stream.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "ihm2mpc_internal.h"
+#include "sqp_body.hpp"
 
 static thread_local std::string g_err;
 
@@ -207,6 +209,178 @@ void free_instance_bounds(ihm2mpc_handle *h)
     h->inst_b = false; h->inst_b_ok = false;
 }
 
+// ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
+// The catalogue is the three objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
+// (the leading one-sided entries per lane rebuild_slots laid it out for) and its NSLOT holds the table's slots per lane; of those
+// that fit the configuration, the first in catalogue order is launched.
+const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2()};
+
+// the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
+int path_class(const ihm2mpc_handle *h) { return h->alat_on ? 2 : h->path_on ? 1 : 0; }
+
+// the first entry of the catalogue with the fields of `want` and at least its NSLOT; nullptr: none
+const QpInst *find_inst(const QpKey &want)
+{
+    for (const QpTable &t : qp_catalogue)
+        for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
+            const QpKey &k = e->key;
+            if (k.kind == want.kind && k.nsoft == want.nsoft && k.path == want.path && k.uni == want.uni && k.sqp == want.sqp &&
+                k.irk == want.irk && k.dyn == want.dyn && k.nslot >= want.nslot)
+                return e;
+        }
+    return nullptr;
+}
+
+// The slot tables the per-step QP takes for the handle's rows: (NSOFT, the largest NSLOT that comes with it) per NSOFT of its
+// instantiations, in catalogue order.  NSOFT = 0: every side hard.
+std::vector<std::pair<int, int>> slot_limits(const ihm2mpc_handle *h)
+{
+    std::vector<std::pair<int, int>> v;
+    for (const QpTable &t : qp_catalogue)
+        for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
+            if (e->key.kind != QP_WAVE || e->key.path != path_class(h)) continue;
+            auto p = std::find_if(v.begin(), v.end(), [&](const std::pair<int, int> &q) { return q.first == e->key.nsoft; });
+            if (p == v.end()) v.push_back({e->key.nsoft, e->key.nslot});
+            else p->second = std::max(p->second, e->key.nslot);
+        }
+    return v;
+}
+
+size_t qp_lds_bytes(const ihm2mpc_handle *h)
+{
+    const size_t N = h->N, NS = h->NS;
+    const int nck = h->path_on ? (h->alat_on ? 15 : 14) : 12;
+    const int uni = h->uniform_H && h->uniform_CD;
+    return sizeof(double) * (NS * (10 + 10 + 8 + 8 + 2 * nck + 10 + (h->path_on ? (h->alat_on ? 6 : 2) : 0)) + N * (8 + 4 + 16 + 8 + 8) + 136 + (uni ? 20 + (h->path_on ? 0 : 200 + 90) : 0));
+}
+
+// The per-step QP for the handle's table; nullptr: none takes it (or not in the LDS)
+const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
+{
+    if (lds > 160 * 1024) return nullptr;
+    const int uni = h->uniform_H && h->uniform_CD;
+    // few instances (at most one per CU): four wavefronts per instance, slots from the 256-lane table
+    // (per-instance bounds: the 64-lane table alone carries them -- k_qp_wave's results are the four-wave kernel's bit for bit)
+    if (h->block_qp && !h->inst_b && h->nslot_lane_blk >= 1 && h->B <= h->n_cu && h->nslot_lane * 64 <= (h->N + 1) * 12)
+        if (const QpInst *e = find_inst({QP_BLOCK, h->nslot_lane_blk, h->nsoft_lane, path_class(h), uni, 0, 0, 0})) return e;
+    return find_inst({QP_WAVE, h->nslot_lane, h->nsoft_lane, path_class(h), uni, 0, 0, 0});
+}
+
+// The persistent loop for the handle's configuration; nullptr: none (ihm2mpc_run_steps then launches per step, which gives the same
+// results).  The catalogue has it for the kinematic and the dynamic OCP models, not for the lateral-acceleration row; with soft sides,
+// track rows, the collocation integrator or a dynamic model for batch-shared tables only (UNI = 1).
+const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds)
+{
+    const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP, irk = h->cfg.integrator_type != IHM2MPC_INTEG_ERK;
+    const bool dyn = h->cfg.model != IHM2MPC_MODEL_FKIN6;
+    if (irk && (!h->irk_tab || (sqp && h->sqp_globalization && !h->ls_phi))) return nullptr;
+    if (sqp && !h->ls_x) return nullptr;        // the caller allocates the line-search buffers first
+    if (lds > 160 * 1024) return nullptr;
+    // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
+    if (dyn && !irk && lds < (size_t)ihm2::s_count(1) * 64 * sizeof(double)) return nullptr;
+    return find_inst({QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn});
+}
+
+// the launch record (ihm2mpc_get_launch_record) from the key of what was launched; a k_steps key with `per_step` != 0: run_steps
+// launched per step instead (1 no instantiation, 2 the batch is not resident), the key's fields are 0
+void note_launch(ihm2mpc_handle *h, const QpKey &k, int per_step = 0)
+{
+    int32_t *r = h->launch_rec;
+    if (k.kind != QP_STEPS) {
+        r[0] = k.kind; r[1] = k.nslot; r[2] = k.nsoft; r[3] = k.path; r[4] = k.uni;
+    } else {
+        r[5] = per_step ? 2 : 1; r[6] = k.nslot; r[7] = k.nsoft; r[8] = k.path; r[9] = k.uni; r[10] = k.sqp; r[11] = k.irk; r[12] = k.dyn;
+        r[13] = per_step;
+    }
+}
+
+QpArgs qp_args(ihm2mpc_handle *h)
+{
+    QpArgs a;
+    a.B = h->B; a.N = h->N; a.iter_max = h->cfg.ipm_iter_max; a.nslots = h->nslot_lane * 64; a.m_act = h->m_act;
+    a.nslots_can = h->nslot_lane * 64;
+    a.tol = h->cfg.ipm_tol; a.mu0 = h->cfg.ipm_mu0; a.tau0 = h->cfg.ipm_tau0;
+    a.Hs = h->Hs; a.Gy = h->Gy; a.CD = h->CD; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.slot_kc = h->slot_kc;
+    a.hs_bs = 0; a.hs_te = h->N * 100; a.gy_bs = 0; a.gy_te = h->N * 120; a.sl_bs = 0;
+    if (h->inst_w) { a.Hs = h->iHs; a.Gy = h->iGy; a.hs_bs = 200; a.hs_te = 100; a.gy_bs = 240; a.gy_te = 120; }
+    if (h->inst_b) { a.sl_bs = h->nslot_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }
+    a.x = h->x; a.u = h->u; a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e;
+    a.pi = h->pi; a.lam = h->lam; a.res = h->res; a.qp_res = h->qp_res; a.u0 = h->u0; a.status = h->status; a.qp_iter = h->qp_iter;
+    a.lin = h->lin; a.g = h->q_g; a.rg = h->q_rg; a.P = h->q_P; a.M = h->q_M + (size_t)QM_PAD * 64;
+    a.slot_zw = h->slot_zw; a.slot_Zw = h->slot_Zw; a.slk = h->slk;
+    a.track_id = h->track_id; a.widths = h->widths; a.car_L = h->car_L; a.car_W = h->car_W;
+    a.lam_a = h->lam_a; a.slk_a = h->slk_a;
+    a.symmetrize = (h->cfg.model == IHM2MPC_MODEL_FDYN6) ? 1 : 0;
+    return a;
+}
+
+// one block of 64 x NW lanes per instance, `args` the kernel's arguments
+void launch_inst(ihm2mpc_handle *h, const QpInst *e, void **args, size_t lds)
+{
+    (void)hipFuncSetAttribute(e->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipLaunchKernel(e->kernel, dim3(h->B), dim3(e->threads), args, lds, h->stream);
+    note_launch(h, e->key);
+}
+
+// The per-step QP; non-zero: no instantiation takes the table (ready() has refused the tables without one), or not in the LDS
+int launch_qp(ihm2mpc_handle *h)
+{
+    const size_t lds = qp_lds_bytes(h);
+    const QpInst *e = select_qp(h, lds);
+    if (!e) return 1;
+    QpArgs a = qp_args(h);
+    if (e->key.kind == QP_BLOCK) { a.slot_kc = h->slot_kc_blk; a.slot_lb = h->slot_lb_blk; a.slot_ub = h->slot_ub_blk; a.nslots = h->nslot_lane_blk * 256; }
+    void *args[] = {&a};
+    launch_inst(h, e, args, lds);
+    return 0;
+}
+
+// n_steps control steps in one launch (k_steps), histories into h->hist_*.  Returns 0 launched, 1 the configuration has no persistent
+// instantiation (the caller then runs ihm2mpc_step n_steps times, which gives the same results).
+int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop)
+{
+    const size_t lds = qp_lds_bytes(h);
+    const QpInst *e = select_steps(h, lds);
+    if (!e) return 1;
+    const bool irk_plant = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
+    if (irk_plant && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;
+    const bool sqp = e->key.sqp;
+    QpArgs a = qp_args(h);
+    StepArgs s;
+    s.ocp_model = h->cfg.model;
+    s.n_steps = n_steps; s.model = model; s.M_sim = M_sim; s.M = h->cfg.M; s.nknots = h->cfg.nknots; s.lap_wrap = h->lap_wrap ? 1 : 0;
+    s.freeze = freeze; s.s_target = s_target; s.dt = h->cfg.dt; s.lap_stop = lap_stop;
+    s.sqp_iters = sqp ? (h->cfg.nlp_solver_max_iter > 0 ? h->cfg.nlp_solver_max_iter : 1) : 0;
+    s.s_ref = h->s_ref; s.kappa_ref = h->kappa_ref;
+    s.x0 = h->x0; s.yref = h->yref; s.yref_e = h->yref_e; s.lin = h->lin;
+    s.active = (freeze || h->active_set) ? h->active : nullptr;
+    s.hist_u0 = h->hist_u0; s.hist_x0 = h->hist_x0; s.hist_st = h->hist_st; s.hist_it = h->hist_it;
+    s.irk_tab = (const ihm2::IrkTab *)h->irk_tab;
+    s.sim_irk_tab = irk_plant ? (const ihm2::IrkTab *)h->sim_irk_tab : nullptr;
+    // every field of s is set: upload it (and the line search's block in the SQP mode)
+    static_assert(sizeof(StepArgs) <= 32 * sizeof(double), "step_args holds 256 bytes");
+    static_assert(sizeof(ihm2::LsArgs) <= 64 * sizeof(double), "ls_args holds 512 bytes");
+    // both blocks go through a pinned staging slot (two slots, used alternately) and are uploaded in stream order: the host does
+    // not wait for the previous launch (run_steps(wait = false) enqueues in pieces while the host does other work)
+    const int slot = (h->args_idx++) & 1;
+    if (hipEventSynchronize(h->args_ev[slot]) != hipSuccess) return 1;          // the upload that last used this slot has been issued long ago
+    char *stage = (char *)h->args_host[slot];
+    std::memcpy(stage, &s, sizeof(StepArgs));
+    if (hipMemcpyAsync(h->step_args, stage, sizeof(StepArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
+    if (sqp) {
+        ihm2::LsArgs ls_host = ihm2::make_ls_args(h);
+        if (e->key.irk) ls_host.phase = 3;        // the trial points' collocation rollouts are done in the loop, one step length at a time
+        std::memcpy(stage + 512, &ls_host, sizeof(ihm2::LsArgs));
+        if (hipMemcpyAsync(h->ls_args, stage + 512, sizeof(ihm2::LsArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
+    }
+    if (hipEventRecord(h->args_ev[slot], h->stream) != hipSuccess) return 1;
+    const StepArgs *sdev = (const StepArgs *)h->step_args;
+    const ihm2::LsArgs *ls = (const ihm2::LsArgs *)h->ls_args;
+    void *args[] = {&sdev, &a, &ls};
+    launch_inst(h, e, args, lds);
+    return 0;
+}
+
 int ready(ihm2mpc_handle *h)
 {
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
@@ -214,7 +388,16 @@ int ready(ihm2mpc_handle *h)
     if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called");
     if (h->inst_w && !h->uniform_CD) return fail("per-instance weights need stage-independent general rows C, D (the QP keeps one copy of them)");
     if (h->inst_b && !h->inst_b_ok) return fail("the per-instance bounds do not fit the batch-shared constraint pattern any more: set them again, or pass NULL");
-    if (!h->slots_fit) return fail("the constraint rows fit no QP kernel: at most 10 slots per lane of 64 (a two-sided hard row is one slot, a row with a soft side two), of which at most 4 soft; with soft sides the hard two-sided rows get 10 - 4 or 8 - 3 (8 - 2 without track rows) of them");
+    if (!h->slots_fit) {        // the limits of the catalogue's instantiations for these rows
+        std::string hard = "none", soft;
+        for (const auto &[S, NSL] : slot_limits(h))
+            if (S == 0) hard = std::to_string(NSL);
+            else soft += (soft.empty() ? "" : " or ") + std::to_string(NSL) + " of which " + std::to_string(S) + " soft";
+        static const char *rows[3] = {"without track rows", "with track rows", "with track rows and the lateral-acceleration row"};
+        return fail("the constraint rows fit no QP kernel: %s a lane of 64 takes at most %s slots when all sides are hard; with soft sides, %s "
+                    "(a two-sided hard row is one slot, a row with a soft side two; a lane's one-sided slots lead it)", rows[path_class(h)],
+                    hard.c_str(), soft.empty() ? "none" : soft.c_str());
+    }
     if (h->alat_on) {
         // the row belongs to the kinematic constraint set of old/generate_acaods_interface.py:198-209, which comes with the track rows and SQP_RTI (old/generate.py:21)
         if (h->cfg.model != IHM2MPC_MODEL_FKIN6) return fail("the lateral-acceleration row is a row of the kinematic model (old/generate_acaods_interface.py:206: `[] if is_dynamic else [a_lat]`)");
@@ -568,18 +751,13 @@ static int rebuild_slots(ihm2mpc_handle *h)
             soft_total += (int)r.sl + (int)r.su;
             m_act += (int)r.fl + (int)r.fu + (int)r.sl + (int)r.su;
         }
-    // (NSOFT, NSLOT) of the kernel instantiations that take this kind of table, in the launchers' order (kernels_qp.hip)
-    struct Cand { int S, NSL; };
-    std::vector<Cand> cands;
-    if (soft_total == 0) cands = {{0, 8}};
-    else if (h->alat_on) cands = {{4, 10}};
-    else if (h->path_on) cands = {{3, 8}, {4, 10}};
-    else cands = {{2, 8}, {4, 10}};
     std::vector<Slot> lanes[64];
-    int per_lane = 0, soft_lane = 0, total = 0, S_used = 0;
+    int per_lane = 0, total = 0, S_used = 0;
     bool placed = false;
-    for (const Cand &cd : cands) {
-        const int S = cd.S;
+    // the layouts of the per-step QP's instantiations for these rows, in catalogue order: NSOFT = 0 for an all-hard table, NSOFT > 0 with soft sides
+    for (const auto &lim : slot_limits(h)) {
+        const int S = lim.first, NSL = lim.second;
+        if ((S == 0) != (soft_total == 0)) continue;
         std::vector<Slot> ones[64], twos[64];       // one-sided slots (soft ones first), two-sided slots
         int nsoft[64] = {0};
         auto tail = [&](int l) { return (int)twos[l].size() + std::max(0, (int)ones[l].size() - S); };     // entries behind the first S
@@ -615,7 +793,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
             pl = std::max(pl, S + tail(l));
             sl_max = std::max(sl_max, nsoft[l]);
         }
-        if (soft_total > 0 && (sl_max > S || pl > cd.NSL)) continue;
+        if (sl_max > S || pl > NSL) continue;
         // lay the lanes out: S leading one-sided entries (padding where a lane has fewer), then the rest
         total = 0;
         for (int l = 0; l < 64; l++) {
@@ -630,12 +808,11 @@ static int rebuild_slots(ihm2mpc_handle *h)
         }
         per_lane = 0;
         for (int l = 0; l < 64; l++) per_lane = std::max(per_lane, (int)lanes[l].size());
-        soft_lane = sl_max; S_used = S; placed = true;
+        S_used = S; placed = true;
         break;
     }
-    h->slots_fit = placed && per_lane * 64 <= MAX_SLOTS && soft_lane <= 4;
+    h->slots_fit = placed && per_lane * 64 <= MAX_SLOTS;
     if (!h->slots_fit) return 0;        // ready() reports it: the setters come one by one and a later one may make the rows fit
-    if (soft_total > 0) soft_lane = S_used;      // what the launchers select the instantiation by: its NSOFT
     const size_t n = (size_t)per_lane * 64;
     std::vector<int32_t> kc(n, -1);
     std::vector<double> slb(n, -INFINITY), sub(n, INFINITY), zw(n, 0.0), Zw(n, -1.0);
@@ -645,10 +822,10 @@ static int rebuild_slots(ihm2mpc_handle *h)
             const size_t e = l + 64 * r;
             kc[e] = s.kc; slb[e] = s.lb; sub[e] = s.ub; zw[e] = s.zw; Zw[e] = s.Zw;
         }
-    h->nslots = total; h->m_act = m_act; h->nslot_lane = per_lane; h->nsoft_lane = soft_lane;
+    h->nslots = total; h->m_act = m_act; h->nslot_lane = per_lane; h->nsoft_lane = S_used;      // what the selection takes the instantiation by: its NSOFT
     // the same rows over 256 lanes for the four-wave latency kernel (all-hard tables: a row is one two-sided slot)
     h->nslot_lane_blk = 0;
-    if (soft_lane == 0 && total > 0 && total <= 1024) {
+    if (S_used == 0 && total > 0 && total <= 1024) {
         // entry e of this table IS entry e of the 64-lane table (thread t of the block holds the entries t, t + 256): the slot sums of the
         // four-wave body are taken in the order of the 64-lane table, which makes its results those of the one-wave body bit for bit
         const int per_blk = ((int)n + 255) / 256;
@@ -1004,7 +1181,7 @@ static int sqp_iterations(ihm2mpc_handle *h, int n_iter, bool join)
         ihm2_launch_linearize(h);
         if (it == 0 && join) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
         if (it == n_iter - 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        if (ihm2_launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
+        if (launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
         if (h->cfg.integrator_type != IHM2MPC_INTEG_ERK && h->sqp_globalization) {
             // collocation integrator: the rollouts of the line search's trial points (all step lengths of the ladder) in their own launch
             int n_alpha = 1;
@@ -1041,7 +1218,7 @@ int ihm2mpc_solve(ihm2mpc_handle *h, int32_t n_iter)
         for (int it = 0; it < n_iter; it++) {
             ihm2_launch_linearize(h);
             if (it == n_iter - 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-            if (ihm2_launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
+            if (launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
         }
     }
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1285,7 +1462,7 @@ int ihm2mpc_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_targe
         ihm2_launch_linearize(h);
         HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        if (ihm2_launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
+        if (launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
     }
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     HIP_TRY(hipGetLastError());
@@ -1341,14 +1518,12 @@ int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_
     if (resident) {
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        rc = ihm2_launch_steps(h, model, M_sim, s_target, n_steps, freeze ? 1 : 0, lap_stop, h->hist_u0, h->hist_x0, h->hist_st, h->hist_it);
+        rc = launch_steps(h, model, M_sim, s_target, n_steps, freeze ? 1 : 0, lap_stop);
         if (rc == 0) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     }
     if (rc != 0) {
         if (freeze) return fail("no persistent loop for this configuration (needs batch-shared weights and rows for soft tables or the collocation integrator, and a batch of at most %d): call ihm2mpc_step per control period", 4 * h->n_cu);
-        // the record of the fallback (a k_steps launch writes its own): the per-step QP launches below update [0..4]
-        for (int i = 6; i < 13; i++) h->launch_rec[i] = 0;
-        h->launch_rec[5] = 2; h->launch_rec[13] = resident ? 1 : 2;
+        note_launch(h, QpKey{QP_STEPS}, resident ? 1 : 2);      // the per-step QP launches below update [0..4]
         for (size_t i = 0; i < n; i++) {      // launches per step, histories by device-to-device copies in stream order
             if (ihm2mpc_step(h, model, M_sim, s_target)) return -1;
             HIP_TRY(hipMemcpyAsync(h->hist_u0 + i * B * 2, h->u0, B * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));

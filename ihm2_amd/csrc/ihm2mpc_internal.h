@@ -152,7 +152,7 @@ struct ihm2mpc_handle {
     double *hist_u0, *hist_x0;      // (steps,B,2), (steps,B,8)
     int32_t *hist_st, *hist_it;     // (steps,B)
 
-    // ---- what the launchers last launched (ihm2mpc_get_launch_record), written at the launch sites ----
+    // ---- what was last launched (ihm2mpc_get_launch_record), written from the catalogue's keys (api.hip: note_launch) ----
     int32_t launch_rec[16];
 };
 
@@ -176,12 +176,65 @@ void ihm2_launch_sim_irk(ihm2mpc_handle *h, int model, int M_sim, const double *
                          const int32_t *active);
 void ihm2_launch_copy_iterate(ihm2mpc_handle *h);   // x, u, pi, lam, slk -> ls_x, ls_u, ls_pi, ls_lam, ls_slk
 void ihm2_launch_line_search(ihm2mpc_handle *h, int it, int last, int phase = 0, int j_limit = 0);
-int ihm2_launch_qp(ihm2mpc_handle *h);
-// the persistent per-instance loop (kernels_qp.hip); returns 1 if the configuration has no instantiation of it
-int ihm2_launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop,
-                      double *hist_u0, double *hist_x0, int32_t *hist_st, int32_t *hist_it);   // returns non-zero if the problem does not fit the kernel's limits
 void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, hipStream_t stream,
                      const int32_t *active);
 void ihm2_launch_sim_cart(ihm2mpc_handle *h, int model, int M, double dt, int n_steps, double v_dyn, const double *x, const double *u,
                           double *xn, hipStream_t stream);
 void ihm2_launch_project(ihm2mpc_handle *h, double s_tol, const double *xc, double *s_guess, double *xf, hipStream_t stream);
+
+// --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
+// Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'
+// symbols name these types.)
+namespace ihm2 { struct IrkTab; }
+namespace {
+
+struct QpArgs {
+    int B, N, iter_max, nslots, m_act;
+    int nslots_can;     // entries of the 64-lane slot table: the order in which the slot sums (mu, mu_aff) are taken, whatever the number of waves per instance
+    double tol, mu0, tau0;
+    // shared
+    const double *Hs, *Gy, *CD, *slot_lb, *slot_ub, *slot_zw, *slot_Zw;
+    const int32_t *slot_kc;
+    // per-instance tuning (api.hip: ihm2mpc_set_instance_weights / _bounds): doubles of Hs / Gy / slot_lb, slot_ub per instance (0: batch-shared)
+    // and the offset of the terminal stage's Hs / Gy block (N * 100, N * 120 batch-shared; 100, 120 per instance: (B,2,100), (B,2,120))
+    int hs_bs, hs_te, gy_bs, gy_te, sl_bs;
+    // per instance
+    double *x, *u;
+    const double *x0, *yref, *yref_e;
+    double *pi, *lam, *res, *qp_res, *u0;
+    int32_t *status, *qp_iter;
+    const double *lin;
+    double *g, *rg, *P, *M, *slk;
+    // track rows
+    const int32_t *track_id;
+    const double *widths;
+    double car_L, car_W;
+    // lateral-acceleration row (PATH == 2): its multipliers and slack values, (B, N+1, 2) = lower, upper side -- beside the 28 columns of the other rows
+    double *lam_a, *slk_a;
+    int symmetrize;     // P_k := (P_k + P_k') / 2 in the factor sweep (riccati_mfma.hpp): needed by the open-loop unstable dynamic model as written (fdyn6)
+};
+
+struct StepArgs {
+    int n_steps, model, M_sim, M, nknots, lap_wrap, freeze;
+    int ocp_model;                          // the model of the shooting intervals (IHM2MPC_MODEL_FKIN6 / FDYN6 / FDYN6U); `model` is the plant's
+    int sqp_iters;                          // 0: one RTI iteration per step; > 0: SQP mode, that many iterations with the line search
+    double s_target, dt, lap_stop;
+    const double *s_ref, *kappa_ref;
+    double *x0, *yref, *yref_e, *lin;      // the same arrays as QpArgs', writable
+    int32_t *active;                        // (B) or nullptr = all active
+    double *hist_u0, *hist_x0;              // (n_steps,B,2), (n_steps,B,8) or nullptr
+    int32_t *hist_st, *hist_it;             // (n_steps,B) or nullptr
+    const ihm2::IrkTab *irk_tab;            // IRK = 1: the tableau of the shooting intervals' collocation step, in device memory
+    const ihm2::IrkTab *sim_irk_tab;        // plant steps by collocation (python/main.py:395-400: Radau IIA x M_sim) instead of RK4 x M_sim; nullptr: RK4
+};
+
+}  // namespace
+
+// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0, 1, 2) returns the table of the ones it
+// holds, in its order of preference (kernels_qp.hip: QP_INSTANCES).  A key holds the template parameters as the launch record gives them
+// (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.
+enum { QP_WAVE = 1, QP_BLOCK = 2, QP_STEPS = 3 };
+struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn; };
+struct QpInst { QpKey key; int threads; const void *kernel; };
+struct QpTable { const QpInst *inst; int n; };
+QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2();

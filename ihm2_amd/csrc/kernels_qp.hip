@@ -45,32 +45,6 @@ using namespace ihm2;
 
 namespace {
 
-struct QpArgs {
-    int B, N, iter_max, nslots, m_act;
-    int nslots_can;     // entries of the 64-lane slot table: the order in which the slot sums (mu, mu_aff) are taken, whatever the number of waves per instance
-    double tol, mu0, tau0;
-    // shared
-    const double *Hs, *Gy, *CD, *slot_lb, *slot_ub, *slot_zw, *slot_Zw;
-    const int32_t *slot_kc;
-    // per-instance tuning (api.hip: ihm2mpc_set_instance_weights / _bounds): doubles of Hs / Gy / slot_lb, slot_ub per instance (0: batch-shared)
-    // and the offset of the terminal stage's Hs / Gy block (N * 100, N * 120 batch-shared; 100, 120 per instance: (B,2,100), (B,2,120))
-    int hs_bs, hs_te, gy_bs, gy_te, sl_bs;
-    // per instance
-    double *x, *u;
-    const double *x0, *yref, *yref_e;
-    double *pi, *lam, *res, *qp_res, *u0;
-    int32_t *status, *qp_iter;
-    const double *lin;
-    double *g, *rg, *P, *M, *slk;
-    // track rows
-    const int32_t *track_id;
-    const double *widths;
-    double car_L, car_W;
-    // lateral-acceleration row (PATH == 2): its multipliers and slack values, (B, N+1, 2) = lower, upper side -- beside the 28 columns of the other rows
-    double *lam_a, *slk_a;
-    int symmetrize;     // P_k := (P_k + P_k') / 2 in the factor sweep (riccati_mfma.hpp): needed by the open-loop unstable dynamic model as written (fdyn6)
-};
-
 #define INF_BOUND 1e20
 // Depths of the prefetch rings: records of the factor sweep (stages ahead), rows of the vector / forward sweeps (a pass of those sweeps is
 // 2 SWEEP_RING stages of straight-line code).  The kernel's loop is as large as the instruction cache two CUs share (k_qp_wave<5,0,0,1>:
@@ -1160,7 +1134,6 @@ __global__ __launch_bounds__(64) void k_qp_wave(QpArgs a)
 
 // The latency kernel: NW wavefronts per instance (qp_wave_body with NW > 1), for batches that leave most of the chip idle -- the
 // reference's own use is ONE car at 20 Hz.  Each wave sits on its own SIMD of the CU and keeps the full register budget.
-#if QP_SET == 0
 template <int NSLOT, int UNI, int NW>
 __global__ __launch_bounds__(64 * NW) void k_qp_block(QpArgs a)
 {
@@ -1168,7 +1141,6 @@ __global__ __launch_bounds__(64 * NW) void k_qp_block(QpArgs a)
     if ((int)blockIdx.x >= a.B) return;          // block-uniform
     qp_wave_body<NSLOT, 0, 0, UNI, NW>(a, blockIdx.x, sm);
 }
-#endif
 
 // ---- persistent per-instance loop: n_steps control steps of the MiL loop (python/main.py:476-517) in ONE launch ----
 // A wavefront owns an instance and runs, step after step,  [lap wrap] -> plant (lane 0) -> reference ramp + warm-start shift
@@ -1235,20 +1207,6 @@ __device__ __noinline__ void call_line_search(const LsArgs &ls, int b, int it, i
 {
     line_search_body<MODEL, ROLL>(ls, b, it, last);
 }
-
-struct StepArgs {
-    int n_steps, model, M_sim, M, nknots, lap_wrap, freeze;
-    int ocp_model;                          // the model of the shooting intervals (IHM2MPC_MODEL_FKIN6 / FDYN6 / FDYN6U); `model` is the plant's
-    int sqp_iters;                          // 0: one RTI iteration per step; > 0: SQP mode, that many iterations with the line search
-    double s_target, dt, lap_stop;
-    const double *s_ref, *kappa_ref;
-    double *x0, *yref, *yref_e, *lin;      // the same arrays as QpArgs', writable
-    int32_t *active;                        // (B) or nullptr = all active
-    double *hist_u0, *hist_x0;              // (n_steps,B,2), (n_steps,B,8) or nullptr
-    int32_t *hist_st, *hist_it;             // (n_steps,B) or nullptr
-    const IrkTab *irk_tab;                  // IRK = 1: the tableau of the shooting intervals' collocation step, in device memory
-    const IrkTab *sim_irk_tab;              // plant steps by collocation (python/main.py:395-400: Radau IIA x M_sim) instead of RK4 x M_sim; nullptr: RK4
-};
 
 // SQP = 0: one RTI iteration per step (the SQP code is compiled out: next to the QP body it changed the register allocation of
 // the whole kernel and tripled the step time); SQP = 1: sqp_iters iterations with the KKT test and the line search.
@@ -1394,253 +1352,41 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 #ifndef QP_SET
 #error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations) or -DQP_SET=2 (dynamic OCP models in the persistent loop)"
 #endif
-static size_t qp_lds_bytes(const ihm2mpc_handle *h)
-{
-    const size_t N = h->N, NS = h->NS;
-    const int nck = h->path_on ? (h->alat_on ? 15 : 14) : 12;
-    const int uni = h->uniform_H && h->uniform_CD;
-    return sizeof(double) * (NS * (10 + 10 + 8 + 8 + 2 * nck + 10 + (h->path_on ? (h->alat_on ? 6 : 2) : 0)) + N * (8 + 4 + 16 + 8 + 8) + 136 + (uni ? 20 + (h->path_on ? 0 : 200 + 90) : 0));
-}
-
-static QpArgs qp_args(ihm2mpc_handle *h)
-{
-    QpArgs a;
-    a.B = h->B; a.N = h->N; a.iter_max = h->cfg.ipm_iter_max; a.nslots = h->nslot_lane * 64; a.m_act = h->m_act;
-    a.nslots_can = h->nslot_lane * 64;
-    a.tol = h->cfg.ipm_tol; a.mu0 = h->cfg.ipm_mu0; a.tau0 = h->cfg.ipm_tau0;
-    a.Hs = h->Hs; a.Gy = h->Gy; a.CD = h->CD; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.slot_kc = h->slot_kc;
-    a.hs_bs = 0; a.hs_te = h->N * 100; a.gy_bs = 0; a.gy_te = h->N * 120; a.sl_bs = 0;
-    if (h->inst_w) { a.Hs = h->iHs; a.Gy = h->iGy; a.hs_bs = 200; a.hs_te = 100; a.gy_bs = 240; a.gy_te = 120; }
-    if (h->inst_b) { a.sl_bs = h->nslot_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }
-    a.x = h->x; a.u = h->u; a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e;
-    a.pi = h->pi; a.lam = h->lam; a.res = h->res; a.qp_res = h->qp_res; a.u0 = h->u0; a.status = h->status; a.qp_iter = h->qp_iter;
-    a.lin = h->lin; a.g = h->q_g; a.rg = h->q_rg; a.P = h->q_P; a.M = h->q_M + (size_t)QM_PAD * 64;
-    a.slot_zw = h->slot_zw; a.slot_Zw = h->slot_Zw; a.slk = h->slk;
-    a.track_id = h->track_id; a.widths = h->widths; a.car_L = h->car_L; a.car_W = h->car_W;
-    a.lam_a = h->lam_a; a.slk_a = h->slk_a;
-    a.symmetrize = (h->cfg.model == IHM2MPC_MODEL_FDYN6) ? 1 : 0;
-    return a;
-}
-
-// ihm2mpc_get_launch_record: the launch sites below note what they launch (host-side stores, include/ihm2mpc.h)
-static inline void record_qp(ihm2mpc_handle *h, int kind, int ns, int no, int pt, int un)
-{
-    int32_t *r = h->launch_rec;
-    r[0] = kind; r[1] = ns; r[2] = no; r[3] = pt; r[4] = un;
-}
-
-static inline void record_steps(ihm2mpc_handle *h, int ns, int no, int pt, int un, int sq, int ir, int dy)
-{
-    int32_t *r = h->launch_rec;
-    r[5] = 1; r[6] = ns; r[7] = no; r[8] = pt; r[9] = un; r[10] = sq; r[11] = ir; r[12] = dy; r[13] = 0;
-}
-
-// n_steps control steps in one launch (k_steps).  Returns 0 launched, 1 the configuration has no persistent instantiation
-// (the caller then runs ihm2mpc_step n_steps times, which gives the same results).  The all-hard tables are launched from the
-// QP_SET = 0 object, the soft / track-row tables from the QP_SET = 1 object.
+// The instantiations of this object: its part of the catalogue api.hip selects from, which takes the first entry that holds a table,
+// so that an NSLOT comes before the larger ones of the same kind.  WAVE(NSLOT, NSOFT, PATH, UNI) k_qp_wave, BLOCK(NSLOT, UNI, NW)
+// k_qp_block, STEPS(NSLOT, NSOFT, PATH, UNI, IRK, DYN) k_steps in both SQP modes.
 #if QP_SET == 0
-int ihm2_launch_steps_soft(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop,
-                           double *hist_u0, double *hist_x0, int32_t *hist_st, int32_t *hist_it);
-int ihm2_launch_steps_dyn(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop,
-                          double *hist_u0, double *hist_x0, int32_t *hist_st, int32_t *hist_it);
-int ihm2_launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop,
-                      double *hist_u0, double *hist_x0, int32_t *hist_st, int32_t *hist_it)
+#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
+    BLOCK(2, 0, 4) BLOCK(2, 1, 4)                                                                                                         \
+    WAVE(5, 0, 0, 0) WAVE(5, 0, 0, 1) WAVE(8, 0, 0, 0) WAVE(8, 0, 0, 1) WAVE(10, 0, 0, 0) WAVE(10, 0, 0, 1)                               \
+    STEPS(5, 0, 0, 0, 0, 0) STEPS(5, 0, 0, 1, 0, 0) STEPS(5, 0, 0, 1, 1, 0)                                                               \
+    STEPS(8, 0, 0, 0, 0, 0) STEPS(8, 0, 0, 1, 0, 0) STEPS(8, 0, 0, 1, 1, 0)                                                               \
+    STEPS(10, 0, 0, 1, 0, 0) STEPS(10, 0, 0, 1, 1, 0)
 #elif QP_SET == 1
-int ihm2_launch_steps_soft(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop,
-                           double *hist_u0, double *hist_x0, int32_t *hist_st, int32_t *hist_it)
-#else
-int ihm2_launch_steps_dyn(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop,
-                          double *hist_u0, double *hist_x0, int32_t *hist_st, int32_t *hist_it)
+#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
+    WAVE(8, 2, 0, 0) WAVE(8, 2, 0, 1) WAVE(10, 4, 0, 0) WAVE(10, 4, 0, 1)                                                                 \
+    WAVE(8, 0, 1, 0) WAVE(8, 0, 1, 1) WAVE(8, 3, 1, 0) WAVE(8, 3, 1, 1) WAVE(10, 4, 1, 0) WAVE(10, 4, 1, 1)                               \
+    WAVE(8, 0, 2, 1) WAVE(10, 4, 2, 1)                                                                                                    \
+    STEPS(8, 2, 0, 1, 0, 0) STEPS(8, 2, 0, 1, 1, 0) STEPS(10, 4, 0, 1, 0, 0) STEPS(10, 4, 0, 1, 1, 0)                                     \
+    STEPS(8, 0, 1, 1, 0, 0) STEPS(8, 0, 1, 1, 1, 0) STEPS(8, 3, 1, 1, 0, 0) STEPS(8, 3, 1, 1, 1, 0)                                       \
+    STEPS(10, 4, 1, 1, 0, 0) STEPS(10, 4, 1, 1, 1, 0)
+#elif QP_SET == 2
+#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
+    STEPS(5, 0, 0, 1, 0, 1) STEPS(5, 0, 0, 1, 1, 1) STEPS(8, 0, 0, 1, 0, 1) STEPS(8, 0, 0, 1, 1, 1)                                       \
+    STEPS(8, 2, 0, 1, 0, 1) STEPS(8, 2, 0, 1, 1, 1) STEPS(10, 4, 0, 1, 0, 1) STEPS(10, 4, 0, 1, 1, 1)                                     \
+    STEPS(8, 0, 1, 1, 0, 1) STEPS(8, 0, 1, 1, 1, 1) STEPS(8, 3, 1, 1, 0, 1) STEPS(8, 3, 1, 1, 1, 1)                                       \
+    STEPS(10, 4, 1, 1, 0, 1) STEPS(10, 4, 1, 1, 1, 1)
 #endif
-{
-    if (h->alat_on) return 1;       // the lateral-acceleration row has no instantiation of the persistent loop: launches per step (same results)
-    const bool dyn = h->cfg.model != IHM2MPC_MODEL_FKIN6;
-#if QP_SET == 0
-    if (dyn) return ihm2_launch_steps_dyn(h, model, M_sim, s_target, n_steps, freeze, lap_stop, hist_u0, hist_x0, hist_st, hist_it);
-#elif QP_SET == 1
-    if (dyn) return 1;
-#else
-    if (!dyn || !(h->uniform_H && h->uniform_CD)) return 1;     // the dynamic models come with batch-shared tables only (the reference's OCP has them)
-#endif
-    const bool irk_plant = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
-    if (irk_plant && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;
-    const bool irk = h->cfg.integrator_type != IHM2MPC_INTEG_ERK;       // collocation step on the shooting intervals: batch-shared tables only
-    if (irk && !(h->irk_tab && h->uniform_H && h->uniform_CD && (h->cfg.nlp_solver_type != IHM2MPC_SQP || !h->sqp_globalization || h->ls_phi))) return 1;
-    const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP;
-    if (sqp && !h->ls_x) return 1;        // the caller allocates the line-search buffers first
-    const bool hard = !h->path_on && h->nsoft_lane == 0 && h->nslot_lane <= 10;
-#if QP_SET == 0
-    if (!hard) return ihm2_launch_steps_soft(h, model, M_sim, s_target, n_steps, freeze, lap_stop, hist_u0, hist_x0, hist_st, hist_it);
-#elif QP_SET == 1
-    if (hard) return 1;
-#endif
-    const size_t lds = qp_lds_bytes(h);
-    if (lds > 160 * 1024) return 1;
-    // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
-    if (h->cfg.model != IHM2MPC_MODEL_FKIN6 && !irk && lds < (size_t)s_count(1) * 64 * sizeof(double)) return 1;
-    QpArgs a = qp_args(h);
-    StepArgs s;
-    s.ocp_model = h->cfg.model;
-    s.n_steps = n_steps; s.model = model; s.M_sim = M_sim; s.M = h->cfg.M; s.nknots = h->cfg.nknots; s.lap_wrap = h->lap_wrap ? 1 : 0;
-    s.freeze = freeze; s.s_target = s_target; s.dt = h->cfg.dt; s.lap_stop = lap_stop;
-    s.sqp_iters = sqp ? (h->cfg.nlp_solver_max_iter > 0 ? h->cfg.nlp_solver_max_iter : 1) : 0;
-    s.s_ref = h->s_ref; s.kappa_ref = h->kappa_ref;
-    s.x0 = h->x0; s.yref = h->yref; s.yref_e = h->yref_e; s.lin = h->lin;
-    s.active = (freeze || h->active_set) ? h->active : nullptr;
-    s.hist_u0 = hist_u0; s.hist_x0 = hist_x0; s.hist_st = hist_st; s.hist_it = hist_it;
-    s.irk_tab = (const IrkTab *)h->irk_tab;
-    s.sim_irk_tab = irk_plant ? (const IrkTab *)h->sim_irk_tab : nullptr;
-    // every field of s is set: upload it (and the line search's block in the SQP mode)
-    static_assert(sizeof(StepArgs) <= 32 * sizeof(double), "step_args holds 256 bytes");
-    static_assert(sizeof(LsArgs) <= 64 * sizeof(double), "ls_args holds 512 bytes");
-    // both blocks go through a pinned staging slot (two slots, used alternately) and are uploaded in stream order: the host does
-    // not wait for the previous launch (run_steps(wait = false) enqueues in pieces while the host does other work)
-    const int slot = (h->args_idx++) & 1;
-    if (hipEventSynchronize(h->args_ev[slot]) != hipSuccess) return 1;          // the upload that last used this slot has been issued long ago
-    char *stage = (char *)h->args_host[slot];
-    std::memcpy(stage, &s, sizeof(StepArgs));
-    if (hipMemcpyAsync(h->step_args, stage, sizeof(StepArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
-    if (sqp) {
-        LsArgs ls_host = make_ls_args(h);
-        if (irk) ls_host.phase = 3;        // the trial points' collocation rollouts are done in the loop, one step length at a time
-        std::memcpy(stage + 512, &ls_host, sizeof(LsArgs));
-        if (hipMemcpyAsync(h->ls_args, stage + 512, sizeof(LsArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
-    }
-    if (hipEventRecord(h->args_ev[slot], h->stream) != hipSuccess) return 1;
-    const StepArgs *sdev = (const StepArgs *)h->step_args;
-    const LsArgs *ls = (const LsArgs *)h->ls_args;
-    const int uni = h->uniform_H && h->uniform_CD;
-    // one instantiation: slots per lane, soft slots per lane, track rows, batch-shared tables, SQP mode, collocation, dynamic model
-#define LAUNCH_K(NS_, NO_, PT_, UN_, SQ_, IR_, DY_)                                                                                        \
-    do {                                                                                                                                    \
-        (void)hipFuncSetAttribute((const void *)k_steps<NS_, NO_, PT_, UN_, SQ_, IR_, DY_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_steps<NS_, NO_, PT_, UN_, SQ_, IR_, DY_>), dim3(h->B), dim3(64), lds, h->stream, sdev, a, ls);                \
-        record_steps(h, NS_, NO_, PT_, UN_, SQ_, IR_, DY_);                                                                                \
-    } while (0)
-    // SQP mode and integrator at run time
-#if QP_SET == 2
-#define LAUNCH_STEPS(NS_, NO_, PT_, UN_)                                                                                                   \
-    do {                                                                                                                                    \
-        if (irk) { if (sqp) LAUNCH_K(NS_, NO_, PT_, 1, 1, 1, 1); else LAUNCH_K(NS_, NO_, PT_, 1, 0, 1, 1); }                                \
-        else { if (sqp) LAUNCH_K(NS_, NO_, PT_, 1, 1, 0, 1); else LAUNCH_K(NS_, NO_, PT_, 1, 0, 0, 1); }                                    \
-    } while (0)
-#else
-#define LAUNCH_STEPS(NS_, NO_, PT_, UN_)                                                                                                   \
-    do {                                                                                                                                    \
-        if (irk) { if (sqp) LAUNCH_K(NS_, NO_, PT_, 1, 1, 1, 0); else LAUNCH_K(NS_, NO_, PT_, 1, 0, 1, 0); }                                \
-        else { if (sqp) LAUNCH_K(NS_, NO_, PT_, UN_, 1, 0, 0); else LAUNCH_K(NS_, NO_, PT_, UN_, 0, 0, 0); }                                \
-    } while (0)
-#endif
-#if QP_SET != 1
-    if (hard) {
-        if (h->nslot_lane <= 5) { if (uni) LAUNCH_STEPS(5, 0, 0, 1); else LAUNCH_STEPS(5, 0, 0, 0); }
-        else if (h->nslot_lane <= 8) { if (uni) LAUNCH_STEPS(8, 0, 0, 1); else LAUNCH_STEPS(8, 0, 0, 0); }
-        else {      // long horizons (N <= 79 at 8 rows per stage): kinematic model, batch-shared tables
-#if QP_SET == 0
-            if (!uni) return 1;
-            LAUNCH_STEPS(10, 0, 0, 1);
-#else
-            return 1;
-#endif
-        }
-    }
-#endif
-#if QP_SET != 0
-    // the soft / track-row tables: batch-shared Hessians and rows only (the reference's OCP has them)
-    if (!hard) {
-        if (!uni) return 1;
-        const int per_lane = h->nslot_lane, nsoft = h->nsoft_lane;
-        if (!h->path_on) {
-            if (nsoft <= 2 && per_lane <= 8) LAUNCH_STEPS(8, 2, 0, 1);
-            else if (nsoft <= 4 && per_lane <= 10) LAUNCH_STEPS(10, 4, 0, 1);
-            else return 1;
-        } else {
-            // (the NSOFT of an instantiation = the leading ONE-SIDED entries of a lane, api.hip::rebuild_slots: an all-hard table takes NSOFT = 0)
-            if (nsoft == 0) { if (per_lane <= 8) LAUNCH_STEPS(8, 0, 1, 1); else return 1; }
-            else if (nsoft <= 3 && per_lane <= 8) LAUNCH_STEPS(8, 3, 1, 1);
-            else if (nsoft <= 4 && per_lane <= 10) LAUNCH_STEPS(10, 4, 1, 1);
-            else return 1;
-        }
-    }
-#endif
-#undef LAUNCH_STEPS
-#undef LAUNCH_K
-    return 0;
-}
 
-#if QP_SET != 2
-#if QP_SET == 0
-int ihm2_launch_qp_hard(ihm2mpc_handle *h)
-#else
-int ihm2_launch_qp_hard(ihm2mpc_handle *h);
-int ihm2_launch_qp(ihm2mpc_handle *h)
-#endif
+#define WAVE(NS, NO, PT, UN) {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0}, 64, (const void *)k_qp_wave<NS, NO, PT, UN>},
+#define BLOCK(NS, UN, NW) {{QP_BLOCK, NS, 0, 0, UN, 0, 0, 0}, 64 * NW, (const void *)k_qp_block<NS, UN, NW>},
+#define STEPS(NS, NO, PT, UN, IR, DY)                                                                  \
+    {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>}, \
+    {{QP_STEPS, NS, NO, PT, UN, 1, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 1, IR, DY>},
+#define QP_TABLE_(n) ihm2_qp_set##n
+#define QP_TABLE(n) QP_TABLE_(n)
+QpTable QP_TABLE(QP_SET)()      // (a host function's table stays out of the device code image)
 {
-#if QP_SET == 1
-    if (!h->path_on && h->nsoft_lane == 0 && h->nslot_lane <= 10) return ihm2_launch_qp_hard(h);
-#endif
-    QpArgs a = qp_args(h);
-    const int uni = h->uniform_H && h->uniform_CD;
-    const size_t lds = qp_lds_bytes(h);
-    if (lds > 160 * 1024) return 1;
-    const int per_lane = h->nslot_lane, nsoft = h->nsoft_lane;
-#define LAUNCH_QP(NS_, NO_, PT_)                                                                                          \
-    do {                                                                                                                  \
-        if (uni) {                                                                                                        \
-            (void)hipFuncSetAttribute((const void *)k_qp_wave<NS_, NO_, PT_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_qp_wave<NS_, NO_, PT_, 1>), dim3(h->B), dim3(64), lds, h->stream, a);                   \
-            record_qp(h, 1, NS_, NO_, PT_, 1);                                                                            \
-        } else {                                                                                                          \
-            (void)hipFuncSetAttribute((const void *)k_qp_wave<NS_, NO_, PT_, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_qp_wave<NS_, NO_, PT_, 0>), dim3(h->B), dim3(64), lds, h->stream, a);                   \
-            record_qp(h, 1, NS_, NO_, PT_, 0);                                                                            \
-        }                                                                                                                 \
-    } while (0)
-#if QP_SET == 0
-    // few instances (at most one per CU): four wavefronts per instance, slots from the 256-lane table
-    // (per-instance bounds: the 64-lane table alone carries them -- k_qp_wave's results are the four-wave kernel's bit for bit)
-    if (h->block_qp && !h->inst_b && nsoft == 0 && !h->path_on && h->nslot_lane_blk >= 1 && h->nslot_lane_blk <= 2 && h->B <= h->n_cu && h->nslot_lane * 64 <= (h->N + 1) * 12) {
-        a.slot_kc = h->slot_kc_blk; a.slot_lb = h->slot_lb_blk; a.slot_ub = h->slot_ub_blk; a.nslots = h->nslot_lane_blk * 256;
-        if (uni) {
-            (void)hipFuncSetAttribute((const void *)k_qp_block<2, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((k_qp_block<2, 1, 4>), dim3(h->B), dim3(256), lds, h->stream, a);
-            record_qp(h, 2, 2, 0, 0, 1);
-        } else {
-            (void)hipFuncSetAttribute((const void *)k_qp_block<2, 0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((k_qp_block<2, 0, 4>), dim3(h->B), dim3(256), lds, h->stream, a);
-            record_qp(h, 2, 2, 0, 0, 0);
-        }
-        return 0;
-    }
-    if (nsoft == 0 && per_lane <= 5) LAUNCH_QP(5, 0, 0);
-    else if (nsoft == 0 && per_lane <= 8) LAUNCH_QP(8, 0, 0);
-    else if (nsoft == 0 && per_lane <= 10) LAUNCH_QP(10, 0, 0);
-    else return 2;
-#else
-    if (h->alat_on) {
-        // track rows + the lateral-acceleration row (ready() has checked: kinematic model, track rows on, batch-shared tables)
-        if (!uni || !h->path_on || nsoft > 4 || per_lane > 10 || (nsoft == 0 && per_lane > 8)) return 2;
-        if (nsoft == 0) {       // all sides hard
-            (void)hipFuncSetAttribute((const void *)k_qp_wave<8, 0, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((k_qp_wave<8, 0, 2, 1>), dim3(h->B), dim3(64), lds, h->stream, a);
-            record_qp(h, 1, 8, 0, 2, 1);
-        } else {
-            (void)hipFuncSetAttribute((const void *)k_qp_wave<10, 4, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((k_qp_wave<10, 4, 2, 1>), dim3(h->B), dim3(64), lds, h->stream, a);
-            record_qp(h, 1, 10, 4, 2, 1);
-        }
-    } else if (!h->path_on) {
-        if (nsoft <= 2 && per_lane <= 8) LAUNCH_QP(8, 2, 0);
-        else if (nsoft <= 4 && per_lane <= 10) LAUNCH_QP(10, 4, 0);
-        else return 2;
-    } else {
-        if (nsoft == 0) { if (per_lane <= 8) LAUNCH_QP(8, 0, 1); else return 2; }
-        else if (nsoft <= 3 && per_lane <= 8) LAUNCH_QP(8, 3, 1);
-        else if (nsoft <= 4 && per_lane <= 10) LAUNCH_QP(10, 4, 1);
-        else return 2;
-    }
-#endif
-#undef LAUNCH_QP
-    return 0;
+    static const QpInst inst[] = {QP_INSTANCES(WAVE, BLOCK, STEPS)};
+    return {inst, (int)(sizeof(inst) / sizeof(inst[0]))};
 }
-#endif

@@ -1,8 +1,8 @@
 """Every instantiation of the QP kernels on constraint layouts built for them (tests/layouts.py), in both scheduler builds.
 
 Which instantiation runs is decided by the slot table api.hip::rebuild_slots packs from the rows (slots per lane, leading one-sided
-entries per lane) and by the launchers' thresholds (kernels_qp.hip).  Each layout below is named for the table it is meant to give;
-the launch record (BatchedOcpSolver.get_launch_record, written by the launch sites) says what actually ran, and the last test checks
+entries per lane) and by the catalogue of instantiations it is selected from (kernels_qp.hip: QP_INSTANCES).  Each layout below is
+named for the table it is meant to give; the launch record (BatchedOcpSolver.get_launch_record) says what actually ran, and the last test checks
 that the module as a whole launched exactly the list of instantiations written there.
 
 Per solvable layout, over 3 RTI iterations from sample_x0:
@@ -70,6 +70,9 @@ TABLE = {
 REFUSED = {
     "hard_11_per_lane": Lay("hard_11_per_lane", N=54, xbox="all"),                                   # 648 slots
     "soft_5_per_lane": Lay("soft_5_per_lane", N=40, soft=1.0, soft_rows=(1, 3, 6, 7), soft_kind="both", seed=16),      # 320 soft sides: 5 per lane
+    # all-hard tables with track rows: <8,0,1> and <8,0,2> take at most 8 slots per lane
+    "path_hard_9_per_lane": Lay("path_hard_9_per_lane", N=40, path=True, xbox="all"),                 # 560 slots
+    "alat_hard_10_per_lane": Lay("alat_hard_10_per_lane", N=40, path=True, alat=True, alat_max=10.0, xbox="all"),    # 599 slots
 }
 
 EXPECTED_QP = {
@@ -333,7 +336,7 @@ def test_layout_past_a_limit_is_refused_and_the_handle_recovers(track, name, bui
     assert s.get_launch_record() == before            # nothing was launched
     assert np.all(np.isfinite(s.get_x())) and np.all(np.isfinite(s.get_u()))
     # a fitting layout on the same handle: solves, and gives what a fresh handle gives
-    fit = L.Layout("fit", N=lay.N, seed=lay.seed)
+    fit = L.Layout("fit", N=lay.N, seed=lay.seed, path=lay.path, alat=lay.alat, alat_max=lay.alat_max)       # the handle keeps its track rows
     L.apply(s.data, fit)
     s._push_bounds()
     fresh = _solver(track, fit, B, build, "0")
