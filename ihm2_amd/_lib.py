@@ -112,6 +112,9 @@ SYMBOLS = {
     "ihm2mpc_get_cart_state": (C.c_int, [_H, c_double_p, c_double_p]),
     "ihm2mpc_sim_advance_cart": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double]),
     "ihm2mpc_get_x0": (C.c_int, [_H, c_double_p]),
+    "ihm2mpc_set_x0_sensitivities": (C.c_int, [_H, C.c_int32]),
+    "ihm2mpc_get_x0_sensitivities": (C.c_int, [_H, c_double_p, c_double_p]),
+    "ihm2mpc_get_sens_u0_device": (C.c_int, [_H, C.c_void_p]),
 }
 
 _lib = None

@@ -214,6 +214,7 @@ class IHM2Controller(Controller):
         track_rows_penalty: tuple | None = (100.0, 100.0),
         lateral_acceleration_row: bool = False,
         recover_failed: bool = False,
+        x0_sensitivities: bool = False,
     ) -> None:
         self.recover_failed = recover_failed
         self.Nf, self.dt, self.s_target, self.B = Nf, dt, s_target, int(batch_size)
@@ -259,6 +260,10 @@ class IHM2Controller(Controller):
         self.solver.set_x(x_pred)
         self.solver.set_u(u_pred)
         self.last_status = np.zeros(self.B, dtype=np.int32)
+        # x0_sensitivities: every compute_control also forms K0 = du_0/dx_0 (feedback_gain), for u0 + K0 (x - x0) between two solves
+        self.x0_sensitivities = bool(x0_sensitivities)
+        if self.x0_sensitivities:
+            self.solver.set_x0_sensitivities(1)
 
     @classmethod
     def with_live_options(cls, s_ref, kappa_ref, *args, **kw) -> "IHM2Controller":
@@ -296,6 +301,15 @@ class IHM2Controller(Controller):
             return None if bad[0] else u0[0]
         u0[bad] = np.nan
         return u0
+
+    @property
+    def feedback_gain(self) -> np.ndarray:
+        """``K0 = du_0/dx_0`` of the last ``compute_control``: ``(2, 8)`` for a batch of one, else ``(B, 2, 8)`` (NaN rows where
+        the solve failed).  Needs ``x0_sensitivities=True``."""
+        if not self.x0_sensitivities:
+            raise RuntimeError("feedback_gain needs IHM2Controller(..., x0_sensitivities=True)")
+        _, K = self.solver.get_x0_sensitivities()
+        return K[0] if self.B == 1 else K
 
     def warm_start(self, x0: np.ndarray, v_ref_scale: float = 1.0) -> None:
         """Replace the cold-start prediction (a car at rest at s = -6, ``python/main.py:242-246``) by a rollout of the

@@ -381,6 +381,34 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
     return 0;
 }
 
+// x0 sensitivities (kernels_sens.hip): the point the last QP is linearised at, copied after the linearisation ...
+int sens_snapshot(ihm2mpc_handle *h)
+{
+    if (!h->sens_mode || h->sens_quiet) return 0;
+    HIP_TRY(hipMemcpyAsync(h->sens_xbar, h->x, (size_t)h->B * h->NS * NX * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->sens_ubar, h->u, (size_t)h->B * h->N * NU * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+// ... and the kernel after that QP
+void sens_after_qp(ihm2mpc_handle *h)
+{
+    if (!h->sens_mode || h->sens_quiet) return;
+    ihm2_launch_sens(h);
+    h->sens_state = 1;
+}
+
+// readable sensitivities: the mode is on and the last solve / step computed them
+int sens_readable(const ihm2mpc_handle *h)
+{
+    if (!h->sens_mode) return fail("x0 sensitivities are off: ihm2mpc_set_x0_sensitivities(h, 1 or 2) before the solve");
+    if (h->sens_state == 2)
+        return fail("the last step came from ihm2mpc_run_steps, which computes no x0 sensitivities (the persistent loop is left as it is): "
+                    "call ihm2mpc_solve, ihm2mpc_compute_control or ihm2mpc_step");
+    if (h->sens_state != 1) return fail("no solve has run since x0 sensitivities were set to mode %d: nothing to read yet", h->sens_mode);
+    return 0;
+}
+
 int ready(ihm2mpc_handle *h)
 {
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
@@ -520,7 +548,7 @@ int ihm2mpc_free(ihm2mpc_handle *h)
                     h->slot_kc, h->slot_lb, h->slot_ub, h->slot_zw, h->slot_Zw, h->slk, h->lam_a, h->slk_a, h->widths, h->X_ref, h->Y_ref, h->phi_ref, h->xc, h->s_guess, h->x, h->u, h->x0, h->yref, h->yref_e, h->pi, h->lam, h->res, h->qp_res, h->dyn10, h->ls_phi, h->slot_kc_blk, h->slot_lb_blk, h->slot_ub_blk,
                     h->status, h->qp_iter, h->active, h->u0, h->lin, h->q_g, h->q_rg, h->q_P, h->q_M, h->scratch, h->step_args, h->Wd, h->st_lb, h->st_ub, h->st_sz, h->st_sZ,
                     h->ls_x, h->ls_u, h->ls_pi, h->ls_lam, h->ls_slk, h->ls_wpi, h->ls_wlam, h->ls_alpha, h->ls_args, h->ls_done, h->ls_status, h->ls_iter, h->ls_qp_acc, h->ls_pending, h->irk_tab, h->sim_irk_tab,
-                    h->hist_u0, h->hist_x0, h->hist_st, h->hist_it};
+                    h->hist_u0, h->hist_x0, h->hist_st, h->hist_it, h->sens_xbar, h->sens_ubar, h->sens_u0, h->sens_x, h->sens_u};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     free_instance_weights(h);
     free_instance_bounds(h);
@@ -1217,8 +1245,12 @@ int ihm2mpc_solve(ihm2mpc_handle *h, int32_t n_iter)
     } else {
         for (int it = 0; it < n_iter; it++) {
             ihm2_launch_linearize(h);
-            if (it == n_iter - 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+            if (it == n_iter - 1) {
+                if (sens_snapshot(h)) return -1;
+                HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+            }
             if (launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
+            if (it == n_iter - 1) sens_after_qp(h);
         }
     }
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
@@ -1330,6 +1362,44 @@ int ihm2mpc_get_qp_iter(ihm2mpc_handle *h, int32_t *qp_iter)
     if (!qp_iter) return fail("null argument");
     HIP_TRY(hipMemcpyAsync(qp_iter, h->qp_iter, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int ihm2mpc_set_x0_sensitivities(ihm2mpc_handle *h, int32_t mode)
+{
+    CHECK_H(h);
+    if (mode < 0 || mode > 2) return fail("x0 sensitivity mode %d: 0 (off), 1 (du_0/dx_0) or 2 (the whole horizon)", mode);
+    if (mode != 0 && h->cfg.nlp_solver_type == IHM2MPC_SQP)
+        return fail("x0 sensitivities are implemented for SQP_RTI: in the SQP mode the line search scales the step and the multipliers, "
+                    "which leaves no QP solution to differentiate");
+    const size_t B = h->B, N = h->N, NS = h->NS;
+    if (mode >= 1 && !h->sens_u0) {
+        if (dalloc(&h->sens_xbar, B * NS * NX) || dalloc(&h->sens_ubar, B * N * NU) || dalloc(&h->sens_u0, B * NU * NX)) return -1;
+    }
+    if (mode == 2 && !h->sens_x) {
+        if (dalloc(&h->sens_x, B * NS * NX * NX) || dalloc(&h->sens_u, B * N * NU * NX)) return -1;
+    }
+    if (mode != h->sens_mode) h->sens_state = 0;
+    h->sens_mode = mode;
+    return 0;
+}
+
+int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens_u)
+{
+    CHECK_H(h);
+    if (sens_readable(h)) return -1;
+    if (sens_x && h->sens_mode != 2) return fail("sens_x needs x0 sensitivity mode 2 (mode 1 computes du_0/dx_0 only)");
+    if (sens_x && download(h, h->sens_x, sens_x, h->NS * NX * NX)) return -1;
+    if (sens_u && download(h, h->sens_mode == 2 ? h->sens_u : h->sens_u0, sens_u, h->sens_mode == 2 ? h->N * NU * NX : NU * NX)) return -1;
+    return 0;
+}
+
+int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)
+{
+    CHECK_H(h);
+    if (!dptr) return fail("null argument");
+    if (sens_readable(h)) return -1;
+    HIP_TRY(hipMemcpyAsync(dptr, h->sens_u0, (size_t)h->B * NU * NX * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 
@@ -1460,9 +1530,11 @@ int ihm2mpc_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_targe
         if (sqp_iterations(h, sqp_iter_count(h), true)) return -1;
     } else {
         ihm2_launch_linearize(h);
+        if (sens_snapshot(h)) return -1;
         HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
         if (launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
+        sens_after_qp(h);
     }
     HIP_TRY(hipEventRecord(h->ev[2], h->stream));
     HIP_TRY(hipGetLastError());
@@ -1513,6 +1585,10 @@ int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_
     static const bool rounds = [] { const char *e = getenv("IHM2MPC_PERSISTENT_ROUNDS"); return e && e[0] == '1'; }();
     const bool resident = B <= (size_t)4 * h->n_cu || (rounds && !freeze);
     int rc = 1;
+    // x0 sensitivities: none from the persistent loop, and none from its launches per step either (the same results either way)
+    if (h->sens_mode) h->sens_state = 2;
+    struct Quiet { ihm2mpc_handle *h; bool was; ~Quiet() { h->sens_quiet = was; } } quiet{h, h->sens_quiet};
+    h->sens_quiet = true;
     if (h->cfg.nlp_solver_type == IHM2MPC_SQP && sqp_buffers(h)) return -1;
     if (h->cfg.nlp_solver_type == IHM2MPC_SQP && h->cfg.integrator_type != IHM2MPC_INTEG_ERK && h->sqp_globalization && sqp_phi_buffer(h, nullptr)) return -1;
     if (resident) {

@@ -154,6 +154,14 @@ struct ihm2mpc_handle {
 
     // ---- what was last launched (ihm2mpc_get_launch_record), written from the catalogue's keys (api.hip: note_launch) ----
     int32_t launch_rec[16];
+
+    // ---- x0 sensitivities of the last RTI QP (ihm2mpc_set_x0_sensitivities, kernels_sens.hip): allocated on first use ----
+    int sens_mode;                  // 0 off, 1 the stage-0 gain, 2 the whole horizon
+    int sens_state;                 // 0 nothing computed in this mode yet, 1 valid for the last solve / step, 2 the last step came from run_steps
+    bool sens_quiet;                // run_steps' launches per step: no snapshot, no sensitivity launch (the persistent loop has none either)
+    double *sens_xbar, *sens_ubar;  // (B,NS,8), (B,N,2) the point the last QP was linearised at
+    double *sens_u0;                // (B,2,8) du_0 / dx_0
+    double *sens_x, *sens_u;        // (B,NS,8,8), (B,N,2,8) (mode 2)
 };
 
 // --- launchers (each defined in one .hip file) ---
@@ -181,6 +189,9 @@ void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, c
 void ihm2_launch_sim_cart(ihm2mpc_handle *h, int model, int M, double dt, int n_steps, double v_dyn, const double *x, const double *u,
                           double *xn, hipStream_t stream);
 void ihm2_launch_project(ihm2mpc_handle *h, double s_tol, const double *xc, double *s_guess, double *xf, hipStream_t stream);
+// kernels_sens.hip: du/dx0, dx/dx0 of the last RTI QP's solution (h->sens_mode 1 or 2), after the QP on h->stream
+void ihm2_launch_sens(ihm2mpc_handle *h);
+size_t ihm2_sens_lds_bytes(const ihm2mpc_handle *h);
 
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'

@@ -59,6 +59,7 @@ class BatchedOcpSolver:
             ipm_mu0=d.ipm_mu0, ipm_tau0=d.ipm_tau0, nlp_tol=d.nlp_tol, integrator_type=d.integrator, sim_integrator_type=d.sim_integrator)
         self._h = C.c_void_p()
         _lib.check(self.lib.ihm2mpc_create(C.byref(cfg), C.byref(self._h)))
+        self._sens_mode = 0
         self._s_ref, self._kappa_ref = s_ref.copy(), kappa_ref.copy()
         self._track_widths = None if track_widths is None else np.atleast_2d(_f64(track_widths))
         self._push_tracks()
@@ -443,6 +444,26 @@ class BatchedOcpSolver:
     def get_status_device(self, dptr: int):
         _lib.check(self.lib.ihm2mpc_get_status_device(self._h, C.c_void_p(dptr)))
 
+    # ---- sensitivities of the solution with respect to x0 (acados: eval_param_sens(j, 0, "ex"); get(k, "sens_x" / "sens_u")) ----
+    def set_x0_sensitivities(self, mode: int = 2):
+        """0 off; 1 ``du_0/dx_0`` only (the feedback gain K0); 2 the whole horizon.  Every later RTI ``solve`` /
+        ``compute_control`` / ``step`` computes them after its QP (refused in the SQP mode; ``run_steps`` computes none)."""
+        _lib.check(self.lib.ihm2mpc_set_x0_sensitivities(self._h, int(mode)))
+        self._sens_mode = int(mode)
+
+    def get_x0_sensitivities(self):
+        """``(sens_x, sens_u)`` of the last solve: mode 2 ``(B,N+1,8,8)``, ``(B,N,2,8)`` with ``sens_x[b,k,i,j] = dx_k,i/dx0_j``;
+        mode 1 ``(None, (B,2,8))``.  NaN rows for instances whose status is neither 0 nor 2."""
+        full = self._sens_mode == 2
+        sx = np.empty((self.B, self.N + 1, NX, NX)) if full else None
+        su = np.empty((self.B, self.N, NU, NX)) if full else np.empty((self.B, NU, NX))
+        _lib.check(self.lib.ihm2mpc_get_x0_sensitivities(self._h, _ptr(sx) if full else None, _ptr(su)))
+        return sx, su
+
+    def get_sens_u0_device(self, dptr: int):
+        """``du_0/dx_0`` ``(B,2,8)`` into device memory, stream-ordered."""
+        _lib.check(self.lib.ihm2mpc_get_sens_u0_device(self._h, C.c_void_p(dptr)))
+
     # ---- plant ----
     def sim_step(self, x, u, model: int = 0, M_sim: int = 100):
         x = _f64(x, (self.B, NX), "x"); u = _f64(u, (self.B, NU), "u")
@@ -622,7 +643,38 @@ class AcadosOcpSolver:
         """Runs the solver (for a view: the whole batch) and returns this instance's status."""
         return int(self.batch.solve()[self.i])
 
+    def eval_param_sens(self, index: int, stage: int = 0, field: str = "ex") -> None:
+        """acados' ``eval_param_sens``: the sensitivities of the last solution with respect to ``x0[index]``, read afterwards by
+        ``get(k, "sens_x")`` / ``get(k, "sens_u")``.  Only ``field = "ex"`` at stage 0 exists here; the batch computes them in its
+        solves once ``BatchedOcpSolver.set_x0_sensitivities`` is on (mode 1: ``get(0, "sens_u")`` only)."""
+        if field != "ex":
+            raise Exception(f"AcadosOcpSolver.eval_param_sens(): field '{field}' is not supported (only 'ex', the initial state)")
+        if stage != 0:
+            raise Exception("AcadosOcpSolver.eval_param_sens(): the initial state is a parameter of stage 0 only")
+        if not 0 <= int(index) < NX:
+            raise Exception(f"AcadosOcpSolver.eval_param_sens(): index {index} out of range [0, {NX})")
+        if self.batch._sens_mode == 0:
+            raise Exception("AcadosOcpSolver.eval_param_sens(): x0 sensitivities are off -- call set_x0_sensitivities(1 or 2) on the "
+                            "batch before solve()")
+        sx, su = self.batch.get_x0_sensitivities()
+        j = int(index)
+        self._sens = (None if sx is None else sx[self.i, :, :, j].copy(), su[self.i, ..., j].copy())
+
     def get(self, stage: int, field: str) -> np.ndarray:
+        if field in ("sens_x", "sens_u"):
+            sens = getattr(self, "_sens", None)
+            if sens is None:
+                raise Exception(f"AcadosOcpSolver.get(): '{field}' needs eval_param_sens() first")
+            sx, su = sens
+            if field == "sens_x":
+                if sx is None:
+                    raise Exception("AcadosOcpSolver.get(): 'sens_x' needs x0 sensitivity mode 2 (mode 1 holds du_0/dx_0 only)")
+                return sx[stage].copy()
+            if su.ndim == 1:            # mode 1: stage 0 only
+                if stage != 0:
+                    raise Exception("AcadosOcpSolver.get(): x0 sensitivity mode 1 holds 'sens_u' of stage 0 only")
+                return su.copy()
+            return su[stage].copy()
         sizes = {"x": NX, "u": NU, "pi": NX, "lam": NLAM}
         if field not in sizes:
             raise Exception(f"AcadosOcpSolver.get(): '{field}' is not a valid argument.")

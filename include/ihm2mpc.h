@@ -28,6 +28,7 @@
  *   ihm2mpc_compute_control   <- IHM2Controller.compute_control(x) as one call            python/main.py:297-334
  *   ihm2mpc_step              <- one iteration of the MiL loop (plant + compute_control)  python/main.py:476-517
  *   ihm2mpc_run_steps         <- n iterations of that loop in one launch                  python/main.py:448-517
+ *   ihm2mpc_set/get_x0_sensitivities <- solver.eval_param_sens(j, 0, "ex"); solver.get(k, "sens_x" / "sens_u") (acados)
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -260,6 +261,26 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *       [13] why it went per step: 0 it did not, 1 the configuration has no k_steps instantiation, 2 the batch exceeds the resident limit
  *   [14..15] 0 (reserved) */
 int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
+
+/* ---- sensitivities of the solution with respect to the initial state (acados: eval_param_sens(index, 0, "ex"), then
+ * get(stage, "sens_x" | "sens_u")) ----
+ * The last RTI QP of an instance, linearised at (xbar, ubar), differentiated at its returned solution: the interior point's KKT system
+ * at that iterate with the primal gaps t = max(gap, IHM2MPC_SENS_TAU) in place of its own slacks -- every present side adds
+ * sigma r r' to the stage Hessian (hard: lam / t; soft: the slack eliminated in series, 1 / (t / lam + 1 / (Z + nu / max(s, tau))),
+ * nu = max(z + Z s - lam, 0)) -- solved as an equality-constrained LQ problem from dx_0 = e_j.  One kernel after the QP;
+ * the QP and every other output are unchanged.
+ * mode: 0 off (the default), 1 du_0/dx_0 only (the feedback gain K0 of u0 + K0 (x - x0)), 2 the whole horizon.  Memory on first use.
+ * While the mode is on, ihm2mpc_solve, ihm2mpc_compute_control and ihm2mpc_step take a copy of (x, u) after the linearisation and
+ * launch the kernel after the QP of their last RTI iteration, in stream order.  Refused in the SQP mode (the line search scales the step
+ * and the multipliers: no QP solution is returned).  ihm2mpc_run_steps computes none (the persistent loop is unchanged). */
+#define IHM2MPC_SENS_TAU 1e-9
+int ihm2mpc_set_x0_sensitivities(ihm2mpc_handle *h, int32_t mode);
+/* sens_x (B,N+1,8,8): sens_x[b][k][i][j] = d x_k,i / d x0_j (mode 2 only; stage 0 is the identity); sens_u: mode 1 (B,2,8) =
+ * d u_0 / d x0, mode 2 (B,N,2,8) = d u_k / d x0.  Either pointer may be NULL.  NaN for instances whose status is neither 0 nor 2.
+ * Refused before a solve with the mode on and after ihm2mpc_run_steps. */
+int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens_u);
+/* du_0 / dx0 (B,2,8) into device memory (either mode), stream-ordered like ihm2mpc_get_u0_device */
+int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr);
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */
