@@ -75,6 +75,8 @@ SYMBOLS = {
     "ihm2mpc_compute_control": (C.c_int, [_H, c_double_p, C.c_double, c_double_p, c_int32_p]),
     "ihm2mpc_reserve_history": (C.c_int, [_H, C.c_int32]),
     "ihm2mpc_run_steps": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "ihm2mpc_run_steps_sens": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, c_double_p, c_double_p, c_int32_p, c_int32_p,
+                                         c_double_p]),
     "ihm2mpc_set_sqp_options": (C.c_int, [_H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, c_double_p]),
     "ihm2mpc_get_sqp_stats": (C.c_int, [_H, c_int32_p, c_double_p]),
     "ihm2mpc_linearize": (C.c_int, [_H]),

@@ -250,6 +250,7 @@ class ClosedLoopResult:
     lap_time: np.ndarray     # (B,) seconds (nan if not finished)
     runtimes_ms: list = field(default_factory=list)
     alive_history: np.ndarray | None = None   # (steps, B) alive at the start of each step
+    feedback_gain: np.ndarray | None = None   # (steps, B, 2, 8) K0 = du_0/dx_0 of the solve behind u (IHM2Controller(x0_sensitivities=True)); NaN where u is zeroed
 
     def stats(self) -> dict:
         v = np.hypot(self.x[..., 3], self.x[..., 4])
@@ -259,13 +260,29 @@ class ClosedLoopResult:
                 "control_steps_per_s": float(self.u.shape[0] * self.u.shape[1] / (np.sum(self.runtimes_ms) * 1e-3))}
 
 
+def _gain(solver) -> np.ndarray:
+    """``du_0/dx_0`` ``(B, 2, 8)`` of the solver's last solve, in either x0 sensitivity mode."""
+    _, su = solver.get_x0_sensitivities()
+    return su if su.ndim == 3 else su[:, 0]
+
+
+def _masked_gains(ks, alive_rows) -> np.ndarray | None:
+    """The gains of the steps, NaN where the car was not alive (where its u is zeroed)."""
+    if ks is None:
+        return None
+    return np.array([np.where(a[:, None, None], k, np.nan) for k, a in zip(ks, alive_rows)])
+
+
 def run_closed_loop(controller: IHM2Controller, simulator: Simulator, x0: np.ndarray, n_steps: int, lap_length: float | None = None,
                     interation_end_callback: Callable | None = None) -> ClosedLoopResult:
     """``python/main.py:448-517`` for a batch.  Instances that fail (status not in {0,2}, NaN) or finish the lap are
-    frozen: they keep their last state and a zero input, as the reference stops its single loop."""
+    frozen: they keep their last state and a zero input, as the reference stops its single loop.  With
+    ``IHM2Controller(x0_sensitivities=True)`` the result's ``feedback_gain`` holds ``K0`` of every step."""
     B = controller.B
     x = np.asarray(x0, dtype=np.float64).reshape(B, 8).copy()
     xs, us, sts, runtimes = [x.copy()], [], [], []
+    sens = getattr(controller, "x0_sensitivities", False)
+    ks, u_alive = ([], []) if sens else (None, None)
     alive = np.ones(B, dtype=bool)
     finished = np.zeros(B, dtype=bool)
     lap_time = np.full(B, np.nan)
@@ -279,6 +296,8 @@ def run_closed_loop(controller: IHM2Controller, simulator: Simulator, x0: np.nda
         bad = alive & ~np.isin(st, (0, 2))
         alive &= ~bad
         u = np.where(alive[:, None], np.nan_to_num(u), 0.0)
+        if sens:
+            ks.append(np.asarray(controller.feedback_gain).reshape(B, 2, 8)); u_alive.append(alive.copy())
         xn = simulator.simulate(x, u)
         nan = alive & np.any(np.isnan(xn), axis=1)          # python/main.py:503-504
         alive &= ~nan
@@ -293,22 +312,27 @@ def run_closed_loop(controller: IHM2Controller, simulator: Simulator, x0: np.nda
             interation_end_callback(i, x, u, st)
         if not alive.any():
             break
-    return ClosedLoopResult(np.array(xs), np.array(us), np.array(sts), alive, finished, lap_time, runtimes, np.array(alive_hist))
+    return ClosedLoopResult(np.array(xs), np.array(us), np.array(sts), alive, finished, lap_time, runtimes, np.array(alive_hist),
+                            _masked_gains(ks, u_alive))
 
 
 def run_closed_loop_device(controller: IHM2Controller, simulator: Simulator, x0: np.ndarray, n_steps: int, lap_length: float | None = None
                            ) -> ClosedLoopResult:
     """Same loop as :func:`run_closed_loop`, with the state resident on the device: one ``ihm2mpc_step`` per control period
     (plant beside the linearisation), and per step only ``x0`` (B,8), ``u0`` (B,2) and the status (B,) cross the boundary for
-    the bookkeeping.  Frozen instances (failed / finished) are masked out of the plant (``ihm2mpc_set_active``)."""
+    the bookkeeping.  Frozen instances (failed / finished) are masked out of the plant (``ihm2mpc_set_active``).  With x0 sensitivities
+    on, the gain of every solve is read back as well (``feedback_gain``)."""
     B, s = controller.B, controller.solver
     code = _PLANT_CODE[simulator.variant]
     x = np.asarray(x0, dtype=np.float64).reshape(B, 8).copy()
     xs, us, sts, runtimes, alive_hist = [x.copy()], [], [], [], []
     alive = np.ones(B, dtype=bool); finished = np.zeros(B, dtype=bool); lap_time = np.full(B, np.nan)
+    sens = getattr(controller, "x0_sensitivities", False)
+    ks, u_alive = ([], []) if sens else (None, None)
     t0 = time.perf_counter()
     s.set_active(None)
     s.set_x0(x); s.prepare_step(controller.s_target); st = s.solve(); u = s.get_u0()          # control for the initial state
+    K = _gain(s) if sens else None
     runtimes.append((time.perf_counter() - t0) * 1e3)
     mask_dirty = False
     for i in range(n_steps):
@@ -317,6 +341,8 @@ def run_closed_loop_device(controller: IHM2Controller, simulator: Simulator, x0:
         if bad.any():
             alive &= ~bad; mask_dirty = True
         us.append(np.where(alive[:, None], np.nan_to_num(u), 0.0)); sts.append(st.copy())
+        if sens:
+            ks.append(K); u_alive.append(alive.copy())
         if not alive.any():
             xs.append(x.copy())
             break
@@ -325,6 +351,8 @@ def run_closed_loop_device(controller: IHM2Controller, simulator: Simulator, x0:
         t0 = time.perf_counter()
         s.step(controller.s_target, model=code, M_sim=simulator.config.num_steps)     # x <- plant(x, u); u <- NMPC(x)
         xn = s.get_x0(); u = s.get_u0(); st = s.get_status()
+        if sens:
+            K = _gain(s)
         runtimes.append((time.perf_counter() - t0) * 1e3)
         nan = alive & np.any(np.isnan(xn), axis=1)
         if nan.any():
@@ -338,7 +366,8 @@ def run_closed_loop_device(controller: IHM2Controller, simulator: Simulator, x0:
         xs.append(x.copy())
     controller.last_status = st
     s.set_active(None)
-    return ClosedLoopResult(np.array(xs), np.array(us), np.array(sts), alive, finished, lap_time, runtimes, np.array(alive_hist))
+    return ClosedLoopResult(np.array(xs), np.array(us), np.array(sts), alive, finished, lap_time, runtimes, np.array(alive_hist),
+                            _masked_gains(ks, u_alive))
 
 
 def run_closed_loop_persistent(controller: IHM2Controller, simulator: Simulator, x0: np.ndarray, n_steps: int, lap_length: float | None = None
@@ -346,26 +375,31 @@ def run_closed_loop_persistent(controller: IHM2Controller, simulator: Simulator,
     """Same loop as :func:`run_closed_loop_device` in ONE launch (``ihm2mpc_run_steps``): every car runs its control periods back
     to back on its own wavefront, the freezing rules (failed solve, NaN plant state, lap done) are applied on the device, and the
     histories come back once at the end.  For batches that fit the device at once (4 cars per compute unit) and the reference's
-    OCP; otherwise the solver reports it and :func:`run_closed_loop_device` is the loop to use."""
+    OCP; otherwise the solver reports it and :func:`run_closed_loop_device` is the loop to use.  With x0 sensitivities on, the loop
+    computes the gain of every solve as well (``ihm2mpc_run_steps_sens``: ``feedback_gain``)."""
     B, s = controller.B, controller.solver
     code = _PLANT_CODE[simulator.variant]
     x = np.asarray(x0, dtype=np.float64).reshape(B, 8).copy()
+    sens = getattr(controller, "x0_sensitivities", False)
     t0 = time.perf_counter()
     s.set_active(None)
     s.set_x0(x); s.prepare_step(controller.s_target); st0 = s.solve(); u_first = s.get_u0()     # control for the initial state
+    K_first = _gain(s) if sens else None
     h = s.run_steps(controller.s_target, n_steps, model=code, M_sim=simulator.config.num_steps, freeze=True,
-                    lap_stop=np.inf if lap_length is None else lap_length + 1.0, u0_hist=True, x0_hist=True, status_hist=True)
+                    lap_stop=np.inf if lap_length is None else lap_length + 1.0, u0_hist=True, x0_hist=True, status_hist=True,
+                    sens_u0_hist=True if sens else None)
     wall_ms = (time.perf_counter() - t0) * 1e3
     us_raw = np.concatenate([u_first[None], h["u0"][:-1]]); sts = np.concatenate([st0[None], h["status"][:-1]])
+    ks_raw = np.concatenate([K_first[None], h["sens_u0"][:-1]]) if sens else None
     xs = np.concatenate([x[None], h["x0"]])
     # the bookkeeping of run_closed_loop_device, replayed on the histories (the device applied the same rules)
     alive = np.ones(B, dtype=bool); finished = np.zeros(B, dtype=bool); lap_time = np.full(B, np.nan)
-    alive_hist, us = [], []
+    alive_hist, us, u_alive = [], [], []
     n_done = n_steps
     for i in range(n_steps):
         alive_hist.append(alive.copy())
         alive &= np.isin(sts[i], (0, 2))
-        us.append(np.where(alive[:, None], np.nan_to_num(us_raw[i]), 0.0))
+        us.append(np.where(alive[:, None], np.nan_to_num(us_raw[i]), 0.0)); u_alive.append(alive.copy())
         if not alive.any():
             n_done = i + 1
             break
@@ -378,7 +412,7 @@ def run_closed_loop_persistent(controller: IHM2Controller, simulator: Simulator,
     controller.last_status = s.get_status()
     s.set_active(None)
     return ClosedLoopResult(xs[:n_done + 1], np.array(us), sts[:n_done], alive, finished, lap_time, [wall_ms / max(n_done, 1)] * n_done,
-                            np.array(alive_hist))
+                            np.array(alive_hist), _masked_gains(None if ks_raw is None else ks_raw[:n_done], u_alive))
 
 
 def closed_loop(track_data: str | MotionPlan, simulator_type=SimModelVariant.KIN6_DYN6, motion_planner_type: type | None = None,

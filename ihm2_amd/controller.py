@@ -305,7 +305,8 @@ class IHM2Controller(Controller):
     @property
     def feedback_gain(self) -> np.ndarray:
         """``K0 = du_0/dx_0`` of the last ``compute_control``: ``(2, 8)`` for a batch of one, else ``(B, 2, 8)`` (NaN rows where
-        the solve failed).  Needs ``x0_sensitivities=True``."""
+        the solve failed).  Needs ``x0_sensitivities=True``; the closed-loop runners then collect it at every step
+        (``ClosedLoopResult.feedback_gain``; ``run_closed_loop_persistent`` inside its one launch, ``ihm2mpc_run_steps_sens``)."""
         if not self.x0_sensitivities:
             raise RuntimeError("feedback_gain needs IHM2Controller(..., x0_sensitivities=True)")
         _, K = self.solver.get_x0_sensitivities()

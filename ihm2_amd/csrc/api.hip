@@ -210,10 +210,10 @@ void free_instance_bounds(ihm2mpc_handle *h)
 }
 
 // ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
-// The catalogue is the three objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
+// The catalogue is the four objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
 // (the leading one-sided entries per lane rebuild_slots laid it out for) and its NSLOT holds the table's slots per lane; of those
 // that fit the configuration, the first in catalogue order is launched.
-const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2()};
+const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3()};
 
 // the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
 int path_class(const ihm2mpc_handle *h) { return h->alat_on ? 2 : h->path_on ? 1 : 0; }
@@ -225,7 +225,7 @@ const QpInst *find_inst(const QpKey &want)
         for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
             const QpKey &k = e->key;
             if (k.kind == want.kind && k.nsoft == want.nsoft && k.path == want.path && k.uni == want.uni && k.sqp == want.sqp &&
-                k.irk == want.irk && k.dyn == want.dyn && k.nslot >= want.nslot)
+                k.irk == want.irk && k.dyn == want.dyn && k.sens == want.sens && k.nslot >= want.nslot)
                 return e;
         }
     return nullptr;
@@ -268,8 +268,9 @@ const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
 
 // The persistent loop for the handle's configuration; nullptr: none (ihm2mpc_run_steps then launches per step, which gives the same
 // results).  The catalogue has it for the kinematic and the dynamic OCP models, not for the lateral-acceleration row; with soft sides,
-// track rows, the collocation integrator or a dynamic model for batch-shared tables only (UNI = 1).
-const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds)
+// track rows, the collocation integrator or a dynamic model for batch-shared tables only (UNI = 1).  sens = 1 (ihm2mpc_run_steps_sens):
+// the loop with x0 sensitivities, for the kinematic OCP model in the RTI mode.
+const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds, int sens = 0)
 {
     const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP, irk = h->cfg.integrator_type != IHM2MPC_INTEG_ERK;
     const bool dyn = h->cfg.model != IHM2MPC_MODEL_FKIN6;
@@ -278,7 +279,7 @@ const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds)
     if (lds > 160 * 1024) return nullptr;
     // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
     if (dyn && !irk && lds < (size_t)ihm2::s_count(1) * 64 * sizeof(double)) return nullptr;
-    return find_inst({QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn});
+    return find_inst({QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
 }
 
 // the launch record (ihm2mpc_get_launch_record) from the key of what was launched; a k_steps key with `per_step` != 0: run_steps
@@ -290,7 +291,7 @@ void note_launch(ihm2mpc_handle *h, const QpKey &k, int per_step = 0)
         r[0] = k.kind; r[1] = k.nslot; r[2] = k.nsoft; r[3] = k.path; r[4] = k.uni;
     } else {
         r[5] = per_step ? 2 : 1; r[6] = k.nslot; r[7] = k.nsoft; r[8] = k.path; r[9] = k.uni; r[10] = k.sqp; r[11] = k.irk; r[12] = k.dyn;
-        r[13] = per_step;
+        r[13] = per_step; r[14] = k.sens;
     }
 }
 
@@ -336,11 +337,12 @@ int launch_qp(ihm2mpc_handle *h)
 }
 
 // n_steps control steps in one launch (k_steps), histories into h->hist_*.  Returns 0 launched, 1 the configuration has no persistent
-// instantiation (the caller then runs ihm2mpc_step n_steps times, which gives the same results).
-int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop)
+// instantiation (the caller then runs ihm2mpc_step n_steps times, which gives the same results).  sens: the loop with x0 sensitivities
+// (k_steps<..., SENS = 1>), their history into h->hist_k; its LDS is the larger of the QP's and k_sens' (the body reuses the QP's).
+int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop, int sens = 0)
 {
-    const size_t lds = qp_lds_bytes(h);
-    const QpInst *e = select_steps(h, lds);
+    const size_t lds = sens ? std::max(qp_lds_bytes(h), ihm2_sens_lds_bytes(h)) : qp_lds_bytes(h);
+    const QpInst *e = select_steps(h, lds, sens);
     if (!e) return 1;
     const bool irk_plant = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
     if (irk_plant && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;
@@ -357,9 +359,11 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
     s.hist_u0 = h->hist_u0; s.hist_x0 = h->hist_x0; s.hist_st = h->hist_st; s.hist_it = h->hist_it;
     s.irk_tab = (const ihm2::IrkTab *)h->irk_tab;
     s.sim_irk_tab = irk_plant ? (const ihm2::IrkTab *)h->sim_irk_tab : nullptr;
-    // every field of s is set: upload it (and the line search's block in the SQP mode)
+    s.sens = sens ? (const SensArgs *)h->sens_args : nullptr;
+    // every field of s is set: upload it (and the line search's block in the SQP mode, the x0 sensitivities' block with SENS)
     static_assert(sizeof(StepArgs) <= 32 * sizeof(double), "step_args holds 256 bytes");
     static_assert(sizeof(ihm2::LsArgs) <= 64 * sizeof(double), "ls_args holds 512 bytes");
+    static_assert(sizeof(SensArgs) <= 64 * sizeof(double), "sens_args holds 512 bytes");
     // both blocks go through a pinned staging slot (two slots, used alternately) and are uploaded in stream order: the host does
     // not wait for the previous launch (run_steps(wait = false) enqueues in pieces while the host does other work)
     const int slot = (h->args_idx++) & 1;
@@ -372,6 +376,13 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
         if (e->key.irk) ls_host.phase = 3;        // the trial points' collocation rollouts are done in the loop, one step length at a time
         std::memcpy(stage + 512, &ls_host, sizeof(ihm2::LsArgs));
         if (hipMemcpyAsync(h->ls_args, stage + 512, sizeof(ihm2::LsArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
+    }
+    if (sens) {         // (the RTI mode only: the second half of the slot is free)
+        SensArgs sa;
+        ihm2_sens_args(h, &sa);
+        sa.hist = h->hist_k; sa.sweep_step = n_steps - 1;
+        std::memcpy(stage + 512, &sa, sizeof(SensArgs));
+        if (hipMemcpyAsync(h->sens_args, stage + 512, sizeof(SensArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
     }
     if (hipEventRecord(h->args_ev[slot], h->stream) != hipSuccess) return 1;
     const StepArgs *sdev = (const StepArgs *)h->step_args;
@@ -404,7 +415,7 @@ int sens_readable(const ihm2mpc_handle *h)
     if (!h->sens_mode) return fail("x0 sensitivities are off: ihm2mpc_set_x0_sensitivities(h, 1 or 2) before the solve");
     if (h->sens_state == 2)
         return fail("the last step came from ihm2mpc_run_steps, which computes no x0 sensitivities (the persistent loop is left as it is): "
-                    "call ihm2mpc_solve, ihm2mpc_compute_control or ihm2mpc_step");
+                    "call ihm2mpc_run_steps_sens, ihm2mpc_solve, ihm2mpc_compute_control or ihm2mpc_step");
     if (h->sens_state != 1) return fail("no solve has run since x0 sensitivities were set to mode %d: nothing to read yet", h->sens_mode);
     return 0;
 }
@@ -548,7 +559,8 @@ int ihm2mpc_free(ihm2mpc_handle *h)
                     h->slot_kc, h->slot_lb, h->slot_ub, h->slot_zw, h->slot_Zw, h->slk, h->lam_a, h->slk_a, h->widths, h->X_ref, h->Y_ref, h->phi_ref, h->xc, h->s_guess, h->x, h->u, h->x0, h->yref, h->yref_e, h->pi, h->lam, h->res, h->qp_res, h->dyn10, h->ls_phi, h->slot_kc_blk, h->slot_lb_blk, h->slot_ub_blk,
                     h->status, h->qp_iter, h->active, h->u0, h->lin, h->q_g, h->q_rg, h->q_P, h->q_M, h->scratch, h->step_args, h->Wd, h->st_lb, h->st_ub, h->st_sz, h->st_sZ,
                     h->ls_x, h->ls_u, h->ls_pi, h->ls_lam, h->ls_slk, h->ls_wpi, h->ls_wlam, h->ls_alpha, h->ls_args, h->ls_done, h->ls_status, h->ls_iter, h->ls_qp_acc, h->ls_pending, h->irk_tab, h->sim_irk_tab,
-                    h->hist_u0, h->hist_x0, h->hist_st, h->hist_it, h->sens_xbar, h->sens_ubar, h->sens_u0, h->sens_x, h->sens_u};
+                    h->hist_u0, h->hist_x0, h->hist_st, h->hist_it, h->sens_xbar, h->sens_ubar, h->sens_u0, h->sens_x, h->sens_u,
+                    h->sens_args, h->hist_k};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     free_instance_weights(h);
     free_instance_bounds(h);
@@ -1374,7 +1386,8 @@ int ihm2mpc_set_x0_sensitivities(ihm2mpc_handle *h, int32_t mode)
                     "which leaves no QP solution to differentiate");
     const size_t B = h->B, N = h->N, NS = h->NS;
     if (mode >= 1 && !h->sens_u0) {
-        if (dalloc(&h->sens_xbar, B * NS * NX) || dalloc(&h->sens_ubar, B * N * NU) || dalloc(&h->sens_u0, B * NU * NX)) return -1;
+        if (dalloc(&h->sens_xbar, B * NS * NX) || dalloc(&h->sens_ubar, B * N * NU) || dalloc(&h->sens_u0, B * NU * NX) || dalloc(&h->sens_args, 64))
+            return -1;
     }
     if (mode == 2 && !h->sens_x) {
         if (dalloc(&h->sens_x, B * NS * NX * NX) || dalloc(&h->sens_u, B * N * NU * NX)) return -1;
@@ -1542,28 +1555,36 @@ int ihm2mpc_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_targe
 }
 
 // room for the histories of ihm2mpc_run_steps: growing them costs a few device allocations, which a caller that times its
-// run_steps calls wants to have behind it
+// run_steps calls wants to have behind it (and, while an x0 sensitivity mode is on, for the gain history of ihm2mpc_run_steps_sens)
 int ihm2mpc_reserve_history(ihm2mpc_handle *h, int32_t n_steps)
 {
     CHECK_H(h);
     if (n_steps < 1) return fail("n_steps must be >= 1");
     const size_t B = h->B, n = n_steps;
-    if (h->hist_cap >= n) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (void *p : {(void *)h->hist_u0, (void *)h->hist_x0, (void *)h->hist_st, (void *)h->hist_it}) if (p) (void)hipFree(p);
-    h->hist_u0 = h->hist_x0 = nullptr; h->hist_st = h->hist_it = nullptr; h->hist_cap = 0;
-    if (dalloc(&h->hist_u0, n * B * 2) || dalloc(&h->hist_x0, n * B * 8) || dalloc(&h->hist_st, n * B) || dalloc(&h->hist_it, n * B)) return -1;
-    h->hist_cap = n;
+    if (h->hist_cap < n) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (void *p : {(void *)h->hist_u0, (void *)h->hist_x0, (void *)h->hist_st, (void *)h->hist_it}) if (p) (void)hipFree(p);
+        h->hist_u0 = h->hist_x0 = nullptr; h->hist_st = h->hist_it = nullptr; h->hist_cap = 0;
+        if (dalloc(&h->hist_u0, n * B * 2) || dalloc(&h->hist_x0, n * B * 8) || dalloc(&h->hist_st, n * B) || dalloc(&h->hist_it, n * B)) return -1;
+        h->hist_cap = n;
+    }
+    if (h->sens_mode && h->hist_k_cap < n) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->hist_k) (void)hipFree(h->hist_k);
+        h->hist_k = nullptr; h->hist_k_cap = 0;
+        if (dalloc(&h->hist_k, n * B * NU * NX)) return -1;
+        h->hist_k_cap = n;
+    }
     return 0;
 }
 
 // n_steps control steps of the MiL loop with everything on the device (python/main.py:476-517).  Where the configuration has a
 // persistent instantiation (fkin6 OCP, RTI, all-hard constraint table) this is ONE launch in which every instance runs its
-// steps back to back; otherwise n_steps x ihm2mpc_step.  Same results either way.
-int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_target, int32_t n_steps, int32_t freeze, double lap_stop,
-                      double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist)
+// steps back to back; otherwise n_steps x ihm2mpc_step.  Same results either way.  sens (ihm2mpc_run_steps_sens): with the x0
+// sensitivities of every step -- k_steps<..., SENS = 1>, or ihm2mpc_step with k_sens behind every QP -- and their history.
+static int run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_target, int32_t n_steps, int32_t freeze, double lap_stop,
+                     double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist, bool sens, double *sens_u0_hist)
 {
-    CHECK_H(h);
     if (ready(h)) return -1;
     if (M_sim < 1) return fail("M_sim must be >= 1");
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
@@ -1585,17 +1606,19 @@ int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_
     static const bool rounds = [] { const char *e = getenv("IHM2MPC_PERSISTENT_ROUNDS"); return e && e[0] == '1'; }();
     const bool resident = B <= (size_t)4 * h->n_cu || (rounds && !freeze);
     int rc = 1;
-    // x0 sensitivities: none from the persistent loop, and none from its launches per step either (the same results either way)
-    if (h->sens_mode) h->sens_state = 2;
+    // x0 sensitivities: without `sens` none from the persistent loop, and none from its launches per step either (the same results
+    // either way); with it, the last step's are readable afterwards
+    if (h->sens_mode) h->sens_state = sens ? 0 : 2;
     struct Quiet { ihm2mpc_handle *h; bool was; ~Quiet() { h->sens_quiet = was; } } quiet{h, h->sens_quiet};
-    h->sens_quiet = true;
+    h->sens_quiet = !sens;
     if (h->cfg.nlp_solver_type == IHM2MPC_SQP && sqp_buffers(h)) return -1;
     if (h->cfg.nlp_solver_type == IHM2MPC_SQP && h->cfg.integrator_type != IHM2MPC_INTEG_ERK && h->sqp_globalization && sqp_phi_buffer(h, nullptr)) return -1;
     if (resident) {
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        rc = launch_steps(h, model, M_sim, s_target, n_steps, freeze ? 1 : 0, lap_stop);
+        rc = launch_steps(h, model, M_sim, s_target, n_steps, freeze ? 1 : 0, lap_stop, sens ? 1 : 0);
         if (rc == 0) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        if (rc == 0 && sens) h->sens_state = 1;
     }
     if (rc != 0) {
         if (freeze) return fail("no persistent loop for this configuration (needs batch-shared weights and rows for soft tables or the collocation integrator, and a batch of at most %d): call ihm2mpc_step per control period", 4 * h->n_cu);
@@ -1606,6 +1629,7 @@ int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_
             HIP_TRY(hipMemcpyAsync(h->hist_x0 + i * B * 8, h->x0, B * 8 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipMemcpyAsync(h->hist_st + i * B, h->status, B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(hipMemcpyAsync(h->hist_it + i * B, h->qp_iter, B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+            if (sens) HIP_TRY(hipMemcpyAsync(h->hist_k + i * B * NU * NX, h->sens_u0, B * NU * NX * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1614,7 +1638,23 @@ int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_
     if (x0_hist) HIP_TRY(hipMemcpyAsync(x0_hist, h->hist_x0, n * B * 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (status_hist) HIP_TRY(hipMemcpyAsync(status_hist, h->hist_st, n * B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     if (qp_iter_hist) HIP_TRY(hipMemcpyAsync(qp_iter_hist, h->hist_it, n * B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (sens_u0_hist) HIP_TRY(hipMemcpyAsync(sens_u0_hist, h->hist_k, n * B * NU * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return 0;
+}
+
+int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_target, int32_t n_steps, int32_t freeze, double lap_stop,
+                      double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist)
+{
+    CHECK_H(h);
+    return run_steps(h, model, M_sim, s_target, n_steps, freeze, lap_stop, u0_hist, x0_hist, status_hist, qp_iter_hist, false, nullptr);
+}
+
+int ihm2mpc_run_steps_sens(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_target, int32_t n_steps, int32_t freeze, double lap_stop,
+                           double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist, double *sens_u0_hist)
+{
+    CHECK_H(h);
+    if (!h->sens_mode) return fail("x0 sensitivities are off: ihm2mpc_set_x0_sensitivities(h, 1 or 2) before ihm2mpc_run_steps_sens");
+    return run_steps(h, model, M_sim, s_target, n_steps, freeze, lap_stop, u0_hist, x0_hist, status_hist, qp_iter_hist, true, sens_u0_hist);
 }
 
 // ---- Cartesian side of the ROS stack (N2 plants, N3 projection) ----

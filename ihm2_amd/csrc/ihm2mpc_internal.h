@@ -162,6 +162,9 @@ struct ihm2mpc_handle {
     double *sens_xbar, *sens_ubar;  // (B,NS,8), (B,N,2) the point the last QP was linearised at
     double *sens_u0;                // (B,2,8) du_0 / dx_0
     double *sens_x, *sens_u;        // (B,NS,8,8), (B,N,2,8) (mode 2)
+    double *sens_args;              // device copy of the persistent loop's SensArgs (512 B), allocated with the buffers above
+    size_t hist_k_cap;              // steps hist_k holds
+    double *hist_k;                 // (steps,B,2,8) du_0/dx0 of every step of ihm2mpc_run_steps_sens, grown on demand
 };
 
 // --- launchers (each defined in one .hip file) ---
@@ -225,6 +228,27 @@ struct QpArgs {
     int symmetrize;     // P_k := (P_k + P_k') / 2 in the factor sweep (riccati_mfma.hpp): needed by the open-loop unstable dynamic model as written (fdyn6)
 };
 
+// x0 sensitivities (sens_body.hpp): k_sens takes the block by value, k_steps<..., SENS = 1> from device memory (StepArgs.sens)
+struct SensArgs {
+    int B, N, mode, nslots, path, alat;
+    double tau;
+    // stage Hessians: instance base stride, offset of the terminal block, stride between stages (0: one block for every k < N)
+    const double *Hs;
+    int hs_bs, hs_te, hs_ks;
+    const double *CD;
+    const int32_t *slot_kc;
+    const double *slot_lb, *slot_ub, *slot_zw, *slot_Zw;
+    int sl_bs;          // doubles of slot_lb / slot_ub per instance (0: batch-shared)
+    const int32_t *track_id;
+    const double *widths;
+    double car_L, car_W;
+    const double *lin, *xbar, *ubar, *x, *u, *lam, *slk, *lam_a, *slk_a;
+    const int32_t *status;
+    double *sens_u0, *sens_x, *sens_u;
+    double *hist;       // (n_steps,B,2,8) du_0/dx0 of every step of the persistent loop, or nullptr (k_sens)
+    int sweep_step;     // mode 2: the step whose solve the forward sweep differentiates (k_sens: 0, k_steps: the last)
+};
+
 struct StepArgs {
     int n_steps, model, M_sim, M, nknots, lap_wrap, freeze;
     int ocp_model;                          // the model of the shooting intervals (IHM2MPC_MODEL_FKIN6 / FDYN6 / FDYN6U); `model` is the plant's
@@ -237,15 +261,20 @@ struct StepArgs {
     int32_t *hist_st, *hist_it;             // (n_steps,B) or nullptr
     const ihm2::IrkTab *irk_tab;            // IRK = 1: the tableau of the shooting intervals' collocation step, in device memory
     const ihm2::IrkTab *sim_irk_tab;        // plant steps by collocation (python/main.py:395-400: Radau IIA x M_sim) instead of RK4 x M_sim; nullptr: RK4
+    const SensArgs *sens;                   // SENS = 1: the x0 sensitivities' block in device memory (h->sens_args); nullptr otherwise
 };
 
 }  // namespace
 
-// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0, 1, 2) returns the table of the ones it
+// kernels_sens.hip: the SensArgs of the handle's x0 sensitivities into *out (hist = nullptr, sweep_step = 0: k_sens' own).  (Through a
+// void pointer: a function with the unnamed namespace's type in its signature could not be defined in another translation unit.)
+void ihm2_sens_args(const ihm2mpc_handle *h, void *out);
+
+// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0, 1, 2, 3) returns the table of the ones it
 // holds, in its order of preference (kernels_qp.hip: QP_INSTANCES).  A key holds the template parameters as the launch record gives them
 // (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.
 enum { QP_WAVE = 1, QP_BLOCK = 2, QP_STEPS = 3 };
-struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn; };
+struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens; };
 struct QpInst { QpKey key; int threads; const void *kernel; };
 struct QpTable { const QpInst *inst; int n; };
-QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2();
+QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3();

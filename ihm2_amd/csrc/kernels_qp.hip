@@ -40,6 +40,7 @@
 #include "sqp_body.hpp"
 #include "irk_body.hpp"
 #include "riccati_mfma.hpp"
+#include "sens_body.hpp"
 
 using namespace ihm2;
 
@@ -1215,7 +1216,12 @@ __device__ __noinline__ void call_line_search(const LsArgs &ls, int b, int it, i
 // with the interval lanes).
 // DYN = 1: the shooting intervals carry a dynamic OCP model (StepArgs.ocp_model: fdyn6 or fdyn6u, chosen per launch); a template parameter so
 // that the kinematic kernels stay what they were (the run-time choice alone cost the benchmarked kernel 2 %: 988 k -> 968 k solves/s).
-template <int NSLOT, int NSOFT, int PATH, int UNI, int SQP, int IRK = 0, int DYN = 0>
+// SENS = 1 (RTI only, ihm2mpc_run_steps_sens): the x0 sensitivities of every step's solve -- (x, u) copied to StepArgs.sens->xbar / ubar after
+// the linearisation, where ihm2mpc_step takes its copy, and k_sens' body (sens_body.hpp) called after the QP: du_0/dx0 into sens_u0 and the
+// step's history row, in mode 2 the forward sweep over the horizon on the last step.  The body reuses the QP's LDS from offset 0 (the QP and
+// the linearisation write theirs before they read it).  A template parameter for the reason DYN is one: a run-time flag and the call it
+// guards would change the register allocation of the benchmarked kernels.
+template <int NSLOT, int NSOFT, int PATH, int UNI, int SQP, int IRK = 0, int DYN = 0, int SENS = 0>
 __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, const LsArgs *lsp)
 {
     // the loop's own arguments are read from device memory where they are used: as by-value kernel arguments they stayed in
@@ -1235,6 +1241,17 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
             if (s.hist_x0 && lane < 8) s.hist_x0[((size_t)t * B + b) * 8 + lane] = s.x0[(size_t)b * 8 + lane];
             if (s.hist_st && lane == 0) s.hist_st[(size_t)t * B + b] = a.status[b];
             if (s.hist_it && lane == 0) s.hist_it[(size_t)t * B + b] = 0;
+        }
+        if constexpr (SENS != 0) {          // no solve from here on: NaN gains, and a NaN horizon for the read-back of mode 2
+            const SensArgs &sa = *s.sens;
+            const int NS = N + 1;
+            if (sa.hist && lane < 16)
+                for (int t = step; t < s.n_steps; t++) sa.hist[((size_t)t * B + b) * 16 + lane] = NAN;
+            if (lane < 16) sa.sens_u0[(size_t)b * 16 + lane] = NAN;
+            if (sa.mode == 2) {
+                for (int e = lane; e < NS * 64; e += 64) sa.sens_x[(size_t)b * NS * 64 + e] = NAN;
+                for (int e = lane; e < N * 16; e += 64) sa.sens_u[(size_t)b * N * 16 + e] = NAN;
+            }
         }
     };
     for (int step = 0; step < s.n_steps; step++) {
@@ -1305,6 +1322,12 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
                 }
             }
             __syncthreads();
+            if constexpr (SENS != 0) {      // the point the QP is linearised at (api.hip: sens_snapshot)
+                const SensArgs &sa = *s.sens;
+                const int NS = N + 1;
+                for (int e = lane; e < NS * 8; e += 64) ((double *)sa.xbar)[(size_t)b * NS * 8 + e] = a.x[(size_t)b * NS * 8 + e];
+                for (int e = lane; e < N * 2; e += 64) ((double *)sa.ubar)[(size_t)b * N * 2 + e] = a.u[(size_t)b * N * 2 + e];
+            }
             if (it == 0) {
                 if (s.freeze) {     // python/main.py:503-504: a NaN plant state stops the car where it was
                     const double v = (lane < 8) ? s.x0[(size_t)b * 8 + lane] : 0.0;
@@ -1322,6 +1345,10 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
             // SQP loops 13-17 % and the soft / track-row loops 2-9 % (their register allocation tips into scratch); the stand-alone QP kernels take it
             qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, SQP ? 0 : 1>(a, b, sm, SQP || step + 1 == s.n_steps);
             __syncthreads();
+            if constexpr (SENS != 0) {
+                sens_body(*s.sens, b, sm, step);
+                __syncthreads();
+            }
             if (SQP) {
                 const int last = it == n_it - 1;
                 if constexpr (!DYN) call_line_search<IHM2MPC_MODEL_FKIN6, IRK != 0>(ls, b, it, last);
@@ -1345,16 +1372,16 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 
 }  // namespace
 
-// This file is compiled THREE times (Makefile): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
-// soft / track-row instantiations, QP_SET = 2 the persistent loop of the dynamic OCP models (all tables) -- same flags, same (default)
-// scheduler.  Separate objects are separate device code images: the benchmarked kernels' image does not move when another set grows.  `make ilp` builds both again under
+// This file is compiled FOUR times (Makefile): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
+// soft / track-row instantiations, QP_SET = 2 the persistent loop of the dynamic OCP models (all tables), QP_SET = 3 the persistent loop
+// with x0 sensitivities (SENS = 1) for every RTI loop of the sets 0 and 1 -- same flags, same (default) scheduler.  Separate objects are separate device code images: the benchmarked kernels' image does not move when another set grows.  `make ilp` builds both again under
 // LLVM's iterative ILP scheduler into the test artefact libihm2mpc_ilp.so (tests/test_gpu_configs.py compares the two builds).
 #ifndef QP_SET
-#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations) or -DQP_SET=2 (dynamic OCP models in the persistent loop)"
+#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop) or -DQP_SET=3 (the persistent loop with x0 sensitivities)"
 #endif
 // The instantiations of this object: its part of the catalogue api.hip selects from, which takes the first entry that holds a table,
 // so that an NSLOT comes before the larger ones of the same kind.  WAVE(NSLOT, NSOFT, PATH, UNI) k_qp_wave, BLOCK(NSLOT, UNI, NW)
-// k_qp_block, STEPS(NSLOT, NSOFT, PATH, UNI, IRK, DYN) k_steps in both SQP modes.
+// k_qp_block, STEPS(NSLOT, NSOFT, PATH, UNI, IRK, DYN) k_steps in both SQP modes (QP_SET = 3: in the RTI mode, with SENS = 1).
 #if QP_SET == 0
 #define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
     BLOCK(2, 0, 4) BLOCK(2, 1, 4)                                                                                                         \
@@ -1376,13 +1403,25 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
     STEPS(8, 2, 0, 1, 0, 1) STEPS(8, 2, 0, 1, 1, 1) STEPS(10, 4, 0, 1, 0, 1) STEPS(10, 4, 0, 1, 1, 1)                                     \
     STEPS(8, 0, 1, 1, 0, 1) STEPS(8, 0, 1, 1, 1, 1) STEPS(8, 3, 1, 1, 0, 1) STEPS(8, 3, 1, 1, 1, 1)                                       \
     STEPS(10, 4, 1, 1, 0, 1) STEPS(10, 4, 1, 1, 1, 1)
+#elif QP_SET == 3
+#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
+    STEPS(5, 0, 0, 0, 0, 0) STEPS(5, 0, 0, 1, 0, 0) STEPS(5, 0, 0, 1, 1, 0)                                                               \
+    STEPS(8, 0, 0, 0, 0, 0) STEPS(8, 0, 0, 1, 0, 0) STEPS(8, 0, 0, 1, 1, 0)                                                               \
+    STEPS(10, 0, 0, 1, 0, 0) STEPS(10, 0, 0, 1, 1, 0)                                                                                     \
+    STEPS(8, 2, 0, 1, 0, 0) STEPS(8, 2, 0, 1, 1, 0) STEPS(10, 4, 0, 1, 0, 0) STEPS(10, 4, 0, 1, 1, 0)                                     \
+    STEPS(8, 0, 1, 1, 0, 0) STEPS(8, 0, 1, 1, 1, 0) STEPS(8, 3, 1, 1, 0, 0) STEPS(8, 3, 1, 1, 1, 0)                                       \
+    STEPS(10, 4, 1, 1, 0, 0) STEPS(10, 4, 1, 1, 1, 0)
 #endif
 
 #define WAVE(NS, NO, PT, UN) {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0}, 64, (const void *)k_qp_wave<NS, NO, PT, UN>},
 #define BLOCK(NS, UN, NW) {{QP_BLOCK, NS, 0, 0, UN, 0, 0, 0}, 64 * NW, (const void *)k_qp_block<NS, UN, NW>},
+#if QP_SET == 3
+#define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 1>},
+#else
 #define STEPS(NS, NO, PT, UN, IR, DY)                                                                  \
     {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>}, \
     {{QP_STEPS, NS, NO, PT, UN, 1, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 1, IR, DY>},
+#endif
 #define QP_TABLE_(n) ihm2_qp_set##n
 #define QP_TABLE(n) QP_TABLE_(n)
 QpTable QP_TABLE(QP_SET)()      // (a host function's table stays out of the device code image)

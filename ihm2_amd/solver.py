@@ -252,10 +252,13 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_reserve_history(self._h, int(n_steps)))
 
     def run_steps(self, s_target: float, n_steps: int, model: int = 0, M_sim: int = 25, freeze: bool = False, lap_stop: float = np.inf,
-                  u0_hist=None, x0_hist=None, status_hist=None, qp_iter_hist=None, wait: bool = True):
+                  u0_hist=None, x0_hist=None, status_hist=None, qp_iter_hist=None, wait: bool = True, sens_u0_hist=None):
         """``n_steps`` control steps (plant + ``compute_control``) in one launch, every instance running ahead on its own
         wavefront (``ihm2mpc_run_steps``).  Histories are written into the given arrays -- ``(n_steps, B, 2)``, ``(n_steps, B, 8)``,
-        ``(n_steps, B)`` int32 twice -- or, for ``True``, into fresh ones; returns a dict of those that were asked for."""
+        ``(n_steps, B)`` int32 twice -- or, for ``True``, into fresh ones; returns a dict of those that were asked for.
+        ``sens_u0_hist`` (an array or ``True``): the loop with x0 sensitivities (``ihm2mpc_run_steps_sens``, needs
+        ``set_x0_sensitivities(1 or 2)``), ``out["sens_u0"]`` ``(n_steps, B, 2, 8)`` = ``du_0/dx_0`` of every step's solve; afterwards
+        ``get_x0_sensitivities`` reads the last step's."""
         n = int(n_steps)
         out = {}
         def buf(v, shape, dtype, name):
@@ -268,10 +271,14 @@ class BatchedOcpSolver:
             return a
         u = buf(u0_hist, (n, self.B, NU), np.float64, "u0"); x = buf(x0_hist, (n, self.B, NX), np.float64, "x0")
         st = buf(status_hist, (n, self.B), np.int32, "status"); it = buf(qp_iter_hist, (n, self.B), np.int32, "qp_iter")
-        _lib.check(self.lib.ihm2mpc_run_steps(
-            self._h, int(model), int(M_sim), float(s_target), n, int(bool(freeze)), float(lap_stop),
-            None if u is None else _ptr(u), None if x is None else _ptr(x),
-            None if st is None else st.ctypes.data_as(_lib.c_int32_p), None if it is None else it.ctypes.data_as(_lib.c_int32_p)))
+        hists = (None if u is None else _ptr(u), None if x is None else _ptr(x),
+                 None if st is None else st.ctypes.data_as(_lib.c_int32_p), None if it is None else it.ctypes.data_as(_lib.c_int32_p))
+        if sens_u0_hist is None or sens_u0_hist is False:
+            _lib.check(self.lib.ihm2mpc_run_steps(self._h, int(model), int(M_sim), float(s_target), n, int(bool(freeze)), float(lap_stop), *hists))
+        else:
+            k = buf(sens_u0_hist, (n, self.B, NU, NX), np.float64, "sens_u0")
+            _lib.check(self.lib.ihm2mpc_run_steps_sens(self._h, int(model), int(M_sim), float(s_target), n, int(bool(freeze)), float(lap_stop),
+                                                       *hists, _ptr(k)))
         if wait:
             self.synchronize()
         return out
@@ -412,7 +419,8 @@ class BatchedOcpSolver:
 
         ``qp``: the last per-step QP launch, e.g. ``"k_qp_wave<8,2,0,1>"`` (NSLOT, NSOFT, PATH, UNI) or ``"k_qp_block<2,1,4>"``
         (slots per thread, UNI, wavefronts); ``steps``: the last ``run_steps``, ``"k_steps<...>"`` (NSLOT, NSOFT, PATH, UNI, SQP, IRK,
-        DYN) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` / ``"not_resident"``.  ``None`` where nothing was launched yet."""
+        DYN, and an eighth 1 for the loop with x0 sensitivities) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` /
+        ``"not_resident"``.  ``None`` where nothing was launched yet."""
         rec = np.zeros(16, dtype=np.int32)
         _lib.check(self.lib.ihm2mpc_get_launch_record(self._h, rec.ctypes.data_as(_lib.c_int32_p)))
         r = [int(v) for v in rec]
@@ -423,7 +431,7 @@ class BatchedOcpSolver:
             qp = "k_qp_block<%d,%d,4>" % (r[1], r[4])
         steps, fallback = None, None
         if r[5] == 1:
-            steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13])
+            steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13]) if r[14] == 0 else "k_steps<%d,%d,%d,%d,%d,%d,%d,1>" % tuple(r[6:13])
         elif r[5] == 2:
             steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
         return {"qp": qp, "steps": steps, "steps_fallback": fallback}
@@ -447,7 +455,8 @@ class BatchedOcpSolver:
     # ---- sensitivities of the solution with respect to x0 (acados: eval_param_sens(j, 0, "ex"); get(k, "sens_x" / "sens_u")) ----
     def set_x0_sensitivities(self, mode: int = 2):
         """0 off; 1 ``du_0/dx_0`` only (the feedback gain K0); 2 the whole horizon.  Every later RTI ``solve`` /
-        ``compute_control`` / ``step`` computes them after its QP (refused in the SQP mode; ``run_steps`` computes none)."""
+        ``compute_control`` / ``step`` computes them after its QP (refused in the SQP mode; ``run_steps`` computes none unless it is
+        given ``sens_u0_hist``)."""
         _lib.check(self.lib.ihm2mpc_set_x0_sensitivities(self._h, int(mode)))
         self._sens_mode = int(mode)
 

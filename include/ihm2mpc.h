@@ -29,6 +29,7 @@
  *   ihm2mpc_step              <- one iteration of the MiL loop (plant + compute_control)  python/main.py:476-517
  *   ihm2mpc_run_steps         <- n iterations of that loop in one launch                  python/main.py:448-517
  *   ihm2mpc_set/get_x0_sensitivities <- solver.eval_param_sens(j, 0, "ex"); solver.get(k, "sens_x" / "sens_u") (acados)
+ *   ihm2mpc_run_steps_sens    <- the same after every solve of ihm2mpc_run_steps' loop
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -259,7 +260,8 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *   [5] last ihm2mpc_run_steps: 0 none yet, 1 one k_steps launch, 2 launches per step (ihm2mpc_step n_steps times);
  *       [6..12] the k_steps parameters NSLOT, NSOFT, PATH, UNI, SQP, IRK, DYN (0 when [5] != 1);
  *       [13] why it went per step: 0 it did not, 1 the configuration has no k_steps instantiation, 2 the batch exceeds the resident limit
- *   [14..15] 0 (reserved) */
+ *       [14] SENS: 1 the k_steps launch computed x0 sensitivities (ihm2mpc_run_steps_sens), 0 otherwise (0 when [5] != 1)
+ *   [15] 0 (reserved) */
 int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
 
 /* ---- sensitivities of the solution with respect to the initial state (acados: eval_param_sens(index, 0, "ex"), then
@@ -272,12 +274,13 @@ int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
  * mode: 0 off (the default), 1 du_0/dx_0 only (the feedback gain K0 of u0 + K0 (x - x0)), 2 the whole horizon.  Memory on first use.
  * While the mode is on, ihm2mpc_solve, ihm2mpc_compute_control and ihm2mpc_step take a copy of (x, u) after the linearisation and
  * launch the kernel after the QP of their last RTI iteration, in stream order.  Refused in the SQP mode (the line search scales the step
- * and the multipliers: no QP solution is returned).  ihm2mpc_run_steps computes none (the persistent loop is unchanged). */
+ * and the multipliers: no QP solution is returned).  ihm2mpc_run_steps computes none (the persistent loop is unchanged);
+ * ihm2mpc_run_steps_sens computes them at every step. */
 #define IHM2MPC_SENS_TAU 1e-9
 int ihm2mpc_set_x0_sensitivities(ihm2mpc_handle *h, int32_t mode);
 /* sens_x (B,N+1,8,8): sens_x[b][k][i][j] = d x_k,i / d x0_j (mode 2 only; stage 0 is the identity); sens_u: mode 1 (B,2,8) =
  * d u_0 / d x0, mode 2 (B,N,2,8) = d u_k / d x0.  Either pointer may be NULL.  NaN for instances whose status is neither 0 nor 2.
- * Refused before a solve with the mode on and after ihm2mpc_run_steps. */
+ * Refused before a solve with the mode on and after ihm2mpc_run_steps (after ihm2mpc_run_steps_sens: the last step's). */
 int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens_u);
 /* du_0 / dx0 (B,2,8) into device memory (either mode), stream-ordered like ihm2mpc_get_u0_device */
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr);
@@ -319,7 +322,7 @@ int ihm2mpc_get_u0_async(ihm2mpc_handle *h, double *pinned_dst);
  * one host-device round trip and one wait -- the call of a real-time controller (mpc_control_node.cpp:105-255). */
 int ihm2mpc_compute_control(ihm2mpc_handle *h, const double *x0, double s_target, double *u0, int32_t *status);
 /* device room for the histories of up to n_steps steps (run_steps grows it on demand; reserving keeps the allocations out of
- * a timed call) */
+ * a timed call); while an x0 sensitivity mode is on, also for the gain history of ihm2mpc_run_steps_sens */
 int ihm2mpc_reserve_history(ihm2mpc_handle *h, int32_t n_steps);
 /* n_steps control steps of the MiL loop (python/main.py:476-517: plant, reference ramp + shift, one RTI iteration) in ONE
  * launch: every instance runs its steps back to back on its own wavefront, so no instance waits for the slowest QP of the
@@ -342,6 +345,19 @@ int ihm2mpc_reserve_history(ihm2mpc_handle *h, int32_t n_steps);
  * launch keeps what an earlier call left). */
 int ihm2mpc_run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_target, int32_t n_steps, int32_t freeze,
                       double lap_stop, double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist);
+/* ihm2mpc_run_steps, and x0 sensitivities at every step (acados: eval_param_sens(j, 0, "ex") after each solve of the MiL loop).
+ * Needs x0 sensitivity mode 1 or 2 (ihm2mpc_set_x0_sensitivities; refused while it is off).
+ * sens_u0_hist (n_steps,B,2,8): du_0/dx0 of every step's solve, the value ihm2mpc_step followed by ihm2mpc_get_x0_sensitivities gives at
+ * that step -- bit for bit wherever ihm2mpc_run_steps equals n_steps x ihm2mpc_step bit for bit; may be NULL.  NaN where the solve's
+ * status is neither 0 nor 2 and, with freeze, on every step of a car that no longer solves, from the step it stopped (its u0 row is 0).
+ * Afterwards ihm2mpc_get_x0_sensitivities and ihm2mpc_get_sens_u0_device read the last step's (mode 2: its whole horizon; NaN for a car
+ * that did not solve it).  Every other output -- the four histories, x, u, pi, lam, the slacks -- is that of ihm2mpc_run_steps bit for bit.
+ * One launch of the persistent loop with the sensitivity kernel's body behind every QP (kinematic OCP, the tables ihm2mpc_run_steps takes
+ * in one launch); otherwise n_steps x ihm2mpc_step with the sensitivity kernel after each QP (freeze refused there, as in
+ * ihm2mpc_run_steps).  The history is copied in stream order like the others. */
+int ihm2mpc_run_steps_sens(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_target, int32_t n_steps, int32_t freeze,
+                           double lap_stop, double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist,
+                           double *sens_u0_hist);
 
 /* ---- Cartesian side of the ROS stack ----
  * Plants of the simulation node (src/ihm2/src/sim_node.cpp:197-257), state (X, Y, phi, v_x, v_y, r, T, delta): */

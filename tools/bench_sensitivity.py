@@ -4,9 +4,13 @@
   (a) batch B = 1024 and 8192: RTI steps (prepare_step + solve) with the mode 0, 1, 2; the handle's events time the QP phase
       (ihm2mpc_get_timings: from after the linearisation to after the last kernel of the solve), which with the mode on holds the
       sensitivity kernel as well -- its cost is the difference of the medians (the QPs are the same: every other output is bit-identical);
-  (b) the one-car controller: wall-clock latency of IHM2Controller.compute_control with and without x0_sensitivities=True.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] > result.json"""
+  (b) the one-car controller: wall-clock latency of IHM2Controller.compute_control with and without x0_sensitivities=True;
+  (c) closed loops of n control steps (bench.py's persistent setup: one untimed step, a warm-up call, then the timed call): plain
+      run_steps, run_steps_sens in mode 1 (the gain of every step into pinned memory) and n x step() with mode 1 and the gain read back
+      in stream order; solves/s and the time each adds per step.  B = 8192 takes launches per step in both run_steps calls.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops] > result.json"""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -61,12 +65,72 @@ def one_car_latency(sens, steps, warmup):
     return dict(p50_ms=float(np.median(lat)), p90_ms=float(np.percentile(lat, 90)))
 
 
+def loop_throughput(B, n, warmup, how):
+    """Solves/s over n control steps of configs[1]: how = "run_steps" (no sensitivities), "run_steps_sens" or "n_x_step" (mode 1)."""
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    ocp, track = bench.build_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    if how != "run_steps":
+        s.set_x0_sensitivities(1)
+    s.set_x0(bench.sample_x0(track, B, 20240607)); s.init_guess()
+    s.set_lap_wrap(True)
+    m = max(n, warmup, 1)
+    u0 = s.alloc_pinned((m, B, 2))
+    k = s.alloc_pinned((m, B, 2, 8)) if how != "run_steps" else None
+    s.reserve_history(m)
+    s.step(40.0, model=0, M_sim=25)
+    if how == "n_x_step":       # the gain of every step into a device history, as run_steps_sens keeps it when it launches per step
+        hip = ctypes.CDLL("libamdhip64.so")
+        dk = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(dk), ctypes.c_size_t(m * B * 16 * 8)) == 0
+
+    def run(steps):
+        if how == "n_x_step":
+            for i in range(steps):
+                s.step(40.0, model=0, M_sim=25)
+                s.get_u0_async(u0[i])
+                s.get_sens_u0_device(dk.value + i * B * 16 * 8)
+            return
+        kw = dict(sens_u0_hist=k[:steps]) if how == "run_steps_sens" else {}
+        s.run_steps(40.0, steps, model=0, M_sim=25, u0_hist=u0[:steps], wait=False, **kw)
+
+    if warmup:
+        run(warmup)
+    s.synchronize()
+    t0 = time.perf_counter()
+    run(n)
+    s.synchronize()
+    el = time.perf_counter() - t0
+    rec = s.get_launch_record()["steps"] if how != "n_x_step" else "per_step"
+    if how == "n_x_step":
+        assert hip.hipMemcpy(ctypes.c_void_p(k.ctypes.data), dk, ctypes.c_size_t(n * B * 16 * 8), 2) == 0      # hipMemcpyDeviceToHost
+        hip.hipFree(dk)
+    ok = float(np.isfinite(np.asarray(k[:n])).all(axis=(2, 3)).mean()) if k is not None else None
+    s.free()
+    return dict(solves_per_s=B * n / el, ms_per_step=el * 1e3 / n, launch=rec, finite_gain_rows=ok)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--loop-steps", default="20,500")
+    ap.add_argument("--only-loops", action="store_true")
     a = ap.parse_args()
-    out = {"batch": {}, "one_car": {}}
+    out = {"batch": {}, "one_car": {}, "loops": {}}
+    for B in (1024, 8192):
+        for n in (int(v) for v in a.loop_steps.split(",")):
+            if B == 8192 and n > 100:
+                continue        # launches per step: the rate does not depend on n
+            r = {how: loop_throughput(B, n, a.warmup, how) for how in ("run_steps", "run_steps_sens", "n_x_step")}
+            for how in ("run_steps_sens", "n_x_step"):
+                r[how]["added_ms_per_step"] = r[how]["ms_per_step"] - r["run_steps"]["ms_per_step"]
+            out["loops"][f"B{B}_n{n}"] = r
+            print(json.dumps({f"B{B}_n{n}": r}), file=sys.stderr, flush=True)
+    if a.only_loops:
+        print(json.dumps(out))
+        return
     for B in (1024, 8192):
         r = {m: batch_timings(B, m, a.steps, a.warmup) for m in (0, 1, 2)}
         for m in (1, 2):
