@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -44,14 +45,15 @@ namespace {
         HIP_TRY(hipSetDevice((h)->cfg.device));           \
     } while (0)
 
-template <typename T>
-int dalloc(T **p, size_t n)
+// Allocates a group of buffers, given as (buffer, elements) pairs, all or none: a failure releases what the call allocated and reports
+// the HIP error.  (A grower releases the group's old arrays first.)
+int alloc_all() { return 0; }
+
+template <typename T, typename... Rest>
+int alloc_all(DevBuf<T> &b, size_t n, Rest &&...rest)
 {
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-    HIP_TRY(hipMemset(*p, 0, n * sizeof(T)));
-    // the handle's streams are non-blocking: they do not wait for the null stream the fill runs on, and an upload that
-    // overtakes it would be zeroed afterwards
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(b.alloc(n));
+    if (alloc_all(rest...)) { b.reset(); return -1; }
     return 0;
 }
 
@@ -160,17 +162,16 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
 {
     const int B = h->B, NS = h->NS;
     h->inst_b_ok = false;
-    if (check_instance_pattern(h, h->ih_lb, h->ih_ub)) return -1;
+    if (check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
     const size_t n = (size_t)h->nslot_lane * 64;
-    if (n > h->i_slot_cap) {
-        if (h->i_slot_lb) { (void)hipFree(h->i_slot_lb); (void)hipFree(h->i_slot_ub); h->i_slot_lb = h->i_slot_ub = nullptr; }
-        h->i_slot_cap = 0;
-        if (dalloc(&h->i_slot_lb, (size_t)B * n) || dalloc(&h->i_slot_ub, (size_t)B * n)) return -1;
-        h->i_slot_cap = n;
+    if ((size_t)B * n > h->i_slot_lb.size()) {
+        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
+        h->i_slot_lb.reset(); h->i_slot_ub.reset();
+        if (alloc_all(h->i_slot_lb, (size_t)B * n, h->i_slot_ub, (size_t)B * n)) return -1;
     }
     std::vector<double> slb((size_t)B * n), sub((size_t)B * n), stl((size_t)B * NS * NC), stu((size_t)B * NS * NC);
     for (int b = 0; b < B; b++) {
-        const double *il = h->ih_lb + (size_t)b * NS * 12, *iu = h->ih_ub + (size_t)b * NS * 12;
+        const double *il = h->ih_lb.data() + (size_t)b * NS * 12, *iu = h->ih_ub.data() + (size_t)b * NS * 12;
         for (size_t e = 0; e < n; e++) {
             const int kc = h->host_kc[e], k = kc >> 4, c = kc & 15;
             double lo = h->host_slb[e], up = h->host_sub[e];
@@ -190,23 +191,6 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
     if (upload_shared(h, stl.data(), h->i_st_lb, stl.size()) || upload_shared(h, stu.data(), h->i_st_ub, stu.size())) return -1;
     h->inst_b_ok = true;
     return 0;
-}
-
-void free_instance_weights(ihm2mpc_handle *h)
-{
-    for (double *p : {h->iHs, h->iGy, h->iWd}) if (p) (void)hipFree(p);
-    h->iHs = h->iGy = h->iWd = nullptr;
-    h->inst_w = false;
-}
-
-void free_instance_bounds(ihm2mpc_handle *h)
-{
-    for (double *p : {h->i_slot_lb, h->i_slot_ub, h->i_st_lb, h->i_st_ub, h->i_lbu, h->i_ubu, h->i_lg, h->i_ug}) if (p) (void)hipFree(p);
-    h->i_slot_lb = h->i_slot_ub = h->i_st_lb = h->i_st_ub = h->i_lbu = h->i_ubu = h->i_lg = h->i_ug = nullptr;
-    h->i_slot_cap = 0;
-    delete[] h->ih_lb; delete[] h->ih_ub;
-    h->ih_lb = h->ih_ub = nullptr;
-    h->inst_b = false; h->inst_b_ok = false;
 }
 
 // ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
@@ -355,11 +339,11 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
     s.sqp_iters = sqp ? (h->cfg.nlp_solver_max_iter > 0 ? h->cfg.nlp_solver_max_iter : 1) : 0;
     s.s_ref = h->s_ref; s.kappa_ref = h->kappa_ref;
     s.x0 = h->x0; s.yref = h->yref; s.yref_e = h->yref_e; s.lin = h->lin;
-    s.active = (freeze || h->active_set) ? h->active : nullptr;
+    s.active = (freeze || h->active_set) ? h->active.get() : nullptr;
     s.hist_u0 = h->hist_u0; s.hist_x0 = h->hist_x0; s.hist_st = h->hist_st; s.hist_it = h->hist_it;
-    s.irk_tab = (const ihm2::IrkTab *)h->irk_tab;
-    s.sim_irk_tab = irk_plant ? (const ihm2::IrkTab *)h->sim_irk_tab : nullptr;
-    s.sens = sens ? (const SensArgs *)h->sens_args : nullptr;
+    s.irk_tab = h->irk_tab;
+    s.sim_irk_tab = irk_plant ? h->sim_irk_tab.get() : nullptr;
+    s.sens = sens ? (const SensArgs *)h->sens_args.get() : nullptr;
     // every field of s is set: upload it (and the line search's block in the SQP mode, the x0 sensitivities' block with SENS)
     static_assert(sizeof(StepArgs) <= 32 * sizeof(double), "step_args holds 256 bytes");
     static_assert(sizeof(ihm2::LsArgs) <= 64 * sizeof(double), "ls_args holds 512 bytes");
@@ -385,8 +369,8 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
         if (hipMemcpyAsync(h->sens_args, stage + 512, sizeof(SensArgs), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
     }
     if (hipEventRecord(h->args_ev[slot], h->stream) != hipSuccess) return 1;
-    const StepArgs *sdev = (const StepArgs *)h->step_args;
-    const ihm2::LsArgs *ls = (const ihm2::LsArgs *)h->ls_args;
+    const StepArgs *sdev = (const StepArgs *)h->step_args.get();
+    const ihm2::LsArgs *ls = (const ihm2::LsArgs *)h->ls_args.get();
     void *args[] = {&sdev, &a, &ls};
     launch_inst(h, e, args, lds);
     return 0;
@@ -465,6 +449,17 @@ int field_info(ihm2mpc_handle *h, const char *field, FieldInfo *fi)
 
 }  // namespace
 
+// Runs with the handle's device current.  Nothing of the handle's may still run when its streams and buffers go; the buffers release
+// themselves after this body.
+ihm2mpc_handle::~ihm2mpc_handle()
+{
+    for (hipStream_t s : {stream, stream2}) if (s) (void)hipStreamSynchronize(s);
+    (void)ihm2mpc_comm_free(this);
+    for (hipEvent_t e : {ev_fork, ev_join, ev[0], ev[1], ev[2], ev[3], args_ev[0], args_ev[1]}) if (e) (void)hipEventDestroy(e);
+    for (void *p : args_host) if (p) (void)hipHostFree(p);
+    for (hipStream_t s : {stream, stream2}) if (s) (void)hipStreamDestroy(s);
+}
+
 // classical RK4 is stable for |z| < 2.785 on the negative real axis: z = -(dt / M) / t for the first-order actuator lags
 static bool rk4_unstable(double dt, int M) { return dt / M / 1e-3 >= 2.78; }
 
@@ -500,52 +495,43 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail("libihm2mpc is built for gfx950 (MI355X) only; device %d is %s", cfg->device, prop.gcnArchName);
 
-    ihm2mpc_handle *h = new ihm2mpc_handle();
-    memset(h, 0, sizeof *h);
+    auto h = std::make_unique<ihm2mpc_handle>();     // value-initialised (ihm2mpc_internal.h); released on every failure below
     h->cfg = *cfg;
     h->B = cfg->batch;
     h->N = cfg->N;
     h->NS = cfg->N + 1;
     h->n_cu = prop.multiProcessorCount;
     { const char *e = getenv("IHM2MPC_BLOCK_QP"); h->block_qp = !(e && e[0] == '0'); }
-    const size_t B = h->B, N = h->N, NS = h->NS;
+    const size_t B = h->B, N = h->N, NS = h->NS, nt = (size_t)cfg->ntracks * cfg->nknots;
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&h->ev[i]));
-#define DA(p, n) if (dalloc(&h->p, (n))) return -1
-    DA(s_ref, (size_t)cfg->ntracks * cfg->nknots); DA(kappa_ref, (size_t)cfg->ntracks * cfg->nknots);
-    DA(track_id, B);
-    DA(Hs, NS * 100); DA(Gy, NS * 120); DA(lbx, NS * 8); DA(ubx, NS * 8); DA(lbu, N * 2); DA(ubu, N * 2);
-    DA(CD, N * 20); DA(lg, N * 2); DA(ug, N * 2);
-    DA(slot_kc_blk, 1024); DA(slot_lb_blk, 1024); DA(slot_ub_blk, 1024);
-    DA(slot_kc, MAX_SLOTS); DA(slot_lb, MAX_SLOTS); DA(slot_ub, MAX_SLOTS); DA(slot_zw, MAX_SLOTS); DA(slot_Zw, MAX_SLOTS);
-    DA(slk, B * NS * NLAM); DA(widths, (size_t)cfg->ntracks * 2); DA(lam_a, B * NS * 2); DA(slk_a, B * NS * 2);
-    h->alat_on = 0; h->slots_fit = true; h->alat_lb = -INFINITY; h->alat_ub = INFINITY; h->alat_sz[0] = h->alat_sz[1] = 0.0; h->alat_sZ[0] = h->alat_sZ[1] = -1.0;
-    DA(X_ref, (size_t)cfg->ntracks * cfg->nknots); DA(Y_ref, (size_t)cfg->ntracks * cfg->nknots); DA(phi_ref, (size_t)cfg->ntracks * cfg->nknots);
-    DA(xc, B * 8); DA(s_guess, B);
-    DA(step_args, 32);
     for (int i = 0; i < 2; i++) {      // pinned staging of the persistent loop's argument blocks (uploaded without a host wait)
         HIP_TRY(hipHostMalloc(&h->args_host[i], 1024, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&h->args_ev[i], hipEventDisableTiming));
     }
-    DA(Wd, N * 144 + 64); DA(st_lb, NS * NC); DA(st_ub, NS * NC); DA(st_sz, NS * NLAM); DA(st_sZ, NS * NLAM);
+    if (alloc_all(h->s_ref, nt, h->kappa_ref, nt, h->track_id, B, h->Hs, NS * 100, h->Gy, NS * 120, h->lbx, NS * 8, h->ubx, NS * 8,
+                  h->lbu, N * 2, h->ubu, N * 2, h->CD, N * 20, h->lg, N * 2, h->ug, N * 2, h->slot_kc_blk, 1024, h->slot_lb_blk, 1024,
+                  h->slot_ub_blk, 1024, h->slot_kc, MAX_SLOTS, h->slot_lb, MAX_SLOTS, h->slot_ub, MAX_SLOTS, h->slot_zw, MAX_SLOTS,
+                  h->slot_Zw, MAX_SLOTS, h->slk, B * NS * NLAM, h->widths, (size_t)cfg->ntracks * 2, h->lam_a, B * NS * 2, h->slk_a, B * NS * 2,
+                  h->X_ref, nt, h->Y_ref, nt, h->phi_ref, nt, h->xc, B * 8, h->s_guess, B, h->step_args, 32, h->Wd, N * 144 + 64,
+                  h->st_lb, NS * NC, h->st_ub, NS * NC, h->st_sz, NS * NLAM, h->st_sZ, NS * NLAM, h->x, B * NS * 8, h->u, B * N * 2, h->x0, B * 8,
+                  h->yref, B * N * 12, h->yref_e, B * 8, h->pi, B * NS * 8, h->lam, B * NS * NLAM, h->res, B * 4, h->qp_res, B * 4, h->status, B,
+                  h->qp_iter, B, h->active, B, h->u0, B * 2,
+                  h->lin, (B * N + B) * LIN_REC,      // + one spare record per instance (the kinematic plant's, never read)
+                  h->q_g, B * NS * 10, h->q_rg, B * NS * 10, h->q_P, B * NS * 64, h->q_M, (B * N + 2 * QM_PAD) * 64, h->scratch, B * 24))
+        return -1;
+    h->alat_on = 0; h->slots_fit = true; h->alat_lb = -INFINITY; h->alat_ub = INFINITY; h->alat_sz[0] = h->alat_sz[1] = 0.0; h->alat_sZ[0] = h->alat_sZ[1] = -1.0;
     h->sqp_globalization = 0; h->sqp_use_suff = 0; h->sqp_full_step_dual = 0;
     h->sqp_alpha_min = 0.05; h->sqp_alpha_red = 0.7; h->sqp_eps = 1e-4;
     for (int i = 0; i < 4; i++) h->sqp_tol[i] = cfg->nlp_tol;
-    h->host_lb = new double[NS * NC]; h->host_ub = new double[NS * NC];
-    h->host_sz = new double[NS * NLAM]; h->host_sZ = new double[NS * NLAM];
-    h->host_kc = new int32_t[MAX_SLOTS]; h->host_slb = new double[MAX_SLOTS]; h->host_sub = new double[MAX_SLOTS];
-    for (size_t i = 0; i < NS * NC; i++) { h->host_lb[i] = -INFINITY; h->host_ub[i] = INFINITY; }
-    for (size_t i = 0; i < NS * NLAM; i++) { h->host_sz[i] = 0.0; h->host_sZ[i] = -1.0; }
-    DA(x, B * NS * 8); DA(u, B * N * 2); DA(x0, B * 8); DA(yref, B * N * 12); DA(yref_e, B * 8);
-    DA(pi, B * NS * 8); DA(lam, B * NS * NLAM); DA(res, B * 4); DA(qp_res, B * 4); DA(status, B); DA(qp_iter, B); DA(active, B); DA(u0, B * 2);
-    DA(lin, (B * N + B) * LIN_REC);      // + one spare record per instance (the kinematic plant's, never read)
-    DA(q_g, B * NS * 10); DA(q_rg, B * NS * 10); DA(q_P, B * NS * 64); DA(q_M, (B * N + 2 * QM_PAD) * 64); DA(scratch, B * 24);
-#undef DA
-    if (ihm2_upload_irk_tab(h)) return fail("could not upload the collocation tableau");
-    *out = h;
+    h->host_lb.assign(NS * NC, -INFINITY); h->host_ub.assign(NS * NC, INFINITY);
+    h->host_sz.assign(NS * NLAM, 0.0); h->host_sZ.assign(NS * NLAM, -1.0);
+    h->host_kc.resize(MAX_SLOTS); h->host_slb.resize(MAX_SLOTS); h->host_sub.resize(MAX_SLOTS);
+    if (ihm2_upload_irk_tab(h.get())) return fail("could not upload the collocation tableau");
+    *out = h.release();
     return 0;
 }
 
@@ -553,25 +539,6 @@ int ihm2mpc_free(ihm2mpc_handle *h)
 {
     if (!h) return 0;
     (void)hipSetDevice(h->cfg.device);
-    (void)hipStreamSynchronize(h->stream);
-    (void)ihm2mpc_comm_free(h);
-    void *ptrs[] = {h->s_ref, h->kappa_ref, h->track_id, h->Hs, h->Gy, h->lbx, h->ubx, h->lbu, h->ubu, h->CD, h->lg, h->ug,
-                    h->slot_kc, h->slot_lb, h->slot_ub, h->slot_zw, h->slot_Zw, h->slk, h->lam_a, h->slk_a, h->widths, h->X_ref, h->Y_ref, h->phi_ref, h->xc, h->s_guess, h->x, h->u, h->x0, h->yref, h->yref_e, h->pi, h->lam, h->res, h->qp_res, h->dyn10, h->ls_phi, h->slot_kc_blk, h->slot_lb_blk, h->slot_ub_blk,
-                    h->status, h->qp_iter, h->active, h->u0, h->lin, h->q_g, h->q_rg, h->q_P, h->q_M, h->scratch, h->step_args, h->Wd, h->st_lb, h->st_ub, h->st_sz, h->st_sZ,
-                    h->ls_x, h->ls_u, h->ls_pi, h->ls_lam, h->ls_slk, h->ls_wpi, h->ls_wlam, h->ls_alpha, h->ls_args, h->ls_done, h->ls_status, h->ls_iter, h->ls_qp_acc, h->ls_pending, h->irk_tab, h->sim_irk_tab,
-                    h->hist_u0, h->hist_x0, h->hist_st, h->hist_it, h->sens_xbar, h->sens_ubar, h->sens_u0, h->sens_x, h->sens_u,
-                    h->sens_args, h->hist_k};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    free_instance_weights(h);
-    free_instance_bounds(h);
-    delete[] h->host_lb; delete[] h->host_ub; delete[] h->host_sz; delete[] h->host_sZ;
-    delete[] h->host_kc; delete[] h->host_slb; delete[] h->host_sub;
-    for (int i = 0; i < 4; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    for (int i = 0; i < 2; i++) { if (h->args_host[i]) (void)hipHostFree(h->args_host[i]); if (h->args_ev[i]) (void)hipEventDestroy(h->args_ev[i]); }
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return 0;
 }
@@ -614,21 +581,16 @@ int ihm2mpc_build_tracks(ihm2mpc_handle *h, int32_t max_seg, const int32_t *nseg
     for (int t = 0; t < h->cfg.ntracks; t++)
         if (nseg[t] < 2 || nseg[t] > max_seg) return fail("track %d has %d spline segments (2 .. max_seg = %d)", t, nseg[t], max_seg);
     const size_t nc = (size_t)h->cfg.ntracks * max_seg;
-    double *dev = nullptr;
-    int32_t *dseg = nullptr;
-    HIP_TRY(hipMalloc((void **)&dev, nc * 9 * sizeof(double)));
-    if (hipMalloc((void **)&dseg, h->cfg.ntracks * sizeof(int32_t)) != hipSuccess) { (void)hipFree(dev); return fail("out of device memory"); }
+    DevBuf<double> dev;
+    DevBuf<int32_t> dseg;
+    HIP_TRY(dev.alloc(nc * 9));
+    if (dseg.alloc(h->cfg.ntracks) != hipSuccess) return fail("out of device memory");
     double *cX = dev, *cY = dev + nc * 4, *work = dev + nc * 8;
-    int rc = 0;
     if (hipMemcpyAsync(cX, coeffs_X, nc * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(cY, coeffs_Y, nc * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipMemcpyAsync(dseg, nseg, h->cfg.ntracks * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail("upload of the spline coefficients failed");
-    if (!rc) {
-        ihm2_launch_build_tracks(h, max_seg, dseg, cX, cY, work);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) rc = fail("track-table kernels failed");
-    }
-    (void)hipFree(dev); (void)hipFree(dseg);
-    if (rc) return rc;
+        hipMemcpyAsync(dseg, nseg, h->cfg.ntracks * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail("upload of the spline coefficients failed");
+    ihm2_launch_build_tracks(h, max_seg, dseg, cX, cY, work);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return fail("track-table kernels failed");
     h->tracks_set = true; h->geometry_set = true;
     return 0;
 }
@@ -643,26 +605,20 @@ int ihm2mpc_fit_tracks(ihm2mpc_handle *h, int32_t max_pts, const int32_t *npts, 
     for (int t = 0; t < nt; t++)
         if (npts[t] < 3 || npts[t] > max_pts) return fail("track %d has %d centre-line points (3 .. max_pts = %d)", t, npts[t], max_pts);
     const size_t m = 7 * (size_t)max_pts, nwork = (size_t)nt * m * (m + 2), nxy = (size_t)nt * max_pts * 2, nc = (size_t)nt * max_pts * 4;
-    double *dev = nullptr;
-    int32_t *di = nullptr;
-    HIP_TRY(hipMalloc((void **)&dev, (nwork + nxy + 2 * nc) * sizeof(double)));
-    if (hipMalloc((void **)&di, 2 * (size_t)nt * sizeof(int32_t)) != hipSuccess) { (void)hipFree(dev); return fail("out of device memory"); }
+    DevBuf<double> dev;          // zero-filled: cX, cY past a track's 4 npts coefficients stay 0
+    DevBuf<int32_t> di;
+    HIP_TRY(dev.alloc(nwork + nxy + 2 * nc));
+    if (di.alloc(2 * (size_t)nt) != hipSuccess) return fail("out of device memory");
     double *work = dev, *dxy = dev + nwork, *cX = dxy + nxy, *cY = cX + nc;
     std::vector<int32_t> flags(nt, 1);
-    int rc = 0;
     if (hipMemcpyAsync(dxy, xy, nxy * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipMemcpyAsync(di, npts, nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipMemsetAsync(cX, 0, 2 * nc * sizeof(double), h->stream) != hipSuccess) rc = fail("upload of the centre lines failed");
-    if (!rc) {
-        ihm2_launch_track_fit(h, max_pts, di, dxy, curv_weight, work, cX, cY, di + nt);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(coeffs_X, cX, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipMemcpyAsync(coeffs_Y, cY, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipMemcpyAsync(flags.data(), di + nt, nt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) rc = fail("spline-fit kernel failed");
-    }
-    (void)hipFree(dev); (void)hipFree(di);
-    if (rc) return rc;
+        hipMemcpyAsync(di, npts, nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail("upload of the centre lines failed");
+    ihm2_launch_track_fit(h, max_pts, di, dxy, curv_weight, work, cX, cY, di + nt);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(coeffs_X, cX, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipMemcpyAsync(coeffs_Y, cY, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipMemcpyAsync(flags.data(), di + nt, nt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) return fail("spline-fit kernel failed");
     for (int t = 0; t < nt; t++)
         if (flags[t]) return fail("the spline fit of track %d is singular (coincident centre-line points?)", t);
     return 0;
@@ -727,7 +683,8 @@ int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const doubl
 {
     CHECK_H(h);
     if (!W && !W_e) {
-        free_instance_weights(h);
+        h->iHs.reset(); h->iGy.reset(); h->iWd.reset();
+        h->inst_w = false;
         h->uniform_H = h->shared_uniform_H;
         return 0;
     }
@@ -749,10 +706,7 @@ int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const doubl
         std::memcpy(&Wd[(size_t)b * 208], Wb, 144 * sizeof(double));
         std::memcpy(&Wd[(size_t)b * 208 + 144], Web, 64 * sizeof(double));
     }
-    if (!h->iHs && (dalloc(&h->iHs, (size_t)B * 200) || dalloc(&h->iGy, (size_t)B * 240) || dalloc(&h->iWd, (size_t)B * 208))) {
-        free_instance_weights(h);
-        return -1;
-    }
+    if (!h->iHs && alloc_all(h->iHs, (size_t)B * 200, h->iGy, (size_t)B * 240, h->iWd, (size_t)B * 208)) return -1;
     if (upload_shared(h, Hs.data(), h->iHs, Hs.size()) || upload_shared(h, Gy.data(), h->iGy, Gy.size()) ||
         upload_shared(h, Wd.data(), h->iWd, Wd.size()))
         return -1;
@@ -877,8 +831,8 @@ static int rebuild_slots(ihm2mpc_handle *h)
         if (upload_shared(h, lbb.data(), h->slot_lb_blk, lbb.size()) || upload_shared(h, ubb.data(), h->slot_ub_blk, ubb.size())) return -1;
         h->nslot_lane_blk = per_blk;
     }
-    if (upload_shared(h, h->host_lb, h->st_lb, (size_t)NS * NC) || upload_shared(h, h->host_ub, h->st_ub, (size_t)NS * NC) ||
-        upload_shared(h, h->host_sz, h->st_sz, (size_t)NS * NLAM) || upload_shared(h, h->host_sZ, h->st_sZ, (size_t)NS * NLAM))
+    if (upload_shared(h, h->host_lb.data(), h->st_lb, (size_t)NS * NC) || upload_shared(h, h->host_ub.data(), h->st_ub, (size_t)NS * NC) ||
+        upload_shared(h, h->host_sz.data(), h->st_sz, (size_t)NS * NLAM) || upload_shared(h, h->host_sZ.data(), h->st_sZ, (size_t)NS * NLAM))
         return -1;
     for (size_t e = 0; e < n; e++) { h->host_kc[e] = kc[e]; h->host_slb[e] = slb[e]; h->host_sub[e] = sub[e]; }
     if (n) {
@@ -938,12 +892,17 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
 {
     CHECK_H(h);
     const bool none = !lbx && !ubx && !lbu && !ubu && !lg && !ug;
-    if (none) { free_instance_bounds(h); return 0; }
+    if (none) {
+        h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset();
+        h->i_lbu.reset(); h->i_ubu.reset(); h->i_lg.reset(); h->i_ug.reset();
+        h->ih_lb = std::vector<double>(); h->ih_ub = std::vector<double>();
+        h->inst_b = false; h->inst_b_ok = false;
+        return 0;
+    }
     if (!lbx || !ubx || !lbu || !ubu || !lg || !ug) return fail("lbx, ubx, lbu, ubu, lg, ug must all be given, or all be NULL (batch-shared bounds again)");
     if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called (the batch-shared table gives the pattern)");
     const int B = h->B, N = h->N, NS = h->NS;
-    double *il = new double[(size_t)B * NS * 12], *iu = new double[(size_t)B * NS * 12];
-    auto bad = [&](int rc) { delete[] il; delete[] iu; return rc; };
+    std::vector<double> il((size_t)B * NS * 12), iu((size_t)B * NS * 12);
     for (int b = 0; b < B; b++)
         for (int k = 0; k < NS; k++)
             for (int c = 0; c < 12; c++) {
@@ -951,24 +910,18 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
                 if (c < 8) { if (k >= 1) { lb = lbx[((size_t)b * NS + k) * 8 + c]; ub = ubx[((size_t)b * NS + k) * 8 + c]; } }
                 else if (c < 10) { if (k < N) { lb = lbu[((size_t)b * N + k) * 2 + c - 8]; ub = ubu[((size_t)b * N + k) * 2 + c - 8]; } }
                 else { if (k < N) { lb = lg[((size_t)b * N + k) * 2 + c - 10]; ub = ug[((size_t)b * N + k) * 2 + c - 10]; } }
-                if (lb != lb || ub != ub) return bad(fail("instance %d, stage %d, row %d (%s): bound is NaN", b, k, c, row_name(c)));
-                if (lb > ub) return bad(fail("instance %d, stage %d, row %d (%s): lower bound %g > upper bound %g", b, k, c, row_name(c), lb, ub));
+                if (lb != lb || ub != ub) return fail("instance %d, stage %d, row %d (%s): bound is NaN", b, k, c, row_name(c));
+                if (lb > ub) return fail("instance %d, stage %d, row %d (%s): lower bound %g > upper bound %g", b, k, c, row_name(c), lb, ub);
                 il[((size_t)b * NS + k) * 12 + c] = (std::fabs(lb) < 1e20) ? lb : -INFINITY;      // as ihm2mpc_set_bounds
                 iu[((size_t)b * NS + k) * 12 + c] = (std::fabs(ub) < 1e20) ? ub : INFINITY;
             }
     // the pattern check before anything of the handle changes
-    if (check_instance_pattern(h, il, iu)) return bad(-1);
-    if (!h->i_st_lb) {
-        const size_t nb = (size_t)B;
-        if (dalloc(&h->i_st_lb, nb * NS * NC) || dalloc(&h->i_st_ub, nb * NS * NC) || dalloc(&h->i_lbu, nb * N * 2) || dalloc(&h->i_ubu, nb * N * 2) ||
-            dalloc(&h->i_lg, nb * N * 2) || dalloc(&h->i_ug, nb * N * 2)) {
-            bad(0);
-            free_instance_bounds(h);
-            return -1;
-        }
-    }
-    delete[] h->ih_lb; delete[] h->ih_ub;
-    h->ih_lb = il; h->ih_ub = iu;
+    if (check_instance_pattern(h, il.data(), iu.data())) return -1;
+    const size_t nb = (size_t)B;
+    if (!h->i_st_lb && alloc_all(h->i_st_lb, nb * NS * NC, h->i_st_ub, nb * NS * NC, h->i_lbu, nb * N * 2, h->i_ubu, nb * N * 2,
+                                 h->i_lg, nb * N * 2, h->i_ug, nb * N * 2))
+        return -1;
+    h->ih_lb = std::move(il); h->ih_ub = std::move(iu);
     if (upload_shared(h, lbu, h->i_lbu, (size_t)B * N * 2) || upload_shared(h, ubu, h->i_ubu, (size_t)B * N * 2) ||
         upload_shared(h, lg, h->i_lg, (size_t)B * N * 2) || upload_shared(h, ug, h->i_ug, (size_t)B * N * 2))
         return -1;
@@ -1170,11 +1123,9 @@ static int sqp_buffers(ihm2mpc_handle *h)
 {
     if (h->ls_x) return 0;
     const size_t B = h->B, N = h->N, NS = h->NS;
-#define DA(p, n) if (dalloc(&h->p, (n))) return -1
-    DA(ls_x, B * NS * 8); DA(ls_u, B * N * 2); DA(ls_pi, B * NS * 8); DA(ls_lam, B * NS * NLAM); DA(ls_slk, B * NS * NLAM);
-    DA(ls_wpi, B * NS * 8); DA(ls_wlam, B * NS * NLAM); DA(ls_alpha, B); DA(ls_args, 64); DA(ls_done, B); DA(ls_status, B); DA(ls_iter, B); DA(ls_qp_acc, B);
-#undef DA
-    return 0;
+    return alloc_all(h->ls_x, B * NS * 8, h->ls_u, B * N * 2, h->ls_pi, B * NS * 8, h->ls_lam, B * NS * NLAM, h->ls_slk, B * NS * NLAM,
+                     h->ls_wpi, B * NS * 8, h->ls_wlam, B * NS * NLAM, h->ls_alpha, B, h->ls_args, 64, h->ls_done, B, h->ls_status, B,
+                     h->ls_iter, B, h->ls_qp_acc, B, h->ls_pending, B);
 }
 
 // SQP mode with the collocation integrator: room for the line search's trial-point rollouts (every step length of the ladder)
@@ -1194,14 +1145,10 @@ static int sqp_phi_buffer(ihm2mpc_handle *h, int *n_alpha_out)
     const size_t B = h->B, N = h->N;
     const int n_alpha = ladder_length(h->sqp_alpha_min, h->sqp_alpha_red);
     if (n_alpha > IHM2MPC_LS_MAX_TRIALS) return fail("backtracking ladder longer than %d trial steps", IHM2MPC_LS_MAX_TRIALS);
-    if (!h->ls_phi || h->ls_nalpha < n_alpha) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->ls_phi) (void)hipFree(h->ls_phi);
-        h->ls_phi = nullptr;
-        HIP_TRY(hipMalloc((void **)&h->ls_phi, (size_t)n_alpha * B * N * 8 * sizeof(double)));
-        h->ls_nalpha = n_alpha;
+    if (h->ls_phi.size() < (size_t)n_alpha * B * N * 8) {
+        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old one
+        HIP_TRY(h->ls_phi.alloc((size_t)n_alpha * B * N * 8));
     }
-    if (!h->ls_pending) HIP_TRY(hipMalloc((void **)&h->ls_pending, (size_t)B * sizeof(int32_t)));
     if (n_alpha_out) *n_alpha_out = n_alpha;
     return 0;
 }
@@ -1385,13 +1332,9 @@ int ihm2mpc_set_x0_sensitivities(ihm2mpc_handle *h, int32_t mode)
         return fail("x0 sensitivities are implemented for SQP_RTI: in the SQP mode the line search scales the step and the multipliers, "
                     "which leaves no QP solution to differentiate");
     const size_t B = h->B, N = h->N, NS = h->NS;
-    if (mode >= 1 && !h->sens_u0) {
-        if (dalloc(&h->sens_xbar, B * NS * NX) || dalloc(&h->sens_ubar, B * N * NU) || dalloc(&h->sens_u0, B * NU * NX) || dalloc(&h->sens_args, 64))
-            return -1;
-    }
-    if (mode == 2 && !h->sens_x) {
-        if (dalloc(&h->sens_x, B * NS * NX * NX) || dalloc(&h->sens_u, B * N * NU * NX)) return -1;
-    }
+    if (mode >= 1 && !h->sens_u0 && alloc_all(h->sens_xbar, B * NS * NX, h->sens_ubar, B * N * NU, h->sens_u0, B * NU * NX, h->sens_args, 64))
+        return -1;
+    if (mode == 2 && !h->sens_x && alloc_all(h->sens_x, B * NS * NX * NX, h->sens_u, B * N * NU * NX)) return -1;
     if (mode != h->sens_mode) h->sens_state = 0;
     h->sens_mode = mode;
     return 0;
@@ -1459,7 +1402,7 @@ int ihm2mpc_sim_advance(ihm2mpc_handle *h, int32_t model, int32_t M_sim)
     if (M_sim < 1) return fail("M_sim must be >= 1");
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
-    ihm2_launch_sim(h, model, M_sim, h->x0, h->u0, h->x0, h->stream, h->active_set ? h->active : nullptr);
+    ihm2_launch_sim(h, model, M_sim, h->x0, h->u0, h->x0, h->stream, h->active_set ? h->active.get() : nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1535,7 +1478,7 @@ int ihm2mpc_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_targe
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
     HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-    ihm2_launch_sim(h, model, M_sim, h->x0, h->u0, h->x0, h->stream2, h->active_set ? h->active : nullptr);
+    ihm2_launch_sim(h, model, M_sim, h->x0, h->u0, h->x0, h->stream2, h->active_set ? h->active.get() : nullptr);
     ihm2_launch_prepare(h, s_target, 1, h->stream2);
     HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
     ihm2_launch_prepare(h, s_target, 2, h->stream);
@@ -1561,19 +1504,15 @@ int ihm2mpc_reserve_history(ihm2mpc_handle *h, int32_t n_steps)
     CHECK_H(h);
     if (n_steps < 1) return fail("n_steps must be >= 1");
     const size_t B = h->B, n = n_steps;
-    if (h->hist_cap < n) {
+    // (a run_steps(wait = false) launch may still write the old buffers)
+    if (h->hist_u0.size() < n * B * 2) {
         HIP_TRY(hipStreamSynchronize(h->stream));
-        for (void *p : {(void *)h->hist_u0, (void *)h->hist_x0, (void *)h->hist_st, (void *)h->hist_it}) if (p) (void)hipFree(p);
-        h->hist_u0 = h->hist_x0 = nullptr; h->hist_st = h->hist_it = nullptr; h->hist_cap = 0;
-        if (dalloc(&h->hist_u0, n * B * 2) || dalloc(&h->hist_x0, n * B * 8) || dalloc(&h->hist_st, n * B) || dalloc(&h->hist_it, n * B)) return -1;
-        h->hist_cap = n;
+        h->hist_u0.reset(); h->hist_x0.reset(); h->hist_st.reset(); h->hist_it.reset();
+        if (alloc_all(h->hist_u0, n * B * 2, h->hist_x0, n * B * 8, h->hist_st, n * B, h->hist_it, n * B)) return -1;
     }
-    if (h->sens_mode && h->hist_k_cap < n) {
+    if (h->sens_mode && h->hist_k.size() < n * B * NU * NX) {
         HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->hist_k) (void)hipFree(h->hist_k);
-        h->hist_k = nullptr; h->hist_k_cap = 0;
-        if (dalloc(&h->hist_k, n * B * NU * NX)) return -1;
-        h->hist_k_cap = n;
+        HIP_TRY(h->hist_k.alloc(n * B * NU * NX));
     }
     return 0;
 }
@@ -1698,7 +1637,7 @@ int ihm2mpc_sim_step_dyn10(ihm2mpc_handle *h, int32_t M_sim, const double *x, co
     if (M_sim < 1) return fail("M_sim must be >= 1");
     const bool irk = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;
     if (!irk && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the torque lags (t_T = 1e-3 s): use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
-    if (!h->dyn10) { HIP_TRY(hipMalloc((void **)&h->dyn10, (size_t)h->B * 35 * sizeof(double))); }
+    if (!h->dyn10) HIP_TRY(h->dyn10.alloc((size_t)h->B * 35));
     double *xs = h->dyn10, *us = h->dyn10 + (size_t)h->B * 15, *xn = h->dyn10 + (size_t)h->B * 20;
     if (upload(h, x, xs, 15) || upload(h, u, us, 5)) return -1;
     // the handle's plant integrator (python/main.py:395-400: IRK, GAUSS_RADAU_IIA): collocation steps of at most dt / M_sim, each

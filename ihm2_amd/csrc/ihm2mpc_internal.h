@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/ihm2mpc.h"
 
 // Floating-point contraction.  The sources are compiled with -ffp-contract=on (Makefile) and switch to `fast` HERE, for everything that follows in
@@ -32,8 +34,48 @@
 #define LIN_REC 96   // doubles per (instance, interval) linearisation record: A (64) | B (16) | b (8) | rb (8: the QP's dynamics residual, riccati_mfma.hpp)
 
 struct ihm2mpc_comm;      // comm.hip: RCCL communicator + staging buffers of a one-process-per-GPU job
+namespace ihm2 { struct IrkTab; }
 
+// The owner of one device array (host code only).  alloc(n) gives n elements, zero-filled: the fill runs on the null stream and is waited
+// for, since the handle's streams are non-blocking and an upload that overtook it would be zeroed afterwards.  It converts to T *, which
+// the argument blocks and the launches take.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    // the old array is released first; on failure the buffer is empty
+    hipError_t alloc(size_t n)
+    {
+        reset();
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, n * sizeof(T));
+        if (e == hipSuccess) e = hipMemset(q, 0, n * sizeof(T));
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) { (void)hipFree(q); return e; }
+        p_ = (T *)q; n_ = n;
+        return hipSuccess;
+    }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr; n_ = 0;
+    }
+    size_t size() const { return n_; }     // elements
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// Created by value-initialisation (std::make_unique<ihm2mpc_handle>() in ihm2mpc_create): there is no user-provided constructor, so every
+// scalar member starts at zero and every buffer empty.  The destructor (api.hip) waits for both streams and releases what is not a buffer.
 struct ihm2mpc_handle {
+    ~ihm2mpc_handle();
+
     ihm2mpc_config cfg;
     ihm2mpc_comm *comm;            // nullptr until ihm2mpc_comm_init
     int B, N, NS;
@@ -46,88 +88,89 @@ struct ihm2mpc_handle {
     bool uniform_H, uniform_CD;    // stage Hessians / general rows identical for all k < N (QP kernel keeps them in LDS)
 
     // ---- shared problem data (device) ----
-    double *s_ref, *kappa_ref;     // (ntracks, nknots)
-    int32_t *track_id;             // (B)
-    double *Hs;                    // (NS,10,10)  cost_scale * V'WV ; terminal: W_e padded with I
-    double *Gy;                    // (NS,10,12)  cost_scale * V'W  ; terminal: W_e in the first 8x8
-    double *lbx, *ubx;             // (NS,8)
-    double *lbu, *ubu;             // (N,2)
-    double *CD;                    // (N,2,10)  general rows [C D]
-    double *lg, *ug;               // (N,2)
+    DevBuf<double> s_ref, kappa_ref;     // (ntracks, nknots)
+    DevBuf<int32_t> track_id;            // (B)
+    DevBuf<double> Hs;                   // (NS,10,10)  cost_scale * V'WV ; terminal: W_e padded with I
+    DevBuf<double> Gy;                   // (NS,10,12)  cost_scale * V'W  ; terminal: W_e in the first 8x8
+    DevBuf<double> lbx, ubx;             // (NS,8)
+    DevBuf<double> lbu, ubu;             // (N,2)
+    DevBuf<double> CD;                   // (N,2,10)  general rows [C D]
+    DevBuf<double> lg, ug;               // (N,2)
     // compact table of the constraint slots that have at least one finite side
     // -- laid out for the QP kernel: entry lane + 64 r belongs to lane `lane`; a lane's soft slots come first --
     int nslots, m_act;             // m_act: number of one-sided inequality pairs (finite sides + one per soft slack)
     int nslot_lane, nsoft_lane;    // slots per lane / leading one-sided entries per lane (the NSOFT of the instantiation that takes the table; 0: all-hard)
     bool slots_fit;                // false: the rows set so far fit no instantiation (reported by the next solve: a later setter may still change them)
-    int32_t *slot_kc;              // (nslot_lane*64) stage * 16 + row, -1 = padding
-    int32_t *slot_kc_blk;          // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
-    double *slot_lb_blk, *slot_ub_blk;
+    DevBuf<int32_t> slot_kc;             // (nslot_lane*64) stage * 16 + row, -1 = padding
+    DevBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
+    DevBuf<double> slot_lb_blk, slot_ub_blk;
     int nslot_lane_blk;            // 0: no such table (soft sides present)
     bool block_qp;                 // use k_qp_block for batches of at most one instance per CU (IHM2MPC_BLOCK_QP=0 turns it off)
-    double *slot_lb, *slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
-    double *slot_zw, *slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot
+    DevBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
+    DevBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot
     // host copies the table is rebuilt from (set_bounds / set_soft may come in either order)
-    double *host_lb, *host_ub;     // (NS*NC) per (stage, row), +-inf = absent
-    double *host_sz, *host_sZ;     // (NS*NLAM) per one-sided constraint: NC lower then NC upper
+    std::vector<double> host_lb, host_ub;     // (NS*NC) per (stage, row), +-inf = absent
+    std::vector<double> host_sz, host_sZ;     // (NS*NLAM) per one-sided constraint: NC lower then NC upper
     // nonlinear track-boundary rows (rows 12, 13 of the stages 1..N)
     int path_on;
     double car_L, car_W, lh[NH], uh[NH];
-    double *widths;                // (ntracks, 2) = (w_R, w_L), device
+    DevBuf<double> widths;               // (ntracks, 2) = (w_R, w_L)
     // lateral-acceleration row of the kinematic constraint set (row 14 of the stages 1..N-1; ihm2mpc_set_alat_constraint)
     int alat_on;
     double alat_lb, alat_ub, alat_sz[2], alat_sZ[2];      // bounds (+-inf = absent), slack penalties of the lower / upper side (sZ < 0 = hard)
     // Cartesian side (ROS stack): centre-line geometry per track, Cartesian plant state and projection guess per instance
     bool geometry_set;
-    double *X_ref, *Y_ref, *phi_ref;   // (ntracks, nknots)
-    double *xc;                    // (B,8) (X, Y, phi, v_x, v_y, r, T, delta)
-    double *s_guess;               // (B)
+    DevBuf<double> X_ref, Y_ref, phi_ref;   // (ntracks, nknots)
+    DevBuf<double> xc;                   // (B,8) (X, Y, phi, v_x, v_y, r, T, delta)
+    DevBuf<double> s_guess;              // (B)
 
     // ---- per-instance state, instance-major ----
-    double *x;      // (B,NS,8)
-    double *u;      // (B,N,2)
-    double *x0;     // (B,8)
-    double *yref;   // (B,N,12)
-    double *yref_e; // (B,8)
-    double *pi;     // (B,NS,8)
-    double *lam;    // (B,NS,28)
-    double *slk;    // (B,NS,28) slack values of the soft sides after the last QP (0 for hard sides)
-    double *lam_a, *slk_a;   // (B,NS,2) multipliers and slack values of the lateral-acceleration row: lower, upper side
-    double *res;    // (B,4)
-    double *ls_phi; // (n_alpha, B, N, 8) IRK rollouts at the trial points of the line search (SQP mode with the IRK integrator)
-    int ls_nalpha;
-    void *irk_tab;       // device copy of the OCP integrator's collocation tableau (irk_body.hpp: IrkTab), nullptr for ERK
-    void *sim_irk_tab;   // the same for the plant steps of the persistent loop (step dt / sim_irk_M), allocated on first use
+    DevBuf<double> x;      // (B,NS,8)
+    DevBuf<double> u;      // (B,N,2)
+    DevBuf<double> x0;     // (B,8)
+    DevBuf<double> yref;   // (B,N,12)
+    DevBuf<double> yref_e; // (B,8)
+    DevBuf<double> pi;     // (B,NS,8)
+    DevBuf<double> lam;    // (B,NS,28)
+    DevBuf<double> slk;    // (B,NS,28) slack values of the soft sides after the last QP (0 for hard sides)
+    DevBuf<double> lam_a, slk_a;   // (B,NS,2) multipliers and slack values of the lateral-acceleration row: lower, upper side
+    DevBuf<double> res;    // (B,4)
+    // (n_alpha, B, N, 8) IRK rollouts at the trial points of the line search (SQP mode with the IRK integrator), grown on demand: its
+    // n_alpha (the ladder it was grown for, sqp_body.hpp: make_ls_args) is the stride the line search reads it with
+    DevBuf<double> ls_phi;
+    DevBuf<ihm2::IrkTab> irk_tab;       // the OCP integrator's collocation tableau, empty for ERK
+    DevBuf<ihm2::IrkTab> sim_irk_tab;   // the same for the plant steps of the persistent loop (step dt / sim_irk_M), allocated on first use
     int sim_irk_M;
-    int32_t *ls_pending; // (B) instances whose line search goes past the first rollouts (two-launch ladder)
-    double *dyn10;  // (B,35) staging of the fdyn10 plant: x (15), u (5), x_next (15); allocated on first use
-    double *qp_res; // (B,4) KKT residuals of the QP at its returned point, relative to the scales of its tolerances
-    int32_t *status, *qp_iter;   // (B)
-    int32_t *active;             // (B) plant mask of the device-resident closed loop (nullptr-equivalent while !active_set)
+    DevBuf<double> dyn10;  // (B,35) staging of the fdyn10 plant: x (15), u (5), x_next (15); allocated on first use
+    DevBuf<double> qp_res; // (B,4) KKT residuals of the QP at its returned point, relative to the scales of its tolerances
+    DevBuf<int32_t> status, qp_iter;   // (B)
+    DevBuf<int32_t> active;            // (B) plant mask of the device-resident closed loop (nullptr-equivalent while !active_set)
     bool active_set;
     bool freeze_armed;           // a run_steps(freeze) call initialised the mask: later calls keep what the device made of it
     bool lap_wrap;               // prepare_step / step move cars that passed s = L back by one lap first
-    double *u0;     // (B,2) first control of the last solve
+    DevBuf<double> u0;     // (B,2) first control of the last solve
 
-    double *lin;    // (B,N,96) linearisation records [A | B | b | rb], then B spare records (the kinematic plant's by-product)
+    DevBuf<double> lin;    // (B,N,96) linearisation records [A | B | b | rb], then B spare records (the kinematic plant's by-product)
     // ---- QP workspace in HBM/L2 (everything else of the QP lives in LDS / registers) ----
-    double *q_g;    // (B,NS,10) QP gradient
-    double *q_rg;   // (B,NS,10) stationarity residual of the interior-point iterate (follows the step between two evaluations from the data)
-    double *q_P;    // (B,NS,64) Riccati matrices of the current factorisation
-    double *q_M;    // (QM_PAD + B*N + QM_PAD, 64) closed-loop matrices A - B K (row-major; the vector recursion reads them
-                    // transposed), padded at both ends: the sweeps' prefetch rings run QM_PAD rows past an instance unclamped
-    double *scratch;   // (B, 3*8) plant scratch
+    DevBuf<double> q_g;    // (B,NS,10) QP gradient
+    DevBuf<double> q_rg;   // (B,NS,10) stationarity residual of the interior-point iterate (follows the step between two evaluations from the data)
+    DevBuf<double> q_P;    // (B,NS,64) Riccati matrices of the current factorisation
+    DevBuf<double> q_M;    // (QM_PAD + B*N + QM_PAD, 64) closed-loop matrices A - B K (row-major; the vector recursion reads them
+                           // transposed), padded at both ends: the sweeps' prefetch rings run QM_PAD rows past an instance unclamped
+    DevBuf<double> scratch;   // (B, 3*8) plant scratch
 
     // ---- SQP mode (cfg.nlp_solver_type == IHM2MPC_SQP): convergence test + merit line search, kernels_sqp.hip ----
     int sqp_globalization, sqp_use_suff, sqp_full_step_dual;   // globalization: 0 FIXED_STEP, 1 MERIT_BACKTRACKING
     double sqp_alpha_min, sqp_alpha_red, sqp_eps, sqp_tol[4];
-    double *Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
-    double *st_lb, *st_ub;          // (NS,NC) device copies of host_lb / host_ub
-    double *st_sz, *st_sZ;          // (NS,NLAM) device copies of host_sz / host_sZ
-    // allocated by the first SQP solve: the iterate the QP was built at, merit weights, per-solve bookkeeping
-    double *ls_x, *ls_u, *ls_pi, *ls_lam, *ls_slk, *ls_wpi, *ls_wlam, *ls_alpha;
-    int32_t *ls_done, *ls_status, *ls_iter, *ls_qp_acc;
-    double *step_args;              // device copy of the persistent loop's own argument block (256 B), allocated with the handle
-    double *ls_args;                // device copy of the line search's argument block for the persistent loop (512 B)
+    DevBuf<double> Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
+    DevBuf<double> st_lb, st_ub;           // (NS,NC) device copies of host_lb / host_ub
+    DevBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of host_sz / host_sZ
+    // allocated together by the first SQP solve (api.hip: sqp_buffers): the iterate the QP was built at, merit weights, per-solve bookkeeping
+    DevBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
+    DevBuf<int32_t> ls_done, ls_status, ls_iter, ls_qp_acc;
+    DevBuf<int32_t> ls_pending;            // (B) instances whose line search goes past the first rollouts (two-launch ladder)
+    DevBuf<double> ls_args;                // device copy of the line search's argument block for the persistent loop (512 B)
+    DevBuf<double> step_args;              // device copy of the persistent loop's own argument block (256 B), allocated with the handle
     void *args_host[2];             // pinned staging of both blocks (1 KB each), used alternately
     hipEvent_t args_ev[2];          // recorded after a slot's upload: the slot is free again once it has passed
     int args_idx;
@@ -138,19 +181,17 @@ struct ihm2mpc_handle {
     bool inst_w, inst_b;
     bool inst_b_ok;                // false: a later setter changed the shared pattern and the stored values no longer fit it
     bool shared_uniform_H;         // uniform_H of the batch-shared weights (restored when the per-instance weights go)
-    double *iHs, *iGy, *iWd;       // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
-    double *ih_lb, *ih_ub;         // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
-    double *i_slot_lb, *i_slot_ub; // (B,nslot_lane*64) the slot table's bounds per instance
-    size_t i_slot_cap;             // entries per instance the two arrays hold
-    double *i_st_lb, *i_st_ub;     // (B,NS,NC) the SQP mode's bounds per instance
-    double *i_lbu, *i_ubu, *i_lg, *i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
-    int32_t *host_kc;              // host copies of the slot table (MAX_SLOTS): the per-instance values are scattered into its pattern
-    double *host_slb, *host_sub;
+    DevBuf<double> iHs, iGy, iWd;          // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
+    std::vector<double> ih_lb, ih_ub;      // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
+    DevBuf<double> i_slot_lb, i_slot_ub;   // (B,nslot_lane*64) the slot table's bounds per instance, grown on demand
+    DevBuf<double> i_st_lb, i_st_ub;       // (B,NS,NC) the SQP mode's bounds per instance
+    DevBuf<double> i_lbu, i_ubu, i_lg, i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
+    std::vector<int32_t> host_kc;          // host copies of the slot table (MAX_SLOTS): the per-instance values are scattered into its pattern
+    std::vector<double> host_slb, host_sub;
 
     // ---- history of ihm2mpc_run_steps, grown on demand ----
-    size_t hist_cap;                // steps the buffers hold
-    double *hist_u0, *hist_x0;      // (steps,B,2), (steps,B,8)
-    int32_t *hist_st, *hist_it;     // (steps,B)
+    DevBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)
+    DevBuf<int32_t> hist_st, hist_it;      // (steps,B)
 
     // ---- what was last launched (ihm2mpc_get_launch_record), written from the catalogue's keys (api.hip: note_launch) ----
     int32_t launch_rec[16];
@@ -159,12 +200,11 @@ struct ihm2mpc_handle {
     int sens_mode;                  // 0 off, 1 the stage-0 gain, 2 the whole horizon
     int sens_state;                 // 0 nothing computed in this mode yet, 1 valid for the last solve / step, 2 the last step came from run_steps
     bool sens_quiet;                // run_steps' launches per step: no snapshot, no sensitivity launch (the persistent loop has none either)
-    double *sens_xbar, *sens_ubar;  // (B,NS,8), (B,N,2) the point the last QP was linearised at
-    double *sens_u0;                // (B,2,8) du_0 / dx_0
-    double *sens_x, *sens_u;        // (B,NS,8,8), (B,N,2,8) (mode 2)
-    double *sens_args;              // device copy of the persistent loop's SensArgs (512 B), allocated with the buffers above
-    size_t hist_k_cap;              // steps hist_k holds
-    double *hist_k;                 // (steps,B,2,8) du_0/dx0 of every step of ihm2mpc_run_steps_sens, grown on demand
+    DevBuf<double> sens_xbar, sens_ubar;   // (B,NS,8), (B,N,2) the point the last QP was linearised at
+    DevBuf<double> sens_u0;                // (B,2,8) du_0 / dx_0
+    DevBuf<double> sens_args;              // device copy of the persistent loop's SensArgs (512 B), allocated with the buffers above
+    DevBuf<double> sens_x, sens_u;         // (B,NS,8,8), (B,N,2,8) (mode 2)
+    DevBuf<double> hist_k;                 // (steps,B,2,8) du_0/dx0 of every step of ihm2mpc_run_steps_sens, grown on demand
 };
 
 // --- launchers (each defined in one .hip file) ---
@@ -199,7 +239,6 @@ size_t ihm2_sens_lds_bytes(const ihm2mpc_handle *h);
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'
 // symbols name these types.)
-namespace ihm2 { struct IrkTab; }
 namespace {
 
 struct QpArgs {

@@ -161,7 +161,7 @@ int ihm2_upload_irk_tab(ihm2mpc_handle *h)
 {
     if (h->cfg.integrator_type == IHM2MPC_INTEG_ERK) return 0;
     const IrkTab tab = make_tab(h->cfg.integrator_type, h->cfg.dt / h->cfg.M);
-    if (!h->irk_tab && hipMalloc(&h->irk_tab, sizeof(IrkTab)) != hipSuccess) return 1;
+    if (!h->irk_tab && h->irk_tab.alloc(1) != hipSuccess) return 1;
     if (hipMemcpyAsync(h->irk_tab, &tab, sizeof(IrkTab), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
     return hipStreamSynchronize(h->stream) == hipSuccess ? 0 : 1;
 }
@@ -172,7 +172,7 @@ int ihm2_upload_sim_irk_tab(ihm2mpc_handle *h, int M_sim)
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK) return 1;
     if (h->sim_irk_tab && h->sim_irk_M == M_sim) return 0;
     const IrkTab tab = make_tab(h->cfg.sim_integrator_type, h->cfg.dt / M_sim);
-    if (!h->sim_irk_tab && hipMalloc(&h->sim_irk_tab, sizeof(IrkTab)) != hipSuccess) return 1;
+    if (!h->sim_irk_tab && h->sim_irk_tab.alloc(1) != hipSuccess) return 1;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return 1;          // a launch in flight may still read the old tableau
     if (hipMemcpy(h->sim_irk_tab, &tab, sizeof(IrkTab), hipMemcpyHostToDevice) != hipSuccess) return 1;
     h->sim_irk_M = M_sim;

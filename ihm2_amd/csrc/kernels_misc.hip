@@ -130,7 +130,7 @@ void ihm2_launch_prepare(ihm2mpc_handle *h, double s_target, int mode, hipStream
 
 void ihm2_launch_init_guess(ihm2mpc_handle *h, double v_ref_scale, int only_failed)
 {
-    const int32_t *mask = only_failed ? h->status : nullptr;
+    const int32_t *mask = only_failed ? h->status.get() : nullptr;
     // the rollout is an RK4 rollout whatever the OCP's integrator: with IRK (one step per interval) it takes the 25 sub-steps RK4 needs
     // on the actuator lags (a guess: the first linearisation sees its defects against the OCP's own discretisation)
     // (sub-steps of at most 2 ms: RK4 is stable on the 1 ms torque lag up to 2.78 ms -- a longer interval takes more of them)
