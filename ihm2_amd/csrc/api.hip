@@ -1350,6 +1350,34 @@ int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens
     return 0;
 }
 
+int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0,
+                                       double *grad_yref, double *grad_yref_e)
+{
+    CHECK_H(h);
+    if (h->cfg.nlp_solver_type == IHM2MPC_SQP)
+        return fail("adjoint sensitivities are implemented for SQP_RTI: in the SQP mode the line search scales the step and the multipliers, "
+                    "which leaves no QP solution to differentiate");
+    if (n_seeds < 1 || n_seeds > 8) return fail("adjoint sensitivities: n_seeds = %d, one call takes 1 to 8 seeds", n_seeds);
+    const bool unit_u0 = !seed_x && !seed_u;
+    if (unit_u0 && n_seeds != 2)
+        return fail("adjoint sensitivities: seed_x and seed_u both NULL stands for the two unit seeds on u_0 and needs n_seeds = 2, not %d", n_seeds);
+    // the factorisation is that of the x0 sensitivities: their snapshot of (xbar, ubar) must belong to the last solve
+    if (sens_readable(h)) return -1;
+    const size_t B = h->B, N = h->N, NS = h->NS, S = n_seeds;
+    if (h->adj_gx0.size() < B * S * NX &&
+        alloc_all(h->adj_sx, B * S * NS * NX, h->adj_su, B * S * N * NU, h->adj_gx0, B * S * NX, h->adj_gy, B * S * N * NY, h->adj_gye, B * S * NX))
+        return -1;
+    if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (seed_u) HIP_TRY(hipMemcpyAsync(h->adj_su, seed_u, B * S * N * NU * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, h->adj_gy, B * S * N * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, h->adj_gye, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));      // the seeds may be reused and the gradients read as soon as we return
+    return 0;
+}
+
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)
 {
     CHECK_H(h);

@@ -1,0 +1,353 @@
+// kernels_adj.hip -- adjoint sensitivities of the last RTI QP's solution: the gradient of a scalar function of the solution with respect
+// to the initial state and the reference (acados: eval_adjoint_solution_sensitivity(seed_x, seed_u)).
+//
+// The differentiated system is k_sens' (kernels_sens.hip, DESIGN.md §4 "x0 sensitivities"): M = [[Ht, E'], [E, 0]] with
+// Ht_k = H_k + sum_i sigma_i r_i r_i' and E the rows x_0 = . , x_{k+1} - A_k x_k - B_k u_k = . .  A change of the stage gradients and of the
+// initial state moves the solution by M [dz; dpi] = [-dg; (dx0, 0, ..)].  For seeds s_k = dL/dz_k let [zeta; nu] = M^-1 [s; 0] (M is
+// symmetric); then dL = -zeta' dg + nu_0' dx0, and with g_k = H_k z_k - Gy_k yref_k (kernels_qp.hip)
+//   dL/dx0 = nu_0,   dL/dyref_k = Gy_k' zeta_k  (k < N),   dL/dyref_e = GyT' zeta_N[0:8].
+// [zeta; nu] is the solution of the affine LQ problem with the linear terms q_k = -s_k from zeta_x,0 = 0:
+//   backward  l_x = q_x + A_k' p_{k+1},  l_u = q_u + B_k' p_{k+1},  kappa_k = -Quu_k^-1 l_u,  p_k = l_x + K_k' l_u,  p_N = q_x,N
+//   forward   zeta_u,k = K_k zeta_x,k + kappa_k,  zeta_x,k+1 = A_k zeta_x,k + B_k zeta_u,k;   nu_0 = -p_0
+// on the gains K_k and the Quu_k of the backward Riccati sweep on Ht.
+//
+// Mapping: one wavefront per instance.  Phase 1 is k_sens' factorisation -- the row weights over the slot table, the Riccati sweep, one
+// output entry per lane -- in a copy of its own that also keeps Quu_k^-1 (the objects that hold sens_body.hpp stay as they are); its
+// helpers (side_sigma, SSYNC) and its argument block are sens_body.hpp's.  Phases 2 and 3 carry vectors of 8 / 10 entries, so the lane
+// (seed = lane >> 3, row = lane & 7) runs up to eight seeds through both sweeps at the cost of one; p and zeta_x change hands through
+// LDS (two buffers: a stage reads one and writes the other), kappa_k of all stages and seeds waits in LDS for the forward sweep.  fp64.
+#include <cmath>
+
+#include "ihm2mpc_internal.h"
+#include "sens_body.hpp"
+
+namespace {
+
+struct AdjArgs {
+    SensArgs s;         // k_sens' block (sens_u0, sens_x, sens_u, hist unused)
+    // dg_k / dyref_k = -Gy_k: instance base stride, offset of the terminal block, stride between stages -- as hs_bs, hs_te, hs_ks
+    const double *Gy;
+    int gy_bs, gy_te, gy_ks;
+    int n_seeds;        // 1..8
+    int unit_u0;        // the two unit seeds on u_0 (n_seeds = 2) instead of seed_x / seed_u
+    const double *seed_x, *seed_u;      // (B,n_seeds,N+1,8), (B,n_seeds,N,2); nullptr = zero
+    double *grad_x0, *grad_yref, *grad_yref_e;      // (B,n_seeds,8), (B,n_seeds,N,12), (B,n_seeds,8)
+};
+
+// LDS of one instance (doubles) behind the factorisation's arrays: see the carve-up in k_adj
+__host__ __device__ constexpr size_t adj_lds_doubles(size_t N)
+{
+    return (N + 1) * (SENS_NR + 6) + N * 16 + 64 + 64 + 16 + 100 + 64 + 16 + 84 + N * 4 + N * 16 + 128 + 128;
+}
+
+__global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
+{
+    extern __shared__ double sm[];
+    const SensArgs &a = aa.s;
+    const int b = blockIdx.x;
+    if (b >= a.B) return;
+    const int lane = threadIdx.x;
+    const int N = a.N, NS = N + 1, S = aa.n_seeds;
+    // ---- LDS carve-up (doubles) ----
+    double *w = sm;                  // NS*15  row weights sigma_lower + sigma_upper
+    double *hc = w + NS * SENS_NR;   // NS*2   d h_R / d psi, d h_L / d psi of the track rows at xbar
+    double *ha = hc + NS * 2;        // NS*4   d a_lat / d (v_x, v_y, T, delta) at xbar
+    double *Kl = ha + NS * 4;        // N*16   gains K_k
+    double *P = Kl + N * 16;         // 64
+    double *Al = P + 64;             // 64
+    double *Bl = Al + 64;            // 16
+    double *Ht = Bl + 16;            // 100
+    double *PA = Ht + 100;           // 64
+    double *PB = PA + 64;            // 16
+    double *Q = PB + 16;             // 84: Qxx (64) | Qux (16) | Quu (4)
+    double *Qi = Q + 84;             // N*4    Quu_k^-1 (row-major)
+    double *kap = Qi + N * 4;        // N*16   kappa_k of seed j at (k * 8 + j) * 2
+    double *pv = kap + N * 16;       // 2*64   p_k of the eight seeds, two buffers
+    double *zx = pv + 128;           // 2*64   zeta_x,k of the eight seeds, two buffers
+
+    const size_t bs = (size_t)b;
+    const int sd = lane >> 3, row = lane & 7;       // phases 2 and 3: this lane's seed and row
+    const bool live = sd < S;
+    double *gx0 = aa.grad_x0 + (bs * S + sd) * 8, *gyr = aa.grad_yref + (bs * S + sd) * N * 12, *gye = aa.grad_yref_e + (bs * S + sd) * 8;
+    const int st = a.status[b];
+    if (st != 0 && st != 2) {        // no solution to differentiate (wave-uniform)
+        if (live) {
+            gx0[row] = NAN;
+            gye[row] = NAN;
+            for (int e = row; e < N * 12; e += 8) gyr[e] = NAN;
+        }
+        return;
+    }
+
+    // ======== phase 1: the factorisation of sens_body.hpp (sens_body), keeping Quu_k^-1 ========
+    const double *xb = a.xbar + bs * NS * 8, *ubb = a.ubar + bs * N * 2;
+    const double *xo = a.x + bs * NS * 8, *uo = a.u + bs * N * 2;
+    const double *lamb = a.lam + bs * NS * 28, *slkb = a.slk + bs * NS * 28;
+    const double *lamab = a.lam_a + bs * NS * 2, *slkab = a.slk_a + bs * NS * 2;
+    const double *linb = a.lin + bs * N * LIN_REC;
+    const double *Hs0 = a.Hs + bs * a.hs_bs, *HsT = Hs0 + a.hs_te;
+    const double *slb = a.slot_lb + bs * a.sl_bs, *sub = a.slot_ub + bs * a.sl_bs;
+
+    // ---- row gradients of the nonlinear rows at xbar, zero weights ----
+    double w_R = 0.0, w_L = 0.0;
+    if (a.path) {
+        const int trk = a.track_id[b];
+        w_R = a.widths[trk * 2 + 0]; w_L = a.widths[trk * 2 + 1];
+    }
+    for (int k = lane; k < NS; k += 64) {
+        // the track rows as the QP forms them (kernels_qp.hip: qp_wave_body), stages 1..N
+        const double psi = xb[k * 8 + 2], sgn = (psi > 0.0) - (psi < 0.0);
+        const double dfoot = -0.5 * a.car_L * cos(fabs(psi)) * sgn, dlat = -0.5 * a.car_W * sin(psi);
+        hc[k * 2 + 0] = (a.path && k >= 1) ? dfoot + dlat : 0.0;
+        hc[k * 2 + 1] = (a.path && k >= 1) ? -dfoot + dlat : 0.0;
+        double g4[4] = {0.0, 0.0, 0.0, 0.0};
+        if (a.alat && k >= 1 && k < N) ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
+#pragma unroll
+        for (int q = 0; q < 4; q++) ha[k * 4 + q] = g4[q];
+    }
+    for (int e = lane; e < NS * SENS_NR; e += 64) w[e] = 0.0;
+    SSYNC();
+
+    // coefficient of row c of stage k on the variable j of z_k = (dx_k, du_k)
+    auto rcoef = [&](int k, int c, int j) -> double {
+        if (c < 10) return (j == c) ? 1.0 : 0.0;
+        if (c < 12) return a.CD[((size_t)k * 2 + (c - 10)) * 10 + j];
+        if (c < 14) return (j == 1) ? ((c == 12) ? 1.0 : -1.0) : (j == 2) ? hc[k * 2 + (c - 12)] : 0.0;
+        return (j == 3) ? ha[k * 4] : (j == 4) ? ha[k * 4 + 1] : (j == 6) ? ha[k * 4 + 2] : (j == 7) ? ha[k * 4 + 3] : 0.0;
+    };
+
+    // ---- row weights: every entry of the slot table on the lane that owns it in the QP (a split row's halves share a lane: no race) ----
+    for (int s = lane; s < a.nslots; s += 64) {
+        const int kc = a.slot_kc[s];
+        if (kc < 0) continue;
+        const int k = kc >> 4, c = kc & 15;
+        // row value at xbar (as the QP forms it) and the row times the step
+        double cz, rdz = 0.0;
+        if (c < 8) cz = xb[k * 8 + c];
+        else if (c < 10) cz = ubb[k * 2 + c - 8];
+        else if (c == 14) {
+            double g4[4];
+            cz = ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
+        } else if (c >= 12) {
+            const double n = xb[k * 8 + 1], psi = xb[k * 8 + 2];
+            const double foot = -0.5 * a.car_L * sin(fabs(psi)), lat = 0.5 * a.car_W * cos(psi);
+            cz = (c == 12) ? n + foot + lat - w_R : -n - foot + lat - w_L;
+        } else {
+            cz = 0.0;
+            for (int j = 0; j < 8; j++) cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + j], xb[k * 8 + j], cz);
+            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 8], ubb[k * 2 + 0], cz);
+            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 9], ubb[k * 2 + 1], cz);
+        }
+        for (int j = 0; j < 10; j++) {
+            const double dzj = (j < 8) ? xo[k * 8 + j] - xb[k * 8 + j] : (k < N) ? uo[k * 2 + j - 8] - ubb[k * 2 + j - 8] : 0.0;
+            rdz = fma(rcoef(k, c, j), dzj, rdz);
+        }
+        const double lb = slb[s], ub = sub[s], zw = a.slot_zw[s], Zw = a.slot_Zw[s];
+        const bool soft = Zw >= 0.0;
+        double sig = 0.0;
+        if (sfin(lb)) {
+            const double lm = (c == 14) ? lamab[k * 2] : lamb[k * 28 + c];
+            const double sl = soft ? ((c == 14) ? slkab[k * 2] : slkb[k * 28 + c]) : 0.0;
+            sig += side_sigma(lm, rdz - (lb - cz) + sl, sl, zw, Zw, a.tau);
+        }
+        if (sfin(ub)) {
+            const double lm = (c == 14) ? lamab[k * 2 + 1] : lamb[k * 28 + 14 + c];
+            const double sl = soft ? ((c == 14) ? slkab[k * 2 + 1] : slkb[k * 28 + 14 + c]) : 0.0;
+            sig += side_sigma(lm, (ub - cz) - rdz + sl, sl, zw, Zw, a.tau);
+        }
+        w[k * SENS_NR + c] += sig;
+    }
+    SSYNC();
+
+    // entry (i, j) of Ht_k = H_k + sum_c w_c r_c r_c'
+    auto htilde = [&](int k, int i, int j) -> double {
+        const double *Hk = (k == N) ? HsT : Hs0 + (size_t)k * a.hs_ks;
+        double v = Hk[i * 10 + j];
+        const int cmax = (k == N) ? 8 : 10;       // terminal stage: no input rows; general rows only for k < N
+        if (i == j && i < cmax) v += w[k * SENS_NR + i];
+        if (k < N)
+            for (int c = 10; c < 12; c++) v = fma(w[k * SENS_NR + c] * rcoef(k, c, i), rcoef(k, c, j), v);
+        for (int c = 12; c < SENS_NR; c++) {
+            const double wc = w[k * SENS_NR + c];
+            if (wc != 0.0) v = fma(wc * rcoef(k, c, i), rcoef(k, c, j), v);
+        }
+        return v;
+    };
+
+    // ---- backward Riccati sweep on Ht: P_N = Ht_N[x,x]; K_k = -Quu^-1 Qux, P_k = Qxx + Qux' K_k ----
+    {
+        const int i = lane >> 3, j = lane & 7;
+        P[lane] = htilde(N, i, j);
+    }
+    // the record of stage k is fetched one stage ahead, into registers
+    double ra = linb[(size_t)(N - 1) * LIN_REC + lane], rbv = (lane < 16) ? linb[(size_t)(N - 1) * LIN_REC + 64 + lane] : 0.0;
+    for (int k = N - 1; k >= 0; k--) {
+        Al[lane] = ra;
+        if (lane < 16) Bl[lane] = rbv;
+        if (k > 0) {
+            ra = linb[(size_t)(k - 1) * LIN_REC + lane];
+            if (lane < 16) rbv = linb[(size_t)(k - 1) * LIN_REC + 64 + lane];
+        }
+        for (int e = lane; e < 100; e += 64) Ht[e] = htilde(k, e / 10, e % 10);
+        SSYNC();
+        {
+            const int i = lane >> 3, j = lane & 7;
+            double acc = 0.0;
+#pragma unroll
+            for (int l = 0; l < 8; l++) acc = fma(P[i * 8 + l], Al[l * 8 + j], acc);
+            PA[lane] = acc;
+            if (lane < 16) {
+                const int ii = lane >> 1, m = lane & 1;
+                double accb = 0.0;
+#pragma unroll
+                for (int l = 0; l < 8; l++) accb = fma(P[ii * 8 + l], Bl[l * 2 + m], accb);
+                PB[lane] = accb;
+            }
+        }
+        SSYNC();
+        {
+            const int i = lane >> 3, j = lane & 7;
+            double acc = Ht[i * 10 + j];
+#pragma unroll
+            for (int l = 0; l < 8; l++) acc = fma(Al[l * 8 + i], PA[l * 8 + j], acc);
+            Q[lane] = acc;
+            if (lane < 16) {        // Qux (m, j)
+                const int m = lane >> 3, jj = lane & 7;
+                double q = Ht[(8 + m) * 10 + jj];
+#pragma unroll
+                for (int l = 0; l < 8; l++) q = fma(Bl[l * 2 + m], PA[l * 8 + jj], q);
+                Q[64 + lane] = q;
+            } else if (lane < 20) {  // Quu (m, n)
+                const int m = (lane - 16) >> 1, n = (lane - 16) & 1;
+                double q = Ht[(8 + m) * 10 + 8 + n];
+#pragma unroll
+                for (int l = 0; l < 8; l++) q = fma(Bl[l * 2 + m], PB[l * 2 + n], q);
+                Q[80 + (lane - 16)] = q;
+            }
+        }
+        SSYNC();
+        if (lane < 16) {
+            const int m = lane >> 3, j = lane & 7;
+            const double q00 = Q[80], q01 = 0.5 * (Q[81] + Q[82]), q11 = Q[83];
+            const double idet = 1.0 / (q00 * q11 - q01 * q01);
+            const double i0 = (m == 0) ? q11 * idet : -q01 * idet, i1 = (m == 0) ? -q01 * idet : q00 * idet;
+            Kl[k * 16 + lane] = -(i0 * Q[64 + j] + i1 * Q[72 + j]);
+            if (j == 0) { Qi[k * 4 + m * 2] = i0; Qi[k * 4 + m * 2 + 1] = i1; }      // Quu_k^-1, row m
+        }
+        SSYNC();
+        {
+            const int i = lane >> 3, j = lane & 7;
+            const double *K = Kl + k * 16;
+            const double pij = Q[i * 8 + j] + Q[64 + i] * K[j] + Q[72 + i] * K[8 + j];
+            const double pji = Q[j * 8 + i] + Q[64 + j] * K[i] + Q[72 + j] * K[8 + i];
+            P[lane] = 0.5 * (pij + pji);
+        }
+        SSYNC();
+    }
+
+    // ======== phase 2: the backward vector sweep, eight seeds at once ========
+    const double *sxp = (live && aa.seed_x && !aa.unit_u0) ? aa.seed_x + (bs * S + sd) * NS * 8 + row : nullptr;
+    const double *sup = (live && aa.seed_u && !aa.unit_u0) ? aa.seed_u + (bs * S + sd) * N * 2 : nullptr;
+    auto seed_of_x = [&](int k) -> double { return sxp ? sxp[k * 8] : 0.0; };
+    auto seed_of_u = [&](int k, int m) -> double {
+        if (aa.unit_u0) return (live && k == 0 && m == sd) ? 1.0 : 0.0;
+        return sup ? sup[k * 2 + m] : 0.0;
+    };
+    int cur = 0;
+    double pk = -seed_of_x(N);
+    pv[lane] = pk;
+    // the record and the seeds of stage k are fetched one stage ahead, into registers
+    ra = linb[(size_t)(N - 1) * LIN_REC + lane]; rbv = (lane < 16) ? linb[(size_t)(N - 1) * LIN_REC + 64 + lane] : 0.0;
+    double qx = seed_of_x(N - 1), qu0 = seed_of_u(N - 1, 0), qu1 = seed_of_u(N - 1, 1);
+    for (int k = N - 1; k >= 0; k--) {
+        Al[lane] = ra;
+        if (lane < 16) Bl[lane] = rbv;
+        double lx = -qx, lu0 = -qu0, lu1 = -qu1;
+        if (k > 0) {
+            ra = linb[(size_t)(k - 1) * LIN_REC + lane];
+            if (lane < 16) rbv = linb[(size_t)(k - 1) * LIN_REC + 64 + lane];
+            qx = seed_of_x(k - 1); qu0 = seed_of_u(k - 1, 0); qu1 = seed_of_u(k - 1, 1);
+        }
+        SSYNC();
+        const double *p = pv + cur * 64 + sd * 8;
+#pragma unroll
+        for (int l = 0; l < 8; l++) {
+            const double pl = p[l];
+            lx = fma(Al[l * 8 + row], pl, lx);
+            lu0 = fma(Bl[l * 2 + 0], pl, lu0);
+            lu1 = fma(Bl[l * 2 + 1], pl, lu1);
+        }
+        const double *K = Kl + k * 16, *qi = Qi + k * 4;
+        if (row < 2) kap[(k * 8 + sd) * 2 + row] = -(qi[row * 2] * lu0 + qi[row * 2 + 1] * lu1);
+        pk = lx + K[row] * lu0 + K[8 + row] * lu1;
+        cur ^= 1;
+        pv[cur * 64 + lane] = pk;
+        SSYNC();
+    }
+    if (live) gx0[row] = -pk;        // nu_0 = -p_0
+
+    // ======== phase 3: the forward sweep and the products with Gy ========
+    const double *Gy0 = aa.Gy + bs * aa.gy_bs, *GyT = Gy0 + aa.gy_te;
+    cur = 0;
+    zx[lane] = 0.0;
+    ra = linb[lane]; rbv = (lane < 16) ? linb[64 + lane] : 0.0;
+    for (int k = 0; k < N; k++) {
+        Al[lane] = ra;
+        if (lane < 16) Bl[lane] = rbv;
+        if (k + 1 < N) {
+            ra = linb[(size_t)(k + 1) * LIN_REC + lane];
+            if (lane < 16) rbv = linb[(size_t)(k + 1) * LIN_REC + 64 + lane];
+        }
+        SSYNC();
+        const double *zk = zx + cur * 64 + sd * 8, *K = Kl + k * 16, *G = Gy0 + (size_t)k * aa.gy_ks;
+        double u0 = kap[(k * 8 + sd) * 2], u1 = kap[(k * 8 + sd) * 2 + 1];
+        double xn = 0.0, g0 = 0.0, g1 = 0.0;
+#pragma unroll
+        for (int l = 0; l < 8; l++) {
+            const double zl = zk[l];
+            u0 = fma(K[l], zl, u0);
+            u1 = fma(K[8 + l], zl, u1);
+            xn = fma(Al[row * 8 + l], zl, xn);
+            g0 = fma(G[l * 12 + row], zl, g0);
+            if (row < 4) g1 = fma(G[l * 12 + 8 + row], zl, g1);
+        }
+        xn = fma(Bl[row * 2 + 0], u0, xn);
+        xn = fma(Bl[row * 2 + 1], u1, xn);
+        g0 = fma(G[8 * 12 + row], u0, g0);
+        g0 = fma(G[9 * 12 + row], u1, g0);
+        if (live) gyr[k * 12 + row] = g0;          // columns row and (row < 4) 8 + row of Gy_k' zeta_k
+        if (row < 4) {
+            g1 = fma(G[8 * 12 + 8 + row], u0, g1);
+            g1 = fma(G[9 * 12 + 8 + row], u1, g1);
+            if (live) gyr[k * 12 + 8 + row] = g1;
+        }
+        cur ^= 1;
+        zx[cur * 64 + lane] = xn;
+        SSYNC();
+    }
+    {
+        const double *zk = zx + cur * 64 + sd * 8;
+        double ge = 0.0;
+#pragma unroll
+        for (int l = 0; l < 8; l++) ge = fma(GyT[l * 12 + row], zk[l], ge);
+        if (live) gye[row] = ge;
+    }
+}
+
+}  // namespace
+
+// The handle's adjoint evaluation on h->stream: seeds from h->adj_sx / h->adj_su (nullptr = zero; unit_u0: the two unit seeds on u_0),
+// gradients into h->adj_gx0, h->adj_gy, h->adj_gye.
+void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0)
+{
+    AdjArgs a;
+    ihm2_sens_args(h, &a.s);
+    a.Gy = h->Gy; a.gy_bs = 0; a.gy_te = h->N * 120; a.gy_ks = 120;
+    if (h->inst_w) { a.Gy = h->iGy; a.gy_bs = 240; a.gy_te = 120; a.gy_ks = 0; }
+    a.n_seeds = n_seeds; a.unit_u0 = unit_u0;
+    a.seed_x = seed_x; a.seed_u = seed_u;
+    a.grad_x0 = h->adj_gx0; a.grad_yref = h->adj_gy; a.grad_yref_e = h->adj_gye;
+    const size_t lds = sizeof(double) * adj_lds_doubles((size_t)h->N);
+    (void)hipFuncSetAttribute((const void *)k_adj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_adj, dim3(h->B), dim3(64), lds, h->stream, a);
+}

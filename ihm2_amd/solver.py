@@ -473,6 +473,36 @@ class BatchedOcpSolver:
         """``du_0/dx_0`` ``(B,2,8)`` into device memory, stream-ordered."""
         _lib.check(self.lib.ihm2mpc_get_sens_u0_device(self._h, C.c_void_p(dptr)))
 
+    # ---- adjoint sensitivities of the same solution (acados: eval_adjoint_solution_sensitivity(seed_x, seed_u)) ----
+    def eval_adjoint_sensitivities(self, seed_x=None, seed_u=None):
+        """Gradients of scalar functions ``L`` of the last RTI solution with respect to what the solve was fed: ``seed_x``
+        ``(B,S,N+1,8)`` = ``dL/dx_k``, ``seed_u`` ``(B,S,N,2)`` = ``dL/du_k`` for ``S <= 8`` functions at once (``(B,N+1,8)`` /
+        ``(B,N,2)``: one, and the outputs drop that axis; one of the two may be ``None`` = zero).  Both ``None``: the two unit seeds on
+        ``u_0``, i.e. the Jacobians of the first control.  Returns ``dict(x0=(B,S,8), yref=(B,S,N,12), yref_e=(B,S,8))``, NaN rows for
+        instances whose status is neither 0 nor 2.  Needs ``set_x0_sensitivities(1 or 2)`` before the solve and must follow the solve
+        directly (``ihm2mpc_eval_adjoint_sensitivities``)."""
+        B, N = self.B, self.N
+        given = seed_x if seed_x is not None else seed_u
+        if given is None:
+            S, squeeze = 2, False
+        else:
+            squeeze = np.ndim(given) == 3
+            S = 1 if squeeze else int(np.shape(given)[1])
+        sx = None if seed_x is None else _f64(np.asarray(seed_x, dtype=np.float64).reshape(B, S, N + 1, NX), (B, S, N + 1, NX), "seed_x")
+        su = None if seed_u is None else _f64(np.asarray(seed_u, dtype=np.float64).reshape(B, S, N, NU), (B, S, N, NU), "seed_u")
+        out = dict(x0=np.empty((B, S, NX)), yref=np.empty((B, S, N, NY)), yref_e=np.empty((B, S, NX)))
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities(self._h, S, None if sx is None else _ptr(sx), None if su is None else _ptr(su),
+                                                               _ptr(out["x0"]), _ptr(out["yref"]), _ptr(out["yref_e"])))
+        return {k: v[:, 0] for k, v in out.items()} if squeeze else out
+
+    def du0_ds_target(self):
+        """``(B,2)``: the reaction of the first control of the last solve to ``prepare_step``'s ``s_target`` -- the reference ramp puts
+        ``(j / N) s_target`` into ``yref_j[0]`` and ``s_target`` into ``yref_e[0]``, so it is
+        ``sum_j (j / N) du_0/dyref_j[0] + du_0/dyref_e[0]``."""
+        g = self.eval_adjoint_sensitivities()
+        ramp = np.arange(self.N) / self.N
+        return g["yref"][:, :, :, 0] @ ramp + g["yref_e"][:, :, 0]
+
     # ---- plant ----
     def sim_step(self, x, u, model: int = 0, M_sim: int = 100):
         x = _f64(x, (self.B, NX), "x"); u = _f64(u, (self.B, NU), "u")
@@ -668,6 +698,31 @@ class AcadosOcpSolver:
         sx, su = self.batch.get_x0_sensitivities()
         j = int(index)
         self._sens = (None if sx is None else sx[self.i, :, :, j].copy(), su[self.i, ..., j].copy())
+
+    def eval_adjoint_solution_sensitivity(self, seed_x, seed_u, with_respect_to: str = "x0", sanity_checks: bool = True) -> np.ndarray:
+        """acados' ``eval_adjoint_solution_sensitivity``: ``seed_x`` / ``seed_u`` lists of ``(stage, array (nx | nu, n_seeds))`` (either may
+        be ``None`` or empty), the gradient of ``sum_k seed_x[k]' x_k + seed_u[k]' u_k`` of this instance's last solution, one row per
+        seed: ``with_respect_to`` ``"x0"`` ``(n_seeds, 8)``, ``"yref"`` ``(n_seeds, N, 12)`` or ``"yref_e"`` ``(n_seeds, 8)``.  acados
+        differentiates in ``"p_global"``; this OCP has no global parameters (the track tables are data of the batch), so that raises."""
+        if with_respect_to == "p_global":
+            raise Exception("AcadosOcpSolver.eval_adjoint_solution_sensitivity(): this OCP has no p_global (the track tables are batch data, "
+                            "not parameters); the solve's inputs are with_respect_to = 'x0', 'yref' or 'yref_e'")
+        if with_respect_to not in ("x0", "yref", "yref_e"):
+            raise Exception(f"AcadosOcpSolver.eval_adjoint_solution_sensitivity(): with_respect_to '{with_respect_to}' is not supported "
+                            "('x0', 'yref', 'yref_e')")
+        b = self.batch
+        pairs = [(st, np.asarray(v, dtype=np.float64), n, nm) for lst, n, nm in ((seed_x, NX, "seed_x"), (seed_u, NU, "seed_u"))
+                 for st, v in (lst or [])]
+        if not pairs:
+            raise Exception("AcadosOcpSolver.eval_adjoint_solution_sensitivity(): seed_x and seed_u are both empty")
+        S = pairs[0][1].shape[1] if pairs[0][1].ndim == 2 else 0
+        sx, su = np.zeros((b.B, S, b.N + 1, NX)), np.zeros((b.B, S, b.N, NU))
+        for st, v, n, nm in pairs:
+            if v.shape != (n, S) or not 0 <= int(st) <= (b.N if n == NX else b.N - 1):
+                raise Exception(f"AcadosOcpSolver.eval_adjoint_solution_sensitivity(): {nm} entries are (stage, array ({n}, n_seeds)) "
+                                f"with one n_seeds, got stage {st}, shape {v.shape}")
+            (sx if n == NX else su)[self.i, :, int(st), :] += v.T
+        return b.eval_adjoint_sensitivities(sx, su)[with_respect_to][self.i].copy()
 
     def get(self, stage: int, field: str) -> np.ndarray:
         if field in ("sens_x", "sens_u"):

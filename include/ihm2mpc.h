@@ -30,6 +30,7 @@
  *   ihm2mpc_run_steps         <- n iterations of that loop in one launch                  python/main.py:448-517
  *   ihm2mpc_set/get_x0_sensitivities <- solver.eval_param_sens(j, 0, "ex"); solver.get(k, "sens_x" / "sens_u") (acados)
  *   ihm2mpc_run_steps_sens    <- the same after every solve of ihm2mpc_run_steps' loop
+ *   ihm2mpc_eval_adjoint_sensitivities <- solver.eval_adjoint_solution_sensitivity(seed_x, seed_u) (acados)
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -284,6 +285,30 @@ int ihm2mpc_set_x0_sensitivities(ihm2mpc_handle *h, int32_t mode);
 int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens_u);
 /* du_0 / dx0 (B,2,8) into device memory (either mode), stream-ordered like ihm2mpc_get_u0_device */
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr);
+
+/* ---- adjoint sensitivities of the same solution: the gradient of scalar functions of it with respect to the initial state and the
+ * reference (acados: eval_adjoint_solution_sensitivity(seed_x, seed_u)) ----
+ * With M = [[Ht, E'], [E, 0]] the KKT matrix of the x0 sensitivities above (Ht_k = H_k + sum_i sigma_i r_i r_i', E the rows x_0 = . ,
+ * x_{k+1} - A_k x_k - B_k u_k = .) a change of the stage gradients and of the initial state moves the solution by
+ * M [dz; dpi] = [-dg; (dx0, 0, ..)].  For a seed s_k = dL/dz_k (seed_x[k] on x_k, seed_u[k] on u_k) let [zeta; nu] = M^-1 [s; 0]; then,
+ * since g_k = H_k z_k - Gy_k yref_k,
+ *     dL/dx0 = nu_0,     dL/dyref_k = Gy_k' zeta_k  (k < N),     dL/dyref_e = Gy_N' zeta_N[0:8]
+ * -- one backward and one forward vector sweep on the factorisation of the x0 sensitivities (backward: l_x = -s_x + A_k' p_{k+1},
+ * l_u = -s_u + B_k' p_{k+1}, kappa_k = -Quu_k^-1 l_u, p_k = l_x + K_k' l_u, p_N = -s_x,N; forward from zeta_x,0 = 0: zeta_u,k = K_k zeta_x,k
+ * + kappa_k, zeta_x,k+1 = A_k zeta_x,k + B_k zeta_u,k; nu_0 = -p_0), for up to eight seeds in one launch of one kernel.
+ * n_seeds: 1..8.  seed_x (B,n_seeds,N+1,8), seed_u (B,n_seeds,N,2), host arrays; either may be NULL (= zero).  Both NULL, with
+ * n_seeds == 2: the two unit seeds on u_0 -- grad_x0 is then du_0/dx0 (the rows of K0) and grad_yref / grad_yref_e are du_0/dyref,
+ * du_0/dyref_e.  Outputs, any may be NULL: grad_x0 (B,n_seeds,8), grad_yref (B,n_seeds,N,12), grad_yref_e (B,n_seeds,8); NaN for
+ * instances whose status is neither 0 nor 2.  Per-instance weights and bounds are honoured.
+ * Differentiates the last RTI solve (after ihm2mpc_run_steps_sens: the last step's) and needs x0 sensitivity mode 1 or 2 to have been on
+ * for it, which is what keeps the point of linearisation.  Refused while the mode is off, before a solve with the mode on, after
+ * ihm2mpc_run_steps, in the SQP mode, for n_seeds outside 1..8 and for both seeds NULL with n_seeds != 2.  The call reads the iterate,
+ * the multipliers, the slacks, the reference tables and the bounds as that solve left them: it must follow the solve directly -- after
+ * ihm2mpc_prepare_step, a setter of x, u, the multipliers, the slacks, weights or bounds, ihm2mpc_init_guess or ihm2mpc_reinit_failed it
+ * would differentiate a mixture, which is not detected.  It changes no other output and may be called any number of times (a caller may
+ * evaluate several batches of seeds against one solve).  Blocking: the seeds may be reused and the gradients read on return. */
+int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
+                                       double *grad_x0, double *grad_yref, double *grad_yref_e);
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */

@@ -8,7 +8,11 @@
   (c) closed loops of n control steps (bench.py's persistent setup: one untimed step, a warm-up call, then the timed call): plain
       run_steps, run_steps_sens in mode 1 (the gain of every step into pinned memory) and n x step() with mode 1 and the gain read back
       in stream order; solves/s and the time each adds per step.  B = 8192 takes launches per step in both run_steps calls.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops] > result.json"""
+  (d) --adjoint: the adjoint sensitivities (kernels_adj.hip) after one RTI step of the same workload, B = 1024 and 8192, n_seeds = 1,
+      2 (both seeds NULL: the unit seeds on u_0, nothing to upload) and 8 (seed_x and seed_u given): median of --steps calls of
+      ihm2mpc_eval_adjoint_sensitivities -- wall time of the whole call with the seed upload and the three downloads, and HIP events on
+      the handle's stream around the call with every output NULL (the seed upload and the kernel; for the default seeds the kernel alone).
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint] > result.json"""
 import argparse
 import ctypes
 import json
@@ -111,13 +115,63 @@ def loop_throughput(B, n, warmup, how):
     return dict(solves_per_s=B * n / el, ms_per_step=el * 1e3 / n, launch=rec, finite_gain_rows=ok)
 
 
+def adjoint_timings(B, steps, warmup):
+    from ihm2_amd import _lib
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    ocp, track = bench.build_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    s.set_x0_sensitivities(1)
+    s.set_x0(bench.sample_x0(track, B, 20240607))
+    s.init_guess()
+    s.prepare_step(40.0)
+    st = s.solve()
+    stream = ctypes.c_void_p()
+    _lib.check(s.lib.ihm2mpc_get_stream(s._h, ctypes.byref(stream)))
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(ctypes.byref(e)) == 0
+    rng = np.random.default_rng(1)
+    N = s.N
+    out = {"status0": float((st == 0).mean())}
+    for S in (1, 2, 8):
+        sx = None if S == 2 else rng.standard_normal((B, S, N + 1, 8))
+        su = None if S == 2 else rng.standard_normal((B, S, N, 2))
+        g = [np.empty((B, S, 8)), np.empty((B, S, N, 12)), np.empty((B, S, 8))]
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)      # noqa: E731
+        wall, dev = [], []
+        for i in range(warmup + steps):
+            t0 = time.perf_counter()
+            _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities(s._h, S, ptr(sx), ptr(su), *[ptr(a) for a in g]))
+            wall.append((time.perf_counter() - t0) * 1e3)
+        for i in range(warmup + steps):
+            assert hip.hipEventRecord(ev[0], stream) == 0
+            _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities(s._h, S, ptr(sx), ptr(su), None, None, None))
+            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+            ms = ctypes.c_float()
+            assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) == 0
+            dev.append(ms.value)
+        out[f"n_seeds_{S}"] = dict(call_wall_ms=float(np.median(wall[warmup:])), upload_and_kernel_event_ms=float(np.median(dev[warmup:])),
+                                   event_ms_spread=float(np.ptp(dev[warmup:]) / np.median(dev[warmup:])),
+                                   finite_rows=float(np.isfinite(g[1]).all(axis=(1, 2, 3)).mean()))
+    for e in ev:
+        hip.hipEventDestroy(e)
+    s.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--loop-steps", default="20,500")
     ap.add_argument("--only-loops", action="store_true")
+    ap.add_argument("--adjoint", action="store_true")
     a = ap.parse_args()
+    if a.adjoint:
+        print(json.dumps({"adjoint": {str(B): adjoint_timings(B, a.steps, a.warmup) for B in (1024, 8192)}}))
+        return
     out = {"batch": {}, "one_car": {}, "loops": {}}
     for B in (1024, 8192):
         for n in (int(v) for v in a.loop_steps.split(",")):
