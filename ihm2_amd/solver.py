@@ -420,7 +420,9 @@ class BatchedOcpSolver:
         ``qp``: the last per-step QP launch, e.g. ``"k_qp_wave<8,2,0,1>"`` (NSLOT, NSOFT, PATH, UNI) or ``"k_qp_block<2,1,4>"``
         (slots per thread, UNI, wavefronts); ``steps``: the last ``run_steps``, ``"k_steps<...>"`` (NSLOT, NSOFT, PATH, UNI, SQP, IRK,
         DYN, and an eighth 1 for the loop with x0 sensitivities) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` /
-        ``"not_resident"``.  ``None`` where nothing was launched yet."""
+        ``"not_resident"``; ``linearize`` / ``sim``: the kernel of the last linearisation / plant launch outside ``k_steps``
+        (``"k_linearize"``, ``"k_linearize_dyn"``, ``"k_linearize_cols"``, ``"k_linearize_irk"``; ``"k_sim_step_kin"``, ``"k_sim_step"``,
+        ``"k_sim_irk"``).  ``None`` where nothing was launched yet."""
         rec = np.zeros(16, dtype=np.int32)
         _lib.check(self.lib.ihm2mpc_get_launch_record(self._h, rec.ctypes.data_as(_lib.c_int32_p)))
         r = [int(v) for v in rec]
@@ -434,7 +436,9 @@ class BatchedOcpSolver:
             steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13]) if r[14] == 0 else "k_steps<%d,%d,%d,%d,%d,%d,%d,1>" % tuple(r[6:13])
         elif r[5] == 2:
             steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
-        return {"qp": qp, "steps": steps, "steps_fallback": fallback}
+        lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk")[r[15] & 15]
+        sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk")[(r[15] >> 4) & 15]
+        return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim}
 
     # ---- device-pointer variants (zero copy; dptr = integer device address, instance-major layout) ----
     def set_x0_device(self, dptr: int):

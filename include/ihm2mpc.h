@@ -262,7 +262,9 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *       [6..12] the k_steps parameters NSLOT, NSOFT, PATH, UNI, SQP, IRK, DYN (0 when [5] != 1);
  *       [13] why it went per step: 0 it did not, 1 the configuration has no k_steps instantiation, 2 the batch exceeds the resident limit
  *       [14] SENS: 1 the k_steps launch computed x0 sensitivities (ihm2mpc_run_steps_sens), 0 otherwise (0 when [5] != 1)
- *   [15] 0 (reserved) */
+ *   [15] bits 0..3 the last linearisation launch (ihm2mpc_linearize, a solve, ihm2mpc_step): 0 none yet, 1 k_linearize, 2 k_linearize_dyn,
+ *       3 k_linearize_cols, 4 k_linearize_irk;  bits 4..7 the last plant launch (ihm2mpc_sim_step, ihm2mpc_sim_advance, ihm2mpc_step):
+ *       0 none yet, 1 k_sim_step_kin, 2 k_sim_step, 3 k_sim_irk.  Launches inside k_steps are not recorded here. */
 int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
 
 /* ---- sensitivities of the solution with respect to the initial state (acados: eval_param_sens(index, 0, "ex"), then

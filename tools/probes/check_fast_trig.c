@@ -26,6 +26,7 @@ static void fast_sincos(double x, double *sp, double *cp)
     double so = (q & 1) ? cv : sv, co = (q & 1) ? sv : cv;
     so = (q & 2) ? -so : so;
     co = ((q + 1) & 2) ? -co : co;
+    if (!(fabs(x) <= 1e5)) { so = sin(x); co = cos(x); }      /* huge, inf, nan: the library (sincos_lib in the header) */
     *sp = so; *cp = co;
 }
 static double tanh_e(double y) { const double t = exp(-2.0 * fabs(y)); return copysign((1.0 - t) / (1.0 + t), y); }
@@ -43,5 +44,16 @@ int main(void)
     printf("max abs err sin %.3e cos %.3e tanh %.3e ; at 99999.5: %.3e %.3e\n", es, ec, et, fabs(s - sin(99999.5)), fabs(c - cos(99999.5)));
     int bad = 0;
     for (double x = -8; x <= 8; x += 0.785) { fast_sincos(x, &s, &c); if (fabs(s - sin(x)) > 1e-15 || fabs(c - cos(x)) > 1e-15) { printf("bad %g\n", x); bad = 1; } }
+    /* the heading family of tests/edge_states.py: both sides of the quadrant boundaries of the reduction, and reduction indices up to 6e4.
+     * Three fused reduction steps round at the size of r (|r| < 0.8: 5.6e-17 each), the kernel polynomials and libm stay below one ulp of
+     * the result: 5e-16 absolute, also at 1e5 (the header's 1e-16 |x| is a bound on the reduction constants' truncation, far from attained).
+     * 1e5 is the last argument of the lean path; 1.1e5 takes the library branch, which on the host is libm itself: that line checks the
+     * threshold's direction and nothing else (the device's branch is compared with the oracle by tests/test_gpu_edge_states.py). */
+    static const double hd[] = {0.78, 0.79, 1.57, 1.58, 2.35, 2.36, 3.14, 3.15, 4.8, 6.3, 40.0, 1e3, 9.9e4, 99999.5, 1e5, 1.1e5};
+    for (unsigned i = 0; i < 2 * sizeof(hd) / sizeof(hd[0]); i++) {
+        const double x = (i & 1) ? -hd[i / 2] : hd[i / 2];
+        fast_sincos(x, &s, &c);
+        if (fabs(s - sin(x)) > 5e-16 || fabs(c - cos(x)) > 5e-16) { printf("bad heading %g: %.3e %.3e\n", x, fabs(s - sin(x)), fabs(c - cos(x))); bad = 1; }
+    }
     return (bad || es > 2.5e-16 || ec > 2.5e-16 || et > 2.5e-16) ? 1 : 0;
 }
