@@ -1350,8 +1350,9 @@ int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens
     return 0;
 }
 
-int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0,
-                                       double *grad_yref, double *grad_yref_e)
+// ihm2mpc_eval_adjoint_sensitivities and ihm2mpc_eval_adjoint_sensitivities_w (weights: grad_W / grad_W_e are computed and may be asked for)
+static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0, double *grad_yref,
+                        double *grad_yref_e, bool weights, double *grad_W, double *grad_W_e)
 {
     CHECK_H(h);
     if (h->cfg.nlp_solver_type == IHM2MPC_SQP)
@@ -1367,15 +1368,30 @@ int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const
     if (h->adj_gx0.size() < B * S * NX &&
         alloc_all(h->adj_sx, B * S * NS * NX, h->adj_su, B * S * N * NU, h->adj_gx0, B * S * NX, h->adj_gy, B * S * N * NY, h->adj_gye, B * S * NX))
         return -1;
+    if (weights && h->adj_gW.size() < B * S * NY * NY && alloc_all(h->adj_gW, B * S * NY * NY, h->adj_gWe, B * S * NX * NX)) return -1;
     if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (seed_u) HIP_TRY(hipMemcpyAsync(h->adj_su, seed_u, B * S * N * NU * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0);
+    ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0, weights ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, h->adj_gy, B * S * N * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, h->adj_gye, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_W) HIP_TRY(hipMemcpyAsync(grad_W, h->adj_gW, B * S * NY * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, h->adj_gWe, B * S * NX * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));      // the seeds may be reused and the gradients read as soon as we return
     return 0;
+}
+
+int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0,
+                                       double *grad_yref, double *grad_yref_e)
+{
+    return eval_adjoint(h, n_seeds, seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, false, nullptr, nullptr);
+}
+
+int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0,
+                                         double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e)
+{
+    return eval_adjoint(h, n_seeds, seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
 }
 
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)

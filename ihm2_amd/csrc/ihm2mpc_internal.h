@@ -209,6 +209,7 @@ struct ihm2mpc_handle {
     // ---- adjoint sensitivities (ihm2mpc_eval_adjoint_sensitivities, kernels_adj.hip): grown on demand to the largest n_seeds seen ----
     DevBuf<double> adj_sx, adj_su;         // (B,n_seeds,NS,8), (B,n_seeds,N,2) seeds
     DevBuf<double> adj_gx0, adj_gy, adj_gye;   // (B,n_seeds,8), (B,n_seeds,N,12), (B,n_seeds,8) gradients
+    DevBuf<double> adj_gW, adj_gWe;        // (B,n_seeds,12,12), (B,n_seeds,8,8) gradients in the weights (ihm2mpc_eval_adjoint_sensitivities_w)
 };
 
 // --- launchers (each defined in one .hip file) ---
@@ -240,8 +241,9 @@ void ihm2_launch_project(ihm2mpc_handle *h, double s_tol, const double *xc, doub
 void ihm2_launch_sens(ihm2mpc_handle *h);
 size_t ihm2_sens_lds_bytes(const ihm2mpc_handle *h);
 // kernels_adj.hip: the gradients of n_seeds scalar functions of that solution in x0, yref, yref_e into h->adj_gx0, adj_gy, adj_gye;
-// seeds in device memory (nullptr = zero), unit_u0: the two unit seeds on u_0 instead
-void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0);
+// seeds in device memory (nullptr = zero), unit_u0: the two unit seeds on u_0 instead; weights: also the gradients in W, W_e into
+// h->adj_gW, adj_gWe (the other three are the same bits either way)
+void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights);
 
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'

@@ -16,6 +16,14 @@
 // helpers (side_sigma, SSYNC) and its argument block are sens_body.hpp's.  Phases 2 and 3 carry vectors of 8 / 10 entries, so the lane
 // (seed = lane >> 3, row = lane & 7) runs up to eight seeds through both sweeps at the cost of one; p and zeta_x change hands through
 // LDS (two buffers: a stage reads one and writes the other), kappa_k of all stages and seeds waits in LDS for the forward sweep.  fp64.
+//
+// The gradients in the cost weights (k_adj<true>: ihm2mpc_eval_adjoint_sensitivities_w).  The stationarity row of stage k reads
+// H_k dz_k + g_k = c_s V' W_k (V z+_k - yref_k) with z+ the returned solution, so a change dW of the weights moves it by c_s V' dW e_k,
+// e_k = V z+_k - yref_k (terminal: dW_e (x+_N - yref_e)), and on the symmetric matrices
+//   dL/dW = -c_s sum_{k<N} sym((V zeta_k) e_k'),   dL/dW_e = -sym(zeta_N[0:8] (x+_N - yref_e)'),   sym(X) = (X + X') / 2.
+// The forward sweep holds all of V zeta_k in every lane of a seed's group (zeta_x,k in LDS, zeta_u,k in registers); e_k does not depend on
+// the seed and is formed once per stage by 12 lanes.  The lane (seed, row) keeps row `row` of the 12 x 12 sum and six entries of row
+// 8 + (row >> 1) in registers -- 18 of the seed's 144 -- and the sums are symmetrised through LDS when they are written.
 #include <cmath>
 
 #include "ihm2mpc_internal.h"
@@ -32,6 +40,10 @@ struct AdjArgs {
     int unit_u0;        // the two unit seeds on u_0 (n_seeds = 2) instead of seed_x / seed_u
     const double *seed_x, *seed_u;      // (B,n_seeds,N+1,8), (B,n_seeds,N,2); nullptr = zero
     double *grad_x0, *grad_yref, *grad_yref_e;      // (B,n_seeds,8), (B,n_seeds,N,12), (B,n_seeds,8)
+    // k_adj<true> only
+    const double *yref, *yref_e;        // (B,N,12), (B,8) as the solve read them
+    double cs;                          // cost_scale_stage
+    double *grad_W, *grad_W_e;          // (B,n_seeds,12,12), (B,n_seeds,8,8)
 };
 
 // LDS of one instance (doubles) behind the factorisation's arrays: see the carve-up in k_adj
@@ -39,7 +51,14 @@ __host__ __device__ constexpr size_t adj_lds_doubles(size_t N)
 {
     return (N + 1) * (SENS_NR + 6) + N * 16 + 64 + 64 + 16 + 100 + 64 + 16 + 84 + N * 4 + N * 16 + 128 + 128;
 }
+// k_adj<true>: e_k (16) behind those, and at least the 8 x 144 doubles the sums of the eight seeds are symmetrised through
+__host__ __device__ constexpr size_t adjw_lds_doubles(size_t N)
+{
+    return adj_lds_doubles(N) + 16 > 8 * 144 ? adj_lds_doubles(N) + 16 : 8 * 144;
+}
 
+// WG: also the gradients in the cost weights (grad_W, grad_W_e); the three other outputs are computed by the same instructions either way
+template <bool WG>
 __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
 {
     extern __shared__ double sm[];
@@ -64,6 +83,7 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
     double *kap = Qi + N * 4;        // N*16   kappa_k of seed j at (k * 8 + j) * 2
     double *pv = kap + N * 16;       // 2*64   p_k of the eight seeds, two buffers
     double *zx = pv + 128;           // 2*64   zeta_x,k of the eight seeds, two buffers
+    double *ek = zx + 128;           // 16     e_k = V z+_k - yref_k (WG only)
 
     const size_t bs = (size_t)b;
     const int sd = lane >> 3, row = lane & 7;       // phases 2 and 3: this lane's seed and row
@@ -75,6 +95,11 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
             gx0[row] = NAN;
             gye[row] = NAN;
             for (int e = row; e < N * 12; e += 8) gyr[e] = NAN;
+            if (WG) {
+                double *gW = aa.grad_W + (bs * S + sd) * 144, *gWe = aa.grad_W_e + (bs * S + sd) * 64;
+                for (int e = row; e < 144; e += 8) gW[e] = NAN;
+                for (int e = row; e < 64; e += 8) gWe[e] = NAN;
+            }
         }
         return;
     }
@@ -291,9 +316,23 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
     cur = 0;
     zx[lane] = 0.0;
     ra = linb[lane]; rbv = (lane < 16) ? linb[64 + lane] : 0.0;
+    // WG: row `row` of sum_k (V zeta_k) e_k' and the columns hc0 .. hc0 + 5 of its row 8 + (row >> 1)
+    double wr[12], wh[6];
+    const int hr = row >> 1, hc0 = (row & 1) * 6;
+    const double *yrb = WG ? aa.yref + bs * N * 12 : nullptr;
+    if (WG) {
+#pragma unroll
+        for (int j = 0; j < 12; j++) wr[j] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; j++) wh[j] = 0.0;
+    }
     for (int k = 0; k < N; k++) {
         Al[lane] = ra;
         if (lane < 16) Bl[lane] = rbv;
+        if (WG && lane < 12) {       // e_k: y = (x, u, x[6:8] - u) of the returned solution minus yref_k
+            const double y = (lane < 8) ? xo[k * 8 + lane] : (lane < 10) ? uo[k * 2 + lane - 8] : xo[k * 8 + lane - 4] - uo[k * 2 + lane - 10];
+            ek[lane] = y - yrb[k * 12 + lane];
+        }
         if (k + 1 < N) {
             ra = linb[(size_t)(k + 1) * LIN_REC + lane];
             if (lane < 16) rbv = linb[(size_t)(k + 1) * LIN_REC + 64 + lane];
@@ -321,6 +360,14 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
             g1 = fma(G[9 * 12 + 8 + row], u1, g1);
             if (live) gyr[k * 12 + 8 + row] = g1;
         }
+        if (WG) {
+            // V zeta_k: zeta_x,k (8), zeta_u,k (2), zeta_x,k[6:8] - zeta_u,k
+            const double ar = zk[row], ah = (hr == 0) ? u0 : (hr == 1) ? u1 : (hr == 2) ? zk[6] - u0 : zk[7] - u1;
+#pragma unroll
+            for (int j = 0; j < 12; j++) wr[j] = fma(ar, ek[j], wr[j]);
+#pragma unroll
+            for (int j = 0; j < 6; j++) wh[j] = fma(ah, ek[hc0 + j], wh[j]);
+        }
         cur ^= 1;
         zx[cur * 64 + lane] = xn;
         SSYNC();
@@ -331,14 +378,40 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
 #pragma unroll
         for (int l = 0; l < 8; l++) ge = fma(GyT[l * 12 + row], zk[l], ge);
         if (live) gye[row] = ge;
+        if (WG) {
+            // the terminal outer product: both products rounded before they are added, so that entry (i, j) and entry (j, i) get the same bits
+            double *gWe = aa.grad_W_e + (bs * S + sd) * 64;
+            const double *xN = xo + N * 8, *yre = aa.yref_e + bs * 8;
+            const double zi = zk[row], ei = xN[row] - yre[row];
+            double oe[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) oe[j] = -0.5 * (__dmul_rn(zi, xN[j] - yre[j]) + __dmul_rn(zk[j], ei));
+            SSYNC();                    // every lane has read zeta_N: the LDS is free for the staging of the stage sums
+            double *X = sm + sd * 144;
+#pragma unroll
+            for (int j = 0; j < 12; j++) X[row * 12 + j] = wr[j];
+#pragma unroll
+            for (int j = 0; j < 6; j++) X[(8 + hr) * 12 + hc0 + j] = wh[j];
+            SSYNC();
+            if (live) {
+                double *gW = aa.grad_W + (bs * S + sd) * 144;
+                const double f = -0.5 * aa.cs;
+                for (int e = row; e < 144; e += 8) {
+                    const int i = e / 12, j = e - i * 12;
+                    gW[e] = f * (X[i * 12 + j] + X[j * 12 + i]);
+                }
+#pragma unroll
+                for (int j = 0; j < 8; j++) gWe[row * 8 + j] = oe[j];
+            }
+        }
     }
 }
 
 }  // namespace
 
 // The handle's adjoint evaluation on h->stream: seeds from h->adj_sx / h->adj_su (nullptr = zero; unit_u0: the two unit seeds on u_0),
-// gradients into h->adj_gx0, h->adj_gy, h->adj_gye.
-void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0)
+// gradients into h->adj_gx0, h->adj_gy, h->adj_gye and (weights) h->adj_gW, h->adj_gWe.
+void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights)
 {
     AdjArgs a;
     ihm2_sens_args(h, &a.s);
@@ -347,7 +420,15 @@ void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const
     a.n_seeds = n_seeds; a.unit_u0 = unit_u0;
     a.seed_x = seed_x; a.seed_u = seed_u;
     a.grad_x0 = h->adj_gx0; a.grad_yref = h->adj_gy; a.grad_yref_e = h->adj_gye;
+    a.yref = h->yref; a.yref_e = h->yref_e; a.cs = h->cfg.cost_scale_stage;
+    a.grad_W = h->adj_gW; a.grad_W_e = h->adj_gWe;
+    if (weights) {
+        const size_t lds = sizeof(double) * adjw_lds_doubles((size_t)h->N);
+        (void)hipFuncSetAttribute((const void *)k_adj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k_adj<true>, dim3(h->B), dim3(64), lds, h->stream, a);
+        return;
+    }
     const size_t lds = sizeof(double) * adj_lds_doubles((size_t)h->N);
-    (void)hipFuncSetAttribute((const void *)k_adj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_adj, dim3(h->B), dim3(64), lds, h->stream, a);
+    (void)hipFuncSetAttribute((const void *)k_adj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_adj<false>, dim3(h->B), dim3(64), lds, h->stream, a);
 }

@@ -485,6 +485,9 @@ class BatchedOcpSolver:
         ``u_0``, i.e. the Jacobians of the first control.  Returns ``dict(x0=(B,S,8), yref=(B,S,N,12), yref_e=(B,S,8))``, NaN rows for
         instances whose status is neither 0 nor 2.  Needs ``set_x0_sensitivities(1 or 2)`` before the solve and must follow the solve
         directly (``ihm2mpc_eval_adjoint_sensitivities``)."""
+        return self._eval_adjoint(seed_x, seed_u, False)
+
+    def _eval_adjoint(self, seed_x, seed_u, weights: bool):
         B, N = self.B, self.N
         given = seed_x if seed_x is not None else seed_u
         if given is None:
@@ -495,9 +498,27 @@ class BatchedOcpSolver:
         sx = None if seed_x is None else _f64(np.asarray(seed_x, dtype=np.float64).reshape(B, S, N + 1, NX), (B, S, N + 1, NX), "seed_x")
         su = None if seed_u is None else _f64(np.asarray(seed_u, dtype=np.float64).reshape(B, S, N, NU), (B, S, N, NU), "seed_u")
         out = dict(x0=np.empty((B, S, NX)), yref=np.empty((B, S, N, NY)), yref_e=np.empty((B, S, NX)))
-        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities(self._h, S, None if sx is None else _ptr(sx), None if su is None else _ptr(su),
-                                                               _ptr(out["x0"]), _ptr(out["yref"]), _ptr(out["yref_e"])))
+        if weights:
+            out.update(W=np.empty((B, S, NY, NY)), W_e=np.empty((B, S, NX, NX)))
+        fn = self.lib.ihm2mpc_eval_adjoint_sensitivities_w if weights else self.lib.ihm2mpc_eval_adjoint_sensitivities
+        _lib.check(fn(self._h, S, None if sx is None else _ptr(sx), None if su is None else _ptr(su), *[_ptr(v) for v in out.values()]))
         return {k: v[:, 0] for k, v in out.items()} if squeeze else out
+
+    def eval_adjoint_weight_sensitivities(self, seed_x=None, seed_u=None):
+        """``eval_adjoint_sensitivities`` with the gradients in the cost weights: ``dict(x0, yref, yref_e, W=(B,S,12,12),
+        W_e=(B,S,8,8))``, the first three the same bits.  ``W = -c_s sum_k sym((V zeta_k) e_k')`` with ``e_k = V z_k - yref_k`` at the
+        returned solution and ``W_e = -sym(zeta_N (x_N - yref_e)')``: the gradients on the symmetric matrices, ``dL = <W, dW> +
+        <W_e, dW_e>`` for a symmetric change ``dW`` common to all stages (the diagonal entry is ``dL/dq_i`` of a diagonal weight).  Same
+        seed shapes, squeeze rule, preconditions and NaN rows as ``eval_adjoint_sensitivities``
+        (``ihm2mpc_eval_adjoint_sensitivities_w``).  Bounds are not differentiated."""
+        return self._eval_adjoint(seed_x, seed_u, True)
+
+    def du0_dW(self):
+        """``dict(W=(B,2,12,12), W_e=(B,2,8,8))``: the derivative of the first control of the last solve in the cost weights (the two
+        unit seeds on ``u_0``)."""
+        out = dict(W=np.empty((self.B, 2, NY, NY)), W_e=np.empty((self.B, 2, NX, NX)))
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_w(self._h, 2, None, None, None, None, None, _ptr(out["W"]), _ptr(out["W_e"])))
+        return out
 
     def du0_ds_target(self):
         """``(B,2)``: the reaction of the first control of the last solve to ``prepare_step``'s ``s_target`` -- the reference ramp puts
@@ -714,19 +735,33 @@ class AcadosOcpSolver:
         if with_respect_to not in ("x0", "yref", "yref_e"):
             raise Exception(f"AcadosOcpSolver.eval_adjoint_solution_sensitivity(): with_respect_to '{with_respect_to}' is not supported "
                             "('x0', 'yref', 'yref_e')")
-        b = self.batch
+        sx, su = self._adjoint_seeds(seed_x, seed_u, "eval_adjoint_solution_sensitivity")
+        return self.batch.eval_adjoint_sensitivities(sx, su)[with_respect_to][self.i].copy()
+
+    def _adjoint_seeds(self, seed_x, seed_u, who: str):
+        """The batch's seed arrays (B,S,N+1,8), (B,S,N,2) from acados' lists of ``(stage, array (nx | nu, n_seeds))``: this instance's
+        rows, zero elsewhere."""
         pairs = [(st, np.asarray(v, dtype=np.float64), n, nm) for lst, n, nm in ((seed_x, NX, "seed_x"), (seed_u, NU, "seed_u"))
                  for st, v in (lst or [])]
         if not pairs:
-            raise Exception("AcadosOcpSolver.eval_adjoint_solution_sensitivity(): seed_x and seed_u are both empty")
+            raise Exception(f"AcadosOcpSolver.{who}(): seed_x and seed_u are both empty")
+        b = self.batch
         S = pairs[0][1].shape[1] if pairs[0][1].ndim == 2 else 0
         sx, su = np.zeros((b.B, S, b.N + 1, NX)), np.zeros((b.B, S, b.N, NU))
         for st, v, n, nm in pairs:
             if v.shape != (n, S) or not 0 <= int(st) <= (b.N if n == NX else b.N - 1):
-                raise Exception(f"AcadosOcpSolver.eval_adjoint_solution_sensitivity(): {nm} entries are (stage, array ({n}, n_seeds)) "
+                raise Exception(f"AcadosOcpSolver.{who}(): {nm} entries are (stage, array ({n}, n_seeds)) "
                                 f"with one n_seeds, got stage {st}, shape {v.shape}")
             (sx if n == NX else su)[self.i, :, int(st), :] += v.T
-        return b.eval_adjoint_sensitivities(sx, su)[with_respect_to][self.i].copy()
+        return sx, su
+
+    def eval_adjoint_weight_sensitivity(self, seed_x, seed_u):
+        """The gradient of ``sum_k seed_x[k]' x_k + seed_u[k]' u_k`` of this instance's last solution in the cost weights: seeds as for
+        ``eval_adjoint_solution_sensitivity``, returns ``(grad_W (n_seeds, 12, 12), grad_W_e (n_seeds, 8, 8))``
+        (``BatchedOcpSolver.eval_adjoint_weight_sensitivities``).  acados has no counterpart."""
+        sx, su = self._adjoint_seeds(seed_x, seed_u, "eval_adjoint_weight_sensitivity")
+        g = self.batch.eval_adjoint_weight_sensitivities(sx, su)
+        return g["W"][self.i].copy(), g["W_e"][self.i].copy()
 
     def get(self, stage: int, field: str) -> np.ndarray:
         if field in ("sens_x", "sens_u"):

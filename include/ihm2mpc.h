@@ -31,6 +31,8 @@
  *   ihm2mpc_set/get_x0_sensitivities <- solver.eval_param_sens(j, 0, "ex"); solver.get(k, "sens_x" / "sens_u") (acados)
  *   ihm2mpc_run_steps_sens    <- the same after every solve of ihm2mpc_run_steps' loop
  *   ihm2mpc_eval_adjoint_sensitivities <- solver.eval_adjoint_solution_sensitivity(seed_x, seed_u) (acados)
+ *   ihm2mpc_eval_adjoint_sensitivities_w <- the same, and the gradients in the cost weights W, W_e (acados has no counterpart: one
+ *                                           re-solve per weight entry and direction)
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -311,6 +313,29 @@ int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr);
  * evaluate several batches of seeds against one solve).  Blocking: the seeds may be reused and the gradients read on return. */
 int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
                                        double *grad_x0, double *grad_yref, double *grad_yref_e);
+/* The same call with the gradients in the cost weights: a superset of ihm2mpc_eval_adjoint_sensitivities -- grad_x0, grad_yref and
+ * grad_yref_e are the same bits -- with two more outputs.  The QP's stationarity row of stage k < N reads
+ * H_k dz_k + g_k = c_s V' W_k (V z+_k - yref_k), with z+ the returned solution (ihm2mpc_get_x / _get_u after the solve), c_s the
+ * configuration's cost_scale_stage and V the 12 x 10 output selector y = (x, u, x[6:8] - u); the terminal row reads W_e (x+_N - yref_e).
+ * A change dW moves the stage's row by c_s V' dW e_k, e_k = V z+_k - yref_k, so with zeta of the seed as above
+ *     grad_W = -c_s sum_{k<N} sym((V zeta_k) e_k')  (12,12),     grad_W_e = -sym(zeta_N[0:8] (x+_N - yref_e)')  (8,8),
+ * sym(X) = (X + X') / 2: the gradients on the space of symmetric matrices (the weight setters refuse any other), i.e.
+ * dL = <grad_W, dW> + <grad_W_e, dW_e> for every symmetric direction, and for diagonal weights dL/dq_i is the diagonal entry.
+ * grad_W is the derivative in a change common to all stages k < N: exact for per-instance weights (ihm2mpc_set_instance_weights, one W
+ * for every stage) and for a stage-independent shared table; for a stage-dependent shared table it is the derivative in a common shift
+ * of all stages (there is no per-stage output).  Bounds are not differentiated: dL/dbound_i = sigma_i r_i' zeta, and on an active hard
+ * side sigma_i = lam / max(gap, IHM2MPC_SENS_TAU) reaches 1e13 while r_i' zeta is of the order 1 / sigma_i out of a sweep whose absolute
+ * error is about 1e-16 of its scale -- the product has no accuracy that could be stated in advance.
+ * Outputs, any may be NULL: the three of ihm2mpc_eval_adjoint_sensitivities, grad_W (B,n_seeds,12,12), grad_W_e (B,n_seeds,8,8), both
+ * exactly symmetric; NaN for instances whose status is neither 0 nor 2.  Per-instance weights and bounds are honoured (e_k does not
+ * depend on W).  Both seeds NULL with n_seeds == 2: the two unit seeds on u_0, grad_W = du_0/dW.  Same preconditions and refusals as
+ * ihm2mpc_eval_adjoint_sensitivities: x0 sensitivity mode 1 or 2 on for the solve; refused while the mode is off, before a solve with the
+ * mode on, after ihm2mpc_run_steps (after ihm2mpc_run_steps_sens: the last step's), in the SQP mode, for n_seeds outside 1..8 and for
+ * both seeds NULL with n_seeds != 2.  It also reads yref and yref_e as the solve read them: it must follow the solve directly.  Memory
+ * for the two outputs on first use.  It changes no other output, those of ihm2mpc_eval_adjoint_sensitivities included.  Blocking. */
+int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
+                                         double *grad_x0, double *grad_yref, double *grad_yref_e,
+                                         double *grad_W, double *grad_W_e);   /* (B,n_seeds,12,12), (B,n_seeds,8,8) */
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */

@@ -12,7 +12,9 @@
       2 (both seeds NULL: the unit seeds on u_0, nothing to upload) and 8 (seed_x and seed_u given): median of --steps calls of
       ihm2mpc_eval_adjoint_sensitivities -- wall time of the whole call with the seed upload and the three downloads, and HIP events on
       the handle's stream around the call with every output NULL (the seed upload and the kernel; for the default seeds the kernel alone).
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint] > result.json"""
+  (e) --adjoint-weights: the same rows for ihm2mpc_eval_adjoint_sensitivities_w (k_adj<true>: the gradients in the cost weights W, W_e as
+      well; the wall time holds its five downloads).
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights] > result.json"""
 import argparse
 import ctypes
 import json
@@ -115,7 +117,7 @@ def loop_throughput(B, n, warmup, how):
     return dict(solves_per_s=B * n / el, ms_per_step=el * 1e3 / n, launch=rec, finite_gain_rows=ok)
 
 
-def adjoint_timings(B, steps, warmup):
+def adjoint_timings(B, steps, warmup, weights=False):
     from ihm2_amd import _lib
     from ihm2_amd.solver import BatchedOcpSolver
 
@@ -135,26 +137,29 @@ def adjoint_timings(B, steps, warmup):
     rng = np.random.default_rng(1)
     N = s.N
     out = {"status0": float((st == 0).mean())}
+    fn = s.lib.ihm2mpc_eval_adjoint_sensitivities_w if weights else s.lib.ihm2mpc_eval_adjoint_sensitivities
     for S in (1, 2, 8):
         sx = None if S == 2 else rng.standard_normal((B, S, N + 1, 8))
         su = None if S == 2 else rng.standard_normal((B, S, N, 2))
         g = [np.empty((B, S, 8)), np.empty((B, S, N, 12)), np.empty((B, S, 8))]
+        if weights:
+            g += [np.empty((B, S, 12, 12)), np.empty((B, S, 8, 8))]
         ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)      # noqa: E731
         wall, dev = [], []
         for i in range(warmup + steps):
             t0 = time.perf_counter()
-            _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities(s._h, S, ptr(sx), ptr(su), *[ptr(a) for a in g]))
+            _lib.check(fn(s._h, S, ptr(sx), ptr(su), *[ptr(a) for a in g]))
             wall.append((time.perf_counter() - t0) * 1e3)
         for i in range(warmup + steps):
             assert hip.hipEventRecord(ev[0], stream) == 0
-            _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities(s._h, S, ptr(sx), ptr(su), None, None, None))
+            _lib.check(fn(s._h, S, ptr(sx), ptr(su), *[None] * len(g)))
             assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
             ms = ctypes.c_float()
             assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) == 0
             dev.append(ms.value)
         out[f"n_seeds_{S}"] = dict(call_wall_ms=float(np.median(wall[warmup:])), upload_and_kernel_event_ms=float(np.median(dev[warmup:])),
                                    event_ms_spread=float(np.ptp(dev[warmup:]) / np.median(dev[warmup:])),
-                                   finite_rows=float(np.isfinite(g[1]).all(axis=(1, 2, 3)).mean()))
+                                   finite_rows=float(np.isfinite(g[-2]).all(axis=(1, 2, 3)).mean()))
     for e in ev:
         hip.hipEventDestroy(e)
     s.free()
@@ -168,9 +173,11 @@ def main():
     ap.add_argument("--loop-steps", default="20,500")
     ap.add_argument("--only-loops", action="store_true")
     ap.add_argument("--adjoint", action="store_true")
+    ap.add_argument("--adjoint-weights", action="store_true")
     a = ap.parse_args()
-    if a.adjoint:
-        print(json.dumps({"adjoint": {str(B): adjoint_timings(B, a.steps, a.warmup) for B in (1024, 8192)}}))
+    if a.adjoint or a.adjoint_weights:
+        key = "adjoint_weights" if a.adjoint_weights else "adjoint"
+        print(json.dumps({key: {str(B): adjoint_timings(B, a.steps, a.warmup, a.adjoint_weights) for B in (1024, 8192)}}))
         return
     out = {"batch": {}, "one_car": {}, "loops": {}}
     for B in (1024, 8192):
