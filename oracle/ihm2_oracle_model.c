@@ -56,11 +56,12 @@ static inline cplx cs_exp(cplx z) { double e = exp(creal(z)); return cs_make(e, 
 static inline cplx cs_sqrt(cplx z) { double r = sqrt(creal(z)); return cs_make(r, cimag(z) / (2.0 * r)); }
 /* atan2(y, x) with x > 0 (x is always smooth_abs_nonzero(.) > 0 at the call sites) */
 static inline cplx cs_atan2_pos(cplx y, cplx x) { return cs_atan(y / x); }
-/* general atan2 (any quadrant): d atan2(y, x) = (x dy - y dx) / (x^2 + y^2) */
+/* general atan2 (any quadrant): d atan2(y, x) = (x dy - y dx) / (x^2 + y^2).  At the origin the value is atan2's (+-0 or +-pi, as
+ * python/models.py:376-379 has it for a car at rest) and the derivative part, 0/0 as written, is 0 */
 static inline cplx cs_atan2(cplx y, cplx x)
 {
-    double yr = creal(y), xr = creal(x);
-    return cs_make(atan2(yr, xr), (xr * cimag(y) - yr * cimag(x)) / (xr * xr + yr * yr));
+    double yr = creal(y), xr = creal(x), q = xr * xr + yr * yr;
+    return cs_make(atan2(yr, xr), q > 0.0 ? (xr * cimag(y) - yr * cimag(x)) / q : 0.0);
 }
 
 /* python/utils.py:23-32 */

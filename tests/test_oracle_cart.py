@@ -6,6 +6,7 @@ import numpy as np
 
 from oracle import models_np as mnp
 from oracle import oracle as orc
+from project_np import _project_np
 
 Z2 = np.zeros(2)
 
@@ -74,33 +75,6 @@ def test_plant_step_switch_and_no_reversing():
     sol = solve_ivp(lambda t, y: mnp.kin6(y, u[5]), (0, 0.01), x[5], method="Radau", rtol=1e-12, atol=1e-14)
     xfine = orc.sim_step_cart(x[5:6], u[5:6], orc.MODEL_KIN6, 200, dt=0.01)[0]
     assert np.max(np.abs(sol.y[:, -1] - xfine) / (1 + np.abs(xfine))) < 1e-8
-
-
-def _wrap(a):
-    return (a + np.pi) % (2 * np.pi) - np.pi
-
-
-def _project_np(s_ref, X_ref, Y_ref, phi_ref, X, Y, s_guess, s_tol):
-    """Independent NumPy restatement of tracks.cpp:183-288."""
-    n = len(s_ref)
-    lo = max(np.searchsorted(s_ref, max(s_guess - s_tol, s_ref[0]), side="right") - 1, 0)
-    up = np.searchsorted(s_ref, min(s_guess + s_tol, s_ref[-1]), side="right") - 1
-    lo = lo - 1 if lo > 0 else lo
-    up = up + 1 if up < n - 1 else up
-    P = np.stack([X_ref[lo:up + 1], Y_ref[lo:up + 1]], 1)
-    car = np.array([X, Y])
-    i = int(np.argmin(((P - car) ** 2).sum(1)))
-    ip, inx = (i - 1) % len(P), (i + 1) % len(P)
-    ang = lambda a, b, c: abs(_wrap(np.arctan2(c[1] - b[1], c[0] - b[0]) - np.arctan2(a[1] - b[1], a[0] - b[0])))
-    if ang(P[i], car, P[ip]) > ang(P[i], car, P[inx]):
-        a, b, sa, sb = P[ip], P[i], s_ref[lo + ip], s_ref[lo + i]
-    else:
-        a, b, sa, sb = P[i], P[inx], s_ref[lo + i], s_ref[lo + inx]
-    lam = np.dot(car - a, b - a) / np.dot(b - a, b - a)
-    s = sa + lam * (sb - sa)
-    ind = min(lo + i, n - 2)
-    phi = phi_ref[ind] + (phi_ref[ind + 1] - phi_ref[ind]) / (s_ref[ind + 1] - s_ref[ind]) * (s - s_ref[ind])
-    return s, a[0] + lam * (b[0] - a[0]), a[1] + lam * (b[1] - a[1]), phi
 
 
 def test_projection_matches_numpy_restatement(track):
