@@ -56,6 +56,24 @@ def test_product_does_not_import_the_oracle():
                 assert "oracle" not in text.lower().replace("no cpu fallback", ""), f"{f} mentions the oracle"
 
 
+def test_sensitivity_factorisation_is_written_once():
+    """k_sens and k_adj differentiate one linear system: the row weights (the calls of side_sigma) and the entries of Ht (htilde) are
+    written in one file of csrc, which both kernels include -- not in a copy per kernel."""
+    csrc = os.path.join(ROOT, "ihm2_amd", "csrc")
+    calls, defs = [], []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp", ".h", ".cpp")):
+            continue
+        code = re.sub(r"//.*", "", open(os.path.join(csrc, f), errors="ignore").read())
+        if re.search(r"(?<!double )\bside_sigma\(", code):       # a call, not the definition `double side_sigma(`
+            calls.append(f)
+        if "auto htilde = " in code:
+            defs.append(f)
+    assert len(calls) == 1, f"side_sigma( is called in {calls}"
+    assert len(defs) == 1, f"htilde is defined in {defs}"
+    assert calls == defs
+
+
 def test_lean_trig_functions_of_the_models_match_libm(tmp_path):
     """The models' sincos / tanh (csrc/model.hpp: fast_sincos, tanh_e) restated in C with the same constants and operation order:
     within 2.5e-16 absolute of libm over +-64 rad / +-200 (tools/probes/check_fast_trig.c)."""
