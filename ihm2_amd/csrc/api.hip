@@ -194,10 +194,10 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
 }
 
 // ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
-// The catalogue is the four objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
+// The catalogue is the five objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
 // (the leading one-sided entries per lane rebuild_slots laid it out for) and its NSLOT holds the table's slots per lane; of those
 // that fit the configuration, the first in catalogue order is launched.
-const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3()};
+const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4()};
 
 // the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
 int path_class(const ihm2mpc_handle *h) { return h->alat_on ? 2 : h->path_on ? 1 : 0; }
@@ -209,10 +209,33 @@ const QpInst *find_inst(const QpKey &want)
         for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
             const QpKey &k = e->key;
             if (k.kind == want.kind && k.nsoft == want.nsoft && k.path == want.path && k.uni == want.uni && k.sqp == want.sqp &&
-                k.irk == want.irk && k.dyn == want.dyn && k.sens == want.sens && k.nslot >= want.nslot)
+                k.irk == want.irk && k.dyn == want.dyn && k.sens == want.sens && k.nf == want.nf && k.nslot >= want.nslot)
                 return e;
         }
     return nullptr;
+}
+
+// The form of the factor sweep the handle's QP may take (QpKey.nf; riccati_mfma.hpp: PLAIN).  The straight-line stage keeps neither the
+// symmetrising tile (the dynamic model as written needs it) nor the p_k stores (a table without active rows needs them): 0 then.  Otherwise
+// 40 for the horizon 40 -- the horizon as a compile-time constant -- and -1 for every other one.  IHM2MPC_QP_FORM (read once) makes the
+// forms comparable in one build: 1 keeps the horizon 40 on the run-time form as well, 0 keeps every launch on the general form.
+int factor_form(const ihm2mpc_handle *h)
+{
+    static const int limit = [] { const char *e = getenv("IHM2MPC_QP_FORM"); return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : 2; }();
+    if (limit == 0 || h->cfg.model == IHM2MPC_MODEL_FDYN6 || h->m_act == 0) return 0;
+    return (h->N == 40 && limit == 2) ? 40 : -1;
+}
+
+// find_inst with the factor sweep in the form the handle may take, where the catalogue has the instantiation in that form (the
+// compile-time horizon first, then the run-time one), else in the general form
+const QpInst *find_form(const ihm2mpc_handle *h, QpKey want)
+{
+    for (int nf = factor_form(h); nf != 0; nf = (nf > 0) ? -1 : 0) {
+        want.nf = nf;
+        if (const QpInst *e = find_inst(want)) return e;
+    }
+    want.nf = 0;
+    return find_inst(want);
 }
 
 // The slot tables the per-step QP takes for the handle's rows: (NSOFT, the largest NSLOT that comes with it) per NSOFT of its
@@ -247,7 +270,7 @@ const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
     // (per-instance bounds: the 64-lane table alone carries them -- k_qp_wave's results are the four-wave kernel's bit for bit)
     if (h->block_qp && !h->inst_b && h->nslot_lane_blk >= 1 && h->B <= h->n_cu && h->nslot_lane * 64 <= (h->N + 1) * 12)
         if (const QpInst *e = find_inst({QP_BLOCK, h->nslot_lane_blk, h->nsoft_lane, path_class(h), uni, 0, 0, 0})) return e;
-    return find_inst({QP_WAVE, h->nslot_lane, h->nsoft_lane, path_class(h), uni, 0, 0, 0});
+    return find_form(h, {QP_WAVE, h->nslot_lane, h->nsoft_lane, path_class(h), uni, 0, 0, 0});
 }
 
 // The persistent loop for the handle's configuration; nullptr: none (ihm2mpc_run_steps then launches per step, which gives the same
@@ -263,7 +286,7 @@ const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds, int sens = 0)
     if (lds > 160 * 1024) return nullptr;
     // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
     if (dyn && !irk && lds < (size_t)ihm2::s_count(1) * 64 * sizeof(double)) return nullptr;
-    return find_inst({QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
+    return find_form(h, {QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
 }
 
 // the launch record (ihm2mpc_get_launch_record) from the key of what was launched; a k_steps key with `per_step` != 0: run_steps
@@ -271,9 +294,12 @@ const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds, int sens = 0)
 void note_launch(ihm2mpc_handle *h, const QpKey &k, int per_step = 0)
 {
     int32_t *r = h->launch_rec;
+    const int form = (k.nf > 0) ? 2 : (k.nf < 0) ? 1 : 0;       // [15] bits 8..9 / 12..13: the factor sweep's form (QpKey.nf)
     if (k.kind != QP_STEPS) {
         r[0] = k.kind; r[1] = k.nslot; r[2] = k.nsoft; r[3] = k.path; r[4] = k.uni;
+        r[15] = (r[15] & ~0x300) | (form << 8);
     } else {
+        r[15] = (r[15] & ~0x3000) | ((per_step ? 0 : form) << 12);
         r[5] = per_step ? 2 : 1; r[6] = k.nslot; r[7] = k.nsoft; r[8] = k.path; r[9] = k.uni; r[10] = k.sqp; r[11] = k.irk; r[12] = k.dyn;
         r[13] = per_step; r[14] = k.sens;
     }

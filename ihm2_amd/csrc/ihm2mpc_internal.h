@@ -318,11 +318,13 @@ struct StepArgs {
 // void pointer: a function with the unnamed namespace's type in its signature could not be defined in another translation unit.)
 void ihm2_sens_args(const ihm2mpc_handle *h, void *out);
 
-// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0, 1, 2, 3) returns the table of the ones it
+// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0, 1, 2, 3, 4) returns the table of the ones it
 // holds, in its order of preference (kernels_qp.hip: QP_INSTANCES).  A key holds the template parameters as the launch record gives them
-// (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.
+// (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.  nf is not in the record: the
+// form of the factor sweep (qp_wave_body: 0 the general form, 40 straight-line with the horizon 40 compiled in, -1 straight-line with the
+// run-time horizon) -- same results, so the record names the kernel by its other parameters.
 enum { QP_WAVE = 1, QP_BLOCK = 2, QP_STEPS = 3 };
-struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens; };
+struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens, nf; };
 struct QpInst { QpKey key; int threads; const void *kernel; };
 struct QpTable { const QpInst *inst; int n; };
-QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3();
+QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4();

@@ -222,15 +222,19 @@ __device__ __forceinline__ void stream_rows_v1(const double *rows, int N, int e_
 // are parallel over stages / rows run over all NT = 64 NW threads, the constraint slots are spread over NT lanes (NSLOT is then the
 // count per lane of THAT table), reductions go wave -> LDS -> block, hand-offs are s_barriers; the three sequential sweeps run on
 // wave 0 while the others wait.  NW == 1 compiles to exactly the single-wave code (tid == lane, BSYNC == WSYNC).
-template <int NSLOT, int NSOFT, int PATH, int UNI, int NW = 1, int LEAN = 1>
+// NF != 0: the factor sweep in its straight-line form (riccati_mfma.hpp: PLAIN) -- for the launches api.hip selects it for: a table with
+// active rows (no p_k stores) of a model that needs no symmetrising tile.  NF > 0: with the horizon a.N == NF as a compile-time constant;
+// NF = -1: with the run-time horizon.  NF = 0 is the form every other instantiation keeps.
+template <int NSLOT, int NSOFT, int PATH, int UNI, int NW = 1, int LEAN = 1, int NF = 0>
 __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, double *sm, const bool want_res = true)
 {
+    static_assert(NF == 0 || NW == 1, "the straight-line factor sweep parks its idle lanes' stores in the tile the block reductions use");
     // want_res = false (wave-uniform): the stationarity residual of the incoming iterate -- an output only (ihm2mpc_get_residuals), a third of
     // the QP set-up -- is skipped; the persistent RTI loop asks for it on its last step alone
     constexpr int NT = 64 * NW;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #define BSYNC() do { if (NW == 1) WSYNC(); else __syncthreads(); } while (0)
-    const int N = a.N, NS = N + 1;
+    const int N = (NF > 0) ? NF : a.N, NS = N + 1;
     // constraint rows per stage held in LDS: 8 x boxes, 2 u boxes, 2 general rows (+ 2 track rows (+ the lateral-acceleration row, PATH == 2)); the
     // multiplier arrays in HBM always have the full NLAM = 28 columns (14 lower sides, then 14 upper sides); row 14 keeps its two in lam_a / slk_a
     constexpr int NCK = (PATH == 2) ? 15 : PATH ? 14 : 12;
@@ -728,6 +732,9 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             RicLds L;
             L.gt = NS * 10; L.pv = NS * 28; L.gam = NS * 36 + N * 8; L.dz = L.gam + 2 * NS * NCK; L.kff = L.dz + NS * 10; L.Kl = L.kff + N * 4;
             L.Ginv = L.Kl + N * 16; L.hv = L.Ginv + N * 8; L.tile = L.hv + N * 8; L.hc = L.tile + 136; L.ha = L.hc + NS * 2;
+            if constexpr (NF != 0)
+                riccati_sweep_mfma<NCK, PATH != 0, UNI != 0, RIC_RING, ALAT, true, (NF > 0) ? NF : 0>(N, lane, linb, Hs0, HsT, a.CD, L, Pg, Mg, LIN_REC, false, false);
+            else
             riccati_sweep_mfma<NCK, PATH != 0, UNI != 0, RIC_RING, ALAT>(N, lane, linb, Hs0, HsT, a.CD, L, Pg, Mg, LIN_REC, a.m_act == 0, a.symmetrize != 0);
             if (lane < 8) dz[lane] = 0.0;
         }
@@ -1125,12 +1132,13 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 
 #undef BSYNC
 
-template <int NSLOT, int NSOFT, int PATH, int UNI>
+template <int NSLOT, int NSOFT, int PATH, int UNI, int NF = 0>
 __global__ __launch_bounds__(64) void k_qp_wave(QpArgs a)
 {
     extern __shared__ double sm[];
     if ((int)blockIdx.x >= a.B) return;
-    qp_wave_body<NSLOT, NSOFT, PATH, UNI>(a, blockIdx.x, sm);
+    if (NF > 0 && a.N != NF) return;        // (api.hip selects by the handle's horizon)
+    qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, 1, NF>(a, blockIdx.x, sm);
 }
 
 // The latency kernel: NW wavefronts per instance (qp_wave_body with NW > 1), for batches that leave most of the chip idle -- the
@@ -1221,7 +1229,8 @@ __device__ __noinline__ void call_line_search(const LsArgs &ls, int b, int it, i
 // step's history row, in mode 2 the forward sweep over the horizon on the last step.  The body reuses the QP's LDS from offset 0 (the QP and
 // the linearisation write theirs before they read it).  A template parameter for the reason DYN is one: a run-time flag and the call it
 // guards would change the register allocation of the benchmarked kernels.
-template <int NSLOT, int NSOFT, int PATH, int UNI, int SQP, int IRK = 0, int DYN = 0, int SENS = 0>
+// NF: the form of the QP's factor sweep and the compile-time horizon (qp_wave_body).
+template <int NSLOT, int NSOFT, int PATH, int UNI, int SQP, int IRK = 0, int DYN = 0, int SENS = 0, int NF = 0>
 __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, const LsArgs *lsp)
 {
     // the loop's own arguments are read from device memory where they are used: as by-value kernel arguments they stayed in
@@ -1231,7 +1240,8 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
     extern __shared__ double sm[];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.B) return;
-    const int N = a.N;
+    if (NF > 0 && a.N != NF) return;        // (api.hip selects by the handle's horizon)
+    const int N = (NF > 0) ? NF : a.N;
     const size_t B = a.B;
     // a car that stops (freeze) keeps its state: the rest of the history repeats it with zero inputs
     auto stop_from = [&](int step) {
@@ -1343,7 +1353,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
             }
             // LEAN (the sweeps and norm phases on a diet): measured per class of instantiation -- it gains 6-8 % in the all-hard RTI loops and costs the
             // SQP loops 13-17 % and the soft / track-row loops 2-9 % (their register allocation tips into scratch); the stand-alone QP kernels take it
-            qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, SQP ? 0 : 1>(a, b, sm, SQP || step + 1 == s.n_steps);
+            qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, SQP ? 0 : 1, NF>(a, b, sm, SQP || step + 1 == s.n_steps);
             __syncthreads();
             if constexpr (SENS != 0) {
                 sens_body(*s.sens, b, sm, step);
@@ -1372,12 +1382,13 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 
 }  // namespace
 
-// This file is compiled FOUR times (Makefile): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
+// This file is compiled FIVE times (Makefile): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
 // soft / track-row instantiations, QP_SET = 2 the persistent loop of the dynamic OCP models (all tables), QP_SET = 3 the persistent loop
-// with x0 sensitivities (SENS = 1) for every RTI loop of the sets 0 and 1 -- same flags, same (default) scheduler.  Separate objects are separate device code images: the benchmarked kernels' image does not move when another set grows.  `make ilp` builds both again under
+// with x0 sensitivities (SENS = 1) for every RTI loop of the sets 0 and 1 -- same flags, same (default) scheduler -- and QP_SET = 4 the
+// benchmarked pair of set 0 with the straight-line factor sweep (NF).  Separate objects are separate device code images: the benchmarked kernels' image does not move when another set grows.  `make ilp` builds both again under
 // LLVM's iterative ILP scheduler into the test artefact libihm2mpc_ilp.so (tests/test_gpu_configs.py compares the two builds).
 #ifndef QP_SET
-#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop) or -DQP_SET=3 (the persistent loop with x0 sensitivities)"
+#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities) or -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep)"
 #endif
 // The instantiations of this object: its part of the catalogue api.hip selects from, which takes the first entry that holds a table,
 // so that an NSLOT comes before the larger ones of the same kind.  WAVE(NSLOT, NSOFT, PATH, UNI) k_qp_wave, BLOCK(NSLOT, UNI, NW)
@@ -1411,8 +1422,21 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
     STEPS(8, 2, 0, 1, 0, 0) STEPS(8, 2, 0, 1, 1, 0) STEPS(10, 4, 0, 1, 0, 0) STEPS(10, 4, 0, 1, 1, 0)                                     \
     STEPS(8, 0, 1, 1, 0, 0) STEPS(8, 0, 1, 1, 1, 0) STEPS(8, 3, 1, 1, 0, 0) STEPS(8, 3, 1, 1, 1, 0)                                       \
     STEPS(10, 4, 1, 1, 0, 0) STEPS(10, 4, 1, 1, 1, 0)
+#elif QP_SET == 4
+// The reference's OCP (all sides hard, batch-shared weights, RTI, RK4, kinematic model) with the factor sweep in its straight-line form
+// (qp_wave_body: NF): per-step QP and persistent loop, for the horizon 40 as a compile-time constant and for any horizon.  An object of
+// its own (Makefile: without the compiler's own loop unrolling), so that the images of the other sets stay what they were.
+#define QP_INSTANCES(WAVE, BLOCK, STEPS) WAVE(5, 0, 0, 1) STEPS(5, 0, 0, 1, 0, 0)
 #endif
 
+#if QP_SET == 4
+#define WAVE(NS, NO, PT, UN)                                                                          \
+    {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, 40}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, 40>},     \
+    {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, -1}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, -1>},
+#define STEPS(NS, NO, PT, UN, IR, DY)                                                                                    \
+    {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 0, 40}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 0, 40>},         \
+    {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 0, -1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 0, -1>},
+#else
 #define WAVE(NS, NO, PT, UN) {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0}, 64, (const void *)k_qp_wave<NS, NO, PT, UN>},
 #define BLOCK(NS, UN, NW) {{QP_BLOCK, NS, 0, 0, UN, 0, 0, 0}, 64 * NW, (const void *)k_qp_block<NS, UN, NW>},
 #if QP_SET == 3
@@ -1421,6 +1445,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 #define STEPS(NS, NO, PT, UN, IR, DY)                                                                  \
     {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>}, \
     {{QP_STEPS, NS, NO, PT, UN, 1, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 1, IR, DY>},
+#endif
 #endif
 #define QP_TABLE_(n) ihm2_qp_set##n
 #define QP_TABLE(n) QP_TABLE_(n)

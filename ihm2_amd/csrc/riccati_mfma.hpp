@@ -154,12 +154,28 @@ __device__ __forceinline__ void dyn_residual(const int N, const int lane, double
 // Out: LDS arrays of RicLds; HBM: Pg (NS,64), Mg (N,64) in the RIC_IDX layout.  store_p (wave-uniform): also keep p_k, k < N.
 // Hs (NS,10,10), CD (N,2,10): batch-shared; UNI: the same for all k < N (only stage 0 is read).  HsT: the terminal stage's 10x10.  D: depth of the record prefetch ring.
 // ALAT: a fifteenth row per stage, gam[k][14] a a' with a = the four non-zeros in L.ha (stages 1..N-1).
-template <int NCK, bool PATH, bool UNI, int D, bool ALAT = false>
-__device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, const double *__restrict__ linb, const double *__restrict__ Hs,
+//
+// PLAIN: the straight-line form of the stage for the tables with active rows and the models that need no symmetrising tile (store_p and
+// symmetrize are then false by construction: the caller selects the instantiation, api.hip).  Same operations in the same order, so the same
+// bits; what goes is the bookkeeping around them, which at one wave per SIMD costs an issue slot like any product:
+//   * the records come through buffer loads -- per-lane element offsets fixed, the stage as a scalar byte offset that steps down by one
+//     record and is clamped at stage 0 -- instead of addresses rebuilt from k;
+//   * P_k and M_k leave through one running 32-bit offset per lane (both arrays are (., 64): the same entry of the same row);
+//   * the LDS results leave through running per-lane addresses, in ALL lanes: a lane that owns no entry of an array keeps a fixed address in
+//     the transpose tile, which is idle in this form, and a step of zero (the vector sweep's dz[0] trick, for stores) -- no exec-mask region
+//     but the one around the two global stores.  kff_k and K_k are the same register (Kf) in different lanes: one store;
+//   * the next stage's C operand is prepared unconditionally: for k = 0 it reads LDS words in front of gam / gt (inside the carve-up) and
+//     the result is dropped.
+// NF > 0: the horizon as a compile-time constant (N must equal it); with NF a multiple of D the stage guard s < N goes as well.
+template <int NCK, bool PATH, bool UNI, int D, bool ALAT = false, bool PLAIN = false, int NF = 0>
+__device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lane, const double *__restrict__ linb, const double *__restrict__ Hs,
                                                    const double *__restrict__ HsT,
                                                    const double *__restrict__ CD, const RicLds L, double *__restrict__ Pg, double *__restrict__ Mg,
                                                    const int lin_rec, const bool store_p, const bool symmetrize)
 {
+    static_assert(!PLAIN || (UNI && !PATH && !ALAT), "the straight-line stage is written for the batch-shared all-hard tables");
+    static_assert(PLAIN || NF == 0, "a compile-time horizon comes with the straight-line stage");
+    const int N = (NF > 0) ? NF : N_rt;
     const int g = lane >> 4, j = lane & 15;
     const int col = (j < 10) ? j : (j == 12) ? 9 : (j == 13) ? 8 : -1;
     const int row[4] = {g, g + 4, (g < 2) ? 8 + g : -1, (g == 0) ? 9 : (g == 1) ? 8 : -1};
@@ -230,11 +246,33 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, 
 
     // ---- record ring: three loads per lane and stage, D stages ahead (indices clamped, loads unconditional) ----
     double r0[D], r1[D], rB[D];
+    // PLAIN: resource descriptor over the instance's records, the stage's record as scalar byte offset, the lane's elements as vector offsets
+    const int rec_bytes = lin_rec * 8;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(linb), 0, PLAIN ? N * rec_bytes : 0, 0x00020000);
+    const unsigned vo0 = off[0] * 8u, vo1 = off[1] * 8u, voB = offB * 8u;
+    typedef unsigned int ric_u2_t __attribute__((ext_vector_type(2)));
+    auto rec_load = [&](const unsigned voff, const int soff) -> double {        // soff: wave-uniform
+        const ric_u2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, soff, 0);
+        return __hiloint2double((int)v.y, (int)v.x);
+    };
 #pragma unroll
     for (int d = 0; d < D; d++) {
-        const double *rec = linb + (size_t)max(N - 1 - d, 0) * lin_rec;
-        r0[d] = rec[off[0]]; r1[d] = rec[off[1]]; rB[d] = rec[offB];
+        if constexpr (PLAIN) {
+            const int so = max(N - 1 - d, 0) * rec_bytes;
+            r0[d] = rec_load(vo0, so); r1[d] = rec_load(vo1, so); rB[d] = rec_load(voB, so);
+        } else {
+            const double *rec = linb + (size_t)max(N - 1 - d, 0) * lin_rec;
+            r0[d] = rec[off[0]]; r1[d] = rec[off[1]]; rB[d] = rec[offB];
+        }
     }
+    // PLAIN: the running state of the stage's loads and stores (stage k = N - 1 first)
+    int rs = (N - 1 - D) * rec_bytes;                                  // record k - D, clamped where it is used
+    unsigned gofs = (unsigned)((N - 1) * 64 + RIC_IDX(g, j)) * 8u;     // entry of P_k and M_k (lanes j < 8)
+    const bool own10 = j == 10, ownK = j < 8 && g < 2;
+    const int dead = L.tile + lane;                                    // (+ 4 at most: inside the 136 words of the tile)
+    int a_hv = own10 ? L.hv + (N - 1) * 8 + g : dead, a_dz = own10 ? L.dz + N * 10 + g : dead, a_gi = own10 ? L.Ginv + (N - 1) * 8 + 2 * g : dead;
+    int a_kf = own10 ? L.kff + (N - 1) * 4 + g : ownK ? L.Kl + (N - 1) * 16 + g * 8 + j : dead;
+    const int st8 = own10 ? 8 : 0, st10 = own10 ? 10 : 0, stk = own10 ? 4 : ownK ? 16 : 0;
     // C operand of a stage's G product, prepared one stage ahead in two halves: the LDS reads are issued right after the stage's last
     // matrix instruction (before the stage's own LDS stores, whose addresses the compiler cannot tell apart), the arithmetic follows
     // once the transposed P has come back -- the reads' latency and the tile's round trip are covered by the stage's stores
@@ -274,7 +312,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, 
         for (int d = 0; d < D; d++) {
             const int s = s0 + d;
             const int k = N - 1 - s;
-            if (s < N) {
+            if ((NF > 0 && NF % D == 0) || s < N) {
                 RIC_STAMP(0);
                 const double B0 = r0[d], B1 = r1[d], Bmk = rB[d];
                 const d4_t Hk = Hc;
@@ -308,6 +346,30 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, 
                 // unstable dynamic model the antisymmetric rounding noise decided whether ill-conditioned QPs converged; the
                 // reference implementation evaluates symmetric pairs identically).  The tile's round trip is covered by the work
                 // that does not depend on it: the ring refill, the next stage's LDS operands, this stage's stores. ----
+                if constexpr (PLAIN) {
+                    {
+                        const int so = max(rs, 0);
+                        r0[d] = rec_load(vo0, so); r1[d] = rec_load(vo1, so); rB[d] = rec_load(voB, so);
+                        rs -= rec_bytes;
+                    }
+                    prepare_load(k - 1);
+                    RIC_STAMP(5);
+                    sm[a_hv] = W[0] - q0; sm[a_hv + 4] = W[1] - q1;        // P_{k+1} rb_k
+                    sm[a_dz] = S[2]; sm[a_dz + 4] = S[3];
+                    sm[a_gi] = cAa * idet; sm[a_gi + 1] = cBa * idet;
+                    sm[a_kf] = Kf;                                          // kff_k (affine column) and K_k (state columns of the input rows)
+                    a_hv -= st8; a_gi -= st8; a_dz -= st10; a_kf -= stk;
+                    Pd[0] = S[0]; Pd[1] = S[1];
+                    prepare_compute(k - 1);
+                    if (j < 8) {
+                        double2 mm, pp;
+                        mm.x = S[2]; mm.y = S[3];
+                        pp.x = S[0]; pp.y = S[1];
+                        *(double2 *)((char *)Mg + gofs) = mm;
+                        *(double2 *)((char *)Pg + gofs) = pp;
+                    }
+                    gofs -= 512u;
+                } else {
                 if (symmetrize) { sm[a_tw] = S[0]; sm[a_tw + 4 * 17] = S[1]; }
                 {
                     const double *rec = linb + (size_t)max(k - D, 0) * lin_rec;
@@ -346,6 +408,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N, const int lane, 
                     *(double2 *)(Pg + (size_t)k * 64 + RIC_IDX(g, j)) = pp;
                 }
 #endif
+                }
                 RIC_STAMP(6);
             }
         }

@@ -422,7 +422,9 @@ class BatchedOcpSolver:
         DYN, and an eighth 1 for the loop with x0 sensitivities) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` /
         ``"not_resident"``; ``linearize`` / ``sim``: the kernel of the last linearisation / plant launch outside ``k_steps``
         (``"k_linearize"``, ``"k_linearize_dyn"``, ``"k_linearize_cols"``, ``"k_linearize_irk"``; ``"k_sim_step_kin"``, ``"k_sim_step"``,
-        ``"k_sim_irk"``).  ``None`` where nothing was launched yet."""
+        ``"k_sim_irk"``); ``qp_form`` / ``steps_form``: the form of the factor sweep in those two launches, ``"general"``,
+        ``"plain"`` (straight-line stage, run-time horizon) or ``"plain_n40"`` (the horizon 40 compiled in) -- same results, so the
+        kernel names above do not tell them apart.  ``None`` where nothing was launched yet."""
         rec = np.zeros(16, dtype=np.int32)
         _lib.check(self.lib.ihm2mpc_get_launch_record(self._h, rec.ctypes.data_as(_lib.c_int32_p)))
         r = [int(v) for v in rec]
@@ -438,7 +440,9 @@ class BatchedOcpSolver:
             steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
         lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk")[r[15] & 15]
         sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk")[(r[15] >> 4) & 15]
-        return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim}
+        forms = ("general", "plain", "plain_n40", None)
+        return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim,
+                "qp_form": forms[(r[15] >> 8) & 3] if qp else None, "steps_form": forms[(r[15] >> 12) & 3] if r[5] == 1 else None}
 
     # ---- device-pointer variants (zero copy; dptr = integer device address, instance-major layout) ----
     def set_x0_device(self, dptr: int):

@@ -266,7 +266,12 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *       [14] SENS: 1 the k_steps launch computed x0 sensitivities (ihm2mpc_run_steps_sens), 0 otherwise (0 when [5] != 1)
  *   [15] bits 0..3 the last linearisation launch (ihm2mpc_linearize, a solve, ihm2mpc_step): 0 none yet, 1 k_linearize, 2 k_linearize_dyn,
  *       3 k_linearize_cols, 4 k_linearize_irk;  bits 4..7 the last plant launch (ihm2mpc_sim_step, ihm2mpc_sim_advance, ihm2mpc_step):
- *       0 none yet, 1 k_sim_step_kin, 2 k_sim_step, 3 k_sim_irk.  Launches inside k_steps are not recorded here. */
+ *       0 none yet, 1 k_sim_step_kin, 2 k_sim_step, 3 k_sim_irk.  Launches inside k_steps are not recorded here.
+ *       bits 8..9 the form of the factor sweep in the QP of [0], bits 12..13 in the k_steps launch of [5] (0 when [5] != 1): 0 the general
+ *       form, 1 the straight-line stage with the run-time horizon, 2 the straight-line stage with the horizon compiled in (N = 40).  The
+ *       forms give the same bits; a table without active rows and the model IHM2MPC_MODEL_FDYN6 take the general form, and so does every
+ *       configuration without an instantiation in the other two.  IHM2MPC_QP_FORM in the environment (read once) limits the choice:
+ *       1 keeps N = 40 on form 1, 0 keeps every launch on form 0. */
 int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
 
 /* ---- sensitivities of the solution with respect to the initial state (acados: eval_param_sens(index, 0, "ex"), then
