@@ -253,12 +253,14 @@ std::vector<std::pair<int, int>> slot_limits(const ihm2mpc_handle *h)
     return v;
 }
 
-size_t qp_lds_bytes(const ihm2mpc_handle *h)
+// the LDS layout of the QP that takes the handle's rows and weights (qp_lds.hpp): what the kernels carve up is what the launch asks for
+ihm2::QpLds qp_layout(const ihm2mpc_handle *h) { return ihm2::qp_lds(h->N, ihm2::qp_lds_class(path_class(h), h->uniform_H && h->uniform_CD)); }
+size_t qp_lds_bytes(const ihm2mpc_handle *h) { return sizeof(double) * (size_t)qp_layout(h).total; }
+// the persistent loop's: the QP's with its guests (sens: k_sens' body after every QP)
+ihm2::StepsLds steps_lds(const ihm2mpc_handle *h, int sens)
 {
-    const size_t N = h->N, NS = h->NS;
-    const int nck = h->path_on ? (h->alat_on ? 15 : 14) : 12;
-    const int uni = h->uniform_H && h->uniform_CD;
-    return sizeof(double) * (NS * (10 + 10 + 8 + 8 + 2 * nck + 10 + (h->path_on ? (h->alat_on ? 6 : 2) : 0)) + N * (8 + 4 + 16 + 8 + 8) + 136 + (uni ? 20 + (h->path_on ? 0 : 200 + 90) : 0));
+    const bool dyn_rk4 = h->cfg.model != IHM2MPC_MODEL_FKIN6 && h->cfg.integrator_type == IHM2MPC_INTEG_ERK;
+    return ihm2::steps_lds_doubles(qp_layout(h).total, sens ? (int)(ihm2_sens_lds_bytes(h) / sizeof(double)) : 0, dyn_rk4);
 }
 
 // The per-step QP for the handle's table; nullptr: none takes it (or not in the LDS)
@@ -277,15 +279,19 @@ const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
 // results).  The catalogue has it for the kinematic and the dynamic OCP models, not for the lateral-acceleration row; with soft sides,
 // track rows, the collocation integrator or a dynamic model for batch-shared tables only (UNI = 1).  sens = 1 (ihm2mpc_run_steps_sens):
 // the loop with x0 sensitivities, for the kinematic OCP model in the RTI mode.
-const QpInst *select_steps(const ihm2mpc_handle *h, size_t lds, int sens = 0)
+const QpInst *select_steps(const ihm2mpc_handle *h, int sens = 0)
 {
+    const ihm2::StepsLds lds = steps_lds(h, sens);
     const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP, irk = h->cfg.integrator_type != IHM2MPC_INTEG_ERK;
     const bool dyn = h->cfg.model != IHM2MPC_MODEL_FKIN6;
     if (irk && (!h->irk_tab || (sqp && h->sqp_globalization && !h->ls_phi))) return nullptr;
     if (sqp && !h->ls_x) return nullptr;        // the caller allocates the line-search buffers first
-    if (lds > 160 * 1024) return nullptr;
+    if (lds.total() * sizeof(double) > 160 * 1024) return nullptr;
     // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
-    if (dyn && !irk && lds < (size_t)ihm2::s_count(1) * 64 * sizeof(double)) return nullptr;
+    if (!lds.guests_fit()) return nullptr;
+    // the SQP instantiations keep the sweeps' earlier form, whose unclamped prefetch of LDS operands starts in front of the block's LDS at
+    // N = 2 and N = 3 (by 60 and 24 words; the values are never used): those horizons are launched per step
+    if (sqp && !ihm2::qp_sweeps_inside(qp_layout(h), h->N, false, 0, 0)) return nullptr;
     return find_form(h, {QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
 }
 
@@ -351,8 +357,8 @@ int launch_qp(ihm2mpc_handle *h)
 // (k_steps<..., SENS = 1>), their history into h->hist_k; its LDS is the larger of the QP's and k_sens' (the body reuses the QP's).
 int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop, int sens = 0)
 {
-    const size_t lds = sens ? std::max(qp_lds_bytes(h), ihm2_sens_lds_bytes(h)) : qp_lds_bytes(h);
-    const QpInst *e = select_steps(h, lds, sens);
+    const size_t lds = sizeof(double) * (size_t)steps_lds(h, sens).total();
+    const QpInst *e = select_steps(h, sens);
     if (!e) return 1;
     const bool irk_plant = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
     if (irk_plant && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;

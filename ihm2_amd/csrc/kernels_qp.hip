@@ -41,6 +41,8 @@
 #include "irk_body.hpp"
 #include "riccati_mfma.hpp"
 #include "sens_body.hpp"
+#include "qp_lds.hpp"
+#include "wave_sync.hpp"
 
 using namespace ihm2;
 
@@ -57,16 +59,6 @@ namespace {
 #define SWEEP_RING 4
 #endif
 #define SWEEP_DL ((SWEEP_RING >= 8) ? 4 : 2)       // stages the LDS operands are fetched ahead
-
-// The block is ONE wavefront: its lanes run in lockstep and the LDS serves one wave's instructions in
-// order, so a hand-off through LDS needs no s_barrier -- only a compiler fence.  (A __syncthreads()
-// would also drain vmcnt(0), i.e. stall every phase on the record prefetches and P_k stores in flight.)
-#define WSYNC()                                                  \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
 
 __device__ __forceinline__ bool fin(double v) { return fabs(v) < INF_BOUND; }
 
@@ -129,12 +121,16 @@ __device__ __forceinline__ double sum_stride8(double v)
 // pre(k, odd, x0, x1) fetches the LDS operands of a step DL steps ahead of its use (the body's own LDS stores would otherwise
 // pin every LDS load behind them -- the compiler cannot see that the addresses differ -- and put an LDS latency on the
 // recursion chain);  body(k, value, odd, x0, x1).
-template <int DIR, int D, int DL, typename P, typename F>
+// BUF: how a row is loaded.  true: buffer loads on a scalar row offset; false: global loads with per-lane 64-bit addresses, the sweeps' row
+// streaming as it was before the diet -- kept (stream_rows_v1) for the SQP instantiations of the persistent loop, whose register allocation the
+// leaner form tips into scratch (live options: 449 k control steps/s with this form, 380 k with the other).
+template <int DIR, int D, int DL, bool BUF = true, typename P, typename F>
 __device__ __forceinline__ void stream_rows(const double *rows, int N, int e_even, int e_odd, P &&pre, F &&body)
 {
     static_assert(D % 2 == 0 && DL % 2 == 0 && D % DL == 0 && 3 * D <= QM_PAD, "the element index alternates with the step parity");
     // The prefetches run UNCLAMPED past the instance, by at most ceil(N / 2D) 2D + D - N < 3 D rows (D + DL stages of LDS
-    // operands): the streamed array is padded by QM_PAD >= 3 D rows at both ends and the LDS operands sit inside the kernel's LDS carve-up with other arrays on both sides,
+    // operands): the streamed array is padded by QM_PAD >= 3 D rows at both ends and the LDS operands sit inside the kernel's LDS with other
+    // arrays on both sides (qp_lds.hpp: qp_sweeps_inside -- asserted in qp_wave_body, and where it fails the launch is refused, api.hip),
     // so every address is valid and the values fetched for stages outside [0, N) are never used.  (Clamping the indices
     // cost a third of the sweep's instructions in scalar min / shift / add chains.)
     // Two register sets used in turn (a stage of the first half of the loop body takes its row from set 0 and refills set 1, the second
@@ -147,14 +143,18 @@ __device__ __forceinline__ void stream_rows(const double *rows, int N, int e_eve
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(rows) - (size_t)QM_PAD * 64, 0, (N + 2 * QM_PAD) * 512, 0x00020000);
     const unsigned ve = (unsigned)e_even * 8u, vo = (unsigned)e_odd * 8u;
     typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-    auto load_row = [&](const int step, const unsigned voff) -> double {       // step: wave-uniform
-        const int row = (DIR < 0) ? N - 1 - step : step;
-        const u2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, (QM_PAD + row) * 512, 0);
-        return __hiloint2double((int)v.y, (int)v.x);
+    const double *p_even = rows + (size_t)((DIR < 0) ? N - 1 : 0) * 64 + e_even, *p_odd = rows + (size_t)((DIR < 0) ? N - 1 : 0) * 64 + e_odd;
+    auto load_row = [&](const int step, const bool odd) -> double {       // step: wave-uniform
+        if constexpr (BUF) {
+            const int row = (DIR < 0) ? N - 1 - step : step;
+            const u2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, odd ? vo : ve, (QM_PAD + row) * 512, 0);
+            return __hiloint2double((int)v.y, (int)v.x);
+        } else
+            return (odd ? p_odd : p_even)[(ptrdiff_t)DIR * step * 64];
     };
 #pragma unroll
     for (int d = 0; d < D; d++) {
-        r[0][d] = load_row(d, (d & 1) ? vo : ve);
+        r[0][d] = load_row(d, (d & 1) != 0);
         // the initial loads are issued in ring order (fence): the wait counts of the loop are the minimum over both ways into it, and a
         // reordered prologue (oldest slot loaded last) made the steady state wait for all but one load at the top of every pass
         __builtin_amdgcn_sched_barrier(0);
@@ -168,52 +168,17 @@ __device__ __forceinline__ void stream_rows(const double *rows, int N, int e_eve
                 const int s = s0 + h * D + d;
                 const int k = (DIR < 0) ? N - 1 - s : s;
                 const double v = r[h][d], y0 = x0[d % DL], y1 = x1[d % DL];
-                r[h ^ 1][d] = load_row(s + D, (d & 1) ? vo : ve);
+                r[h ^ 1][d] = load_row(s + D, (d & 1) != 0);
                 pre((DIR < 0) ? k - DL : k + DL, (d & 1) != 0, x0[d % DL], x1[d % DL]);
                 if (s < N) body(k, v, (d & 1) != 0, y0, y1);
             }
         }
     }
 }
-
-// The sweeps' row streaming as it was before the diet below (global loads with per-lane 64-bit addresses): kept for the SQP instantiations of the
-// persistent loop, whose register allocation the leaner form tips into scratch (live options: 449 k control steps/s with this form, 380 k with the other).
 template <int DIR, int D, int DL, typename P, typename F>
 __device__ __forceinline__ void stream_rows_v1(const double *rows, int N, int e_even, int e_odd, P &&pre, F &&body)
 {
-    static_assert(D % 2 == 0 && DL % 2 == 0 && D % DL == 0 && 3 * D <= QM_PAD, "the element index alternates with the step parity");
-    // The prefetches run UNCLAMPED past the instance, by at most ceil(N / 2D) 2D + D - N < 3 D rows (D + DL stages of LDS
-    // operands): the streamed array is padded by QM_PAD >= 3 D rows at both ends and the LDS operands sit inside the kernel's LDS carve-up with other arrays on both sides,
-    // so every address is valid and the values fetched for stages outside [0, N) are never used.  (Clamping the indices
-    // cost a third of the sweep's instructions in scalar min / shift / add chains.)
-    // Two register sets used in turn (a stage of the first half of the loop body takes its row from set 0 and refills set 1, the second
-    // half the other way round): every load writes a register whose last value is dead, so nothing has to be copied at the loop's back
-    // edge.  (With ONE set the value in use and its refill were live together, the compiler rotated them with moves at the back edge, and
-    // each move waited for its load: an s_waitcnt vmcnt(0) -- the whole ring drained -- every D stages.)
-    double r[2][D], x0[DL], x1[DL];
-    const double *p_even = rows + (size_t)((DIR < 0) ? N - 1 : 0) * 64 + e_even, *p_odd = rows + (size_t)((DIR < 0) ? N - 1 : 0) * 64 + e_odd;
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-        r[0][d] = ((d & 1) ? p_odd : p_even)[(ptrdiff_t)DIR * d * 64];
-        // the initial loads are issued in ring order (fence): the wait counts of the loop are the minimum over both ways into it, and a
-        // reordered prologue (oldest slot loaded last) made the steady state wait for all but one load at the top of every pass
-        __builtin_amdgcn_sched_barrier(0);
-        if (d < DL) pre((DIR < 0) ? N - 1 - d : d, (d & 1) != 0, x0[d], x1[d]);
-    }
-    for (int s0 = 0; s0 < N; s0 += 2 * D) {
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-#pragma unroll
-            for (int d = 0; d < D; d++) {
-                const int s = s0 + h * D + d;
-                const int k = (DIR < 0) ? N - 1 - s : s;
-                const double v = r[h][d], y0 = x0[d % DL], y1 = x1[d % DL];
-                r[h ^ 1][d] = ((d & 1) ? p_odd : p_even)[(ptrdiff_t)DIR * (s + D) * 64];
-                pre((DIR < 0) ? k - DL : k + DL, (d & 1) != 0, x0[d % DL], x1[d % DL]);
-                if (s < N) body(k, v, (d & 1) != 0, y0, y1);
-            }
-        }
-    }
+    stream_rows<DIR, D, DL, false>(rows, N, e_even, e_odd, pre, body);
 }
 
 // The QP of instance b, solved by the calling wavefront (all 64 lanes, lane = threadIdx.x); sm: the block's dynamic LDS.
@@ -237,7 +202,8 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     const int N = (NF > 0) ? NF : a.N, NS = N + 1;
     // constraint rows per stage held in LDS: 8 x boxes, 2 u boxes, 2 general rows (+ 2 track rows (+ the lateral-acceleration row, PATH == 2)); the
     // multiplier arrays in HBM always have the full NLAM = 28 columns (14 lower sides, then 14 upper sides); row 14 keeps its two in lam_a / slk_a
-    constexpr int NCK = (PATH == 2) ? 15 : PATH ? 14 : 12;
+    constexpr QpLdsClass CLS = qp_lds_class(PATH, UNI != 0);
+    constexpr int NCK = CLS.nck;
     // the instance's weight tables and slot bounds: wave-uniform bases (batch-shared tables: stride 0, terminal at stage N).  Per-instance weights
     // are stage-independent (UNI), and UNI reads stage 0 for every k < N -- which a batch-shared UNI table holds bit for bit as well
     const double *Hs0 = a.Hs + (size_t)b * a.hs_bs, *HsT = Hs0 + a.hs_te;
@@ -247,32 +213,25 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     // UNI: the stage Hessians H_0..H_{N-1} and the general rows [C D]_k do not depend on k (the reference's OCP: one W, one C, D
     // for all stages, python/mpc.py:49-99).  They are then kept in LDS (H only where the budget of 40 KB per instance allows)
     // instead of being fetched through L2 with lane-dependent addresses in every phase.
-    constexpr bool HL = UNI && !PATH, CL = UNI;
-    // ---- LDS carve-up (doubles) ----
-    double *z = sm;                  // NS*10  QP iterate
-    double *gt = z + NS * 10;        // NS*10  stationarity residual / modified gradient
-    double *pi = gt + NS * 10;       // NS*8   QP costates
-    double *pv = pi + NS * 8;        // NS*8   Riccati vector p_k, then dpi_k
-    double *rb = pv + NS * 8;        // N*8    dynamics residual
-    double *gam = rb + N * 8;        // NS*NCK barrier weights per constraint slot
-    double *cf = gam + NS * NCK;     // NS*NCK lam_l - lam_u, then gradient coefficients
-    double *dz = cf + NS * NCK;      // NS*10  step
-    double *kff = dz + NS * 10;      // N*4    feed-forward terms (2 used per stage)
-    double *Kl = kff + N * 4;        // N*16   K_k = Guu^-1 Gux
-    double *Ginv = Kl + N * 16;      // N*8    Guu^-1 as (Gi0, Gi1, Gi2, Gi1, 0, 0, 0, 0)
-    double *Prb = Ginv + N * 8;      // N*8    P_{k+1} rb_k (same for predictor and corrector)
-    double *tile = Prb + N * 8;      // 8*17   transpose tile of the factor sweep
-    double *hc = tile + 136;         // NS*2   d h_R / d psi, d h_L / d psi of the track rows (PATH only)
-    double *ha = hc + (PATH ? NS * 2 : 0);   // NS*4   d a_lat / d (v_x, v_y, T, delta) of the lateral-acceleration row (PATH == 2; zeros where the row is absent)
-    double *Hl = ha + (ALAT ? NS * 4 : 0);   // 200  stage and terminal Hessian (HL only)
-    double *CDl = Hl + (HL ? 200 : 0);       // 20   general rows (CL only)
-    double *spv = CDl + (CL ? 20 : 0);       // 60   the (up to three) non-zeros of every row of the two Hessians (HL only) ...
-    int *spc = reinterpret_cast<int *>(spv + 60);      // 60 ints: ... and their columns
+    constexpr bool HL = CLS.hl, CL = CLS.cl;
+    // ---- LDS carve-up: the layout of qp_lds.hpp, with its neighbour assumptions checked for the compiled-in horizon and the shortest one ----
+    static_assert(qp_factor_inside(qp_lds(40, CLS), 40, NCK) && qp_factor_inside(qp_lds(2, CLS), 2, NCK), "factor stage / block reductions leave their LDS");
+    static_assert(qp_sweeps_inside(qp_lds(40, CLS), 40, LEAN != 0, SWEEP_RING, SWEEP_DL) && (LEAN == 0 || qp_sweeps_inside(qp_lds(2, CLS), 2, true, SWEEP_RING, SWEEP_DL)),
+                  "the sweeps' unclamped LDS prefetch leaves the block (the earlier form does below N = 4: api.hip refuses those launches)");
+    static_assert(NW <= 4, "qp_factor_inside checks the block reductions for four waves");
+    // (the pointers as a chain, each array from its predecessor's end in the layout's order, by lengths evaluated here -- and not as sm + offset:
+    // the same addresses, but the shape and the order of this arithmetic decide the register allocation of the whole kernel, qp_lds.hpp)
+#define LEN(id) qp_lds_len(id, N, NS, CLS)
+    double *z = sm, *gt = z + LEN(QP_Z), *pi = gt + LEN(QP_GT), *pv = pi + LEN(QP_PI), *rb = pv + LEN(QP_PV), *gam = rb + LEN(QP_RB), *cf = gam + LEN(QP_GAM), *dz = cf + LEN(QP_CF);
+    double *kff = dz + LEN(QP_DZ), *Kl = kff + LEN(QP_KFF), *Ginv = Kl + LEN(QP_KL), *Prb = Ginv + LEN(QP_GINV), *tile = Prb + LEN(QP_PRB), *hc = tile + LEN(QP_TILE), *ha = hc + LEN(QP_HC);
+    double *Hl = ha + LEN(QP_HA), *CDl = Hl + LEN(QP_HL), *spv = CDl + LEN(QP_CDL);
+    int *spc = reinterpret_cast<int *>(spv + 60);       // (QP_SPV where it exists)
+#undef LEN
 #define HS(k, i, l) (HL ? Hl[(((k) == N) ? 100 : 0) + (i) * 10 + (l)] : ((k) == N ? HsT : Hs0 + (UNI ? 0 : (k)) * 100)[(i) * 10 + (l)])
 #define CDV(k, r, j) (CL ? CDl[(r) * 10 + (j)] : a.CD[((k) * 2 + (r)) * 10 + (j)])
 
     // reductions over the instance's threads: wave butterfly, then (NW > 1) one LDS word per wave -- the transpose tile of the factor
-    // sweep is free outside the sweep
+    // sweep is free outside the sweep (qp_lds.hpp: qp_reach_block_reduce)
     auto blk_reduce = [&](double v, auto op) -> double {
         v = wave_reduce(v, op);
         if (NW > 1) {
@@ -727,11 +686,12 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         // and P_{k+1} rb_k -> LDS (riccati_mfma.hpp).  The records' rb slots were written by this wave: wait for them. ----
         __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
         if (wv == 0) {
-            // offsets of the carve-up above as plain integers (a difference of two generic pointers into LDS makes the compiler
-            // build both flat addresses -- and mis-fold their null checks in the register-starved instantiations)
+            // the layout's offsets as plain integers formed from N (qp_lds.hpp: qp_lds_ric; a difference of two generic pointers into LDS makes
+            // the compiler build both flat addresses -- and mis-fold their null checks in the register-starved instantiations)
             RicLds L;
-            L.gt = NS * 10; L.pv = NS * 28; L.gam = NS * 36 + N * 8; L.dz = L.gam + 2 * NS * NCK; L.kff = L.dz + NS * 10; L.Kl = L.kff + N * 4;
-            L.Ginv = L.Kl + N * 16; L.hv = L.Ginv + N * 8; L.tile = L.hv + N * 8; L.hc = L.tile + 136; L.ha = L.hc + NS * 2;
+            const QpRic o = qp_lds_ric(N, NS, NCK);
+            L.gt = o.gt; L.pv = o.pv; L.gam = o.gam; L.dz = o.dz; L.kff = o.kff; L.Kl = o.Kl;
+            L.Ginv = o.Ginv; L.hv = o.Prb; L.tile = o.tile; L.hc = o.hc; L.ha = o.ha;
             if constexpr (NF != 0)
                 riccati_sweep_mfma<NCK, PATH != 0, UNI != 0, RIC_RING, ALAT, true, (NF > 0) ? NF : 0>(N, lane, linb, Hs0, HsT, a.CD, L, Pg, Mg, LIN_REC, false, false);
             else
@@ -792,7 +752,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             if (wv == 0) {
                 const int g = lane >> 3, w = lane & 7;
                 double pw = pv[N * 8 + w], pg = 0.0;
-                stream_rows_v1<-1, 8, 4>(Mg, N, RIC_IDX(w, g), RIC_IDX(g, w),
+                stream_rows_v1<-1, QP_V1_RING, QP_V1_DL>(Mg, N, RIC_IDX(w, g), RIC_IDX(g, w),
                     [&](int k, bool odd, double &prb, double &base) { prb = Prb[k * 8 + (odd ? g : w)]; base = pv[k * 8 + (odd ? w : g)]; },
                     [&](int k, double m, bool odd, double prb, double base) {
                         // only the product with the carried value sits on the dependent chain: m * prb and the stage's base term (added
@@ -867,7 +827,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             if (wv == 0) {
                 const int g = lane >> 3, w = lane & 7;
                 double dxw = dz[w], dxg = 0.0;
-                stream_rows_v1<+1, 8, 4>(Mg, N, RIC_IDX(g, w), RIC_IDX(w, g),
+                stream_rows_v1<+1, QP_V1_RING, QP_V1_DL>(Mg, N, RIC_IDX(g, w), RIC_IDX(w, g),
                     [&](int k, bool odd, double &c, double &unused) { c = dz[(k + 1) * 10 + (odd ? w : g)]; unused = 0.0; },
                     [&](int k, double m, bool odd, double c, double) {
                         // the affine term rides in ONE lane's product (an fma off the dependent chain's critical add)
@@ -1235,6 +1195,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 {
     // the loop's own arguments are read from device memory where they are used: as by-value kernel arguments they stayed in
     // registers across the QP body (50 spill reloads inside its loops that k_qp_wave does not have)
+    static_assert(DYN == 0 || s_count(1) == QP_DYN_RK4_WORDS, "the dynamic models' RK4 integrator parks s_count(1) words per lane in the QP's LDS (qp_lds.hpp: steps_lds_doubles)");
     const StepArgs &s = *sp;
     const LsArgs &ls = *lsp;       // in device memory: a by-value kernel argument whose address is taken would be copied to scratch
     extern __shared__ double sm[];

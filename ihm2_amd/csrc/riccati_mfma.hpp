@@ -37,18 +37,13 @@ __device__ long long ric_dbg[8];
 
 #include <hip/hip_runtime.h>
 
+#include "qp_lds.hpp"
+#include "wave_sync.hpp"
+
 namespace ihm2 {
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 #define IHM2_MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-
-// one wavefront per block: an LDS hand-off needs no s_barrier, only a compiler fence (the LDS serves a wave's instructions in order)
-#define RIC_WSYNC()                                              \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
 
 // Lane exchanges at VALU speed (no LDS crossbar): DPP moves inside a 16-lane row.
 template <int CTRL>
@@ -71,7 +66,8 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)
 #define RIC_IDX(row, col) (((((row) & 3) * 8 + (col)) << 1) + ((row) >> 2))
 #define RIC_REC_RB 88       // slot of rb_k in a linearisation record
 
-// LDS arrays of the instance: offsets in doubles from the start of the block's dynamic LDS (the sweep addresses them through its
+// LDS arrays of the instance: offsets in doubles from the start of the block's dynamic LDS, taken from the layout (qp_lds.hpp) as plain
+// integers formed from N (the sweep addresses them through its
 // own extern __shared__ declaration, i.e. as LDS for certain -- a generic pointer handed in through a struct made the compiler
 // emit flat address arithmetic in the register-starved instantiations)
 struct RicLds {
@@ -85,7 +81,7 @@ struct RicLds {
     int Ginv;     // (N,8)    out: Guu^-1 as (Gi0, Gi1, Gi2, Gi1, 0 ..)
     int kff;      // (N,4)    out: kff_k (2 used)
     int dz;       // (NS,10)  out: dz[(k+1)*10 + i] = c_k[i], i < 8
-    int tile;     // (8,17)   scratch: the transpose of P_k (rows padded to 17 against bank conflicts)
+    int tile;     // (8,17)   scratch: the transpose of P_k (QP_TILE_WORDS, rows padded to QP_TILE_ROW against bank conflicts)
 };
 
 // rb_k = A_k z_k + B_k u_k + b_k - z_{k+1} (-> LDS and the record's slot) and gt_k += [A B]_k' pi_{k+1}, all stages in parallel:
@@ -164,7 +160,7 @@ __device__ __forceinline__ void dyn_residual(const int N, const int lane, double
 //   * the LDS results leave through running per-lane addresses, in ALL lanes: a lane that owns no entry of an array keeps a fixed address in
 //     the transpose tile, which is idle in this form, and a step of zero (the vector sweep's dz[0] trick, for stores) -- no exec-mask region
 //     but the one around the two global stores.  kff_k and K_k are the same register (Kf) in different lanes: one store;
-//   * the next stage's C operand is prepared unconditionally: for k = 0 it reads LDS words in front of gam / gt (inside the carve-up) and
+//   * the next stage's C operand is prepared unconditionally: for k = 0 it reads LDS words in front of gam / gt (qp_lds.hpp: qp_reach_plain_operand) and
 //     the result is dropped.
 // NF > 0: the horizon as a compile-time constant (N must equal it); with NF a multiple of D the stage guard s < N goes as well.
 template <int NCK, bool PATH, bool UNI, int D, bool ALAT = false, bool PLAIN = false, int NF = 0>
@@ -221,7 +217,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lan
     const double selA0 = (g == 0) ? 1.0 : 0.0, selA2 = (g == 1) ? 1.0 : 0.0, selB = (g < 2) ? -1.0 : 0.0;
 
     // transpose tile: lane (g, j) writes rows g, g + 4 at column j and reads (row j & 7, columns g, g + 4); the affine column keeps its value
-    const int a_tw = L.tile + g * 17 + j, a_tr = L.tile + (j & 7) * 17 + g;
+    const int a_tw = L.tile + g * QP_TILE_ROW + j, a_tr = L.tile + (j & 7) * QP_TILE_ROW + g;
     const double wS = (j < 8) ? 0.5 : 1.0, wT = (j < 8) ? 0.5 : 0.0;
 
     // ---- terminal stage: P_N = H~_N (state block), p_N = gradient ----
@@ -269,7 +265,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lan
     int rs = (N - 1 - D) * rec_bytes;                                  // record k - D, clamped where it is used
     unsigned gofs = (unsigned)((N - 1) * 64 + RIC_IDX(g, j)) * 8u;     // entry of P_k and M_k (lanes j < 8)
     const bool own10 = j == 10, ownK = j < 8 && g < 2;
-    const int dead = L.tile + lane;                                    // (+ 4 at most: inside the 136 words of the tile)
+    const int dead = L.tile + lane;                                    // (+ 4 at most: inside the tile, qp_lds.hpp: qp_reach_plain_parking)
     int a_hv = own10 ? L.hv + (N - 1) * 8 + g : dead, a_dz = own10 ? L.dz + N * 10 + g : dead, a_gi = own10 ? L.Ginv + (N - 1) * 8 + 2 * g : dead;
     int a_kf = own10 ? L.kff + (N - 1) * 4 + g : ownK ? L.Kl + (N - 1) * 16 + g * 8 + j : dead;
     const int st8 = own10 ? 8 : 0, st10 = own10 ? 10 : 0, stk = own10 ? 4 : ownK ? 16 : 0;
@@ -370,7 +366,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lan
                     }
                     gofs -= 512u;
                 } else {
-                if (symmetrize) { sm[a_tw] = S[0]; sm[a_tw + 4 * 17] = S[1]; }
+                if (symmetrize) { sm[a_tw] = S[0]; sm[a_tw + 4 * QP_TILE_ROW] = S[1]; }
                 {
                     const double *rec = linb + (size_t)max(k - D, 0) * lin_rec;
                     r0[d] = rec[off[0]]; r1[d] = rec[off[1]]; rB[d] = rec[offB];
@@ -394,7 +390,7 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lan
                     sm[L.kff + k * 4 + g] = Kf;
                 }
 #endif
-                RIC_WSYNC();
+                WSYNC();
                 if (symmetrize) {
                     const double T0 = sm[a_tr], T1 = sm[a_tr + 4];
                     Pd[0] = fma(wT, T0, wS * S[0]);

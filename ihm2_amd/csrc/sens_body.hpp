@@ -7,6 +7,7 @@
 
 #include "ihm2mpc_internal.h"
 #include "model.hpp"
+#include "wave_sync.hpp"
 
 namespace {
 
@@ -15,13 +16,7 @@ namespace {
 // LDS of the factorisation (doubles): the arrays w .. Q that sens_body and k_adj carve out in front of their own; sens_factor_body.hpp fills them
 __host__ __device__ constexpr size_t sens_factor_lds_doubles(size_t N) { return (N + 1) * (SENS_NR + 6) + N * 16 + 64 + 64 + 16 + 100 + 64 + 16 + 84; }
 
-// one wavefront: a hand-off through LDS needs a compiler fence, no s_barrier (kernels_qp.hip: WSYNC)
-#define SSYNC()                                                  \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
+#define SSYNC() WSYNC()      // (the name the 16 hand-offs of sens_body, sens_factor_body.hpp and kernels_adj.hip were written with)
 
 __device__ __forceinline__ bool sfin(double v) { return fabs(v) < SENS_INF; }
 

@@ -91,6 +91,25 @@ def test_lean_trig_functions_of_the_models_match_libm(tmp_path):
         assert c in hdr and c in open(src).read()
 
 
+def test_qp_lds_layout_holds_its_arrays_and_its_neighbour_assumptions(tmp_path):
+    """The LDS layout of the interior-point QP (csrc/qp_lds.hpp) as host C++ (tools/probes/check_qp_lds.cpp, N = 2..64, every class of the
+    catalogue): arrays disjoint and in order, total and factor-sweep offsets equal to the closed forms held before, every consumer's
+    reach inside the block -- except the sweeps' earlier form at N = 2, 3, which starts 60 / 24 words in front of it."""
+    import subprocess
+
+    csrc = os.path.join(ROOT, "ihm2_amd", "csrc")
+    ring = re.search(r"#define SWEEP_RING (\d+)", open(os.path.join(csrc, "kernels_qp.hip")).read()).group(1)
+    exe = str(tmp_path / "check_qp_lds")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-DSWEEP_RING=" + ring, "-I", csrc, "-o", exe,
+                           os.path.join(ROOT, "tools", "probes", "check_qp_lds.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout
+    for path, uni in ((0, 0), (0, 1), (1, 0), (1, 1), (2, 1)):
+        assert f"path {path} uni {uni} N 2: the earlier form's vector sweep reaches word -60" in out.stdout
+        assert f"path {path} uni {uni} N 3: the earlier form's vector sweep reaches word -24" in out.stdout
+    assert out.stdout.count("reaches word") == 10
+
+
 def test_oracle_and_library_share_the_interior_point_constants():
     """The checker and the product define the algorithm's constants independently (the product never includes anything under oracle/): same values."""
     import re

@@ -125,6 +125,48 @@ def test_horizons_around_the_ring_depth(track, N, monkeypatch):
                 assert d < 1e-9, (Bp, k)
 
 
+@pytest.mark.parametrize("N,loop", [(3, False), (4, True)])
+def test_sqp_loop_is_refused_where_its_sweeps_leave_the_lds(track, N, loop, monkeypatch):
+    """The SQP instantiations of the persistent loop keep the sweeps' earlier form (kernels_qp.hip: stream_rows_v1), whose unclamped prefetch
+    of LDS operands starts in front of the block's LDS at N = 2, 3 (csrc/qp_lds.hpp: qp_reach_v1_vector; 60 / 24 words): run_steps launches
+    those horizons per step and says so, and runs the loop from N = 4.  Three control steps, bit for bit against three calls of step().
+    (The collocation integrator: at B N <= 128 it is the one configuration in which step() and the loop linearise and simulate with the
+    same code -- see test_horizons_around_the_ring_depth.)"""
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    monkeypatch.setenv("IHM2MPC_BLOCK_QP", "0")
+    ocp = make_ocp(N=N, nlp_solver_type="SQP", nlp_solver_max_iter=2, globalization="MERIT_BACKTRACKING", integrator_type="IRK", sim_method_num_steps=1)
+    x0 = _x0(track, SEEDS[N])
+    res = []
+    for persistent in (False, True):
+        s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+        s.set_lap_wrap(True)
+        s.set_x0(x0); s.init_guess()
+        s.step(40.0, model=-1, M_sim=30)
+        if persistent:
+            h = s.run_steps(40.0, 3, model=-1, M_sim=30, u0_hist=True, x0_hist=True, status_hist=True, qp_iter_hist=True)
+            rec = s.get_launch_record()
+            if loop:
+                assert rec["steps"] == "k_steps<5,0,0,1,1,1,0>"
+            else:
+                assert rec["steps"] == "per_step" and rec["steps_fallback"] == "no_instantiation"
+        else:
+            h = dict(u0=[], x0=[], status=[], qp_iter=[])
+            for _ in range(3):
+                s.step(40.0, model=-1, M_sim=30)
+                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
+            h = {k: np.array(v) for k, v in h.items()}
+        res.append((h, s.get_x(), s.get_u(), s.get_multipliers(), s.get_sqp_stats()))
+        s.free()
+    (ha, xa, ua, ma, sa), (hb, xb, ub, mb, sb) = res
+    for k in ("status", "qp_iter", "x0", "u0"):
+        np.testing.assert_array_equal(ha[k], hb[k], err_msg=k)
+    np.testing.assert_array_equal(xa, xb); np.testing.assert_array_equal(ua, ub)
+    np.testing.assert_array_equal(ma[0], mb[0]); np.testing.assert_array_equal(ma[1], mb[1])
+    np.testing.assert_array_equal(sa["sqp_iter"], sb["sqp_iter"]); np.testing.assert_array_equal(sa["alpha"], sb["alpha"])
+    assert np.isin(ha["status"], (0, 2)).mean() > 0.5
+
+
 def test_general_form_with_the_symmetrising_tile(track, monkeypatch):
     """fdyn6 as written keeps the general stage and its tile: one per-step solve at N = 5 against the oracle, on the same terms."""
     monkeypatch.setenv("IHM2MPC_BLOCK_QP", "0")

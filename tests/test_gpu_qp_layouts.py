@@ -352,6 +352,50 @@ def test_layout_past_a_limit_is_refused_and_the_handle_recovers(track, name, bui
     s.free(); fresh.free()
 
 
+# The LDS classes of the QP (csrc/qp_lds.hpp: rows per stage, track-row slopes, a_lat row, batch-shared H / [C D] kept in LDS) at the two shortest
+# horizons the sweeps treat differently: N = 2 is under every ring depth, N = 4 the first the sweeps' earlier form stays inside the block with.
+# The fourth class, all sides hard with batch-shared weights, is test_gpu_factor_sweep_forms.py::test_horizons_around_the_ring_depth[2] and [4].
+# class -> (layout, kernel, sample_x0 seed per horizon: those of tools/find_factor_sweep_seeds.py, 4 for N = 2 and 1 for N = 4; with the a_lat row the
+# seed 1 leaves two of the eight QPs at N = 4 infeasible in the oracle as well, the seed 4 none)
+SHORT = {
+    "hard_stage_W": (dict(stage_W=True, seed=21), "k_qp_wave<5,0,0,0>", {2: 4, 4: 1}),
+    "path_hard": (dict(path=True), "k_qp_wave<8,0,1,1>", {2: 4, 4: 1}),
+    "alat_hard": (dict(path=True, alat=True, alat_max=4.5), "k_qp_wave<8,0,2,1>", {2: 4, 4: 4}),
+}
+
+
+@pytest.mark.parametrize("N", [2, 4])
+@pytest.mark.parametrize("cls", list(SHORT))
+def test_lds_class_at_the_shortest_horizons(track, cls, N):
+    """One RTI step of 8 instances against the oracle, to the tolerances of test_layout_matches_oracle_and_kkt."""
+    from oracle import oracle as orc
+
+    kw, kernel, seeds = SHORT[cls]
+    lay, B = Lay(f"short_{cls}", N=N, **kw), 8
+    s = _solver(track, lay, B, "default", "0")
+    P = orc.OracleProblem(s.data.as_dict(track.s_ref, track.kappa_ref, track_widths=L.track_widths(lay)))
+    x0, yref, yref_e = _start(s, track, B, seeds[N])
+    x, u = s.get_x(), s.get_u()
+    st = s.solve()
+    assert s.get_launch_record()["qp"] == kernel
+    out = P.rti_step(x, u, x0, yref, yref_e)
+    np.testing.assert_array_equal(st, out["status"])
+    np.testing.assert_array_equal(s.get_qp_iter(), out["qp_iter"])
+    ok = st == 0
+    assert ok.sum() >= 0.6 * B, st
+    xg, ug = s.get_x(), s.get_u()
+    pig, lamg = s.get_multipliers()
+    if lay.alat:
+        lamg = _widen(lamg, s.get_alat_multipliers()[0])
+    pi, lam = out["pi"], out["lam"]
+    ex = np.max(np.abs(xg[ok] - x[ok]) / (1 + np.abs(x[ok]))); eu = np.max(np.abs(ug[ok] - u[ok]) / (1 + np.abs(u[ok])))
+    sp = max(1.0, float(np.abs(pi[ok][:, 1:]).max())); sl_ = max(1.0, float(np.abs(lam[ok]).max()))
+    epi = np.abs(pig[ok][:, 1:] - pi[ok][:, 1:]).max() / sp; elam = np.abs(lamg[ok] - lam[ok]).max() / sl_
+    print(f"{cls} N={N}: x {ex:.2e} u {eu:.2e} pi {epi:.2e} lam {elam:.2e}, status {st.tolist()}, qp_iter {out['qp_iter'].tolist()}")
+    assert ex < 1e-7 and eu < 1e-7 and epi <= 1e-6 and elam <= 1e-6
+    s.free()
+
+
 def test_every_instantiation_was_launched_in_both_builds():
     """The records of this module against the explicit list: adding or removing an instantiation (or moving a layout to another one)
     must touch this list."""

@@ -211,7 +211,7 @@ __device__ __forceinline__ void riccati_sweep_blk2(const int N, const int lane, 
                     sm[L.dz + (a + 2) * 10 + g] = S[2]; sm[L.dz + (a + 2) * 10 + 4 + g] = S[3];
                     sm[L.kff + m * 4 + g] = Kf;
                 }
-                RIC_WSYNC();
+                WSYNC();
                 Pd[0] = S[0]; Pd[1] = S[1];
                 if (j < 8) {
                     double2 pp;

@@ -24,7 +24,7 @@ static Off offsets(int N)
 {
     const int NS = N + 1; Off o; int p = 0;
     o.z = p; p += NS * 10; o.pi = p; p += NS * 8; o.gam = p; p += NS * NCK; o.hc = p; p += NS * 2; o.gt = p; p += NS * 10;
-    o.rb = p; p += N * 8; o.pv = p; p += NS * 8; o.hv = p; p += N * 8; o.Kl = p; p += N * 16; o.Ginv = p; p += N * 8; o.kff = p; p += N * 4; o.dz = p; p += NS * 10; o.tile = p; p += 136;
+    o.rb = p; p += N * 8; o.pv = p; p += NS * 8; o.hv = p; p += N * 8; o.Kl = p; p += N * 16; o.Ginv = p; p += N * 8; o.kff = p; p += N * 4; o.dz = p; p += NS * 10; o.tile = p; p += QP_TILE_WORDS;
     o.total = p; return o;
 }
 
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64) void k_proto(int N, Off o, double *lin_all, con
         dyn_residual<4>(N, lane, lin, sm + o.z, sm + o.pi, sm + o.gt, sm + o.rb, REC);
         __syncthreads();
         if (r == 0) t0 = __builtin_readcyclecounter(), tr += t0 - tq;
-        riccati_sweep_mfma<NCK, PATHV != 0, UNIV != 0, RD>(N, lane, lin, Hs, CD, L, Pg + (size_t)b * (N + 1) * 64, Mg + (size_t)b * N * 64, REC, true, true);
+        riccati_sweep_mfma<NCK, PATHV != 0, UNIV != 0, RD>(N, lane, lin, Hs, Hs + (size_t)N * 100, CD, L, Pg + (size_t)b * (N + 1) * 64, Mg + (size_t)b * N * 64, REC, true, true);
         __syncthreads();
     }
     long long t1 = __builtin_readcyclecounter();
