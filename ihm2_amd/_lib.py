@@ -33,6 +33,7 @@ _H = C.c_void_p
 SYMBOLS = {
     "ihm2mpc_last_error": (C.c_char_p, []),
     "ihm2mpc_version": (C.c_char_p, []),
+    "ihm2mpc_lag_stage_factors": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "ihm2mpc_group_create": (C.c_int, [C.POINTER(_H), C.c_int32, C.POINTER(_H)]),
     "ihm2mpc_group_allgather_results": (C.c_int, [_H, c_double_p, c_int32_p]),
     "ihm2mpc_group_free": (C.c_int, [_H]),

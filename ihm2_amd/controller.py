@@ -243,6 +243,7 @@ class IHM2Controller(Controller):
         opts.sim_method_num_steps = sim_method_num_steps
         # python/main.py:234-236: "IRK" = 4 Gauss-Legendre stages (acados' default collocation), sim_method_num_steps per interval;
         # sim_integrator_type: the plant steps behind this controller's device state (python/main.py:395-400: "IRK", GAUSS_RADAU_IIA)
+        # "ERK_LAG" for either (not in acados): RK4 x sim_method_num_steps with the actuator lags in closed form (4 sub-steps are sized for the car)
         opts.integrator_type = integrator_type
         opts.sim_integrator_type, opts.sim_collocation_type = sim_integrator_type, "GAUSS_RADAU_IIA"
         ocp.solver_options = opts

@@ -194,10 +194,10 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
 }
 
 // ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
-// The catalogue is the five objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
+// The catalogue is the seven objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
 // (the leading one-sided entries per lane rebuild_slots laid it out for) and its NSLOT holds the table's slots per lane; of those
 // that fit the configuration, the first in catalogue order is launched.
-const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4()};
+const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6()};
 
 // the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
 int path_class(const ihm2mpc_handle *h) { return h->alat_on ? 2 : h->path_on ? 1 : 0; }
@@ -282,9 +282,13 @@ const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
 const QpInst *select_steps(const ihm2mpc_handle *h, int sens = 0)
 {
     const ihm2::StepsLds lds = steps_lds(h, sens);
-    const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP, irk = h->cfg.integrator_type != IHM2MPC_INTEG_ERK;
+    const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP;
+    // QpKey.irk: 0 RK4, 1 collocation, 2 RK4 with the closed-form lags
+    const int irk = ihm2_is_irk(h->cfg.integrator_type) ? 1 : (h->cfg.integrator_type == IHM2MPC_INTEG_ERK_LAG) ? 2 : 0;
     const bool dyn = h->cfg.model != IHM2MPC_MODEL_FKIN6;
-    if (irk && (!h->irk_tab || (sqp && h->sqp_globalization && !h->ls_phi))) return nullptr;
+    if (irk == 1 && (!h->irk_tab || (sqp && h->sqp_globalization && !h->ls_phi))) return nullptr;
+    // a plant with the closed-form lags rides on lane N of the loop that linearises with them; the other loops have no such plant
+    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG && irk != 2) return nullptr;
     if (sqp && !h->ls_x) return nullptr;        // the caller allocates the line-search buffers first
     if (lds.total() * sizeof(double) > 160 * 1024) return nullptr;
     // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
@@ -360,7 +364,7 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
     const size_t lds = sizeof(double) * (size_t)steps_lds(h, sens).total();
     const QpInst *e = select_steps(h, sens);
     if (!e) return 1;
-    const bool irk_plant = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
+    const bool irk_plant = ihm2_is_irk(h->cfg.sim_integrator_type);     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
     if (irk_plant && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;
     const bool sqp = e->key.sqp;
     QpArgs a = qp_args(h);
@@ -376,8 +380,14 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
     s.irk_tab = h->irk_tab;
     s.sim_irk_tab = irk_plant ? h->sim_irk_tab.get() : nullptr;
     s.sens = sens ? (const SensArgs *)h->sens_args.get() : nullptr;
+    s.sim_lag = h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG;
+    std::memset(s.lag, 0, sizeof s.lag);
+    if (e->key.irk == 2) {
+        const LagFac lo = ihm2_lag_factors(h->cfg.dt / h->cfg.M), lp = ihm2_lag_factors(h->cfg.dt / M_sim);
+        std::memcpy(s.lag[0], lo.f, sizeof lo.f); std::memcpy(s.lag[1], lp.f, sizeof lp.f);
+    }
     // every field of s is set: upload it (and the line search's block in the SQP mode, the x0 sensitivities' block with SENS)
-    static_assert(sizeof(StepArgs) <= 32 * sizeof(double), "step_args holds 256 bytes");
+    static_assert(sizeof(StepArgs) <= 48 * sizeof(double), "step_args holds 384 bytes");
     static_assert(sizeof(ihm2::LsArgs) <= 64 * sizeof(double), "ls_args holds 512 bytes");
     static_assert(sizeof(SensArgs) <= 64 * sizeof(double), "sens_args holds 512 bytes");
     // both blocks go through a pinned staging slot (two slots, used alternately) and are uploaded in stream order: the host does
@@ -494,11 +504,47 @@ ihm2mpc_handle::~ihm2mpc_handle()
 
 // classical RK4 is stable for |z| < 2.785 on the negative real axis: z = -(dt / M) / t for the first-order actuator lags
 static bool rk4_unstable(double dt, int M) { return dt / M / 1e-3 >= 2.78; }
+// sim_integrator_type ERK_LAG integrates the plain kinematic plant only
+static int lag_plant_refused(const ihm2mpc_handle *h, int model)
+{
+    if (h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK_LAG || model == IHM2MPC_MODEL_FKIN6) return 0;
+    return fail("the plant integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic plant (model 0) only, not for plant "
+                "model %d: create the handle with another sim_integrator_type", model);
+}
 
 extern "C" {
 
 const char *ihm2mpc_last_error(void) { return g_err.c_str(); }
 const char *ihm2mpc_version(void) { return "ihm2mpc 0.1 (gfx950)"; }
+
+// E_0, E_1, E_2: the stage values that make Simpson's rule exact for the first three moments of exp(-t / tau) on [0, h].  With r = h / tau:
+// p1 = m1 / h^2 = (1 - e (1 + r)) / r^2 and p2 = m2 / h^3 = 2 (1 - e (1 + r + r^2 / 2)) / r^3; below r = 1 the differences lose digits
+// (they start at r^2 / 2 and r^3 / 6), so the series  p1 = sum_{k>=2} (-1)^k (k - 1) / k! r^(k-2),  p2 = sum_{k>=3} (-1)^(k+1) (k - 1)(k - 2) / k! r^(k-3)
+int ihm2mpc_lag_stage_factors(double h, double tau, double *out4)
+{
+    if (!out4) return fail("null argument");
+    if (!(h > 0.0) || !(tau > 0.0) || !std::isfinite(h) || !std::isfinite(tau)) return fail("h and tau must be positive and finite");
+    const double r = h / tau, e = exp(-r);
+    double p1, p2;
+    if (r < 1.0) {
+        p1 = 0.0; p2 = 0.0;
+        double t = 0.5;          // r^(k-2) / k!, from k = 2
+        for (int k = 2; k < 40; k++) {
+            p1 += ((k & 1) ? -1.0 : 1.0) * (k - 1) * t;
+            if (k >= 3) p2 += ((k & 1) ? 1.0 : -1.0) * (double)((k - 1) * (k - 2)) * t / r;
+            t *= r / (k + 1);
+        }
+    } else {
+        p1 = (1.0 - e * (1.0 + r)) / (r * r);
+        p2 = 2.0 * (1.0 - e * (1.0 + r + 0.5 * r * r)) / (r * r * r);
+    }
+    const double E1 = 6.0 * (p1 - p2), E2 = 12.0 * p2 - 6.0 * p1;
+    out4[0] = 6.0 * (-expm1(-r) / r) - 4.0 * E1 - E2;
+    out4[1] = E1;
+    out4[2] = E2;
+    out4[3] = e;
+    return 0;
+}
 
 int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
 {
@@ -506,10 +552,16 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
     if (cfg->batch < 1) return fail("batch must be >= 1");
     if (cfg->N < 2 || cfg->N > IHM2MPC_NMAX) return fail("N must be in [2, %d]", IHM2MPC_NMAX);
     if (cfg->M < 1) return fail("M must be >= 1");
-    if (cfg->integrator_type < IHM2MPC_INTEG_ERK || cfg->integrator_type > IHM2MPC_INTEG_IRK_RADAU4 || cfg->sim_integrator_type < IHM2MPC_INTEG_ERK ||
-        cfg->sim_integrator_type > IHM2MPC_INTEG_IRK_RADAU4)
+    if (cfg->integrator_type < IHM2MPC_INTEG_ERK || cfg->integrator_type > IHM2MPC_INTEG_ERK_LAG || cfg->sim_integrator_type < IHM2MPC_INTEG_ERK ||
+        cfg->sim_integrator_type > IHM2MPC_INTEG_ERK_LAG)
         return fail("unknown integrator type (%d, %d)", cfg->integrator_type, cfg->sim_integrator_type);
-    if (cfg->integrator_type != IHM2MPC_INTEG_ERK && cfg->M != 1)
+    if (cfg->integrator_type == IHM2MPC_INTEG_ERK_LAG && cfg->model != IHM2MPC_MODEL_FKIN6)
+        return fail("the integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic OCP model IHM2MPC_MODEL_FKIN6 only, not for "
+                    "the dynamic models (model %d): use ERK or IRK", cfg->model);
+    if (cfg->integrator_type == IHM2MPC_INTEG_ERK_LAG && cfg->nlp_solver_type != IHM2MPC_SQP_RTI)
+        return fail("the integrator ERK_LAG (closed-form actuator lags) is implemented for IHM2MPC_SQP_RTI only: the SQP mode's line-search "
+                    "rollouts have no such integrator; use ERK or IRK");
+    if (ihm2_is_irk(cfg->integrator_type) && cfg->M != 1)
         return fail("the IRK integrator of the shooting intervals takes one step per interval (sim_method_num_steps = 1, python/main.py:236); M = %d", cfg->M);
     if (cfg->integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(cfg->dt, cfg->M))
         return fail("RK4 with %d sub-step(s) of dt = %g is unstable on the actuator lags (t_T = 1e-3 s, t_delta = 0.02 s: |z| = dt / (M t) must stay "
@@ -548,7 +600,7 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
                   h->lbu, N * 2, h->ubu, N * 2, h->CD, N * 20, h->lg, N * 2, h->ug, N * 2, h->slot_kc_blk, 1024, h->slot_lb_blk, 1024,
                   h->slot_ub_blk, 1024, h->slot_kc, MAX_SLOTS, h->slot_lb, MAX_SLOTS, h->slot_ub, MAX_SLOTS, h->slot_zw, MAX_SLOTS,
                   h->slot_Zw, MAX_SLOTS, h->slk, B * NS * NLAM, h->widths, (size_t)cfg->ntracks * 2, h->lam_a, B * NS * 2, h->slk_a, B * NS * 2,
-                  h->X_ref, nt, h->Y_ref, nt, h->phi_ref, nt, h->xc, B * 8, h->s_guess, B, h->step_args, 32, h->Wd, N * 144 + 64,
+                  h->X_ref, nt, h->Y_ref, nt, h->phi_ref, nt, h->xc, B * 8, h->s_guess, B, h->step_args, 48, h->Wd, N * 144 + 64,
                   h->st_lb, NS * NC, h->st_ub, NS * NC, h->st_sz, NS * NLAM, h->st_sZ, NS * NLAM, h->x, B * NS * 8, h->u, B * N * 2, h->x0, B * 8,
                   h->yref, B * N * 12, h->yref_e, B * 8, h->pi, B * NS * 8, h->lam, B * NS * NLAM, h->res, B * 4, h->qp_res, B * 4, h->status, B,
                   h->qp_iter, B, h->active, B, h->u0, B * 2,
@@ -1464,6 +1516,7 @@ int ihm2mpc_sim_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const doub
     if (M_sim < 1) return fail("M_sim must be >= 1");
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
+    if (lag_plant_refused(h, model)) return -1;
     double *xs = h->scratch, *us = h->scratch + (size_t)h->B * 8, *xn = h->scratch + (size_t)h->B * 16;
     if (upload(h, x, xs, NX) || upload(h, u, us, NU)) return -1;
     ihm2_launch_sim(h, model, M_sim, xs, us, xn, h->stream, nullptr);
@@ -1478,6 +1531,7 @@ int ihm2mpc_sim_advance(ihm2mpc_handle *h, int32_t model, int32_t M_sim)
     if (M_sim < 1) return fail("M_sim must be >= 1");
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
+    if (lag_plant_refused(h, model)) return -1;
     ihm2_launch_sim(h, model, M_sim, h->x0, h->u0, h->x0, h->stream, h->active_set ? h->active.get() : nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1548,6 +1602,7 @@ int ihm2mpc_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_targe
     if (M_sim < 1) return fail("M_sim must be >= 1");
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
+    if (lag_plant_refused(h, model)) return -1;
     // The plant step and the reference ramp only feed the QP (through x0 and yref); the warm-start shift and the
     // linearisation only need the previous iterate.  Two branches, joined in front of the QP kernel.
     if (h->lap_wrap) ihm2_launch_wrap_lap(h);
@@ -1604,6 +1659,7 @@ static int run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_t
     if (M_sim < 1) return fail("M_sim must be >= 1");
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
+    if (lag_plant_refused(h, model)) return -1;
     if (n_steps < 1) return fail("n_steps must be >= 1");
     const size_t B = h->B, n = n_steps;
     if (ihm2mpc_reserve_history(h, n_steps)) return -1;
@@ -1711,6 +1767,9 @@ int ihm2mpc_sim_step_dyn10(ihm2mpc_handle *h, int32_t M_sim, const double *x, co
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
     if (!x || !u || !x_next) return fail("null argument");
     if (M_sim < 1) return fail("M_sim must be >= 1");
+    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG)
+        return fail("the plant integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic plant (model 0) only, not for the "
+                    "fdyn10 plant: create the handle with another sim_integrator_type");
     const bool irk = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;
     if (!irk && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the torque lags (t_T = 1e-3 s): use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (!h->dyn10) HIP_TRY(h->dyn10.alloc((size_t)h->B * 35));

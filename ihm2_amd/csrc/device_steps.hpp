@@ -105,17 +105,49 @@ __device__ __forceinline__ void sens_col_copy(const double (&src)[8], double (&d
         if ((cm >> i) & 1u) dst[i] = src[i];
 }
 
+// IHM2MPC_INTEG_ERK_LAG: one RK4 stage of sensitivity column COL of the six vehicle states.  The actuator rows of the stage point are
+// X_a = u + (a - u) E (E: the lag's stage factor, ihm2mpc_lag_stage_factors), so their derivative is E * S_a for a state column and
+// E * S_a + (1 - E) for the lag's own input column; dK and Sacc carry the rows 0..5 only (the rows 6, 7 of S follow a+ in closed form)
+template <int COL>
+__device__ __forceinline__ void sens_col_stage_lag(const double (&J)[8][10], const double (&S)[8], double (&Sacc)[8], double (&dK)[8], double ah,
+                                                   double wh, double E_T, double E_d)
+{
+    constexpr unsigned cm = S_COL_MASK[0][COL];
+    double dX[8];
+#pragma unroll
+    for (int l = 0; l < 6; l++)
+        if ((cm >> l) & 1u) dX[l] = fma(ah, dK[l], S[l]);
+    if ((cm >> 6) & 1u) dX[6] = (COL == 8) ? fma(E_T, S[6], 1.0 - E_T) : E_T * S[6];
+    if ((cm >> 7) & 1u) dX[7] = (COL == 9) ? fma(E_d, S[7], 1.0 - E_d) : E_d * S[7];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        if (!((cm >> i) & 1u)) continue;
+        double acc = 0.0;
+        if (COL >= 8 && ((JU_MASK[0][i] >> (COL - 8)) & 1u)) acc = J[i][COL];
+#pragma unroll
+        for (int l = 0; l < 8; l++)
+            if (((JX_MASK[0][i] & cm) >> l) & 1u) acc = fma(J[i][l], dX[l], acc);
+        dK[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+        if ((cm >> i) & 1u) Sacc[i] = fma(wh, dK[i], Sacc[i]);
+}
+
 #define FOR_ALL_COLS(OP) OP(0) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7) OP(8) OP(9)
 
 // one lane: interval k of instance b.  Sl: this lane's column of the LDS copy of S (dynamic models), nullptr for fkin6
-template <int MODEL>
+// LAG = 1 (fkin6 only): IHM2MPC_INTEG_ERK_LAG -- the two actuator lags in closed form, classical RK4 on the six vehicle states with the
+// lags' moment-fitted stage values (include/ihm2mpc.h); lagf: {E_0, E_1, E_2, e} of the torque lag, then of the steering lag, for h = dt / M
+template <int MODEL, int LAG = 0>
 // xk (8), uk (2): where to integrate from; x_next (8): the state the defect b is taken against; rec: the 88-double record
 // [A | B | b] written at the end; xn_out (8) or nullptr: Phi(x_k, u_k) itself (the kinematic PLANT is this very function on
 // (x0, u0): it then runs in lockstep with the interval lanes of the same wavefront, see k_steps)
 __device__ __forceinline__ void dev_integrate_sens(
     const double *xk, const double *__restrict__ uk, const double *x_next, int tid, int M, double dt, int nknots, const double *__restrict__ s_ref,
-    const double *__restrict__ kappa_ref, double *__restrict__ rec, double *xn_out, double *__restrict__ Sl)
+    const double *__restrict__ kappa_ref, double *__restrict__ rec, double *xn_out, double *__restrict__ Sl, const double *lagf = nullptr)
 {
+    static_assert(LAG == 0 || MODEL == IHM2MPC_MODEL_FKIN6, "the closed-form lags are implemented for the kinematic model");
     double x[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) x[i] = xk[i];
@@ -139,6 +171,54 @@ __device__ __forceinline__ void dev_integrate_sens(
         }
 
     const double h = dt / M;
+    if constexpr (LAG != 0) {
+        // the order of the fkin6 loop below: the four stage evaluations of the state first, then every sensitivity column through its stages
+        double ET[4], ED[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { ET[i] = lagf[i]; ED[i] = lagf[4 + i]; }
+        for (int m = 0; m < M; m++) {
+            double xacc[8], K[8], J4[4][8][10];
+#pragma unroll
+            for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
+            const double dT = x[6] - u_T, dD = x[7] - u_d;
+#pragma unroll
+            for (int st = 0; st < 4; st++) {
+                const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
+                const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+                const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);
+                double X[8];
+#pragma unroll
+                for (int i = 0; i < 6; i++) X[i] = fma(ah, K[i], x[i]);
+                X[6] = fma(dT, ET[sf], u_T);
+                X[7] = fma(dD, ED[sf], u_d);
+                fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
+#pragma unroll
+                for (int i = 0; i < 6; i++) xacc[i] = fma(wh, K[i], xacc[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < 6; i++) x[i] = xacc[i];
+            x[6] = fma(dT, ET[3], u_T);
+            x[7] = fma(dD, ED[3], u_d);
+#define SUBSTEP_COL_LAG(c)                                                                                               \
+            {                                                                                                            \
+                constexpr unsigned cm = S_COL_MASK[0][c];                                                                \
+                double Sa[8], dKc[8];                                                                                    \
+                _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                          \
+                _Pragma("unroll") for (int st = 0; st < 4; st++) {                                                       \
+                    const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);                                       \
+                    const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);                          \
+                    const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);                                                  \
+                    sens_col_stage_lag<c>(J4[st], S[c], Sa, dKc, ah, wh, ET[sf], ED[sf]);                                \
+                }                                                                                                        \
+                _Pragma("unroll") for (int i = 0; i < 6; i++)                                                            \
+                    if ((cm >> i) & 1u) S[c][i] = Sa[i];                                                                 \
+                if ((cm >> 6) & 1u) S[c][6] = (c == 8) ? fma(ET[3], S[c][6], 1.0 - ET[3]) : ET[3] * S[c][6];              \
+                if ((cm >> 7) & 1u) S[c][7] = (c == 9) ? fma(ED[3], S[c][7], 1.0 - ED[3]) : ED[3] * S[c][7];              \
+            }
+            FOR_ALL_COLS(SUBSTEP_COL_LAG)
+#undef SUBSTEP_COL_LAG
+        }
+    } else
     if (!S_IN_LDS) {
         // fkin6: per sub-step FIRST the four stage evaluations of the state (the stage points depend on the state only), their
         // Jacobians kept; THEN every sensitivity column through its four stages with the column's entries in registers throughout.
@@ -227,15 +307,15 @@ __device__ __forceinline__ void dev_integrate_sens(
 }
 
 // one lane: interval k of instance b
-template <int MODEL>
+template <int MODEL, int LAG = 0>
 __device__ __forceinline__ void dev_linearize(
     int b, int k, int N, int M, double dt, int nknots, const double *__restrict__ s_ref,
     const double *__restrict__ kappa_ref, const int32_t *__restrict__ track_id, const double *xs,
-    const double *us, double *lin, double *Sl)
+    const double *us, double *lin, double *Sl, const double *lagf = nullptr)
 {
     const double *xk = xs + ((size_t)b * (N + 1) + k) * 8;
-    dev_integrate_sens<MODEL>(xk, us + ((size_t)b * N + k) * 2, xk + 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
-                              lin + ((size_t)b * N + k) * LIN_REC, nullptr, Sl);
+    dev_integrate_sens<MODEL, LAG>(xk, us + ((size_t)b * N + k) * 2, xk + 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
+                                   lin + ((size_t)b * N + k) * LIN_REC, nullptr, Sl, lagf);
 }
 
 // plant / rollout step: x_next = RK4 x M over dt; model -1 (-2: with fdyn6u) = kin/dyn switch of
@@ -296,16 +376,18 @@ __device__ __forceinline__ void dev_sim_step(int b, int q, int model, int M, dou
 // The plain kinematic plant (model 0) is dev_integrate_sens on (x, u): the same arithmetic as a shooting interval, so that the
 // persistent loop can run it on the spare lane of the linearisation for free (k_steps); its record goes to spare_rec
 // (88 doubles per instance, never read).
+template <int LAG = 0>
 __device__ __forceinline__ void dev_sim_step_kin(int b, int M, double dt, int nknots, const double *__restrict__ s_ref,
                                                  const double *__restrict__ kappa_ref, const int32_t *__restrict__ track_id,
-                                                 const double *xs, const double *us, double *xn, const int32_t *active, double *spare_rec)
+                                                 const double *xs, const double *us, double *xn, const int32_t *active, double *spare_rec,
+                                                 const double *lagf = nullptr)
 {
     if (active && !active[b]) {
         if (xn != xs) for (int i = 0; i < 8; i++) xn[(size_t)b * 8 + i] = xs[(size_t)b * 8 + i];
         return;
     }
-    dev_integrate_sens<IHM2MPC_MODEL_FKIN6>(xs + (size_t)b * 8, us + (size_t)b * 2, xs + (size_t)b * 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
-                                            spare_rec + (size_t)b * LIN_REC, xn + (size_t)b * 8, nullptr);
+    dev_integrate_sens<IHM2MPC_MODEL_FKIN6, LAG>(xs + (size_t)b * 8, us + (size_t)b * 2, xs + (size_t)b * 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
+                                                 spare_rec + (size_t)b * LIN_REC, xn + (size_t)b * 8, nullptr, lagf);
 }
 
 }  // namespace ihm2

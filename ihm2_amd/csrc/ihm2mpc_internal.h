@@ -33,6 +33,13 @@
 #define QM_PAD 24    // >= 3 x ring depth of the vector / forward sweeps: their unclamped prefetch overshoots an instance by < 3 D rows
 #define LIN_REC 96   // doubles per (instance, interval) linearisation record: A (64) | B (16) | b (8) | rb (8: the QP's dynamics residual, riccati_mfma.hpp)
 
+// the collocation integrators among IHM2MPC_INTEG_* (ERK and ERK_LAG are the explicit ones)
+static inline bool ihm2_is_irk(int type) { return type == IHM2MPC_INTEG_IRK_GL4 || type == IHM2MPC_INTEG_IRK_RADAU4; }
+// IHM2MPC_INTEG_ERK_LAG: the stage factors {E_0, E_1, E_2, e} of the torque lag, then of the steering lag, for sub-steps of h
+// (ihm2mpc_lag_stage_factors on the model's two time constants; kernels_linearize.hip) -- computed on the host, a kernel argument
+struct LagFac { double f[8]; };
+LagFac ihm2_lag_factors(double h);
+
 struct ihm2mpc_comm;      // comm.hip: RCCL communicator + staging buffers of a one-process-per-GPU job
 namespace ihm2 { struct IrkTab; }
 
@@ -170,7 +177,7 @@ struct ihm2mpc_handle {
     DevBuf<int32_t> ls_done, ls_status, ls_iter, ls_qp_acc;
     DevBuf<int32_t> ls_pending;            // (B) instances whose line search goes past the first rollouts (two-launch ladder)
     DevBuf<double> ls_args;                // device copy of the line search's argument block for the persistent loop (512 B)
-    DevBuf<double> step_args;              // device copy of the persistent loop's own argument block (256 B), allocated with the handle
+    DevBuf<double> step_args;              // device copy of the persistent loop's own argument block (384 B), allocated with the handle
     void *args_host[2];             // pinned staging of both blocks (1 KB each), used alternately
     hipEvent_t args_ev[2];          // recorded after a slot's upload: the slot is free again once it has passed
     int args_idx;
@@ -310,6 +317,10 @@ struct StepArgs {
     const ihm2::IrkTab *irk_tab;            // IRK = 1: the tableau of the shooting intervals' collocation step, in device memory
     const ihm2::IrkTab *sim_irk_tab;        // plant steps by collocation (python/main.py:395-400: Radau IIA x M_sim) instead of RK4 x M_sim; nullptr: RK4
     const SensArgs *sens;                   // SENS = 1: the x0 sensitivities' block in device memory (h->sens_args); nullptr otherwise
+    // IRK = 2 (IHM2MPC_INTEG_ERK_LAG; behind the fields of the other loops, whose offsets stay): the lags' stage factors (LagFac) for the
+    // shooting intervals' sub-step dt / M, then for the plant's dt / M_sim; sim_lag: the kinematic plant takes that integrator too (lane N)
+    double lag[2][8];
+    int sim_lag;
 };
 
 }  // namespace
@@ -318,7 +329,7 @@ struct StepArgs {
 // void pointer: a function with the unnamed namespace's type in its signature could not be defined in another translation unit.)
 void ihm2_sens_args(const ihm2mpc_handle *h, void *out);
 
-// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0, 1, 2, 3, 4) returns the table of the ones it
+// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0 .. 6) returns the table of the ones it
 // holds, in its order of preference (kernels_qp.hip: QP_INSTANCES).  A key holds the template parameters as the launch record gives them
 // (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.  nf is not in the record: the
 // form of the factor sweep (qp_wave_body: 0 the general form, 40 straight-line with the horizon 40 compiled in, -1 straight-line with the
@@ -327,4 +338,4 @@ enum { QP_WAVE = 1, QP_BLOCK = 2, QP_STEPS = 3 };
 struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens, nf; };
 struct QpInst { QpKey key; int threads; const void *kernel; };
 struct QpTable { const QpInst *inst; int n; };
-QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4();
+QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6();

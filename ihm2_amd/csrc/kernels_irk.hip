@@ -159,7 +159,7 @@ void ihm2_launch_rollout_irk(ihm2mpc_handle *h, int j_begin, int j_end, double *
 
 int ihm2_upload_irk_tab(ihm2mpc_handle *h)
 {
-    if (h->cfg.integrator_type == IHM2MPC_INTEG_ERK) return 0;
+    if (!ihm2_is_irk(h->cfg.integrator_type)) return 0;
     const IrkTab tab = make_tab(h->cfg.integrator_type, h->cfg.dt / h->cfg.M);
     if (!h->irk_tab && h->irk_tab.alloc(1) != hipSuccess) return 1;
     if (hipMemcpyAsync(h->irk_tab, &tab, sizeof(IrkTab), hipMemcpyHostToDevice, h->stream) != hipSuccess) return 1;
@@ -169,7 +169,7 @@ int ihm2_upload_irk_tab(ihm2mpc_handle *h)
 // the plant's tableau for M_sim steps per control period, in device memory for the persistent loop (rebuilt when M_sim changes)
 int ihm2_upload_sim_irk_tab(ihm2mpc_handle *h, int M_sim)
 {
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK) return 1;
+    if (!ihm2_is_irk(h->cfg.sim_integrator_type)) return 1;
     if (h->sim_irk_tab && h->sim_irk_M == M_sim) return 0;
     const IrkTab tab = make_tab(h->cfg.sim_integrator_type, h->cfg.dt / M_sim);
     if (!h->sim_irk_tab && h->sim_irk_tab.alloc(1) != hipSuccess) return 1;

@@ -5,6 +5,8 @@
 // Replaces what acados' ERK integrator does inside AcadosOcpSolver.solve() for the reference
 // (python/main.py:325; options old/generate.py:23-25 with sim_method_num_steps = M).
 // RK4 tableau as dpc/main.py:87-97.
+// IHM2MPC_INTEG_ERK_LAG (k_linearize<FKIN6, LAG = 1>): the same tableau on the six vehicle states, the two actuator lags in closed form
+// (device_steps.hpp: dev_integrate_sens<MODEL, LAG>; include/ihm2mpc.h).
 //
 // Mapping: one lane per (b, k) pair, k fastest (instance-major arrays): a wavefront reads 64
 // consecutive 64-byte state rows (4 KB contiguous) and writes 64 consecutive 704-byte records.
@@ -21,18 +23,23 @@ using namespace ihm2;
 
 namespace {
 
-template <int MODEL>
+// LAG = 1 (IHM2MPC_INTEG_ERK_LAG): the kernel takes the lags' stage factors as one more argument (LF = LagFac); with LAG = 0 the pack is
+// empty and the kernel's arguments are what they were
+__device__ __forceinline__ const double *lag_ptr() { return nullptr; }
+__device__ __forceinline__ const double *lag_ptr(const LagFac &l) { return l.f; }
+
+template <int MODEL, int LAG = 0, typename... LF>
 __global__ __launch_bounds__(64) void k_linearize(
     int B, int N, int M, double dt, int nknots, const double *__restrict__ s_ref,
     const double *__restrict__ kappa_ref, const int32_t *__restrict__ track_id, const double *__restrict__ xs,
-    const double *__restrict__ us, double *__restrict__ lin)
+    const double *__restrict__ us, double *__restrict__ lin, LF... lf)
 {
     const long t = (long)blockIdx.x * 64 + threadIdx.x;
     const int b = (int)(t / N);
     const int k = (int)(t % N);
     if (b >= B) return;
     extern __shared__ double s_lds[];
-    dev_linearize<MODEL>(b, k, N, M, dt, nknots, s_ref, kappa_ref, track_id, xs, us, lin, s_lds + threadIdx.x);      // (unused by fkin6)
+    dev_linearize<MODEL, LAG>(b, k, N, M, dt, nknots, s_ref, kappa_ref, track_id, xs, us, lin, s_lds + threadIdx.x, lag_ptr(lf...));      // (unused by fkin6)
 }
 
 // ---- small batches (the single real-time controller, B = 1): one sensitivity COLUMN per lane ----
@@ -240,26 +247,45 @@ __global__ __launch_bounds__(64) void k_sim_step(int B, int model, int M, double
 }
 
 // the plain kinematic plant (model 0): the integrator of the shooting intervals on (x, u), see dev_sim_step_kin
+template <int LAG = 0, typename... LF>
 __global__ __launch_bounds__(64) void k_sim_step_kin(int B, int M, double dt, int nknots, const double *__restrict__ s_ref,
                                                      const double *__restrict__ kappa_ref, const int32_t *__restrict__ track_id, const double *xs,
-                                                     const double *__restrict__ us, double *xn, const int32_t *__restrict__ active, double *spare_rec)
+                                                     const double *__restrict__ us, double *xn, const int32_t *__restrict__ active, double *spare_rec,
+                                                     LF... lf)
 {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    dev_sim_step_kin(b, M, dt, nknots, s_ref, kappa_ref, track_id, xs, us, xn, active, spare_rec);
+    dev_sim_step_kin<LAG>(b, M, dt, nknots, s_ref, kappa_ref, track_id, xs, us, xn, active, spare_rec, lag_ptr(lf...));
 }
 
 }  // namespace
 
 // the launch record's [15] (ihm2mpc_get_launch_record): low four bits the last linearisation kernel, the next four the last plant kernel
+// (5 / 4: k_linearize / k_sim_step_kin with the closed-form actuator lags, IHM2MPC_INTEG_ERK_LAG)
 static void note_lin(ihm2mpc_handle *h, int code) { h->launch_rec[15] = (h->launch_rec[15] & ~0xF) | code; }
 static void note_sim(ihm2mpc_handle *h, int code) { h->launch_rec[15] = (h->launch_rec[15] & ~0xF0) | (code << 4); }
 
+// The stage factors of both actuator lags for sub-steps of h (include/ihm2mpc.h: ihm2mpc_lag_stage_factors), on the host: no exp on the device
+LagFac ihm2_lag_factors(double h)
+{
+    LagFac l;
+    (void)ihm2mpc_lag_stage_factors(h, k_tT, l.f);
+    (void)ihm2mpc_lag_stage_factors(h, k_tdelta, l.f + 4);
+    return l;
+}
+
 void ihm2_launch_linearize(ihm2mpc_handle *h)
 {
-    if (h->cfg.integrator_type != IHM2MPC_INTEG_ERK) { note_lin(h, 4); ihm2_launch_linearize_irk(h); return; }
+    if (ihm2_is_irk(h->cfg.integrator_type)) { note_lin(h, 4); ihm2_launch_linearize_irk(h); return; }
     const long total = (long)h->B * h->N;
     const int blocks = (int)((total + 63) / 64);
+    if (h->cfg.integrator_type == IHM2MPC_INTEG_ERK_LAG) {
+        // one kernel at every batch size: with sub-steps sized for the car (M = 4) the column-parallel latency path has nothing left to hide
+        note_lin(h, 5);
+        hipLaunchKernelGGL((k_linearize<IHM2MPC_MODEL_FKIN6, 1, LagFac>), dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
+                           h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin, ihm2_lag_factors(h->cfg.dt / h->cfg.M));
+        return;
+    }
     // diagnostic (tools/bench_linearize.py --cols): the column-parallel kernel -- one sensitivity column per wavefront, ten wavefronts
     // per block of 64 intervals -- at any batch size, to measure it against the lane-per-interval kernel
     static const bool force_cols = getenv("IHM2MPC_LINEARIZE_COLS") && getenv("IHM2MPC_LINEARIZE_COLS")[0] == '1';
@@ -280,8 +306,14 @@ void ihm2_launch_linearize(ihm2mpc_handle *h)
 
 void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, hipStream_t stream, const int32_t *active)
 {
-    if (h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK) { note_sim(h, 3); ihm2_launch_sim_irk(h, model, M_sim, x, u, xn, stream, active); return; }
+    if (ihm2_is_irk(h->cfg.sim_integrator_type)) { note_sim(h, 3); ihm2_launch_sim_irk(h, model, M_sim, x, u, xn, stream, active); return; }
     const int blocks = (h->B + 63) / 64;
+    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG) {      // (the callers have refused every plant but model 0)
+        note_sim(h, 4);
+        hipLaunchKernelGGL((k_sim_step_kin<1, LagFac>), dim3(blocks), dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref,
+                           h->track_id, x, u, xn, active, h->lin + (size_t)h->B * h->N * LIN_REC, ihm2_lag_factors(h->cfg.dt / M_sim));
+        return;
+    }
     const bool shared = model == IHM2MPC_MODEL_FKIN6 && (long)h->B * h->N > 128 && h->cfg.integrator_type == IHM2MPC_INTEG_ERK;
     note_sim(h, shared ? 1 : 2);
     // the plain kinematic plant shares the integrator of the shooting intervals (bit-identical to lane N of the persistent loop); for
@@ -289,7 +321,7 @@ void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, c
     // sensitivities would put 0.1 ms on the critical path of ihm2mpc_step: those take the state-only rollout, and so does a handle whose
     // shooting intervals use the collocation integrator (nothing to share: the loop runs the plant as a phase of its own on one lane)
     if (shared)
-        hipLaunchKernelGGL(k_sim_step_kin, dim3(blocks), dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id,
+        hipLaunchKernelGGL(k_sim_step_kin<>, dim3(blocks), dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id,
                            x, u, xn, active, h->lin + (size_t)h->B * h->N * LIN_REC);
     else        // four lanes per instance
         hipLaunchKernelGGL(k_sim_step, dim3((4 * h->B + 63) / 64), dim3(64), 0, stream, h->B, model, M_sim, h->cfg.dt,

@@ -1125,6 +1125,12 @@ __device__ __noinline__ void call_integrate_fkin6(const double *xk, const double
 {
     dev_integrate_sens<IHM2MPC_MODEL_FKIN6>(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, xn_out, nullptr);
 }
+// IRK = 2: the same with the actuator lags in closed form (IHM2MPC_INTEG_ERK_LAG); lagf: the stage factors for this lane's sub-step
+__device__ __noinline__ void call_integrate_fkin6_lag(const double *xk, const double *uk, const double *x_next, int tid, int M, double dt, int nknots,
+                                                      const double *s_ref, const double *kappa_ref, double *rec, double *xn_out, const double *lagf)
+{
+    dev_integrate_sens<IHM2MPC_MODEL_FKIN6, 1>(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, xn_out, nullptr, lagf);
+}
 // The dynamic OCP models (python/models.py:455-606; fdyn6u = the named deviation): dev_integrate_sens with the sub-step's base sensitivities
 // parked in LDS (Sl: the QP's LDS, idle during the linearisation; 55 words per lane) -- the arithmetic of k_linearize_dyn.
 template <int MODEL>
@@ -1182,6 +1188,10 @@ __device__ __noinline__ void call_line_search(const LsArgs &ls, int b, int it, i
 // IRK = 1: the shooting intervals are integrated by the collocation step of kernels_irk.hip (three passes of 16 quads); the kinematic plant
 // stays RK4 x M_sim and takes a phase of its own on lane 0 like the dynamic plants (the state-only rollout: it no longer rides along
 // with the interval lanes).
+// IRK = 2 (RTI, kinematic model): the shooting intervals are integrated by RK4 with the closed-form actuator lags (device_steps.hpp: LAG), M sub-steps
+// sized for the car.  The kinematic plant rides on lane N only when it takes that integrator too (StepArgs.sim_lag, with M_sim sub-steps and its own
+// stage factors); an RK4 x M_sim plant takes a phase of its own as with IRK = 1 -- on lane N its 25 sub-steps would set the length of a
+// linearisation that takes 4.
 // DYN = 1: the shooting intervals carry a dynamic OCP model (StepArgs.ocp_model: fdyn6 or fdyn6u, chosen per launch); a template parameter so
 // that the kinematic kernels stay what they were (the run-time choice alone cost the benchmarked kernel 2 %: 988 k -> 968 k solves/s).
 // SENS = 1 (RTI only, ihm2mpc_run_steps_sens): the x0 sensitivities of every step's solve -- (x, u) copied to StepArgs.sens->xbar / ubar after
@@ -1238,7 +1248,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
         // The kinematic plant (model 0) is one more "interval" of the linearisation -- lane N integrates (x0, u0) with the
         // code of the interval lanes, in lockstep with them -- so it costs no time; the dynamic plants take a phase of their own.
         const bool irk_plant = s.sim_irk_tab != nullptr;
-        const bool kin_plant = !IRK && !irk_plant && s.model == IHM2MPC_MODEL_FKIN6;
+        const bool kin_plant = (IRK == 2 ? s.sim_lag != 0 : !IRK) && !irk_plant && s.model == IHM2MPC_MODEL_FKIN6;
         double *spare = s.lin + (size_t)B * N * LIN_REC;
         if (!kin_plant && act) {
             if (irk_plant) call_sim_irk(s.sim_irk_tab, b, s.model, s.M_sim, s.nknots, s.s_ref, s.kappa_ref, a.track_id, a.u0, s.x0);
@@ -1266,7 +1276,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
                 const int tid = a.track_id[b];
                 const bool with_plant = kin_plant && it == 0 && act;
                 const int om = DYN ? s.ocp_model : IHM2MPC_MODEL_FKIN6;         // wave-uniform
-                if (IRK) {
+                if (IRK == 1) {
                     for (int base = 0; base < N; base += 16) {
                         if constexpr (!DYN) call_linearize_irk<IHM2MPC_MODEL_FKIN6>(s.irk_tab, b, base, N, s.nknots, s.s_ref, s.kappa_ref, tid, a.x, a.u, s.lin);
                         else {
@@ -1281,7 +1291,10 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
                     const double *uk = plant ? a.u0 + (size_t)b * 2 : a.u + ((size_t)b * N + k) * 2;
                     double *rec = plant ? spare + (size_t)b * LIN_REC : s.lin + ((size_t)b * N + k) * LIN_REC;
                     // (the kinematic plant of a dynamic OCP is the fkin6 integrator on its own lane, after the interval lanes)
-                    if (!DYN || plant)
+                    if constexpr (IRK == 2)
+                        call_integrate_fkin6_lag(xk, uk, plant ? xk : xk + 8, tid, plant ? s.M_sim : s.M, s.dt, s.nknots, s.s_ref, s.kappa_ref, rec,
+                                                 plant ? s.x0 + (size_t)b * 8 : nullptr, s.lag[plant ? 1 : 0]);
+                    else if (!DYN || plant)
                         call_integrate_fkin6(xk, uk, plant ? xk : xk + 8, tid, plant ? s.M_sim : s.M, s.dt, s.nknots, s.s_ref, s.kappa_ref, rec,
                                              plant ? s.x0 + (size_t)b * 8 : nullptr);
                     else if constexpr (DYN != 0) {
@@ -1343,13 +1356,13 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 
 }  // namespace
 
-// This file is compiled FIVE times (Makefile): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
+// This file is compiled SEVEN times (Makefile; QP_SET = 5, 6: the loops of IHM2MPC_INTEG_ERK_LAG, below): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
 // soft / track-row instantiations, QP_SET = 2 the persistent loop of the dynamic OCP models (all tables), QP_SET = 3 the persistent loop
 // with x0 sensitivities (SENS = 1) for every RTI loop of the sets 0 and 1 -- same flags, same (default) scheduler -- and QP_SET = 4 the
 // benchmarked pair of set 0 with the straight-line factor sweep (NF).  Separate objects are separate device code images: the benchmarked kernels' image does not move when another set grows.  `make ilp` builds both again under
 // LLVM's iterative ILP scheduler into the test artefact libihm2mpc_ilp.so (tests/test_gpu_configs.py compares the two builds).
 #ifndef QP_SET
-#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities) or -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep)"
+#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities), -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep), -DQP_SET=5 or -DQP_SET=6 (the all-hard RTI loops with the closed-form actuator lags: general form / straight-line factor sweep)"
 #endif
 // The instantiations of this object: its part of the catalogue api.hip selects from, which takes the first entry that holds a table,
 // so that an NSLOT comes before the larger ones of the same kind.  WAVE(NSLOT, NSOFT, PATH, UNI) k_qp_wave, BLOCK(NSLOT, UNI, NW)
@@ -1383,6 +1396,14 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
     STEPS(8, 2, 0, 1, 0, 0) STEPS(8, 2, 0, 1, 1, 0) STEPS(10, 4, 0, 1, 0, 0) STEPS(10, 4, 0, 1, 1, 0)                                     \
     STEPS(8, 0, 1, 1, 0, 0) STEPS(8, 0, 1, 1, 1, 0) STEPS(8, 3, 1, 1, 0, 0) STEPS(8, 3, 1, 1, 1, 0)                                       \
     STEPS(10, 4, 1, 1, 0, 0) STEPS(10, 4, 1, 1, 1, 0)
+#elif QP_SET == 5
+// IRK = 2: the all-hard kinematic RTI loops with the closed-form actuator lags (IHM2MPC_INTEG_ERK_LAG), in objects of their own so that the
+// images of the other sets stay what they were.  SENS = 0 only: ihm2mpc_run_steps_sens launches per step on such a handle.
+#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
+    STEPS(5, 0, 0, 0, 2, 0) STEPS(5, 0, 0, 1, 2, 0) STEPS(8, 0, 0, 0, 2, 0) STEPS(8, 0, 0, 1, 2, 0) STEPS(10, 0, 0, 1, 2, 0)
+#elif QP_SET == 6
+// ... and the benchmarked table's loop with the straight-line factor sweep, as QP_SET = 4 (Makefile: the same flags)
+#define QP_INSTANCES(WAVE, BLOCK, STEPS) STEPS(5, 0, 0, 1, 2, 0)
 #elif QP_SET == 4
 // The reference's OCP (all sides hard, batch-shared weights, RTI, RK4, kinematic model) with the factor sweep in its straight-line form
 // (qp_wave_body: NF): per-step QP and persistent loop, for the horizon 40 as a compile-time constant and for any horizon.  An object of
@@ -1390,7 +1411,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 #define QP_INSTANCES(WAVE, BLOCK, STEPS) WAVE(5, 0, 0, 1) STEPS(5, 0, 0, 1, 0, 0)
 #endif
 
-#if QP_SET == 4
+#if QP_SET == 4 || QP_SET == 6
 #define WAVE(NS, NO, PT, UN)                                                                          \
     {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, 40}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, 40>},     \
     {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, -1}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, -1>},
@@ -1402,6 +1423,8 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 #define BLOCK(NS, UN, NW) {{QP_BLOCK, NS, 0, 0, UN, 0, 0, 0}, 64 * NW, (const void *)k_qp_block<NS, UN, NW>},
 #if QP_SET == 3
 #define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 1>},
+#elif QP_SET == 5
+#define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>},
 #else
 #define STEPS(NS, NO, PT, UN, IR, DY)                                                                  \
     {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>}, \

@@ -25,19 +25,22 @@ _MODEL_IDS = {"fkin6": MODEL_FKIN6, "fdyn6": MODEL_FDYN6, "fdyn6u": MODEL_FDYN6U
 INTEG_RK4 = 0
 INTEG_IRK_GL4 = 1      # IRK, GAUSS_LEGENDRE, 4 stages: acados' default collocation (python/main.py:234-236)
 INTEG_IRK_RADAU4 = 2   # IRK, GAUSS_RADAU_IIA, 4 stages (python/main.py:395-400, python/sim.py:28-33)
+INTEG_ERK_LAG = 3      # RK4 on the six vehicle states, the two actuator lags in closed form (include/ihm2mpc.h: IHM2MPC_INTEG_ERK_LAG); not in acados
 
 
 def integrator_code(integrator_type: str, collocation_type: str = "GAUSS_LEGENDRE") -> int:
     """``AcadosOcpOptions.integrator_type`` / ``AcadosSimOpts.integrator_type`` + ``collocation_type`` -> ``IHM2MPC_INTEG_*``."""
     if integrator_type == "ERK":
         return INTEG_RK4
+    if integrator_type == "ERK_LAG":
+        return INTEG_ERK_LAG
     if integrator_type == "IRK":
         if collocation_type == "GAUSS_LEGENDRE":
             return INTEG_IRK_GL4
         if collocation_type == "GAUSS_RADAU_IIA":
             return INTEG_IRK_RADAU4
         raise ValueError(f"collocation_type {collocation_type!r}: GAUSS_LEGENDRE or GAUSS_RADAU_IIA")
-    raise ValueError(f"integrator_type {integrator_type!r}: ERK or IRK")
+    raise ValueError(f"integrator_type {integrator_type!r}: ERK, IRK or ERK_LAG")
 
 
 @dataclass
@@ -196,8 +199,10 @@ class AcadosOcpOptions:
     hpipm_mode: str = "SPEED_ABS"
     integrator_type: str = "ERK"                  # "ERK": RK4 x sim_method_num_steps (old/generate.py:23-25); "IRK": 4-stage collocation, one step
                                                   # per interval, 3 Newton iterations (python/main.py:234-236)
+                                                  # "ERK_LAG" (fkin6, SQP_RTI): RK4 x sim_method_num_steps with the actuator lags in closed form,
+                                                  # stable for any number of sub-steps (4 are sized for the car)
     collocation_type: str = "GAUSS_LEGENDRE"      # IRK only (acados' default); or "GAUSS_RADAU_IIA"
-    sim_integrator_type: str = "ERK"              # integrator of the plant steps behind this solver (python/main.py:395-400: "IRK")
+    sim_integrator_type: str = "ERK"              # integrator of the plant steps behind this solver (python/main.py:395-400: "IRK"; "ERK_LAG": model 0 only)
     sim_collocation_type: str = "GAUSS_RADAU_IIA"
     sim_method_num_stages: int = 4
     sim_method_num_steps: int = 25                # M; 1 is unstable on this model
@@ -358,7 +363,7 @@ class OcpData:
         sim_integ = integrator_code(o.sim_integrator_type, o.sim_collocation_type)
         if o.sim_method_num_stages != 4:
             raise ValueError("4 stages: the classical RK4 (ERK) or 4-stage collocation (IRK), python/main.py:235")
-        if integ != INTEG_RK4 and o.sim_method_num_steps != 1:
+        if integ in (INTEG_IRK_GL4, INTEG_IRK_RADAU4) and o.sim_method_num_steps != 1:
             raise ValueError("IRK takes one step per shooting interval (sim_method_num_steps = 1, python/main.py:236)")
         if o.nlp_solver_type not in ("SQP_RTI", "SQP"):
             raise ValueError(f"nlp_solver_type {o.nlp_solver_type!r}")

@@ -47,8 +47,10 @@ class AcadosSimSolver:
         o = sim.solver_options
         if o.num_stages != 4:
             raise ValueError("4 stages: the classical RK4 (ERK) or 4-stage collocation (IRK), python/main.py:397")
-        if o.integrator_type not in ("ERK", "IRK"):
+        if o.integrator_type not in ("ERK", "IRK", "ERK_LAG"):
             raise ValueError(f"integrator_type {o.integrator_type!r}")
+        if o.integrator_type == "ERK_LAG" and sim.model.kind != "fkin6":
+            raise ValueError(f"integrator_type 'ERK_LAG' (closed-form actuator lags) integrates the fkin6 sim model only, not {sim.model.kind!r}")
         self.sim, self.B, self.device = sim, int(batch_size), int(device)
         self.model_id = sim.model.model_id
         if o.integrator_type == "IRK" and o.newton_iter != 3 and sim.model.kind != "fdyn10":

@@ -421,8 +421,8 @@ class BatchedOcpSolver:
         (slots per thread, UNI, wavefronts); ``steps``: the last ``run_steps``, ``"k_steps<...>"`` (NSLOT, NSOFT, PATH, UNI, SQP, IRK,
         DYN, and an eighth 1 for the loop with x0 sensitivities) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` /
         ``"not_resident"``; ``linearize`` / ``sim``: the kernel of the last linearisation / plant launch outside ``k_steps``
-        (``"k_linearize"``, ``"k_linearize_dyn"``, ``"k_linearize_cols"``, ``"k_linearize_irk"``; ``"k_sim_step_kin"``, ``"k_sim_step"``,
-        ``"k_sim_irk"``); ``qp_form`` / ``steps_form``: the form of the factor sweep in those two launches, ``"general"``,
+        (``"k_linearize"``, ``"k_linearize_dyn"``, ``"k_linearize_cols"``, ``"k_linearize_irk"``, ``"k_linearize_lag"``; ``"k_sim_step_kin"``,
+        ``"k_sim_step"``, ``"k_sim_irk"``, ``"k_sim_step_kin_lag"``; ``_lag``: the integrator ``"ERK_LAG"``); ``qp_form`` / ``steps_form``: the form of the factor sweep in those two launches, ``"general"``,
         ``"plain"`` (straight-line stage, run-time horizon) or ``"plain_n40"`` (the horizon 40 compiled in) -- same results, so the
         kernel names above do not tell them apart.  ``None`` where nothing was launched yet."""
         rec = np.zeros(16, dtype=np.int32)
@@ -438,8 +438,8 @@ class BatchedOcpSolver:
             steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13]) if r[14] == 0 else "k_steps<%d,%d,%d,%d,%d,%d,%d,1>" % tuple(r[6:13])
         elif r[5] == 2:
             steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
-        lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk")[r[15] & 15]
-        sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk")[(r[15] >> 4) & 15]
+        lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk", "k_linearize_lag")[r[15] & 15]
+        sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk", "k_sim_step_kin_lag")[(r[15] >> 4) & 15]
         forms = ("general", "plain", "plain_n40", None)
         return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim,
                 "qp_form": forms[(r[15] >> 8) & 3] if qp else None, "steps_form": forms[(r[15] >> 12) & 3] if r[5] == 1 else None}

@@ -93,6 +93,23 @@ extern "C" {
 #define IHM2MPC_INTEG_ERK 0
 #define IHM2MPC_INTEG_IRK_GL4 1
 #define IHM2MPC_INTEG_IRK_RADAU4 2
+/* ERK_LAG: classical RK4 x M on the six vehicle states with the two actuator lags (T' = (u_T - T) / t_T, t_T = 1 ms; delta' likewise,
+ * t_delta = 20 ms) taken in closed form -- a named deviation from acados' ERK.  RK4 needs 25 sub-steps per 50 ms
+ * interval only to stay stable on the torque lag; the lags are linear and autonomous on a constant input, so one sub-step h = dt / M from
+ * (v, a) = (x[0:6], x[6:8]) under u is
+ *   a+ = u + (a - u) e,  e_i = exp(-h / t_i)                                   (exact)
+ *   v+ = RK4 on f[0:6], stage j (c = 0, 1/2, 1/2, 1) evaluated at X = (v + c h K_prev[0:6], u + (a - u) E_s(j)),  s = (0, 1, 1, 2)
+ * where the stage factors E_0, E_1, E_2 of a lag make Simpson's rule exact for the first three moments of its transient,
+ * int_0^h t^j exp(-t / t_i) dt, j = 0, 1, 2 (ihm2mpc_lag_stage_factors; sampling the closed form at the stage times instead leaves Simpson
+ * with h / 6 of a transient whose integral is t_T).  The record [A | B | b] is the exact derivative of this map, with the zero pattern of
+ * RK4's.  Any M >= 1 is stable.  For the OCP: IHM2MPC_MODEL_FKIN6 with IHM2MPC_SQP_RTI; for the plants: model 0.
+ * Error of one 50 ms interval against Radau at rtol 1e-13 (max over states of |err| / (1 + |ref|), 60 random states on fsds_competition_1):
+ *                                                  rate-feasible inputs   random inputs
+ *   RK4 x 25 (ERK, M = 25)                               4.0e-8              3.2e-6
+ *   closed-form lags sampled at the stage times, M = 4   3.4e-5              5.4e-3
+ *   ERK_LAG, M = 4                                       2.2e-6              2.4e-5
+ *   ERK_LAG, M = 8                                       1.6e-6              1.8e-6 */
+#define IHM2MPC_INTEG_ERK_LAG 3
 #define IHM2MPC_IRK_NEWTON_ITER 3
 
 typedef struct ihm2mpc_handle ihm2mpc_handle;
@@ -101,7 +118,7 @@ typedef struct ihm2mpc_config {
     int32_t batch;          /* B: independent MPC instances on this device */
     int32_t N;              /* shooting intervals (python/main.py:183: Nf = 40) */
     int32_t M;              /* integrator steps per interval (sim_method_num_steps): RK4 sub-steps, >= 18 at dt = 0.05 for stability (ERK);
-                             * 1 for IRK (python/main.py:236) */
+                             * 1 for IRK (python/main.py:236); any number for ERK_LAG (4 gives sub-steps sized for the car) */
     int32_t model;          /* IHM2MPC_MODEL_* of the OCP */
     int32_t ntracks;        /* number of track tables */
     int32_t nknots;         /* knots per table (python/motion_planning.py:25,402-428: 3*500) */
@@ -121,6 +138,11 @@ typedef struct ihm2mpc_config {
 
 const char *ihm2mpc_last_error(void);
 const char *ihm2mpc_version(void);
+/* Host only (no device is touched): the stage factors of IHM2MPC_INTEG_ERK_LAG for a lag with time constant tau and sub-steps of h,
+ * out4 = (E_0, E_1, E_2, e).  With r = h / tau, e = exp(-r), m0 = tau (1 - e), m1 = tau^2 (1 - e (1 + r)), m2 = 2 tau^3 (1 - e (1 + r + r^2 / 2)):
+ * E_1 = 6 (m1 / h^2 - m2 / h^3), E_2 = 12 m2 / h^3 - 6 m1 / h^2, E_0 = 6 m0 / h - 4 E_1 - E_2 -- evaluated with expm1 and, for r < 1, the
+ * series of the 1 - e (...) terms.  h = 12.5 ms, tau = 1 ms: (0.37708781, 0.03225617, -0.02611426).  Non-zero: h or tau not positive and finite. */
+int ihm2mpc_lag_stage_factors(double h, double tau, double *out4);
 
 int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out);
 int ihm2mpc_free(ihm2mpc_handle *h);
@@ -261,12 +283,13 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *   [0] last per-step QP launch: 0 none yet, 1 k_qp_wave, 2 k_qp_block;  [1..4] its NSLOT, NSOFT, PATH, UNI
  *       (k_qp_block: NSLOT = slots per thread of its 256-lane table, NSOFT = PATH = 0)
  *   [5] last ihm2mpc_run_steps: 0 none yet, 1 one k_steps launch, 2 launches per step (ihm2mpc_step n_steps times);
- *       [6..12] the k_steps parameters NSLOT, NSOFT, PATH, UNI, SQP, IRK, DYN (0 when [5] != 1);
+ *       [6..12] the k_steps parameters NSLOT, NSOFT, PATH, UNI, SQP, IRK, DYN (0 when [5] != 1; IRK: 0 RK4, 1 collocation, 2 ERK_LAG);
  *       [13] why it went per step: 0 it did not, 1 the configuration has no k_steps instantiation, 2 the batch exceeds the resident limit
  *       [14] SENS: 1 the k_steps launch computed x0 sensitivities (ihm2mpc_run_steps_sens), 0 otherwise (0 when [5] != 1)
  *   [15] bits 0..3 the last linearisation launch (ihm2mpc_linearize, a solve, ihm2mpc_step): 0 none yet, 1 k_linearize, 2 k_linearize_dyn,
- *       3 k_linearize_cols, 4 k_linearize_irk;  bits 4..7 the last plant launch (ihm2mpc_sim_step, ihm2mpc_sim_advance, ihm2mpc_step):
- *       0 none yet, 1 k_sim_step_kin, 2 k_sim_step, 3 k_sim_irk.  Launches inside k_steps are not recorded here.
+ *       3 k_linearize_cols, 4 k_linearize_irk, 5 k_linearize with the closed-form lags (ERK_LAG);  bits 4..7 the last plant launch
+ *       (ihm2mpc_sim_step, ihm2mpc_sim_advance, ihm2mpc_step): 0 none yet, 1 k_sim_step_kin, 2 k_sim_step, 3 k_sim_irk, 4 k_sim_step_kin with
+ *       the closed-form lags (ERK_LAG).  Launches inside k_steps are not recorded here.
  *       bits 8..9 the form of the factor sweep in the QP of [0], bits 12..13 in the k_steps launch of [5] (0 when [5] != 1): 0 the general
  *       form, 1 the straight-line stage with the run-time horizon, 2 the straight-line stage with the horizon compiled in (N = 40).  The
  *       forms give the same bits; a table without active rows and the model IHM2MPC_MODEL_FDYN6 take the general form, and so does every
