@@ -504,9 +504,21 @@ ihm2mpc_handle::~ihm2mpc_handle()
 
 // classical RK4 is stable for |z| < 2.785 on the negative real axis: z = -(dt / M) / t for the first-order actuator lags
 static bool rk4_unstable(double dt, int M) { return dt / M / 1e-3 >= 2.78; }
-// sim_integrator_type ERK_LAG integrates the plain kinematic plant only
-static int lag_plant_refused(const ihm2mpc_handle *h, int model)
+// the sub-steps of a plant step: at least one, and with the RK4 plant integrator few enough per step to be stable on `lags` (the message's words)
+static int check_sim_substeps(const ihm2mpc_handle *h, int M_sim, const char *lags)
 {
+    if (M_sim < 1) return fail("M_sim must be >= 1");
+    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim))
+        return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the %s: use M_sim >= %d", M_sim, h->cfg.dt, lags,
+                    (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
+    return 0;
+}
+// the plant arguments of ihm2mpc_sim_step, _sim_advance, _step and the step loops: sub-steps, plant model -2 .. 2, and
+// sim_integrator_type ERK_LAG integrates the plain kinematic plant only
+static int check_plant(const ihm2mpc_handle *h, int model, int M_sim)
+{
+    if (check_sim_substeps(h, M_sim, "actuator lags")) return -1;
+    if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
     if (h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK_LAG || model == IHM2MPC_MODEL_FKIN6) return 0;
     return fail("the plant integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic plant (model 0) only, not for plant "
                 "model %d: create the handle with another sim_integrator_type", model);
@@ -1513,10 +1525,7 @@ int ihm2mpc_sim_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const doub
     CHECK_H(h);
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
     if (!x || !u || !x_next) return fail("null argument");
-    if (M_sim < 1) return fail("M_sim must be >= 1");
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
-    if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
-    if (lag_plant_refused(h, model)) return -1;
+    if (check_plant(h, model, M_sim)) return -1;
     double *xs = h->scratch, *us = h->scratch + (size_t)h->B * 8, *xn = h->scratch + (size_t)h->B * 16;
     if (upload(h, x, xs, NX) || upload(h, u, us, NU)) return -1;
     ihm2_launch_sim(h, model, M_sim, xs, us, xn, h->stream, nullptr);
@@ -1528,10 +1537,7 @@ int ihm2mpc_sim_advance(ihm2mpc_handle *h, int32_t model, int32_t M_sim)
 {
     CHECK_H(h);
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
-    if (M_sim < 1) return fail("M_sim must be >= 1");
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
-    if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
-    if (lag_plant_refused(h, model)) return -1;
+    if (check_plant(h, model, M_sim)) return -1;
     ihm2_launch_sim(h, model, M_sim, h->x0, h->u0, h->x0, h->stream, h->active_set ? h->active.get() : nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1599,10 +1605,7 @@ int ihm2mpc_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_targe
 {
     CHECK_H(h);
     if (ready(h)) return -1;
-    if (M_sim < 1) return fail("M_sim must be >= 1");
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
-    if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
-    if (lag_plant_refused(h, model)) return -1;
+    if (check_plant(h, model, M_sim)) return -1;
     // The plant step and the reference ramp only feed the QP (through x0 and yref); the warm-start shift and the
     // linearisation only need the previous iterate.  Two branches, joined in front of the QP kernel.
     if (h->lap_wrap) ihm2_launch_wrap_lap(h);
@@ -1656,10 +1659,7 @@ static int run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_t
                      double *u0_hist, double *x0_hist, int32_t *status_hist, int32_t *qp_iter_hist, bool sens, double *sens_u0_hist)
 {
     if (ready(h)) return -1;
-    if (M_sim < 1) return fail("M_sim must be >= 1");
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the actuator lags: use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
-    if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
-    if (lag_plant_refused(h, model)) return -1;
+    if (check_plant(h, model, M_sim)) return -1;
     if (n_steps < 1) return fail("n_steps must be >= 1");
     const size_t B = h->B, n = n_steps;
     if (ihm2mpc_reserve_history(h, n_steps)) return -1;
@@ -1766,12 +1766,11 @@ int ihm2mpc_sim_step_dyn10(ihm2mpc_handle *h, int32_t M_sim, const double *x, co
     CHECK_H(h);
     if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
     if (!x || !u || !x_next) return fail("null argument");
-    if (M_sim < 1) return fail("M_sim must be >= 1");
+    if (check_sim_substeps(h, M_sim, "torque lags (t_T = 1e-3 s)")) return -1;
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG)
         return fail("the plant integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic plant (model 0) only, not for the "
                     "fdyn10 plant: create the handle with another sim_integrator_type");
     const bool irk = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;
-    if (!irk && rk4_unstable(h->cfg.dt, M_sim)) return fail("RK4 with M_sim = %d sub-steps of dt = %g is unstable on the torque lags (t_T = 1e-3 s): use M_sim >= %d", M_sim, h->cfg.dt, (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     if (!h->dyn10) HIP_TRY(h->dyn10.alloc((size_t)h->B * 35));
     double *xs = h->dyn10, *us = h->dyn10 + (size_t)h->B * 15, *xn = h->dyn10 + (size_t)h->B * 20;
     if (upload(h, x, xs, 15) || upload(h, u, us, 5)) return -1;

@@ -4,12 +4,18 @@
 //
 //  * dev_prepare / dev_wrap_lap: reference ramp + warm-start shift of IHM2Controller.compute_control (python/main.py:303-322)
 //    and the lap wrap; one wavefront per instance.
-//  * dev_linearize: RK4 x M with forward sensitivities of one shooting interval (HOT LOOP 1); one lane per (instance, interval).
-//  * dev_sim_step: the plant step (python/main.py:476-502); one lane per instance.
+//  * dev_integrate_sens_fkin6 / _fkin6_lag / _dyn: RK4 x M with forward sensitivities of one shooting interval (HOT LOOP 1), one lane per
+//    (instance, interval) -- three functions by what they integrate: fkin6 column-major, fkin6 with the actuator lags in closed form, the
+//    dynamic models stage-major with S in LDS.  dev_linearize: the fkin6 pair on interval k of instance b.
+//  * dev_sim_step: the plant step (python/main.py:476-502); four lanes per instance.  dev_sim_step_kin: the plain kinematic plant, which is
+//    the fkin6 integrator on (x0, u0).
+// The tableau is rk4.hpp's.  The stage loops of this file stay written out, the state-only ones too (dev_sim_step, the state stages of the
+// fkin6 integrators): through a shared step function their listings move, and with call_sim_step's every k_steps that calls it (NOTES.md, R8).
 #pragma once
 
 #include "ihm2mpc_internal.h"
 #include "model.hpp"
+#include "rk4.hpp"
 
 namespace ihm2 {
 
@@ -136,186 +142,214 @@ __device__ __forceinline__ void sens_col_stage_lag(const double (&J)[8][10], con
 
 #define FOR_ALL_COLS(OP) OP(0) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7) OP(8) OP(9)
 
-// one lane: interval k of instance b.  Sl: this lane's column of the LDS copy of S (dynamic models), nullptr for fkin6
-// LAG = 1 (fkin6 only): IHM2MPC_INTEG_ERK_LAG -- the two actuator lags in closed form, classical RK4 on the six vehicle states with the
-// lags' moment-fitted stage values (include/ihm2mpc.h); lagf: {E_0, E_1, E_2, e} of the torque lag, then of the steering lag, for h = dt / M
-template <int MODEL, int LAG = 0>
-// xk (8), uk (2): where to integrate from; x_next (8): the state the defect b is taken against; rec: the 88-double record
-// [A | B | b] written at the end; xn_out (8) or nullptr: Phi(x_k, u_k) itself (the kinematic PLANT is this very function on
-// (x0, u0): it then runs in lockstep with the interval lanes of the same wavefront, see k_steps)
-__device__ __forceinline__ void dev_integrate_sens(
-    const double *xk, const double *__restrict__ uk, const double *x_next, int tid, int M, double dt, int nknots, const double *__restrict__ s_ref,
-    const double *__restrict__ kappa_ref, double *__restrict__ rec, double *xn_out, double *__restrict__ Sl, const double *lagf = nullptr)
-{
-    static_assert(LAG == 0 || MODEL == IHM2MPC_MODEL_FKIN6, "the closed-form lags are implemented for the kinematic model");
-    double x[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) x[i] = xk[i];
-    const double u_T = uk[0];
-    const double u_d = uk[1];
-    TrackSeg trk;
-    trk.init(s_ref + (size_t)tid * nknots, kappa_ref + (size_t)tid * nknots, nknots, x[0]);
+// ---- the three sensitivity integrators: fkin6, fkin6 with closed-form lags, the dynamic models ----
+// Arguments of all three: xk (8), uk (2): where to integrate from; tid: the instance's track; x_next (8): the state the defect b is taken
+// against; rec: the 88-double record written at the end; xn_out (8) or nullptr (fkin6): Phi(x_k, u_k) itself.
+// They share the column stages above and, as text, their first and last lines (so do k_linearize_dyn and the column kernel of
+// kernels_linearize.hip).  Macros, not functions: with x, trk and S handed to a helper by reference the loop head's values come in another
+// order and the registers move (k_linearize: 2408 instead of 2402 instructions), with a shared record the exit block of k_sim_step_kin
+// moves in front of its loop -- and these listings are held fixed (profiles/r7/listing_compare.txt).
+// SENS_LOAD_STATE declares x[8], u_T, u_d and the track segment trk (from the caller's s_ref, kappa_ref, nknots); SENS_WRITE_RECORD writes
+// [A (8x8 row-major) | B (8x2) | b = Phi(x_k,u_k) - x_{k+1}] from S ([column][row], mask row MDL) and the caller's x
+#define SENS_LOAD_STATE(xk, uk, tid)                                                                                     \
+    double x[8];                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < 8; i++) x[i] = (xk)[i];                                                        \
+    const double u_T = (uk)[0];                                                                                          \
+    const double u_d = (uk)[1];                                                                                          \
+    TrackSeg trk;                                                                                                        \
+    trk.init(s_ref + (size_t)(tid) * nknots, kappa_ref + (size_t)(tid) * nknots, nknots, x[0]);
+#define SENS_WRITE_RECORD(rec, S, MDL, x_next)                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < 8; i++) {                                                                                     \
+        _Pragma("unroll") for (int j = 0; j < 8; j++) (rec)[i * 8 + j] = ((S_COL_MASK[MDL][j] >> i) & 1u) ? S[j][i] : 0.0;              \
+        _Pragma("unroll") for (int j = 0; j < 2; j++) (rec)[64 + i * 2 + j] = ((S_COL_MASK[MDL][8 + j] >> i) & 1u) ? S[8 + j][i] : 0.0; \
+        (rec)[80 + i] = x[i] - (x_next)[i];                                                                                             \
+    }
 
-    // S, Sacc, dK: [column][row]; only rows in S_COL_MASK[column] are ever touched
-    constexpr bool S_IN_LDS = MODEL != IHM2MPC_MODEL_FKIN6;
-    double S[10][8], Sacc[10][8], dK[10][8];
+// fkin6, one lane: interval k of instance b.  The kinematic PLANT is this very function on (x0, u0) with xn_out: it then runs in lockstep with
+// the interval lanes of the same wavefront, see k_steps.
+// Per sub-step FIRST the four stage evaluations of the state (the stage points depend on the state only), their
+// Jacobians kept; THEN every sensitivity column through its four stages with the column's entries in registers throughout.
+// Stage-major order (all columns per stage) moved S, Sacc and dK -- 156 values that do not fit the 256 vector registers
+// next to the model evaluation -- between the accumulator file and the vector registers once per STAGE: 507 of the 1617
+// instructions of a stage were v_accvgpr moves; column-major order touches S once per SUB-STEP.  Same arithmetic per
+// column, bit-identical results.
+__device__ __forceinline__ void dev_integrate_sens_fkin6(
+    const double *xk, const double *__restrict__ uk, const double *x_next, int tid, int M, double dt, int nknots, const double *__restrict__ s_ref,
+    const double *__restrict__ kappa_ref, double *__restrict__ rec, double *xn_out)
+{
+    constexpr int MODEL = IHM2MPC_MODEL_FKIN6;
+    SENS_LOAD_STATE(xk, uk, tid)
+    double S[10][8];      // [column][row]; only the rows in S_COL_MASK[column] are ever touched
 #pragma unroll
     for (int c = 0; c < 10; c++)
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            S[c][i] = (c == i) ? 1.0 : 0.0; dK[c][i] = 0.0;
-            if (S_IN_LDS) {
-                Sacc[c][i] = S[c][i];
-                if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = S[c][i];
-            }
-        }
-
+        for (int i = 0; i < 8; i++) S[c][i] = (c == i) ? 1.0 : 0.0;
     const double h = dt / M;
-    if constexpr (LAG != 0) {
-        // the order of the fkin6 loop below: the four stage evaluations of the state first, then every sensitivity column through its stages
-        double ET[4], ED[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) { ET[i] = lagf[i]; ED[i] = lagf[4 + i]; }
-        for (int m = 0; m < M; m++) {
-            double xacc[8], K[8], J4[4][8][10];
-#pragma unroll
-            for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
-            const double dT = x[6] - u_T, dD = x[7] - u_d;
-#pragma unroll
-            for (int st = 0; st < 4; st++) {
-                const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-                const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
-                const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);
-                double X[8];
-#pragma unroll
-                for (int i = 0; i < 6; i++) X[i] = fma(ah, K[i], x[i]);
-                X[6] = fma(dT, ET[sf], u_T);
-                X[7] = fma(dD, ED[sf], u_d);
-                fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
-#pragma unroll
-                for (int i = 0; i < 6; i++) xacc[i] = fma(wh, K[i], xacc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < 6; i++) x[i] = xacc[i];
-            x[6] = fma(dT, ET[3], u_T);
-            x[7] = fma(dD, ED[3], u_d);
-#define SUBSTEP_COL_LAG(c)                                                                                               \
-            {                                                                                                            \
-                constexpr unsigned cm = S_COL_MASK[0][c];                                                                \
-                double Sa[8], dKc[8];                                                                                    \
-                _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                          \
-                _Pragma("unroll") for (int st = 0; st < 4; st++) {                                                       \
-                    const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);                                       \
-                    const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);                          \
-                    const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);                                                  \
-                    sens_col_stage_lag<c>(J4[st], S[c], Sa, dKc, ah, wh, ET[sf], ED[sf]);                                \
-                }                                                                                                        \
-                _Pragma("unroll") for (int i = 0; i < 6; i++)                                                            \
-                    if ((cm >> i) & 1u) S[c][i] = Sa[i];                                                                 \
-                if ((cm >> 6) & 1u) S[c][6] = (c == 8) ? fma(ET[3], S[c][6], 1.0 - ET[3]) : ET[3] * S[c][6];              \
-                if ((cm >> 7) & 1u) S[c][7] = (c == 9) ? fma(ED[3], S[c][7], 1.0 - ED[3]) : ED[3] * S[c][7];              \
-            }
-            FOR_ALL_COLS(SUBSTEP_COL_LAG)
-#undef SUBSTEP_COL_LAG
-        }
-    } else
-    if (!S_IN_LDS) {
-        // fkin6: per sub-step FIRST the four stage evaluations of the state (the stage points depend on the state only), their
-        // Jacobians kept; THEN every sensitivity column through its four stages with the column's entries in registers throughout.
-        // Stage-major order (all columns per stage) moved S, Sacc and dK -- 156 values that do not fit the 256 vector registers
-        // next to the model evaluation -- between the accumulator file and the vector registers once per STAGE: 507 of the 1617
-        // instructions of a stage were v_accvgpr moves; column-major order touches S once per SUB-STEP.  Same arithmetic per
-        // column, bit-identical results.
-        for (int m = 0; m < M; m++) {
-            double xacc[8], K[8], J4[4][8][10];
-#pragma unroll
-            for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
-#pragma unroll
-            for (int st = 0; st < 4; st++) {
-                const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-                const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
-                double X[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-                fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
-#pragma unroll
-                for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) x[i] = xacc[i];
-#define SUBSTEP_COL(c)                                                                                                   \
-            {                                                                                                            \
-                double Sa[8], dKc[8];                                                                                    \
-                _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                          \
-                _Pragma("unroll") for (int st = 0; st < 4; st++) {                                                       \
-                    const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);                                       \
-                    const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);                          \
-                    sens_col_stage<MODEL, c>(J4[st], S[c], nullptr, Sa, dKc, ah, wh);                                    \
-                }                                                                                                        \
-                sens_col_copy<MODEL, c>(Sa, S[c]);                                                                       \
-            }
-            FOR_ALL_COLS(SUBSTEP_COL)
-#undef SUBSTEP_COL
-        }
-    } else
     for (int m = 0; m < M; m++) {
+        double J4[4][8][10];
         double xacc[8], K[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
-#define COPY_S_TO_ACC(c) sens_col_copy<MODEL, c>(S[c], Sacc[c]);
-        if (!S_IN_LDS) { FOR_ALL_COLS(COPY_S_TO_ACC) }      // with S in LDS, Sacc already holds S from the previous sub-step
-#pragma unroll 1
+#pragma unroll
         for (int st = 0; st < 4; st++) {
-            const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-            const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
-            double X[8], J[8][10];
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
+            double X[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-            if (MODEL == IHM2MPC_MODEL_FKIN6) fkin6_eval<true>(X, u_T, u_d, trk, K, J);
-            else fdyn6_eval<true, MODEL == IHM2MPC_MODEL_FDYN6U>(X, u_T, u_d, trk, K, J);
+            fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
 #pragma unroll
             for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
-#define STAGE_COL(c) sens_col_stage<MODEL, c>(J, S[c], S_IN_LDS ? Sl : nullptr, Sacc[c], dK[c], ah, wh);
-            FOR_ALL_COLS(STAGE_COL)
         }
 #pragma unroll
         for (int i = 0; i < 8; i++) x[i] = xacc[i];
-#define COPY_ACC_TO_S(c) sens_col_copy<MODEL, c>(Sacc[c], S[c]);
-        if (!S_IN_LDS) { FOR_ALL_COLS(COPY_ACC_TO_S) }
-        else {
-#pragma unroll
-            for (int c = 0; c < 10; c++)
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = Sacc[c][i];
+#define SUBSTEP_COL(c)                                                                                                   \
+        {                                                                                                                \
+            double Sa[8], dKc[8];                                                                                        \
+            _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                              \
+            _Pragma("unroll") for (int st = 0; st < 4; st++)                                                             \
+                sens_col_stage<MODEL, c>(J4[st], S[c], nullptr, Sa, dKc, rk4_a(st, h), rk4_w(st, h));                    \
+            sens_col_copy<MODEL, c>(Sa, S[c]);                                                                           \
         }
+        FOR_ALL_COLS(SUBSTEP_COL)
+#undef SUBSTEP_COL
     }
-
-    // output record [A (8x8 row-major) | B (8x2) | b = Phi(x_k,u_k) - x_{k+1}]
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) rec[i * 8 + j] = ((S_COL_MASK[MODEL ? 1 : 0][j] >> i) & 1u) ? (S_IN_LDS ? Sacc[j][i] : S[j][i]) : 0.0;
-#pragma unroll
-        for (int j = 0; j < 2; j++) rec[64 + i * 2 + j] = ((S_COL_MASK[MODEL ? 1 : 0][8 + j] >> i) & 1u) ? (S_IN_LDS ? Sacc[8 + j][i] : S[8 + j][i]) : 0.0;
-        rec[80 + i] = x[i] - x_next[i];
-    }
+    SENS_WRITE_RECORD(rec, S, 0, x_next)
     if (xn_out) {
 #pragma unroll
         for (int i = 0; i < 8; i++) xn_out[i] = x[i];
     }
 }
 
-// one lane: interval k of instance b
-template <int MODEL, int LAG = 0>
+// fkin6 with IHM2MPC_INTEG_ERK_LAG: the two actuator lags in closed form, classical RK4 on the six vehicle states with the lags' moment-fitted
+// stage values (include/ihm2mpc.h); lagf: {E_0, E_1, E_2, e} of the torque lag, then of the steering lag, for h = dt / M.  The order of
+// dev_integrate_sens_fkin6: the four stage evaluations of the state first, then every sensitivity column through its stages
+__device__ __forceinline__ void dev_integrate_sens_fkin6_lag(
+    const double *xk, const double *__restrict__ uk, const double *x_next, int tid, int M, double dt, int nknots, const double *__restrict__ s_ref,
+    const double *__restrict__ kappa_ref, double *__restrict__ rec, double *xn_out, const double *lagf)
+{
+    SENS_LOAD_STATE(xk, uk, tid)
+    double S[10][8];      // [column][row]; only the rows in S_COL_MASK[column] are ever touched
+#pragma unroll
+    for (int c = 0; c < 10; c++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) S[c][i] = (c == i) ? 1.0 : 0.0;
+    const double h = dt / M;
+    double ET[4], ED[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { ET[i] = lagf[i]; ED[i] = lagf[4 + i]; }
+    for (int m = 0; m < M; m++) {
+        double J4[4][8][10];
+        const double dT = x[6] - u_T, dD = x[7] - u_d;
+        double xacc[8], K[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
+#pragma unroll
+        for (int st = 0; st < 4; st++) {
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
+            const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);
+            double X[8];
+#pragma unroll
+            for (int i = 0; i < 6; i++) X[i] = fma(ah, K[i], x[i]);
+            X[6] = fma(dT, ET[sf], u_T);
+            X[7] = fma(dD, ED[sf], u_d);
+            fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
+#pragma unroll
+            for (int i = 0; i < 6; i++) xacc[i] = fma(wh, K[i], xacc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) x[i] = xacc[i];
+        x[6] = fma(dT, ET[3], u_T);
+        x[7] = fma(dD, ED[3], u_d);
+#define SUBSTEP_COL_LAG(c)                                                                                               \
+        {                                                                                                                \
+            constexpr unsigned cm = S_COL_MASK[0][c];                                                                    \
+            double Sa[8], dKc[8];                                                                                        \
+            _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                              \
+            _Pragma("unroll") for (int st = 0; st < 4; st++) {                                                           \
+                const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);                                                      \
+                sens_col_stage_lag<c>(J4[st], S[c], Sa, dKc, rk4_a(st, h), rk4_w(st, h), ET[sf], ED[sf]);                \
+            }                                                                                                            \
+            _Pragma("unroll") for (int i = 0; i < 6; i++)                                                                \
+                if ((cm >> i) & 1u) S[c][i] = Sa[i];                                                                     \
+            if ((cm >> 6) & 1u) S[c][6] = (c == 8) ? fma(ET[3], S[c][6], 1.0 - ET[3]) : ET[3] * S[c][6];                  \
+            if ((cm >> 7) & 1u) S[c][7] = (c == 9) ? fma(ED[3], S[c][7], 1.0 - ED[3]) : ED[3] * S[c][7];                  \
+        }
+        FOR_ALL_COLS(SUBSTEP_COL_LAG)
+#undef SUBSTEP_COL_LAG
+    }
+    SENS_WRITE_RECORD(rec, S, 0, x_next)
+    if (xn_out) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) xn_out[i] = x[i];
+    }
+}
+
+// The dynamic models (fdyn6, fdyn6u), one lane: interval k of instance b -- the integrator of the persistent loop (kernels_qp.hip:
+// call_integrate_dyn).  Stage-major: the model and its Jacobian are evaluated once per stage and every column goes through that stage.
+// The sub-step's base sensitivities live in LDS (Sl: this lane's column of the copy, see sens_col_stage) and the running sums Sacc in registers;
+// at the end of a sub-step Sacc is the new base.  k_linearize_dyn (kernels_linearize.hip) is a second text of this function, see there.
+template <int MODEL>
+__device__ __forceinline__ void dev_integrate_sens_dyn(
+    const double *xk, const double *__restrict__ uk, const double *x_next, int tid, int M, double dt, int nknots, const double *__restrict__ s_ref,
+    const double *__restrict__ kappa_ref, double *__restrict__ rec, double *__restrict__ Sl)
+{
+    static_assert(MODEL == IHM2MPC_MODEL_FDYN6 || MODEL == IHM2MPC_MODEL_FDYN6U, "fkin6 has integrators of its own");
+    SENS_LOAD_STATE(xk, uk, tid)
+
+    // S, Sacc, dK: [column][row]; only rows in S_COL_MASK[column] are ever touched (S itself stays the identity: the base is read from Sl)
+    double S[10][8], Sacc[10][8], dK[10][8];
+#pragma unroll
+    for (int c = 0; c < 10; c++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            S[c][i] = (c == i) ? 1.0 : 0.0; dK[c][i] = 0.0;
+            Sacc[c][i] = S[c][i];
+            if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = S[c][i];
+        }
+
+    const double h = dt / M;
+    for (int m = 0; m < M; m++) {
+        double xacc[8], K[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
+#pragma unroll 1
+        for (int st = 0; st < 4; st++) {
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
+            double X[8], J[8][10];
+#pragma unroll
+            for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
+            fdyn6_eval<true, MODEL == IHM2MPC_MODEL_FDYN6U>(X, u_T, u_d, trk, K, J);
+#pragma unroll
+            for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
+#define STAGE_COL(c) sens_col_stage<MODEL, c>(J, S[c], Sl, Sacc[c], dK[c], ah, wh);
+            FOR_ALL_COLS(STAGE_COL)
+#undef STAGE_COL
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++) x[i] = xacc[i];
+#pragma unroll
+        for (int c = 0; c < 10; c++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = Sacc[c][i];
+    }
+
+    SENS_WRITE_RECORD(rec, Sacc, 1, x_next)
+}
+
+// fkin6, one lane: interval k of instance b
+template <int LAG = 0>
 __device__ __forceinline__ void dev_linearize(
     int b, int k, int N, int M, double dt, int nknots, const double *__restrict__ s_ref,
     const double *__restrict__ kappa_ref, const int32_t *__restrict__ track_id, const double *xs,
-    const double *us, double *lin, double *Sl, const double *lagf = nullptr)
+    const double *us, double *lin, const double *lagf = nullptr)
 {
     const double *xk = xs + ((size_t)b * (N + 1) + k) * 8;
-    dev_integrate_sens<MODEL, LAG>(xk, us + ((size_t)b * N + k) * 2, xk + 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
-                                   lin + ((size_t)b * N + k) * LIN_REC, nullptr, Sl, lagf);
+    const double *uk = us + ((size_t)b * N + k) * 2;
+    const int tid = track_id[b];
+    double *rec = lin + ((size_t)b * N + k) * LIN_REC;
+    if constexpr (LAG != 0) dev_integrate_sens_fkin6_lag(xk, uk, xk + 8, tid, M, dt, nknots, s_ref, kappa_ref, rec, nullptr, lagf);
+    else dev_integrate_sens_fkin6(xk, uk, xk + 8, tid, M, dt, nknots, s_ref, kappa_ref, rec, nullptr);
 }
 
 // plant / rollout step: x_next = RK4 x M over dt; model -1 (-2: with fdyn6u) = kin/dyn switch of
@@ -353,8 +387,7 @@ __device__ __forceinline__ void dev_sim_step(int b, int q, int model, int M, dou
         for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
 #pragma unroll 1
         for (int st = 0; st < 4; st++) {
-            const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-            const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
             double X[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
@@ -373,7 +406,7 @@ __device__ __forceinline__ void dev_sim_step(int b, int q, int model, int M, dou
 }
 
 
-// The plain kinematic plant (model 0) is dev_integrate_sens on (x, u): the same arithmetic as a shooting interval, so that the
+// The plain kinematic plant (model 0) is dev_integrate_sens_fkin6 on (x, u): the same arithmetic as a shooting interval, so that the
 // persistent loop can run it on the spare lane of the linearisation for free (k_steps); its record goes to spare_rec
 // (88 doubles per instance, never read).
 template <int LAG = 0>
@@ -386,8 +419,12 @@ __device__ __forceinline__ void dev_sim_step_kin(int b, int M, double dt, int nk
         if (xn != xs) for (int i = 0; i < 8; i++) xn[(size_t)b * 8 + i] = xs[(size_t)b * 8 + i];
         return;
     }
-    dev_integrate_sens<IHM2MPC_MODEL_FKIN6, LAG>(xs + (size_t)b * 8, us + (size_t)b * 2, xs + (size_t)b * 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
-                                                 spare_rec + (size_t)b * LIN_REC, xn + (size_t)b * 8, nullptr, lagf);
+    if constexpr (LAG != 0)
+        dev_integrate_sens_fkin6_lag(xs + (size_t)b * 8, us + (size_t)b * 2, xs + (size_t)b * 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
+                                     spare_rec + (size_t)b * LIN_REC, xn + (size_t)b * 8, lagf);
+    else
+        dev_integrate_sens_fkin6(xs + (size_t)b * 8, us + (size_t)b * 2, xs + (size_t)b * 8, track_id[b], M, dt, nknots, s_ref, kappa_ref,
+                                 spare_rec + (size_t)b * LIN_REC, xn + (size_t)b * 8);
 }
 
 }  // namespace ihm2

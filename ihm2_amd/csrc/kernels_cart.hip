@@ -7,6 +7,7 @@
 // (ihm2mpc_step runs the plant beside the linearisation).
 #include "ihm2mpc_internal.h"
 #include "model.hpp"
+#include "rk4.hpp"
 
 using namespace ihm2;
 
@@ -165,8 +166,7 @@ __global__ __launch_bounds__(64) void k_sim_dyn10(int B, int M, double dt, int n
         for (int i = 0; i < 15; i++) { xacc[i] = x[i]; K[i] = 0.0; }
 #pragma unroll 1
         for (int st = 0; st < 4; st++) {
-            const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-            const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
             double X[15];
 #pragma unroll
             for (int i = 0; i < 15; i++) X[i] = fma(ah, K[i], x[i]);
@@ -309,8 +309,7 @@ __global__ __launch_bounds__(64) void k_sim_cart(int B, int model, int M, double
             for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
 #pragma unroll 1
             for (int st = 0; st < 4; st++) {
-                const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-                const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+                const double ah = rk4_a(st, h), wh = rk4_w(st, h);
                 double X[8];
 #pragma unroll
                 for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);

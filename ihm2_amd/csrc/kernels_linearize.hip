@@ -4,9 +4,11 @@
 //
 // Replaces what acados' ERK integrator does inside AcadosOcpSolver.solve() for the reference
 // (python/main.py:325; options old/generate.py:23-25 with sim_method_num_steps = M).
-// RK4 tableau as dpc/main.py:87-97.
-// IHM2MPC_INTEG_ERK_LAG (k_linearize<FKIN6, LAG = 1>): the same tableau on the six vehicle states, the two actuator lags in closed form
-// (device_steps.hpp: dev_integrate_sens<MODEL, LAG>; include/ihm2mpc.h).
+// RK4 tableau as dpc/main.py:87-97 (rk4.hpp).
+// Kernels: k_linearize<LAG> (fkin6; LAG = 1, IHM2MPC_INTEG_ERK_LAG: the same tableau on the six vehicle states, the two actuator lags in
+// closed form, include/ihm2mpc.h), k_linearize_cols (fkin6, small batches), k_linearize_dyn<MODEL> (fdyn6, fdyn6u); the plants k_sim_step
+// and k_sim_step_kin<LAG>.  The integrators themselves are device_steps.hpp's (dev_integrate_sens_fkin6, _fkin6_lag, _dyn), shared with the
+// persistent loop; k_linearize_dyn and k_linearize_cols carry their own text, see there.
 //
 // Mapping: one lane per (b, k) pair, k fastest (instance-major arrays): a wavefront reads 64
 // consecutive 64-byte state rows (4 KB contiguous) and writes 64 consecutive 704-byte records.
@@ -28,7 +30,7 @@ namespace {
 __device__ __forceinline__ const double *lag_ptr() { return nullptr; }
 __device__ __forceinline__ const double *lag_ptr(const LagFac &l) { return l.f; }
 
-template <int MODEL, int LAG = 0, typename... LF>
+template <int LAG = 0, typename... LF>
 __global__ __launch_bounds__(64) void k_linearize(
     int B, int N, int M, double dt, int nknots, const double *__restrict__ s_ref,
     const double *__restrict__ kappa_ref, const int32_t *__restrict__ track_id, const double *__restrict__ xs,
@@ -38,15 +40,14 @@ __global__ __launch_bounds__(64) void k_linearize(
     const int b = (int)(t / N);
     const int k = (int)(t % N);
     if (b >= B) return;
-    extern __shared__ double s_lds[];
-    dev_linearize<MODEL, LAG>(b, k, N, M, dt, nknots, s_ref, kappa_ref, track_id, xs, us, lin, s_lds + threadIdx.x, lag_ptr(lf...));      // (unused by fkin6)
+    dev_linearize<LAG>(b, k, N, M, dt, nknots, s_ref, kappa_ref, track_id, xs, us, lin, lag_ptr(lf...));
 }
 
 // ---- small batches (the single real-time controller, B = 1): one sensitivity COLUMN per lane ----
 // With few instances the device is empty and the latency of a solve is what counts.  Here wave c of an interval block
 // propagates only column c of S (10 waves per 64 intervals); every lane re-evaluates the model and its Jacobian (10x redundant,
 // on otherwise idle SIMDs) but carries 8 instead of 52 sensitivity entries: 0.11 ms instead of 0.25 ms per linearisation.
-// The formulas per column are those of dev_integrate_sens, but the compiler shares different subexpressions when only one
+// The formulas per column are those of dev_integrate_sens_fkin6, but the compiler shares different subexpressions when only one
 // column is needed, so the records agree with k_linearize's to rounding (1e-15 relative), not bit for bit; it is therefore used
 // for up to 128 intervals only (B <= 3 at N = 40), where nothing is compared bit-wise with the batch path.
 template <int COL>
@@ -54,12 +55,7 @@ __device__ __forceinline__ void dev_integrate_col_fkin6(const double *xk, const 
                                                        const double *__restrict__ s_ref, const double *__restrict__ kappa_ref, double *rec)
 {
     constexpr int MODEL = IHM2MPC_MODEL_FKIN6;
-    double x[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) x[i] = xk[i];
-    const double u_T = uk[0], u_d = uk[1];
-    TrackSeg trk;
-    trk.init(s_ref + (size_t)tid * nknots, kappa_ref + (size_t)tid * nknots, nknots, x[0]);
+    SENS_LOAD_STATE(xk, uk, tid)
     double S[8], Sacc[8], dK[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) { S[i] = (COL == i) ? 1.0 : 0.0; dK[i] = 0.0; Sacc[i] = 0.0; }
@@ -71,8 +67,7 @@ __device__ __forceinline__ void dev_integrate_col_fkin6(const double *xk, const 
         sens_col_copy<MODEL, COL>(S, Sacc);
 #pragma unroll 1
         for (int st = 0; st < 4; st++) {
-            const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-            const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
             double X[8], J[8][10];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
@@ -126,9 +121,15 @@ __host__ __device__ constexpr int dk_pos(int c, int i)
 }
 __host__ __device__ constexpr int dk_count() { return dk_pos(10, 0); }
 
-// The dynamic models keep the integrator in the kernel itself (the code of dev_integrate_sens, written out): as a shared device
-// function the compiler forwarded the LDS-parked base sensitivities through registers (+45 spill stores, +14 %); only the
-// fkin6 integrator is shared with the persistent loop.
+// The dynamic models keep the integrator in the kernel itself: the text of dev_integrate_sens_dyn (device_steps.hpp), extended by the parked dK
+// and the fences of fdyn6_eval.  The two must give the same bits (tests/test_gpu_closed_loop.py: the loop against per-step launches).
+// Tried twice as one function.  As a plain shared device function the compiler forwarded the LDS-parked base sensitivities through registers
+// (+45 spill stores, +14 %).  As one __forceinline__ template dev_integrate_sens_dyn<MODEL, DK_FROM, FENCE> (the loop: DK_FROM = 10, no fences)
+// call_integrate_dyn kept its listing and this kernel did not: fdyn6u 3002 -> 3021 instructions and 256 -> 272 B scratch per lane, fdyn6
+// 3016 -> 3025 and 272 -> 288 B (256 VGPR + 256 AGPR, one wave per SIMD both ways) -- the loads of x_{k+1}, read here next to x_k, and of the
+// track id come in another order; dropping __restrict__ from the function changes nothing.  So: two texts, neither with a dead branch.
+// (Both pay for sens_col_stage's run-time test of Sl: as a compile-time choice this kernel is 2654 / 2661 instructions -- a change of the
+// dynamic models' speed, left for one that measures it.)
 template <int MODEL>
 __global__ __launch_bounds__(64) void k_linearize_dyn(
     int B, int N, int M, double dt, int nknots, const double *__restrict__ s_ref,
@@ -141,95 +142,69 @@ __global__ __launch_bounds__(64) void k_linearize_dyn(
     if (b >= B) return;
 
     const double *xk = xs + ((size_t)b * (N + 1) + k) * 8;
-    double x[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) x[i] = xk[i];
-    const double u_T = us[((size_t)b * N + k) * 2 + 0];
-    const double u_d = us[((size_t)b * N + k) * 2 + 1];
-    const int tid = track_id[b];
-    TrackSeg trk;
-    trk.init(s_ref + (size_t)tid * nknots, kappa_ref + (size_t)tid * nknots, nknots, x[0]);
+    SENS_LOAD_STATE(xk, us + ((size_t)b * N + k) * 2, track_id[b])
 
     // S, Sacc, dK: [column][row]; only rows in S_COL_MASK[column] are ever touched
-    constexpr bool S_IN_LDS = MODEL != IHM2MPC_MODEL_FKIN6;
     extern __shared__ double s_lds[];
-    double *Sl = S_IN_LDS ? s_lds + threadIdx.x : nullptr;
+    double *Sl = s_lds + threadIdx.x;
     double S[10][8], Sacc[10][8], dK[10][8];
 #pragma unroll
     for (int c = 0; c < 10; c++)
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             S[c][i] = (c == i) ? 1.0 : 0.0; dK[c][i] = 0.0;
-            if (S_IN_LDS) {
-                Sacc[c][i] = S[c][i];
-                if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = S[c][i];
-            }
+            Sacc[c][i] = S[c][i];
+            if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = S[c][i];
         }
     // The stage derivatives dK of the last columns (delta_0, u_T, u_delta: 21 entries) wait in LDS as well while the model is evaluated -- what the
     // 160 KB of a CU hold beside S at four waves: (55 + 21) x 512 B = 38 KB per wave.  They are fetched in front of the column's stage and put back
     // behind it: same arithmetic, fewer values alive across the forward-AD evaluation (scratch 400 -> see profiles/r4/kernel_resources.txt).
-    double *Dl = S_IN_LDS ? Sl + s_count(1) * 64 : nullptr;
+    double *Dl = Sl + s_count(1) * 64;
 #pragma unroll
     for (int c = DK_PARK_FROM; c < 10; c++)
 #pragma unroll
         for (int i = 0; i < 8; i++)
-            if (S_IN_LDS && ((S_COL_MASK[1][c] >> i) & 1u)) Dl[dk_pos(c, i) * 64] = 0.0;
+            if ((S_COL_MASK[1][c] >> i) & 1u) Dl[dk_pos(c, i) * 64] = 0.0;
 
     const double h = dt / M;
     for (int m = 0; m < M; m++) {
         double xacc[8], K[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
-#define COPY_S_TO_ACC(c) sens_col_copy<MODEL, c>(S[c], Sacc[c]);
-        if (!S_IN_LDS) { FOR_ALL_COLS(COPY_S_TO_ACC) }      // with S in LDS, Sacc already holds S from the previous sub-step
 #pragma unroll 1
         for (int st = 0; st < 4; st++) {
-            const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-            const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
             double X[8], J[8][10];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-            if (MODEL == IHM2MPC_MODEL_FKIN6) fkin6_eval<true>(X, u_T, u_d, trk, K, J);
-            else fdyn6_eval<true, MODEL == IHM2MPC_MODEL_FDYN6U, false, true>(X, u_T, u_d, trk, K, J);      // (with the scheduling fences between the wheels)
+            fdyn6_eval<true, MODEL == IHM2MPC_MODEL_FDYN6U, false, true>(X, u_T, u_d, trk, K, J);      // (with the scheduling fences between the wheels)
 #pragma unroll
             for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
 #define DYN_STAGE_COL(c)                                                                                                        \
             {                                                                                                                   \
-                if (S_IN_LDS && c >= DK_PARK_FROM) {                                                                            \
+                if (c >= DK_PARK_FROM) {                                                                                        \
                     _Pragma("unroll") for (int i = 0; i < 8; i++)                                                               \
                         if ((S_COL_MASK[1][c] >> i) & 1u) dK[c][i] = Dl[dk_pos(c, i) * 64];                                     \
                 }                                                                                                               \
                 sens_col_stage<MODEL, c>(J, S[c], Sl, Sacc[c], dK[c], ah, wh);                                                  \
-                if (S_IN_LDS && c >= DK_PARK_FROM) {                                                                            \
+                if (c >= DK_PARK_FROM) {                                                                                        \
                     _Pragma("unroll") for (int i = 0; i < 8; i++)                                                               \
                         if ((S_COL_MASK[1][c] >> i) & 1u) Dl[dk_pos(c, i) * 64] = dK[c][i];                                     \
                 }                                                                                                               \
             }
             FOR_ALL_COLS(DYN_STAGE_COL)
+#undef DYN_STAGE_COL
         }
 #pragma unroll
         for (int i = 0; i < 8; i++) x[i] = xacc[i];
-#define COPY_ACC_TO_S(c) sens_col_copy<MODEL, c>(Sacc[c], S[c]);
-        if (!S_IN_LDS) { FOR_ALL_COLS(COPY_ACC_TO_S) }
-        else {
 #pragma unroll
-            for (int c = 0; c < 10; c++)
+        for (int c = 0; c < 10; c++)
 #pragma unroll
-                for (int i = 0; i < 8; i++)
-                    if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = Sacc[c][i];
-        }
+            for (int i = 0; i < 8; i++)
+                if ((S_COL_MASK[1][c] >> i) & 1u) Sl[s_pos(1, c, i) * 64] = Sacc[c][i];
     }
 
-    // output record [A (8x8 row-major) | B (8x2) | b = Phi(x_k,u_k) - x_{k+1}]
-    double *rec = lin + ((size_t)b * N + k) * LIN_REC;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) rec[i * 8 + j] = ((S_COL_MASK[MODEL ? 1 : 0][j] >> i) & 1u) ? (S_IN_LDS ? Sacc[j][i] : S[j][i]) : 0.0;
-#pragma unroll
-        for (int j = 0; j < 2; j++) rec[64 + i * 2 + j] = ((S_COL_MASK[MODEL ? 1 : 0][8 + j] >> i) & 1u) ? (S_IN_LDS ? Sacc[8 + j][i] : S[8 + j][i]) : 0.0;
-        rec[80 + i] = x[i] - xk[8 + i];
-    }
+    SENS_WRITE_RECORD(lin + ((size_t)b * N + k) * LIN_REC, Sacc, 1, xk + 8)
 }
 
 
@@ -282,7 +257,7 @@ void ihm2_launch_linearize(ihm2mpc_handle *h)
     if (h->cfg.integrator_type == IHM2MPC_INTEG_ERK_LAG) {
         // one kernel at every batch size: with sub-steps sized for the car (M = 4) the column-parallel latency path has nothing left to hide
         note_lin(h, 5);
-        hipLaunchKernelGGL((k_linearize<IHM2MPC_MODEL_FKIN6, 1, LagFac>), dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
+        hipLaunchKernelGGL((k_linearize<1, LagFac>), dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
                            h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin, ihm2_lag_factors(h->cfg.dt / h->cfg.M));
         return;
     }
@@ -300,7 +275,7 @@ void ihm2_launch_linearize(ihm2mpc_handle *h)
         hipLaunchKernelGGL(k_linearize_cols, dim3(blocks, 10), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
                            h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
     else
-        hipLaunchKernelGGL(k_linearize<IHM2MPC_MODEL_FKIN6>, dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
+        hipLaunchKernelGGL(k_linearize<>, dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
                            h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
 }
 

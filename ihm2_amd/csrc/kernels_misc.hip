@@ -92,8 +92,7 @@ __global__ __launch_bounds__(64) void k_init_guess(int B, int N, int M, double d
             const double dT0 = x[6] - u_T, dD0 = x[7] - u_d;
 #pragma unroll 1
             for (int st = 0; st < 4; st++) {
-                const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-                const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+                const double ah = rk4_a(st, h), wh = rk4_w(st, h);
                 double X[8];
 #pragma unroll
                 for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);

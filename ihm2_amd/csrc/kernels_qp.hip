@@ -1123,21 +1123,21 @@ __global__ __launch_bounds__(64 * NW) void k_qp_block(QpArgs a)
 __device__ __noinline__ void call_integrate_fkin6(const double *xk, const double *uk, const double *x_next, int tid, int M, double dt, int nknots,
                                                   const double *s_ref, const double *kappa_ref, double *rec, double *xn_out)
 {
-    dev_integrate_sens<IHM2MPC_MODEL_FKIN6>(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, xn_out, nullptr);
+    dev_integrate_sens_fkin6(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, xn_out);
 }
 // IRK = 2: the same with the actuator lags in closed form (IHM2MPC_INTEG_ERK_LAG); lagf: the stage factors for this lane's sub-step
 __device__ __noinline__ void call_integrate_fkin6_lag(const double *xk, const double *uk, const double *x_next, int tid, int M, double dt, int nknots,
                                                       const double *s_ref, const double *kappa_ref, double *rec, double *xn_out, const double *lagf)
 {
-    dev_integrate_sens<IHM2MPC_MODEL_FKIN6, 1>(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, xn_out, nullptr, lagf);
+    dev_integrate_sens_fkin6_lag(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, xn_out, lagf);
 }
-// The dynamic OCP models (python/models.py:455-606; fdyn6u = the named deviation): dev_integrate_sens with the sub-step's base sensitivities
+// The dynamic OCP models (python/models.py:455-606; fdyn6u = the named deviation): dev_integrate_sens_dyn with the sub-step's base sensitivities
 // parked in LDS (Sl: the QP's LDS, idle during the linearisation; 55 words per lane) -- the arithmetic of k_linearize_dyn.
 template <int MODEL>
 __device__ __noinline__ void call_integrate_dyn(const double *xk, const double *uk, const double *x_next, int tid, int M, double dt, int nknots,
                                                 const double *s_ref, const double *kappa_ref, double *rec, double *Sl)
 {
-    dev_integrate_sens<MODEL>(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, nullptr, Sl);
+    dev_integrate_sens_dyn<MODEL>(xk, uk, x_next, tid, M, dt, nknots, s_ref, kappa_ref, rec, Sl);
 }
 // the collocation integrator in the loop: the wave's 16 quads take the intervals base .. base + 15 (kernels_irk.hip: four lanes per interval)
 template <int MODEL>

@@ -56,8 +56,7 @@ __device__ __forceinline__ void rollout(double (&x)[8], double u_T, double u_d, 
         for (int i = 0; i < 8; i++) { xacc[i] = x[i]; K[i] = 0.0; }
 #pragma unroll 1
         for (int st = 0; st < 4; st++) {
-            const double ah = (st == 0) ? 0.0 : ((st == 3) ? h : 0.5 * h);
-            const double wh = (st == 0 || st == 3) ? h * (1.0 / 6.0) : h * (2.0 / 6.0);
+            const double ah = rk4_a(st, h), wh = rk4_w(st, h);
             double X[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
