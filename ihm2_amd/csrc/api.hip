@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ihm2mpc_internal.h"
+#include "qp_catalogue.hpp"
 #include "sqp_body.hpp"
 
 static thread_local std::string g_err;
@@ -79,59 +80,6 @@ int upload_shared(ihm2mpc_handle *h, const double *host, double *dev, size_t n)
     return 0;
 }
 
-// y = Vx x + Vu u of python/mpc.py:49-58 as one 12x10 selector
-void cost_selector(double V[NY][NZ])
-{
-    memset(V, 0, sizeof(double) * NY * NZ);
-    for (int i = 0; i < NX; i++) V[i][i] = 1.0;
-    V[10][6] = 1.0; V[11][7] = 1.0;
-    V[8][8] = 1.0; V[9][9] = 1.0;
-    V[10][8] = -1.0; V[11][9] = -1.0;
-}
-
-// The QP's weight tables of one stage k < N (cost_scale * V'W_k V, cost_scale * V'W_k) and of the terminal stage (W_e padded with I, W_e).
-// ihm2mpc_set_weights and ihm2mpc_set_instance_weights both expand through these: one instance's tables are then those of a batch-shared
-// table with its weights bit for bit.
-void stage_weight_tables(const double *Wk, double cs, double *Hk, double *Gk)
-{
-    double V[NY][NZ];
-    cost_selector(V);
-    double VtW[NZ][NY];
-    for (int i = 0; i < NZ; i++)
-        for (int j = 0; j < NY; j++) {
-            double acc = 0;
-            for (int l = 0; l < NY; l++) acc += V[l][i] * Wk[l * NY + j];
-            VtW[i][j] = acc;
-            Gk[i * 12 + j] = cs * acc;
-        }
-    for (int i = 0; i < NZ; i++)
-        for (int j = 0; j < NZ; j++) {
-            double acc = 0;
-            for (int l = 0; l < NY; l++) acc += VtW[i][l] * V[l][j];
-            Hk[i * 10 + j] = cs * acc;
-        }
-}
-
-void terminal_weight_tables(const double *W_e, double *HN, double *GN)
-{
-    for (int i = 0; i < NX; i++)
-        for (int j = 0; j < NX; j++) {
-            HN[i * 10 + j] = W_e[i * NX + j];
-            GN[i * 12 + j] = W_e[i * NX + j];
-        }
-    HN[8 * 10 + 8] = 1.0;
-    HN[9 * 10 + 9] = 1.0;
-}
-
-// true if the 10x10 Hessian of a stage is symmetric (to rounding)
-bool symmetric10(const double *Hk)
-{
-    for (int i = 0; i < NZ; i++)
-        for (int j = 0; j < i; j++)
-            if (fabs(Hk[i * 10 + j] - Hk[j * 10 + i]) > 1e-12 * (1 + fabs(Hk[i * 10 + j]))) return false;
-    return true;
-}
-
 const char *row_name(int c)
 {
     static const char *names[NC] = {"lbx/ubx[0]", "lbx/ubx[1]", "lbx/ubx[2]", "lbx/ubx[3]", "lbx/ubx[4]", "lbx/ubx[5]", "lbx/ubx[6]", "lbx/ubx[7]",
@@ -139,54 +87,30 @@ const char *row_name(int c)
     return (c >= 0 && c < NC) ? names[c] : "?";
 }
 
-// Per-instance bounds -> the slot table of the batch-shared pattern: the values of instance b sit where the shared table has a finite
-// side (rows 0..11; the track rows and the a_lat row stay batch-shared), and the SQP mode's (NS,NC) bounds alike.  Refuses when the
-// stored values' finite sides differ from the shared table's (a later shared setter may have changed them).
+// Per-instance bounds -> the slot table of the batch-shared pattern (qp_tables.hpp: scatter_slot_bounds), and the SQP mode's (NS,NC)
+// bounds alike.  Refuses when the stored values' finite sides differ from the shared table's (a later shared setter may have changed them).
 int check_instance_pattern(const ihm2mpc_handle *h, const double *il, const double *iu)
 {
-    const int NS = h->NS;
-    for (int b = 0; b < h->B; b++)
-        for (int k = 0; k < NS; k++)
-            for (int c = 0; c < 12; c++) {
-                const double lb = il[((size_t)b * NS + k) * 12 + c], ub = iu[((size_t)b * NS + k) * 12 + c];
-                const double slb = h->host_lb[k * NC + c], sub = h->host_ub[k * NC + c];
-                if (std::isfinite(lb) != std::isfinite(slb) || std::isfinite(ub) != std::isfinite(sub))
-                    return fail("instance %d, stage %d, row %d (%s): the finite sides (%s, %s) differ from the batch-shared table's (%s, %s)", b, k, c,
-                                row_name(c), std::isfinite(lb) ? "lower" : "-", std::isfinite(ub) ? "upper" : "-",
-                                std::isfinite(slb) ? "lower" : "-", std::isfinite(sub) ? "upper" : "-");
-            }
-    return 0;
+    const ihm2::PatternMismatch m = ihm2::find_pattern_mismatch(h->rows, h->B, il, iu);
+    if (!m.found) return 0;
+    return fail("instance %d, stage %d, row %d (%s): the finite sides (%s, %s) differ from the batch-shared table's (%s, %s)", m.b, m.k, m.c,
+                row_name(m.c), m.lower ? "lower" : "-", m.upper ? "upper" : "-", m.shared_lower ? "lower" : "-", m.shared_upper ? "upper" : "-");
 }
 
 int scatter_instance_bounds(ihm2mpc_handle *h)
 {
-    const int B = h->B, NS = h->NS;
+    const int B = h->B;
     h->inst_b_ok = false;
     if (check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
-    const size_t n = (size_t)h->nslot_lane * 64;
+    const size_t n = h->slots.entries();
     if ((size_t)B * n > h->i_slot_lb.size()) {
         HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
         h->i_slot_lb.reset(); h->i_slot_ub.reset();
         if (alloc_all(h->i_slot_lb, (size_t)B * n, h->i_slot_ub, (size_t)B * n)) return -1;
     }
-    std::vector<double> slb((size_t)B * n), sub((size_t)B * n), stl((size_t)B * NS * NC), stu((size_t)B * NS * NC);
-    for (int b = 0; b < B; b++) {
-        const double *il = h->ih_lb.data() + (size_t)b * NS * 12, *iu = h->ih_ub.data() + (size_t)b * NS * 12;
-        for (size_t e = 0; e < n; e++) {
-            const int kc = h->host_kc[e], k = kc >> 4, c = kc & 15;
-            double lo = h->host_slb[e], up = h->host_sub[e];
-            if (kc >= 0 && c < 12) {     // a split (soft) row's halves keep their absent side
-                if (std::isfinite(lo)) lo = il[k * 12 + c];
-                if (std::isfinite(up)) up = iu[k * 12 + c];
-            }
-            slb[(size_t)b * n + e] = lo; sub[(size_t)b * n + e] = up;
-        }
-        for (int k = 0; k < NS; k++)
-            for (int c = 0; c < NC; c++) {
-                stl[((size_t)b * NS + k) * NC + c] = (c < 12) ? il[k * 12 + c] : h->host_lb[k * NC + c];
-                stu[((size_t)b * NS + k) * NC + c] = (c < 12) ? iu[k * 12 + c] : h->host_ub[k * NC + c];
-            }
-    }
+    std::vector<double> slb, sub, stl, stu;
+    ihm2::scatter_slot_bounds(h->slots, B, h->NS, h->ih_lb.data(), h->ih_ub.data(), slb, sub);
+    ihm2::scatter_stage_bounds(h->rows, B, h->ih_lb.data(), h->ih_ub.data(), stl, stu);
     if (n && (upload_shared(h, slb.data(), h->i_slot_lb, slb.size()) || upload_shared(h, sub.data(), h->i_slot_ub, sub.size()))) return -1;
     if (upload_shared(h, stl.data(), h->i_st_lb, stl.size()) || upload_shared(h, stu.data(), h->i_st_ub, stu.size())) return -1;
     h->inst_b_ok = true;
@@ -200,7 +124,7 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
 const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6()};
 
 // the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
-int path_class(const ihm2mpc_handle *h) { return h->alat_on ? 2 : h->path_on ? 1 : 0; }
+int path_class(const ihm2mpc_handle *h) { return h->rows.alat_on ? 2 : h->path_on ? 1 : 0; }
 
 // the first entry of the catalogue with the fields of `want` and at least its NSLOT; nullptr: none
 const QpInst *find_inst(const QpKey &want)
@@ -222,7 +146,7 @@ const QpInst *find_inst(const QpKey &want)
 int factor_form(const ihm2mpc_handle *h)
 {
     static const int limit = [] { const char *e = getenv("IHM2MPC_QP_FORM"); return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : 2; }();
-    if (limit == 0 || h->cfg.model == IHM2MPC_MODEL_FDYN6 || h->m_act == 0) return 0;
+    if (limit == 0 || h->cfg.model == IHM2MPC_MODEL_FDYN6 || h->slots.m_act == 0) return 0;
     return (h->N == 40 && limit == 2) ? 40 : -1;
 }
 
@@ -236,21 +160,6 @@ const QpInst *find_form(const ihm2mpc_handle *h, QpKey want)
     }
     want.nf = 0;
     return find_inst(want);
-}
-
-// The slot tables the per-step QP takes for the handle's rows: (NSOFT, the largest NSLOT that comes with it) per NSOFT of its
-// instantiations, in catalogue order.  NSOFT = 0: every side hard.
-std::vector<std::pair<int, int>> slot_limits(const ihm2mpc_handle *h)
-{
-    std::vector<std::pair<int, int>> v;
-    for (const QpTable &t : qp_catalogue)
-        for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
-            if (e->key.kind != QP_WAVE || e->key.path != path_class(h)) continue;
-            auto p = std::find_if(v.begin(), v.end(), [&](const std::pair<int, int> &q) { return q.first == e->key.nsoft; });
-            if (p == v.end()) v.push_back({e->key.nsoft, e->key.nslot});
-            else p->second = std::max(p->second, e->key.nslot);
-        }
-    return v;
 }
 
 // the LDS layout of the QP that takes the handle's rows and weights (qp_lds.hpp): what the kernels carve up is what the launch asks for
@@ -270,9 +179,9 @@ const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
     const int uni = h->uniform_H && h->uniform_CD;
     // few instances (at most one per CU): four wavefronts per instance, slots from the 256-lane table
     // (per-instance bounds: the 64-lane table alone carries them -- k_qp_wave's results are the four-wave kernel's bit for bit)
-    if (h->block_qp && !h->inst_b && h->nslot_lane_blk >= 1 && h->B <= h->n_cu && h->nslot_lane * 64 <= (h->N + 1) * 12)
-        if (const QpInst *e = find_inst({QP_BLOCK, h->nslot_lane_blk, h->nsoft_lane, path_class(h), uni, 0, 0, 0})) return e;
-    return find_form(h, {QP_WAVE, h->nslot_lane, h->nsoft_lane, path_class(h), uni, 0, 0, 0});
+    if (h->block_qp && !h->inst_b && h->slots.per_blk >= 1 && h->B <= h->n_cu && h->slots.per_lane * 64 <= (h->N + 1) * 12)
+        if (const QpInst *e = find_inst({QP_BLOCK, h->slots.per_blk, h->slots.nsoft, path_class(h), uni, 0, 0, 0})) return e;
+    return find_form(h, {QP_WAVE, h->slots.per_lane, h->slots.nsoft, path_class(h), uni, 0, 0, 0});
 }
 
 // The persistent loop for the handle's configuration; nullptr: none (ihm2mpc_run_steps then launches per step, which gives the same
@@ -296,7 +205,7 @@ const QpInst *select_steps(const ihm2mpc_handle *h, int sens = 0)
     // the SQP instantiations keep the sweeps' earlier form, whose unclamped prefetch of LDS operands starts in front of the block's LDS at
     // N = 2 and N = 3 (by 60 and 24 words; the values are never used): those horizons are launched per step
     if (sqp && !ihm2::qp_sweeps_inside(qp_layout(h), h->N, false, 0, 0)) return nullptr;
-    return find_form(h, {QP_STEPS, h->nslot_lane, h->nsoft_lane, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
+    return find_form(h, {QP_STEPS, h->slots.per_lane, h->slots.nsoft, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
 }
 
 // the launch record (ihm2mpc_get_launch_record) from the key of what was launched; a k_steps key with `per_step` != 0: run_steps
@@ -318,13 +227,13 @@ void note_launch(ihm2mpc_handle *h, const QpKey &k, int per_step = 0)
 QpArgs qp_args(ihm2mpc_handle *h)
 {
     QpArgs a;
-    a.B = h->B; a.N = h->N; a.iter_max = h->cfg.ipm_iter_max; a.nslots = h->nslot_lane * 64; a.m_act = h->m_act;
-    a.nslots_can = h->nslot_lane * 64;
+    a.B = h->B; a.N = h->N; a.iter_max = h->cfg.ipm_iter_max; a.nslots = h->slots.per_lane * 64; a.m_act = h->slots.m_act;
+    a.nslots_can = h->slots.per_lane * 64;
     a.tol = h->cfg.ipm_tol; a.mu0 = h->cfg.ipm_mu0; a.tau0 = h->cfg.ipm_tau0;
     a.Hs = h->Hs; a.Gy = h->Gy; a.CD = h->CD; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.slot_kc = h->slot_kc;
     a.hs_bs = 0; a.hs_te = h->N * 100; a.gy_bs = 0; a.gy_te = h->N * 120; a.sl_bs = 0;
     if (h->inst_w) { a.Hs = h->iHs; a.Gy = h->iGy; a.hs_bs = 200; a.hs_te = 100; a.gy_bs = 240; a.gy_te = 120; }
-    if (h->inst_b) { a.sl_bs = h->nslot_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }
+    if (h->inst_b) { a.sl_bs = h->slots.per_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }
     a.x = h->x; a.u = h->u; a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e;
     a.pi = h->pi; a.lam = h->lam; a.res = h->res; a.qp_res = h->qp_res; a.u0 = h->u0; a.status = h->status; a.qp_iter = h->qp_iter;
     a.lin = h->lin; a.g = h->q_g; a.rg = h->q_rg; a.P = h->q_P; a.M = h->q_M + (size_t)QM_PAD * 64;
@@ -350,7 +259,7 @@ int launch_qp(ihm2mpc_handle *h)
     const QpInst *e = select_qp(h, lds);
     if (!e) return 1;
     QpArgs a = qp_args(h);
-    if (e->key.kind == QP_BLOCK) { a.slot_kc = h->slot_kc_blk; a.slot_lb = h->slot_lb_blk; a.slot_ub = h->slot_ub_blk; a.nslots = h->nslot_lane_blk * 256; }
+    if (e->key.kind == QP_BLOCK) { a.slot_kc = h->slot_kc_blk; a.slot_lb = h->slot_lb_blk; a.slot_ub = h->slot_ub_blk; a.nslots = h->slots.per_blk * 256; }
     void *args[] = {&a};
     launch_inst(h, e, args, lds);
     return 0;
@@ -455,7 +364,7 @@ int ready(ihm2mpc_handle *h)
     if (h->inst_b && !h->inst_b_ok) return fail("the per-instance bounds do not fit the batch-shared constraint pattern any more: set them again, or pass NULL");
     if (!h->slots_fit) {        // the limits of the catalogue's instantiations for these rows
         std::string hard = "none", soft;
-        for (const auto &[S, NSL] : slot_limits(h))
+        for (const auto &[S, NSL] : ihm2::slot_limits(path_class(h)))
             if (S == 0) hard = std::to_string(NSL);
             else soft += (soft.empty() ? "" : " or ") + std::to_string(NSL) + " of which " + std::to_string(S) + " soft";
         static const char *rows[3] = {"without track rows", "with track rows", "with track rows and the lateral-acceleration row"};
@@ -463,7 +372,7 @@ int ready(ihm2mpc_handle *h)
                     "(a two-sided hard row is one slot, a row with a soft side two; a lane's one-sided slots lead it)", rows[path_class(h)],
                     hard.c_str(), soft.empty() ? "none" : soft.c_str());
     }
-    if (h->alat_on) {
+    if (h->rows.alat_on) {
         // the row belongs to the kinematic constraint set of old/generate_acaods_interface.py:198-209, which comes with the track rows and SQP_RTI (old/generate.py:21)
         if (h->cfg.model != IHM2MPC_MODEL_FKIN6) return fail("the lateral-acceleration row is a row of the kinematic model (old/generate_acaods_interface.py:206: `[] if is_dynamic else [a_lat]`)");
         if (!h->path_on) return fail("the lateral-acceleration row comes with the track rows: enable ihm2mpc_set_path_constraints first");
@@ -619,13 +528,11 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
                   h->lin, (B * N + B) * LIN_REC,      // + one spare record per instance (the kinematic plant's, never read)
                   h->q_g, B * NS * 10, h->q_rg, B * NS * 10, h->q_P, B * NS * 64, h->q_M, (B * N + 2 * QM_PAD) * 64, h->scratch, B * 24))
         return -1;
-    h->alat_on = 0; h->slots_fit = true; h->alat_lb = -INFINITY; h->alat_ub = INFINITY; h->alat_sz[0] = h->alat_sz[1] = 0.0; h->alat_sZ[0] = h->alat_sZ[1] = -1.0;
+    h->slots_fit = true;
     h->sqp_globalization = 0; h->sqp_use_suff = 0; h->sqp_full_step_dual = 0;
     h->sqp_alpha_min = 0.05; h->sqp_alpha_red = 0.7; h->sqp_eps = 1e-4;
     for (int i = 0; i < 4; i++) h->sqp_tol[i] = cfg->nlp_tol;
-    h->host_lb.assign(NS * NC, -INFINITY); h->host_ub.assign(NS * NC, INFINITY);
-    h->host_sz.assign(NS * NLAM, 0.0); h->host_sZ.assign(NS * NLAM, -1.0);
-    h->host_kc.resize(MAX_SLOTS); h->host_slb.resize(MAX_SLOTS); h->host_sub.resize(MAX_SLOTS);
+    h->rows = ihm2::ConstraintRows((int)NS);      // no row has a finite side yet; the a_lat row is off and hard
     if (ihm2_upload_irk_tab(h.get())) return fail("could not upload the collocation tableau");
     *out = h.release();
     return 0;
@@ -754,17 +661,12 @@ int ihm2mpc_set_weights(ihm2mpc_handle *h, const double *W, const double *W_e)
     const int N = h->N, NS = h->NS;
     std::vector<double> Hs((size_t)NS * 100, 0.0), Gy((size_t)NS * 120, 0.0);
     const double cs = h->cfg.cost_scale_stage;
-    for (int k = 0; k < N; k++) stage_weight_tables(W + (size_t)k * NY * NY, cs, &Hs[(size_t)k * 100], &Gy[(size_t)k * 120]);
-    terminal_weight_tables(W_e, &Hs[(size_t)N * 100], &Gy[(size_t)N * 120]);
+    for (int k = 0; k < N; k++) ihm2::stage_weight_tables(W + (size_t)k * NY * NY, cs, &Hs[(size_t)k * 100], &Gy[(size_t)k * 120]);
+    ihm2::terminal_weight_tables(W_e, &Hs[(size_t)N * 100], &Gy[(size_t)N * 120]);
     for (int k = 0; k < NS; k++)
-        if (!symmetric10(&Hs[(size_t)k * 100])) return fail("weight matrix of stage %d is not symmetric", k);
-    bool uni = true;
-    for (int k = 1; k < N && uni; k++)
-        for (int i = 0; i < 100; i++)
-            if (Hs[(size_t)k * 100 + i] != Hs[i]) { uni = false; break; }
-    for (int k = 1; k < N && uni; k++)       // "uniform" covers the gradient map as well: the QP kernel keeps one copy of both
-        for (int i = 0; i < 120; i++)
-            if (Gy[(size_t)k * 120 + i] != Gy[i]) { uni = false; break; }
+        if (!ihm2::symmetric10(&Hs[(size_t)k * 100])) return fail("weight matrix of stage %d is not symmetric", k);
+    // "uniform" covers the gradient map as well: the QP kernel keeps one copy of both
+    const bool uni = ihm2::stages_equal(Hs.data(), N, 100) && ihm2::stages_equal(Gy.data(), N, 120);
     if (upload_shared(h, Hs.data(), h->Hs, Hs.size()) || upload_shared(h, Gy.data(), h->Gy, Gy.size())) return -1;
     if (upload_shared(h, W, h->Wd, (size_t)N * 144) || upload_shared(h, W_e, h->Wd + (size_t)N * 144, 64)) return -1;
     h->shared_uniform_H = uni;
@@ -795,10 +697,10 @@ int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const doubl
         for (int i = 0; i < 144; i++) if (Wb[i] != Wb[i]) return fail("instance %d: W[%d][%d] is NaN", b, i / 12, i % 12);
         for (int i = 0; i < 64; i++) if (Web[i] != Web[i]) return fail("instance %d: W_e[%d][%d] is NaN", b, i / 8, i % 8);
         double *Hb = &Hs[(size_t)b * 200], *Gb = &Gy[(size_t)b * 240];
-        stage_weight_tables(Wb, cs, Hb, Gb);
-        terminal_weight_tables(Web, Hb + 100, Gb + 120);
-        if (!symmetric10(Hb)) return fail("instance %d: the weight matrix of the stages 0..%d is not symmetric", b, h->N - 1);
-        if (!symmetric10(Hb + 100)) return fail("instance %d: the weight matrix of stage %d (terminal) is not symmetric", b, h->N);
+        ihm2::stage_weight_tables(Wb, cs, Hb, Gb);
+        ihm2::terminal_weight_tables(Web, Hb + 100, Gb + 120);
+        if (!ihm2::symmetric10(Hb)) return fail("instance %d: the weight matrix of the stages 0..%d is not symmetric", b, h->N - 1);
+        if (!ihm2::symmetric10(Hb + 100)) return fail("instance %d: the weight matrix of stage %d (terminal) is not symmetric", b, h->N);
         std::memcpy(&Wd[(size_t)b * 208], Wb, 144 * sizeof(double));
         std::memcpy(&Wd[(size_t)b * 208 + 144], Web, 64 * sizeof(double));
     }
@@ -811,131 +713,31 @@ int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const doubl
     return 0;
 }
 
-// Constraint-slot table of the QP kernel.  A slot is a (stage, row) pair with its finite sides; a row with a SOFT
-// side is split into one-sided slots (the slack belongs to one side).  Lane `l` of the instance's wavefront owns the
-// entries l, l+64, ...; both halves of a split row go to the same lane (they accumulate into the same LDS words
-// without atomics).  Tables with soft sides: the first S entries of a lane hold ONE-SIDED slots only -- its soft ones first, then hard
-// one-sided ones, else padding -- where S is the NSOFT of the kernel instantiation that will run the table: the kernel keeps slack
-// registers, and one side's registers only, for those (kernels_qp.hip: ONE_SIDED).  All-hard tables: every entry may be two-sided (S = 0).
+// The constraint-slot table of the QP kernels from the handle's rows (qp_tables.hpp: lay_out_slots, for the instantiations the catalogue
+// has for these rows).  A table that fits none leaves the previous one in the handle: ready() reports it, since the setters come one by one
+// and a later one may make the rows fit.
 static int rebuild_slots(ihm2mpc_handle *h)
 {
-    const int NS = h->NS;
-    struct Slot { int kc; double lb, ub, zw, Zw; };
-    struct Row { int kc; double lb, ub, szl, sZl, szu, sZu; bool fl, fu, sl, su; };
-    // the rows with a finite side, stage-major (row 14: the lateral-acceleration row of the stages 1..N-1, kept beside the NC = 14 rows of the tables)
-    std::vector<Row> rows;
-    int m_act = 0, soft_total = 0;
-    for (int k = 0; k < NS; k++)
-        for (int c = 0; c < NC + 1; c++) {
-            const bool extra = c == NC;
-            if (extra && !(h->alat_on && k >= 1 && k < NS - 1)) continue;
-            Row r;
-            r.kc = k * 16 + c;
-            r.lb = extra ? h->alat_lb : h->host_lb[k * NC + c]; r.ub = extra ? h->alat_ub : h->host_ub[k * NC + c];
-            r.fl = std::isfinite(r.lb); r.fu = std::isfinite(r.ub);
-            if (!r.fl && !r.fu) continue;
-            r.szl = extra ? h->alat_sz[0] : h->host_sz[k * NLAM + c]; r.sZl = extra ? h->alat_sZ[0] : h->host_sZ[k * NLAM + c];
-            r.szu = extra ? h->alat_sz[1] : h->host_sz[k * NLAM + NC + c]; r.sZu = extra ? h->alat_sZ[1] : h->host_sZ[k * NLAM + NC + c];
-            r.sl = r.fl && r.sZl >= 0.0; r.su = r.fu && r.sZu >= 0.0;
-            rows.push_back(r);
-            soft_total += (int)r.sl + (int)r.su;
-            m_act += (int)r.fl + (int)r.fu + (int)r.sl + (int)r.su;
-        }
-    std::vector<Slot> lanes[64];
-    int per_lane = 0, total = 0, S_used = 0;
-    bool placed = false;
-    // the layouts of the per-step QP's instantiations for these rows, in catalogue order: NSOFT = 0 for an all-hard table, NSOFT > 0 with soft sides
-    for (const auto &lim : slot_limits(h)) {
-        const int S = lim.first, NSL = lim.second;
-        if ((S == 0) != (soft_total == 0)) continue;
-        std::vector<Slot> ones[64], twos[64];       // one-sided slots (soft ones first), two-sided slots
-        int nsoft[64] = {0};
-        auto tail = [&](int l) { return (int)twos[l].size() + std::max(0, (int)ones[l].size() - S); };     // entries behind the first S
-        // two passes: rows with a soft side first, spread by soft count, then the hard rows by the entries behind the leading ones
-        // (all-hard tables, S = 0: by total count -- round-robin)
-        for (int pass = 0; pass < 2; pass++)
-            for (const Row &r : rows) {
-                if ((r.sl || r.su) != (pass == 0)) continue;
-                int best = 0;       // least-loaded lane; ties -> lowest lane
-                for (int l = 1; l < 64; l++) {
-                    const bool fewer_soft = nsoft[l] < nsoft[best], same_soft = nsoft[l] == nsoft[best];
-                    const int tl = tail(l) + ((S > 0 && pass == 1 && !(r.fl && r.fu) && (int)ones[l].size() < S) ? -1 : 0);
-                    const int tb = tail(best) + ((S > 0 && pass == 1 && !(r.fl && r.fu) && (int)ones[best].size() < S) ? -1 : 0);
-                    const bool fewer = (pass == 0) ? ones[l].size() + twos[l].size() < ones[best].size() + twos[best].size() : tl < tb;
-                    if (pass == 0 ? (fewer_soft || (same_soft && fewer)) : fewer) best = l;
-                }
-                if (!r.sl && !r.su) {
-                    if (S > 0 && !(r.fl && r.fu)) ones[best].push_back({r.kc, r.lb, r.ub, 0.0, -1.0});     // a hard one-sided row may lead
-                    else twos[best].push_back({r.kc, r.lb, r.ub, 0.0, -1.0});
-                } else {
-                    // the soft half in front of a hard half
-                    Slot lo = {r.kc, r.lb, INFINITY, r.sl ? r.szl : 0.0, r.sl ? r.sZl : -1.0}, up = {r.kc, -INFINITY, r.ub, r.su ? r.szu : 0.0, r.su ? r.sZu : -1.0};
-                    if (r.fl && r.sl) ones[best].push_back(lo);
-                    if (r.fu && r.su) ones[best].push_back(up);
-                    if (r.fl && !r.sl) ones[best].push_back(lo);
-                    if (r.fu && !r.su) ones[best].push_back(up);
-                }
-                nsoft[best] += (int)r.sl + (int)r.su;
-            }
-        int pl = 0, sl_max = 0;
-        for (int l = 0; l < 64; l++) {
-            std::stable_partition(ones[l].begin(), ones[l].end(), [](const Slot &s) { return s.Zw >= 0.0; });
-            pl = std::max(pl, S + tail(l));
-            sl_max = std::max(sl_max, nsoft[l]);
-        }
-        if (sl_max > S || pl > NSL) continue;
-        // lay the lanes out: S leading one-sided entries (padding where a lane has fewer), then the rest
-        total = 0;
-        for (int l = 0; l < 64; l++) {
-            lanes[l].clear();
-            const int lead = std::min(S, (int)ones[l].size());
-            for (int i = 0; i < lead; i++) lanes[l].push_back(ones[l][i]);
-            if (!twos[l].empty() || (int)ones[l].size() > S)
-                for (int i = lead; i < S; i++) lanes[l].push_back({-1, -INFINITY, INFINITY, 0.0, -1.0});
-            for (size_t i = S; i < ones[l].size(); i++) lanes[l].push_back(ones[l][i]);
-            for (const Slot &t : twos[l]) lanes[l].push_back(t);
-            for (const Slot &t : lanes[l]) total += t.kc >= 0;
-        }
-        per_lane = 0;
-        for (int l = 0; l < 64; l++) per_lane = std::max(per_lane, (int)lanes[l].size());
-        S_used = S; placed = true;
-        break;
-    }
-    h->slots_fit = placed && per_lane * 64 <= MAX_SLOTS;
-    if (!h->slots_fit) return 0;        // ready() reports it: the setters come one by one and a later one may make the rows fit
-    const size_t n = (size_t)per_lane * 64;
-    std::vector<int32_t> kc(n, -1);
-    std::vector<double> slb(n, -INFINITY), sub(n, INFINITY), zw(n, 0.0), Zw(n, -1.0);
-    for (int l = 0; l < 64; l++)
-        for (size_t r = 0; r < lanes[l].size(); r++) {
-            const Slot &s = lanes[l][r];
-            const size_t e = l + 64 * r;
-            kc[e] = s.kc; slb[e] = s.lb; sub[e] = s.ub; zw[e] = s.zw; Zw[e] = s.Zw;
-        }
-    h->nslots = total; h->m_act = m_act; h->nslot_lane = per_lane; h->nsoft_lane = S_used;      // what the selection takes the instantiation by: its NSOFT
-    // the same rows over 256 lanes for the four-wave latency kernel (all-hard tables: a row is one two-sided slot)
-    h->nslot_lane_blk = 0;
-    if (S_used == 0 && total > 0 && total <= 1024) {
-        // entry e of this table IS entry e of the 64-lane table (thread t of the block holds the entries t, t + 256): the slot sums of the
-        // four-wave body are taken in the order of the 64-lane table, which makes its results those of the one-wave body bit for bit
-        const int per_blk = ((int)n + 255) / 256;
-        std::vector<int32_t> kcb((size_t)per_blk * 256, -1);
-        std::vector<double> lbb((size_t)per_blk * 256, -INFINITY), ubb((size_t)per_blk * 256, INFINITY);
-        for (size_t e = 0; e < n; e++) { kcb[e] = kc[e]; lbb[e] = slb[e]; ubb[e] = sub[e]; }
-        HIP_TRY(hipMemcpyAsync(h->slot_kc_blk, kcb.data(), kcb.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    ihm2::SlotTable t = ihm2::lay_out_slots(h->rows, ihm2::slot_limits(path_class(h)));
+    h->slots_fit = t.fit;
+    if (!t.fit) return 0;
+    h->slots = std::move(t);
+    const ihm2::SlotTable &s = h->slots;
+    const ihm2::ConstraintRows &r = h->rows;
+    if (s.per_blk) {
+        HIP_TRY(hipMemcpyAsync(h->slot_kc_blk, s.kc_blk.data(), s.kc_blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        if (upload_shared(h, lbb.data(), h->slot_lb_blk, lbb.size()) || upload_shared(h, ubb.data(), h->slot_ub_blk, ubb.size())) return -1;
-        h->nslot_lane_blk = per_blk;
+        if (upload_shared(h, s.lb_blk.data(), h->slot_lb_blk, s.lb_blk.size()) || upload_shared(h, s.ub_blk.data(), h->slot_ub_blk, s.ub_blk.size())) return -1;
     }
-    if (upload_shared(h, h->host_lb.data(), h->st_lb, (size_t)NS * NC) || upload_shared(h, h->host_ub.data(), h->st_ub, (size_t)NS * NC) ||
-        upload_shared(h, h->host_sz.data(), h->st_sz, (size_t)NS * NLAM) || upload_shared(h, h->host_sZ.data(), h->st_sZ, (size_t)NS * NLAM))
+    // the SQP mode's copies of the rows
+    if (upload_shared(h, r.lb.data(), h->st_lb, r.lb.size()) || upload_shared(h, r.ub.data(), h->st_ub, r.ub.size()) ||
+        upload_shared(h, r.sz.data(), h->st_sz, r.sz.size()) || upload_shared(h, r.sZ.data(), h->st_sZ, r.sZ.size()))
         return -1;
-    for (size_t e = 0; e < n; e++) { h->host_kc[e] = kc[e]; h->host_slb[e] = slb[e]; h->host_sub[e] = sub[e]; }
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(h->slot_kc, kc.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (const size_t n = s.entries()) {
+        HIP_TRY(hipMemcpyAsync(h->slot_kc, s.kc.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        if (upload_shared(h, slb.data(), h->slot_lb, n) || upload_shared(h, sub.data(), h->slot_ub, n) ||
-            upload_shared(h, zw.data(), h->slot_zw, n) || upload_shared(h, Zw.data(), h->slot_Zw, n))
+        if (upload_shared(h, s.lb.data(), h->slot_lb, n) || upload_shared(h, s.ub.data(), h->slot_ub, n) ||
+            upload_shared(h, s.zw.data(), h->slot_zw, n) || upload_shared(h, s.Zw.data(), h->slot_Zw, n))
             return -1;
     }
     if (h->inst_b) return scatter_instance_bounds(h);      // the per-instance values into the new table (or a refusal: ready() then reports it)
@@ -957,19 +759,8 @@ int ihm2mpc_set_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, 
             for (int j = 0; j < NX; j++) CD[((size_t)k * 2 + r) * 10 + j] = C[((size_t)k * 2 + r) * NX + j];
             for (int j = 0; j < NU; j++) CD[((size_t)k * 2 + r) * 10 + 8 + j] = D[((size_t)k * 2 + r) * NU + j];
         }
-    h->uniform_CD = true;
-    for (int k = 1; k < N && h->uniform_CD; k++)
-        for (int i = 0; i < 20; i++)
-            if (CD[(size_t)k * 20 + i] != CD[i]) { h->uniform_CD = false; break; }
-    for (int k = 0; k < NS; k++)
-        for (int c = 0; c < 12; c++) {       // rows 12, 13 belong to set_path_constraints
-            double lb = -INFINITY, ub = INFINITY;
-            if (c < 8) { if (k >= 1) { lb = lbx[k * 8 + c]; ub = ubx[k * 8 + c]; } }
-            else if (c < 10) { if (k < N) { lb = lbu[k * 2 + c - 8]; ub = ubu[k * 2 + c - 8]; } }
-            else { if (k < N) { lb = lg[k * 2 + c - 10]; ub = ug[k * 2 + c - 10]; } }
-            h->host_lb[k * NC + c] = (std::fabs(lb) < 1e20) ? lb : -INFINITY;
-            h->host_ub[k * NC + c] = (std::fabs(ub) < 1e20) ? ub : INFINITY;
-        }
+    h->uniform_CD = ihm2::stages_equal(CD.data(), N, 20);
+    h->rows.set_box_rows(lbx, ubx, lbu, ubu, lg, ug);
     if (rebuild_slots(h)) return -1;
     if (upload_shared(h, lbx, h->lbx, (size_t)NS * 8) || upload_shared(h, ubx, h->ubx, (size_t)NS * 8) ||
         upload_shared(h, lbu, h->lbu, (size_t)N * 2) || upload_shared(h, ubu, h->ubu, (size_t)N * 2) ||
@@ -999,18 +790,17 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
     if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called (the batch-shared table gives the pattern)");
     const int B = h->B, N = h->N, NS = h->NS;
     std::vector<double> il((size_t)B * NS * 12), iu((size_t)B * NS * 12);
-    for (int b = 0; b < B; b++)
+    for (int b = 0; b < B; b++) {
+        const double *xl = lbx + (size_t)b * NS * 8, *xu = ubx + (size_t)b * NS * 8, *ul = lbu + (size_t)b * N * 2, *uu = ubu + (size_t)b * N * 2;
+        const double *gl = lg + (size_t)b * N * 2, *gu = ug + (size_t)b * N * 2;
         for (int k = 0; k < NS; k++)
             for (int c = 0; c < 12; c++) {
-                double lb = -INFINITY, ub = INFINITY;
-                if (c < 8) { if (k >= 1) { lb = lbx[((size_t)b * NS + k) * 8 + c]; ub = ubx[((size_t)b * NS + k) * 8 + c]; } }
-                else if (c < 10) { if (k < N) { lb = lbu[((size_t)b * N + k) * 2 + c - 8]; ub = ubu[((size_t)b * N + k) * 2 + c - 8]; } }
-                else { if (k < N) { lb = lg[((size_t)b * N + k) * 2 + c - 10]; ub = ug[((size_t)b * N + k) * 2 + c - 10]; } }
+                const auto [lb, ub] = ihm2::box_row(N, k, c, xl, xu, ul, uu, gl, gu);
                 if (lb != lb || ub != ub) return fail("instance %d, stage %d, row %d (%s): bound is NaN", b, k, c, row_name(c));
                 if (lb > ub) return fail("instance %d, stage %d, row %d (%s): lower bound %g > upper bound %g", b, k, c, row_name(c), lb, ub);
-                il[((size_t)b * NS + k) * 12 + c] = (std::fabs(lb) < 1e20) ? lb : -INFINITY;      // as ihm2mpc_set_bounds
-                iu[((size_t)b * NS + k) * 12 + c] = (std::fabs(ub) < 1e20) ? ub : INFINITY;
             }
+        ihm2::box_rows(N, xl, xu, ul, uu, gl, gu, &il[(size_t)b * NS * 12], &iu[(size_t)b * NS * 12], 12);      // as ihm2mpc_set_bounds
+    }
     // the pattern check before anything of the handle changes
     if (check_instance_pattern(h, il.data(), iu.data())) return -1;
     const size_t nb = (size_t)B;
@@ -1035,7 +825,7 @@ int ihm2mpc_set_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft
         const double Z = soft_Z ? soft_Z[i] : -1.0, z = soft_z ? soft_z[i] : 0.0;
         if (Z >= 0.0 && !(z >= 0.0)) return fail("soft_z < 0 at flat index %d (the slack penalty must be non-decreasing)", i);
         if (Z >= 0.0 && !(Z + z > 0.0)) return fail("soft side %d has neither a linear nor a quadratic penalty", i);
-        h->host_sz[i] = z; h->host_sZ[i] = Z;
+        h->rows.sz[i] = z; h->rows.sZ[i] = Z;
     }
     HIP_TRY(hipMemsetAsync(h->slk, 0, (size_t)h->B * h->NS * NLAM * sizeof(double), h->stream));
     if (h->bounds_set && rebuild_slots(h)) return -1;
@@ -1046,7 +836,6 @@ int ihm2mpc_set_path_constraints(ihm2mpc_handle *h, int32_t enable, double car_l
                                  const double *lh, const double *uh)
 {
     CHECK_H(h);
-    const int NS = h->NS;
     if (enable) {
         if (!widths || !lh || !uh) return fail("null argument");
         if (!(car_length >= 0.0) || !(car_width >= 0.0)) return fail("car_length and car_width must be non-negative");
@@ -1056,12 +845,7 @@ int ihm2mpc_set_path_constraints(ihm2mpc_handle *h, int32_t enable, double car_l
         h->car_L = car_length; h->car_W = car_width;
     }
     h->path_on = enable ? 1 : 0;
-    for (int k = 0; k < NS; k++)
-        for (int i = 0; i < NH; i++) {
-            const bool on = enable && k >= 1;       // x_0 is fixed: the rows of stage 0 are constants
-            h->host_lb[k * NC + 12 + i] = (on && std::fabs(lh[i]) < 1e20) ? lh[i] : -INFINITY;
-            h->host_ub[k * NC + 12 + i] = (on && std::fabs(uh[i]) < 1e20) ? uh[i] : INFINITY;
-        }
+    h->rows.set_track_rows(enable != 0, lh, uh);
     if (h->bounds_set && rebuild_slots(h)) return -1;
     return 0;
 }
@@ -1077,12 +861,12 @@ int ihm2mpc_set_alat_constraint(ihm2mpc_handle *h, int32_t enable, double a_lat_
             if (z != z || Z != Z) return fail("soft penalty of the a_lat row is not a number");
             if (Z >= 0.0 && !(z >= 0.0)) return fail("soft_z < 0 on the a_lat row (the slack penalty must be non-decreasing)");
             if (Z >= 0.0 && !(Z + z > 0.0)) return fail("a soft side of the a_lat row has neither a linear nor a quadratic penalty");
-            h->alat_sz[i] = z; h->alat_sZ[i] = Z;
+            h->rows.alat_sz[i] = z; h->rows.alat_sZ[i] = Z;
         }
-        h->alat_lb = (std::fabs(a_lat_min) < 1e20) ? a_lat_min : -INFINITY;
-        h->alat_ub = (std::fabs(a_lat_max) < 1e20) ? a_lat_max : INFINITY;
+        h->rows.alat_lb = ihm2::bound_or(a_lat_min, -INFINITY);
+        h->rows.alat_ub = ihm2::bound_or(a_lat_max, INFINITY);
     }
-    h->alat_on = enable ? 1 : 0;
+    h->rows.alat_on = enable ? 1 : 0;
     HIP_TRY(hipMemsetAsync(h->lam_a, 0, (size_t)h->B * h->NS * 2 * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(h->slk_a, 0, (size_t)h->B * h->NS * 2 * sizeof(double), h->stream));
     if (h->bounds_set && rebuild_slots(h)) return -1;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/ihm2mpc.h"
+#include "ihm2_dims.h"     // NX, NU, NZ, NY, NG, NH, NC, NLAM, MAX_SLOTS
 
 // Floating-point contraction.  The sources are compiled with -ffp-contract=on (Makefile) and switch to `fast` HERE, for everything that follows in
 // the translation unit: a*b + c is then fused wherever the two operations meet, as before -- but by the `contract` flag on the operations, not by
@@ -21,15 +22,8 @@
 // dynamic model's section of model.hpp turns contraction OFF: its results must not depend on what it is inlined into (NOTES.md R4.11).
 #pragma clang fp contract(fast)
 
-#define NX 8
-#define NU 2
-#define NZ 10
-#define NY 12
-#define NG 2
-#define NH 2
-#define NC 14   // two-sided constraint rows per stage: 8 state boxes, 2 input boxes, 2 general rows, 2 track rows
-#define NLAM 28
-#define MAX_SLOTS 640   // 10 per lane
+#include "qp_tables.hpp"      // ConstraintRows, SlotTable: the handle holds one of each
+
 #define QM_PAD 24    // >= 3 x ring depth of the vector / forward sweeps: their unclamped prefetch overshoots an instance by < 3 D rows
 #define LIN_REC 96   // doubles per (instance, interval) linearisation record: A (64) | B (16) | b (8) | rb (8: the QP's dynamics residual, riccati_mfma.hpp)
 
@@ -103,28 +97,21 @@ struct ihm2mpc_handle {
     DevBuf<double> lbu, ubu;             // (N,2)
     DevBuf<double> CD;                   // (N,2,10)  general rows [C D]
     DevBuf<double> lg, ug;               // (N,2)
-    // compact table of the constraint slots that have at least one finite side
-    // -- laid out for the QP kernel: entry lane + 64 r belongs to lane `lane`; a lane's soft slots come first --
-    int nslots, m_act;             // m_act: number of one-sided inequality pairs (finite sides + one per soft slack)
-    int nslot_lane, nsoft_lane;    // slots per lane / leading one-sided entries per lane (the NSOFT of the instantiation that takes the table; 0: all-hard)
+    // the constraint rows as the setters leave them (set_bounds / set_soft / ... may come in any order), and the compact table of the
+    // slots with at least one finite side that rebuild_slots lays out from them for the QP kernels (qp_tables.hpp)
+    ihm2::ConstraintRows rows;
+    ihm2::SlotTable slots;         // the last table that fitted, as the device holds it
     bool slots_fit;                // false: the rows set so far fit no instantiation (reported by the next solve: a later setter may still change them)
-    DevBuf<int32_t> slot_kc;             // (nslot_lane*64) stage * 16 + row, -1 = padding
-    DevBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
-    DevBuf<double> slot_lb_blk, slot_ub_blk;
-    int nslot_lane_blk;            // 0: no such table (soft sides present)
-    bool block_qp;                 // use k_qp_block for batches of at most one instance per CU (IHM2MPC_BLOCK_QP=0 turns it off)
+    DevBuf<int32_t> slot_kc;             // (slots.per_lane*64) stage * 16 + row, -1 = padding
     DevBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
     DevBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot
-    // host copies the table is rebuilt from (set_bounds / set_soft may come in either order)
-    std::vector<double> host_lb, host_ub;     // (NS*NC) per (stage, row), +-inf = absent
-    std::vector<double> host_sz, host_sZ;     // (NS*NLAM) per one-sided constraint: NC lower then NC upper
-    // nonlinear track-boundary rows (rows 12, 13 of the stages 1..N)
+    DevBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
+    DevBuf<double> slot_lb_blk, slot_ub_blk;
+    bool block_qp;                 // use k_qp_block for batches of at most one instance per CU (IHM2MPC_BLOCK_QP=0 turns it off)
+    // nonlinear track-boundary rows (rows 12, 13 of the stages 1..N); the lateral-acceleration row's switch is rows.alat_on
     int path_on;
     double car_L, car_W, lh[NH], uh[NH];
     DevBuf<double> widths;               // (ntracks, 2) = (w_R, w_L)
-    // lateral-acceleration row of the kinematic constraint set (row 14 of the stages 1..N-1; ihm2mpc_set_alat_constraint)
-    int alat_on;
-    double alat_lb, alat_ub, alat_sz[2], alat_sZ[2];      // bounds (+-inf = absent), slack penalties of the lower / upper side (sZ < 0 = hard)
     // Cartesian side (ROS stack): centre-line geometry per track, Cartesian plant state and projection guess per instance
     bool geometry_set;
     DevBuf<double> X_ref, Y_ref, phi_ref;   // (ntracks, nknots)
@@ -170,8 +157,8 @@ struct ihm2mpc_handle {
     int sqp_globalization, sqp_use_suff, sqp_full_step_dual;   // globalization: 0 FIXED_STEP, 1 MERIT_BACKTRACKING
     double sqp_alpha_min, sqp_alpha_red, sqp_eps, sqp_tol[4];
     DevBuf<double> Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
-    DevBuf<double> st_lb, st_ub;           // (NS,NC) device copies of host_lb / host_ub
-    DevBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of host_sz / host_sZ
+    DevBuf<double> st_lb, st_ub;           // (NS,NC) device copies of rows.lb / rows.ub
+    DevBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of rows.sz / rows.sZ
     // allocated together by the first SQP solve (api.hip: sqp_buffers): the iterate the QP was built at, merit weights, per-solve bookkeeping
     DevBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
     DevBuf<int32_t> ls_done, ls_status, ls_iter, ls_qp_acc;
@@ -190,11 +177,9 @@ struct ihm2mpc_handle {
     bool shared_uniform_H;         // uniform_H of the batch-shared weights (restored when the per-instance weights go)
     DevBuf<double> iHs, iGy, iWd;          // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
     std::vector<double> ih_lb, ih_ub;      // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
-    DevBuf<double> i_slot_lb, i_slot_ub;   // (B,nslot_lane*64) the slot table's bounds per instance, grown on demand
+    DevBuf<double> i_slot_lb, i_slot_ub;   // (B,slots.per_lane*64) the slot table's bounds per instance, grown on demand
     DevBuf<double> i_st_lb, i_st_ub;       // (B,NS,NC) the SQP mode's bounds per instance
     DevBuf<double> i_lbu, i_ubu, i_lg, i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
-    std::vector<int32_t> host_kc;          // host copies of the slot table (MAX_SLOTS): the per-instance values are scattered into its pattern
-    std::vector<double> host_slb, host_sub;
 
     // ---- history of ihm2mpc_run_steps, grown on demand ----
     DevBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)

@@ -42,6 +42,7 @@
 #include "riccati_mfma.hpp"
 #include "sens_body.hpp"
 #include "qp_lds.hpp"
+#include "qp_catalogue.hpp"
 #include "wave_sync.hpp"
 
 using namespace ihm2;
@@ -1364,52 +1365,11 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 #ifndef QP_SET
 #error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities), -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep), -DQP_SET=5 or -DQP_SET=6 (the all-hard RTI loops with the closed-form actuator lags: general form / straight-line factor sweep)"
 #endif
-// The instantiations of this object: its part of the catalogue api.hip selects from, which takes the first entry that holds a table,
-// so that an NSLOT comes before the larger ones of the same kind.  WAVE(NSLOT, NSOFT, PATH, UNI) k_qp_wave, BLOCK(NSLOT, UNI, NW)
-// k_qp_block, STEPS(NSLOT, NSOFT, PATH, UNI, IRK, DYN) k_steps in both SQP modes (QP_SET = 3: in the RTI mode, with SENS = 1).
-#if QP_SET == 0
-#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
-    BLOCK(2, 0, 4) BLOCK(2, 1, 4)                                                                                                         \
-    WAVE(5, 0, 0, 0) WAVE(5, 0, 0, 1) WAVE(8, 0, 0, 0) WAVE(8, 0, 0, 1) WAVE(10, 0, 0, 0) WAVE(10, 0, 0, 1)                               \
-    STEPS(5, 0, 0, 0, 0, 0) STEPS(5, 0, 0, 1, 0, 0) STEPS(5, 0, 0, 1, 1, 0)                                                               \
-    STEPS(8, 0, 0, 0, 0, 0) STEPS(8, 0, 0, 1, 0, 0) STEPS(8, 0, 0, 1, 1, 0)                                                               \
-    STEPS(10, 0, 0, 1, 0, 0) STEPS(10, 0, 0, 1, 1, 0)
-#elif QP_SET == 1
-#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
-    WAVE(8, 2, 0, 0) WAVE(8, 2, 0, 1) WAVE(10, 4, 0, 0) WAVE(10, 4, 0, 1)                                                                 \
-    WAVE(8, 0, 1, 0) WAVE(8, 0, 1, 1) WAVE(8, 3, 1, 0) WAVE(8, 3, 1, 1) WAVE(10, 4, 1, 0) WAVE(10, 4, 1, 1)                               \
-    WAVE(8, 0, 2, 1) WAVE(10, 4, 2, 1)                                                                                                    \
-    STEPS(8, 2, 0, 1, 0, 0) STEPS(8, 2, 0, 1, 1, 0) STEPS(10, 4, 0, 1, 0, 0) STEPS(10, 4, 0, 1, 1, 0)                                     \
-    STEPS(8, 0, 1, 1, 0, 0) STEPS(8, 0, 1, 1, 1, 0) STEPS(8, 3, 1, 1, 0, 0) STEPS(8, 3, 1, 1, 1, 0)                                       \
-    STEPS(10, 4, 1, 1, 0, 0) STEPS(10, 4, 1, 1, 1, 0)
-#elif QP_SET == 2
-#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
-    STEPS(5, 0, 0, 1, 0, 1) STEPS(5, 0, 0, 1, 1, 1) STEPS(8, 0, 0, 1, 0, 1) STEPS(8, 0, 0, 1, 1, 1)                                       \
-    STEPS(8, 2, 0, 1, 0, 1) STEPS(8, 2, 0, 1, 1, 1) STEPS(10, 4, 0, 1, 0, 1) STEPS(10, 4, 0, 1, 1, 1)                                     \
-    STEPS(8, 0, 1, 1, 0, 1) STEPS(8, 0, 1, 1, 1, 1) STEPS(8, 3, 1, 1, 0, 1) STEPS(8, 3, 1, 1, 1, 1)                                       \
-    STEPS(10, 4, 1, 1, 0, 1) STEPS(10, 4, 1, 1, 1, 1)
-#elif QP_SET == 3
-#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
-    STEPS(5, 0, 0, 0, 0, 0) STEPS(5, 0, 0, 1, 0, 0) STEPS(5, 0, 0, 1, 1, 0)                                                               \
-    STEPS(8, 0, 0, 0, 0, 0) STEPS(8, 0, 0, 1, 0, 0) STEPS(8, 0, 0, 1, 1, 0)                                                               \
-    STEPS(10, 0, 0, 1, 0, 0) STEPS(10, 0, 0, 1, 1, 0)                                                                                     \
-    STEPS(8, 2, 0, 1, 0, 0) STEPS(8, 2, 0, 1, 1, 0) STEPS(10, 4, 0, 1, 0, 0) STEPS(10, 4, 0, 1, 1, 0)                                     \
-    STEPS(8, 0, 1, 1, 0, 0) STEPS(8, 0, 1, 1, 1, 0) STEPS(8, 3, 1, 1, 0, 0) STEPS(8, 3, 1, 1, 1, 0)                                       \
-    STEPS(10, 4, 1, 1, 0, 0) STEPS(10, 4, 1, 1, 1, 0)
-#elif QP_SET == 5
-// IRK = 2: the all-hard kinematic RTI loops with the closed-form actuator lags (IHM2MPC_INTEG_ERK_LAG), in objects of their own so that the
-// images of the other sets stay what they were.  SENS = 0 only: ihm2mpc_run_steps_sens launches per step on such a handle.
-#define QP_INSTANCES(WAVE, BLOCK, STEPS)                                                                                                  \
-    STEPS(5, 0, 0, 0, 2, 0) STEPS(5, 0, 0, 1, 2, 0) STEPS(8, 0, 0, 0, 2, 0) STEPS(8, 0, 0, 1, 2, 0) STEPS(10, 0, 0, 1, 2, 0)
-#elif QP_SET == 6
-// ... and the benchmarked table's loop with the straight-line factor sweep, as QP_SET = 4 (Makefile: the same flags)
-#define QP_INSTANCES(WAVE, BLOCK, STEPS) STEPS(5, 0, 0, 1, 2, 0)
-#elif QP_SET == 4
-// The reference's OCP (all sides hard, batch-shared weights, RTI, RK4, kinematic model) with the factor sweep in its straight-line form
-// (qp_wave_body: NF): per-step QP and persistent loop, for the horizon 40 as a compile-time constant and for any horizon.  An object of
-// its own (Makefile: without the compiler's own loop unrolling), so that the images of the other sets stay what they were.
-#define QP_INSTANCES(WAVE, BLOCK, STEPS) WAVE(5, 0, 0, 1) STEPS(5, 0, 0, 1, 0, 0)
-#endif
+// The instantiations of this object: its part of the catalogue api.hip selects from (qp_catalogue.hpp: QP_INSTANCES_0 .. QP_INSTANCES_6,
+// where the lists and the meaning of WAVE, BLOCK, STEPS are written down); below, the expansion of its entries to kernel pointers.
+#define QP_INSTANCES_(n) QP_INSTANCES_##n
+#define QP_INSTANCES_OF(n) QP_INSTANCES_(n)
+#define QP_INSTANCES QP_INSTANCES_OF(QP_SET)
 
 #if QP_SET == 4 || QP_SET == 6
 #define WAVE(NS, NO, PT, UN)                                                                          \

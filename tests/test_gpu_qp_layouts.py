@@ -1,7 +1,8 @@
 """Every instantiation of the QP kernels on constraint layouts built for them (tests/layouts.py), in both scheduler builds.
 
-Which instantiation runs is decided by the slot table api.hip::rebuild_slots packs from the rows (slots per lane, leading one-sided
-entries per lane) and by the catalogue of instantiations it is selected from (kernels_qp.hip: QP_INSTANCES).  Each layout below is
+Which instantiation runs is decided by the slot table api.hip::rebuild_slots lays out from the rows (csrc/qp_tables.hpp: lay_out_slots --
+slots per lane, leading one-sided entries per lane; tests/test_slot_table.py checks the tables themselves without a GPU) and by the
+catalogue of instantiations it is selected from (csrc/qp_catalogue.hpp: QP_INSTANCES_0 .. 6).  Each layout below is
 named for the table it is meant to give; the launch record (BatchedOcpSolver.get_launch_record) says what actually ran, and the last test checks
 that the module as a whole launched exactly the list of instantiations written there.
 
@@ -28,52 +29,7 @@ pytestmark = pytest.mark.gpu
 RECORDS = set()
 
 Lay = L.Layout
-# name -> (layout, batch size, IHM2MPC_BLOCK_QP); B > 256 (the CU count) or BLOCK_QP = 0 keeps the all-hard tables on k_qp_wave
-TABLE = {
-    # all-hard tables without track rows: 8 rows per stage (reference layout) -> 8 N slots; 12 per stage with every state box
-    "hard_5_per_lane": (Lay("hard_5_per_lane", N=40), 300, "1"),                                   # 320 slots
-    "hard_5_per_lane_stage_W": (Lay("hard_5_per_lane_stage_W", N=40, stage_W=True, seed=1), 300, "1"),
-    "hard_6_per_lane": (Lay("hard_6_per_lane", N=41), 96, "0"),                                    # 328 slots
-    "hard_8_per_lane_stage_rows": (Lay("hard_8_per_lane_stage_rows", N=64, grows="stagevary"), 96, "0"),   # 512
-    "hard_9_per_lane": (Lay("hard_9_per_lane", N=65), 65, "0"),                                    # 520
-    "hard_10_per_lane_all_boxes": (Lay("hard_10_per_lane_all_boxes", N=53, xbox="all"), 96, "0"),          # 636
-    "hard_10_per_lane_stage_W": (Lay("hard_10_per_lane_stage_W", N=53, xbox="all", stage_W=True, seed=2), 96, "0"),
-    "hard_random_one_sided": (Lay("hard_random_one_sided", N=40, xbox="random", one_sided=0.5, seed=3), 130, "0"),
-    "hard_narrow_rate_row": (Lay("hard_narrow_rate_row", N=40, grows="narrow", seed=4), 96, "0"),
-    "empty_table": (Lay("empty_table", N=40, xbox="none", ubox=False, grows="none"), 70, "0"),
-    # the four-wave kernel: B <= CU count, BLOCK_QP on; B = 1
-    "block_hard": (Lay("block_hard", N=40), 64, "1"),
-    "block_hard_B1": (Lay("block_hard_B1", N=40), 1, "1"),
-    "block_hard_stage_W": (Lay("block_hard_stage_W", N=40, stage_W=True, seed=5), 33, "1"),
-    # soft tables without track rows: <8,2,0> up to 2 soft sides per lane, <10,4,0> up to 4
-    "soft_2_per_lane": (Lay("soft_2_per_lane", N=40, soft=1.0, soft_rows=(1,), soft_kind="both", seed=6), 96, "1"),        # 80 soft sides
-    "soft_2_per_lane_stage_W": (Lay("soft_2_per_lane_stage_W", N=40, soft=1.0, soft_rows=(1,), soft_kind="lower", stage_W=True, seed=7), 96, "1"),
-    # two rows soft on one side and hard on the other in one lane: their soft halves must lead the lane ([s, s, h, h], not [s, h, s, h])
-    "soft_2_per_lane_split_rows": (Lay("soft_2_per_lane_split_rows", N=40, soft=1.0, soft_rows=(1, 3), soft_kind="lower", seed=17), 96, "1"),
-    "soft_3_per_lane_asym": (Lay("soft_3_per_lane_asym", N=40, soft=1.0, soft_rows=(1, 3), soft_kind="asym", seed=8), 96, "1"),   # 160
-    "soft_4_per_lane_mixed": (Lay("soft_4_per_lane_mixed", N=40, soft=1.0, soft_rows=(1, 3, 11), soft_kind="random", seed=9), 130, "1"),
-    "soft_4_per_lane_stage_rows": (Lay("soft_4_per_lane_stage_rows", N=40, soft=1.0, soft_rows=(1, 3), grows="stagevary", seed=10), 96, "1"),
-    "soft_one_sided_rows_padding": (Lay("soft_one_sided_rows_padding", N=40, xbox="all", one_sided=0.6, soft=0.4, soft_rows=(1, 4), seed=11), 96, "1"),
-    # track rows: <8,0,1> all hard, <8,3,1> up to 3 soft sides per lane, <10,4,1> up to 4
-    "path_hard": (Lay("path_hard", N=40, path=True), 96, "1"),
-    "path_hard_stage_W": (Lay("path_hard_stage_W", N=40, path=True, stage_W=True, seed=12), 96, "1"),
-    "path_soft_3_per_lane": (Lay("path_soft_3_per_lane", N=40, path=True, path_soft="upper", ubox=False, width=1.2), 96, "1"),       # 80
-    "path_soft_3_per_lane_stage_W": (Lay("path_soft_3_per_lane_stage_W", N=40, path=True, path_soft="upper", ubox=False, width=1.2, stage_W=True, seed=13), 96, "1"),
-    "path_soft_both_sides": (Lay("path_soft_both_sides", N=40, path=True, path_soft=True, width=1.2), 96, "1"),       # 160
-    "path_soft_4_per_lane": (Lay("path_soft_4_per_lane", N=40, path=True, path_soft=True, soft=1.0, soft_rows=(3,), soft_kind="lower", width=1.2, seed=14), 96, "1"),
-    "path_soft_4_per_lane_stage_W": (Lay("path_soft_4_per_lane_stage_W", N=40, path=True, path_soft=True, soft=1.0, soft_rows=(3,), soft_kind="upper", width=1.2, stage_W=True, seed=15), 96, "1"),
-    # the lateral-acceleration row
-    "alat_hard": (Lay("alat_hard", N=40, path=True, alat=True, alat_max=4.5), 96, "1"),
-    "alat_soft": (Lay("alat_soft", N=40, path=True, alat=True, path_soft=True, alat_soft=True, alat_max=2.5, width=1.2), 96, "1"),
-}
-# past a limit: refused by ready() (reported by the first call that needs the table)
-REFUSED = {
-    "hard_11_per_lane": Lay("hard_11_per_lane", N=54, xbox="all"),                                   # 648 slots
-    "soft_5_per_lane": Lay("soft_5_per_lane", N=40, soft=1.0, soft_rows=(1, 3, 6, 7), soft_kind="both", seed=16),      # 320 soft sides: 5 per lane
-    # all-hard tables with track rows: <8,0,1> and <8,0,2> take at most 8 slots per lane
-    "path_hard_9_per_lane": Lay("path_hard_9_per_lane", N=40, path=True, xbox="all"),                 # 560 slots
-    "alat_hard_10_per_lane": Lay("alat_hard_10_per_lane", N=40, path=True, alat=True, alat_max=10.0, xbox="all"),    # 599 slots
-}
+TABLE, REFUSED = L.TABLE, L.REFUSED       # the layouts and the tables they are named for: tests/layouts.py
 
 EXPECTED_QP = {
     "k_qp_wave<5,0,0,0>", "k_qp_wave<5,0,0,1>", "k_qp_wave<8,0,0,0>", "k_qp_wave<8,0,0,1>", "k_qp_wave<10,0,0,0>", "k_qp_wave<10,0,0,1>",

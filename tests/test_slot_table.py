@@ -1,0 +1,123 @@
+"""The constraint-slot tables of the QP kernels (csrc/qp_tables.hpp: lay_out_slots, called by api.hip::rebuild_slots) without a GPU.
+
+For every layout tests/test_gpu_qp_layouts.py runs or sees refused, and the smallest shapes, the problem is written to a file as the
+solver pushes it (the layout's arrays, the OCP's own track-row and a_lat settings) and tools/probes/check_slot_table.cpp -- built with
+the address and undefined-behaviour sanitizers -- lays the table out through the functions api.hip calls and checks what the kernels
+take from it unchecked: row coverage, one lane per split row, the leading one-sided entries with the soft ones first, padding, the
+first instantiation of the catalogue that fits, the counts, the lane balance, the 256-lane table, the per-instance scatter and the
+weight tables.  Here: the fit / refusal of each layout, the instantiation it is named for, and the tables themselves, entry for entry, as
+digests against tests/golden/slot_tables.json -- recorded from the tables the library uploaded BEFORE the layout code moved into the
+header (tests/golden/make_slot_tables.py), so they pin the entry order every bit of the QP's results depends on."""
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import layouts as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
+
+# the smallest shapes: the horizons 2 and 3 of the reference layout (fewer rows than lanes), and no row at all
+SMALL = {
+    "ref_N2": L.Layout("ref_N2", N=2),
+    "ref_N3": L.Layout("ref_N3", N=3),
+    "empty_table_N2": L.Layout("empty_table_N2", N=2, xbox="none", ubox=False, grows="none"),
+}
+FIT = {**{n: t[0] for n, t in L.TABLE.items()}, **SMALL}
+LAYOUTS = {**FIT, **L.REFUSED}
+
+# The per-step instantiation k_qp_wave<NSLOT, NSOFT, PATH, .> each layout is named for -- what test_gpu_qp_layouts.py's launch records
+# showed for it before the layout code moved (k_qp_block<2,.,4> runs the "block_*" tables: those of <5,0,0> over 256 lanes).
+NAMED_FOR = {
+    "hard_5_per_lane": (5, 0, 0), "hard_5_per_lane_stage_W": (5, 0, 0), "hard_6_per_lane": (8, 0, 0), "hard_8_per_lane_stage_rows": (8, 0, 0),
+    "hard_9_per_lane": (10, 0, 0), "hard_10_per_lane_all_boxes": (10, 0, 0), "hard_10_per_lane_stage_W": (10, 0, 0),
+    "hard_random_one_sided": (5, 0, 0), "hard_narrow_rate_row": (5, 0, 0), "empty_table": (5, 0, 0),
+    "block_hard": (5, 0, 0), "block_hard_B1": (5, 0, 0), "block_hard_stage_W": (5, 0, 0),
+    "soft_2_per_lane": (8, 2, 0), "soft_2_per_lane_stage_W": (8, 2, 0), "soft_2_per_lane_split_rows": (8, 2, 0),
+    "soft_3_per_lane_asym": (10, 4, 0), "soft_4_per_lane_mixed": (10, 4, 0), "soft_4_per_lane_stage_rows": (10, 4, 0),
+    "soft_one_sided_rows_padding": (8, 2, 0),
+    "path_hard": (8, 0, 1), "path_hard_stage_W": (8, 0, 1), "path_soft_3_per_lane": (8, 3, 1), "path_soft_3_per_lane_stage_W": (8, 3, 1),
+    "path_soft_both_sides": (10, 4, 1), "path_soft_4_per_lane": (10, 4, 1), "path_soft_4_per_lane_stage_W": (10, 4, 1),
+    "alat_hard": (8, 0, 2), "alat_soft": (10, 4, 2),
+    "ref_N2": (5, 0, 0), "ref_N3": (5, 0, 0), "empty_table_N2": (5, 0, 0),
+}
+
+
+def problem_text(lay) -> str:
+    """The problem of a layout as check_slot_table.cpp reads it: what test_gpu_qp_layouts.py::_solver leaves in the handle."""
+    data = L.make_ocp(lay).flatten()
+    arr = L.apply(data, lay)
+
+    def nums(a):
+        return " ".join(repr(float(v)) for v in np.asarray(a, dtype=np.float64).ravel())
+
+    out = [lay.name, str(lay.N)] + [nums(arr[n]) for n in ("lbx", "ubx", "lbu", "ubu", "C", "D", "lg", "ug")]
+    soft = data.soft_Z is not None and bool(np.any(np.asarray(data.soft_Z) >= 0.0))         # BatchedOcpSolver._push_soft
+    out.append("1 " + nums(data.soft_z) + " " + nums(data.soft_Z) if soft else "0")
+    out.append("1 " + nums(data.lh) + " " + nums(data.uh) if data.path_on else "0")
+    if data.path_on and data.alat_on:
+        out.append("1 " + nums([data.alat_lb, data.alat_ub]))
+        out.append("0" if data.alat_soft_Z is None else "1 " + nums(np.zeros(2) if data.alat_soft_z is None else data.alat_soft_z) + " " + nums(data.alat_soft_Z))
+    else:
+        out.append("0")
+    return "\n".join(out) + "\n"
+
+
+def wave_entries():
+    """(NSLOT, NSOFT, PATH) of the WAVE entries of the catalogue, in its order."""
+    text = open(os.path.join(CSRC, "qp_catalogue.hpp")).read()
+    lists = re.findall(r"#define QP_INSTANCES_(\d)\(WAVE, BLOCK, STEPS\)((?:.*\\\n)*.*)\n", text)
+    assert [n for n, _ in lists] == list("0123456")
+    return [tuple(int(v) for v in m[:3]) for _, body in lists for m in re.findall(r"\bWAVE\((\d+), (\d+), (\d+), (\d+)\)", body)]
+
+
+@pytest.fixture(scope="module")
+def tables(tmp_path_factory):
+    """name -> (fit, per_lane, nsoft, total, m_act, digest) of every layout, from one run of the probe."""
+    tmp = tmp_path_factory.mktemp("slot_table")
+    exe = str(tmp / "check_slot_table")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tools", "probes", "check_slot_table.cpp")])
+    files = []
+    for name, lay in LAYOUTS.items():
+        files.append(str(tmp / (name + ".txt")))
+        with open(files[-1], "w") as f:
+            f.write(problem_text(lay))
+    out = subprocess.run([exe] + files, capture_output=True, text=True)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-4000:] + out.stderr[-4000:]
+    res = {}
+    for line in out.stdout.splitlines()[:len(files)]:
+        name, fit, per_lane, nsoft, total, m_act, digest = line.split()
+        res[name] = (int(fit), int(per_lane), int(nsoft), int(total), int(m_act), digest)
+    assert list(res) == list(LAYOUTS)
+    return res
+
+
+def test_catalogue_lists_are_the_ones_the_layouts_are_named_for():
+    waves = wave_entries()
+    assert len(waves) == 19 and set(NAMED_FOR) == set(FIT)
+    assert set(NAMED_FOR.values()) == set(waves)          # every per-step instantiation has a layout
+
+
+@pytest.mark.parametrize("name", list(LAYOUTS))
+def test_layout_fits_the_instantiation_it_is_named_for(tables, name):
+    fit, per_lane, nsoft, _, _, _ = tables[name]
+    if name in L.REFUSED:
+        assert fit == 0
+        return
+    assert fit == 1
+    lay = LAYOUTS[name]
+    path = 2 if lay.alat else 1 if lay.path else 0
+    first = next(w for w in wave_entries() if w[2] == path and w[1] == nsoft and w[0] >= per_lane)
+    assert first == NAMED_FOR[name], (per_lane, nsoft)
+
+
+@pytest.mark.parametrize("name", list(LAYOUTS))
+def test_table_is_the_recorded_one_entry_for_entry(tables, name):
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "slot_tables.json")))
+    g = golden[name]
+    assert tables[name] == (g["fit"], g["per_lane"], g["nsoft"], g["total"], g["m_act"], g["digest"])
