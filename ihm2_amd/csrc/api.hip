@@ -101,6 +101,7 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
 {
     const int B = h->B;
     h->inst_b_ok = false;
+    h->slots_full = false;
     if (check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
     const size_t n = h->slots.entries();
     if ((size_t)B * n > h->i_slot_lb.size()) {
@@ -114,14 +115,15 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
     if (n && (upload_shared(h, slb.data(), h->i_slot_lb, slb.size()) || upload_shared(h, sub.data(), h->i_slot_ub, sub.size()))) return -1;
     if (upload_shared(h, stl.data(), h->i_st_lb, stl.size()) || upload_shared(h, stu.data(), h->i_st_ub, stu.size())) return -1;
     h->inst_b_ok = true;
+    h->slots_full = ihm2::slot_table_full(h->slots, 5) && ihm2::slot_bounds_full(h->slots, B, slb, sub);
     return 0;
 }
 
 // ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
-// The catalogue is the seven objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
+// The catalogue is the eight objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
 // (the leading one-sided entries per lane rebuild_slots laid it out for) and its NSLOT holds the table's slots per lane; of those
 // that fit the configuration, the first in catalogue order is launched.
-const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6()};
+const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6(), ihm2_qp_set7()};
 
 // the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
 int path_class(const ihm2mpc_handle *h) { return h->rows.alat_on ? 2 : h->path_on ? 1 : 0; }
@@ -133,7 +135,7 @@ const QpInst *find_inst(const QpKey &want)
         for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
             const QpKey &k = e->key;
             if (k.kind == want.kind && k.nsoft == want.nsoft && k.path == want.path && k.uni == want.uni && k.sqp == want.sqp &&
-                k.irk == want.irk && k.dyn == want.dyn && k.sens == want.sens && k.nf == want.nf && k.nslot >= want.nslot)
+                k.irk == want.irk && k.dyn == want.dyn && k.sens == want.sens && k.nf == want.nf && k.full == want.full && k.nslot >= want.nslot)
                 return e;
         }
     return nullptr;
@@ -142,18 +144,33 @@ const QpInst *find_inst(const QpKey &want)
 // The form of the factor sweep the handle's QP may take (QpKey.nf; riccati_mfma.hpp: PLAIN).  The straight-line stage keeps neither the
 // symmetrising tile (the dynamic model as written needs it) nor the p_k stores (a table without active rows needs them): 0 then.  Otherwise
 // 40 for the horizon 40 -- the horizon as a compile-time constant -- and -1 for every other one.  IHM2MPC_QP_FORM (read once) makes the
-// forms comparable in one build: 1 keeps the horizon 40 on the run-time form as well, 0 keeps every launch on the general form.
+// forms comparable in one build: 2 keeps the slot phases on their general form (slot_form), 1 keeps the horizon 40 on the run-time form
+// as well, 0 keeps every launch on the general form.
+int qp_form_limit()
+{
+    static const int limit = [] { const char *e = getenv("IHM2MPC_QP_FORM"); return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : (e && e[0] == '2') ? 2 : 3; }();
+    return limit;
+}
 int factor_form(const ihm2mpc_handle *h)
 {
-    static const int limit = [] { const char *e = getenv("IHM2MPC_QP_FORM"); return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : 2; }();
+    const int limit = qp_form_limit();
     if (limit == 0 || h->cfg.model == IHM2MPC_MODEL_FDYN6 || h->slots.m_act == 0) return 0;
-    return (h->N == 40 && limit == 2) ? 40 : -1;
+    return (h->N == 40 && limit >= 2) ? 40 : -1;
 }
+// The form of the slot phases (QpKey.full; kernels_qp.hip: qp_wave_body, FULL): 1 where the handle's table -- with its per-instance bounds,
+// if it has any -- is full (qp_tables.hpp: slot_table_full, evaluated where the table is laid out and where bounds are uploaded) and the
+// factor sweep takes the compiled-in horizon, the one form the catalogue has it with.
+int slot_form(const ihm2mpc_handle *h) { return (qp_form_limit() == 3 && h->slots_full && factor_form(h) == 40) ? 1 : 0; }
 
 // find_inst with the factor sweep in the form the handle may take, where the catalogue has the instantiation in that form (the
-// compile-time horizon first, then the run-time one), else in the general form
+// full slot form first, then the compile-time horizon, then the run-time one), else in the general form
 const QpInst *find_form(const ihm2mpc_handle *h, QpKey want)
 {
+    if (slot_form(h)) {
+        want.nf = 40; want.full = 1;
+        if (const QpInst *e = find_inst(want)) return e;
+        want.full = 0;
+    }
     for (int nf = factor_form(h); nf != 0; nf = (nf > 0) ? -1 : 0) {
         want.nf = nf;
         if (const QpInst *e = find_inst(want)) return e;
@@ -216,9 +233,9 @@ void note_launch(ihm2mpc_handle *h, const QpKey &k, int per_step = 0)
     const int form = (k.nf > 0) ? 2 : (k.nf < 0) ? 1 : 0;       // [15] bits 8..9 / 12..13: the factor sweep's form (QpKey.nf)
     if (k.kind != QP_STEPS) {
         r[0] = k.kind; r[1] = k.nslot; r[2] = k.nsoft; r[3] = k.path; r[4] = k.uni;
-        r[15] = (r[15] & ~0x300) | (form << 8);
+        r[15] = (r[15] & ~0x700) | (form << 8) | ((k.full ? 1 : 0) << 10);        // bit 10 / 14: the slot phases' form (QpKey.full)
     } else {
-        r[15] = (r[15] & ~0x3000) | ((per_step ? 0 : form) << 12);
+        r[15] = (r[15] & ~0x7000) | ((per_step ? 0 : form) << 12) | ((!per_step && k.full ? 1 : 0) << 14);
         r[5] = per_step ? 2 : 1; r[6] = k.nslot; r[7] = k.nsoft; r[8] = k.path; r[9] = k.uni; r[10] = k.sqp; r[11] = k.irk; r[12] = k.dyn;
         r[13] = per_step; r[14] = k.sens;
     }
@@ -529,6 +546,7 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
                   h->q_g, B * NS * 10, h->q_rg, B * NS * 10, h->q_P, B * NS * 64, h->q_M, (B * N + 2 * QM_PAD) * 64, h->scratch, B * 24))
         return -1;
     h->slots_fit = true;
+    h->slots_full = false;
     h->sqp_globalization = 0; h->sqp_use_suff = 0; h->sqp_full_step_dual = 0;
     h->sqp_alpha_min = 0.05; h->sqp_alpha_red = 0.7; h->sqp_eps = 1e-4;
     for (int i = 0; i < 4; i++) h->sqp_tol[i] = cfg->nlp_tol;
@@ -720,6 +738,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
 {
     ihm2::SlotTable t = ihm2::lay_out_slots(h->rows, ihm2::slot_limits(path_class(h)));
     h->slots_fit = t.fit;
+    h->slots_full = false;      // until a table and every bound that goes with it are on the device (a table that does not fit: launches are refused)
     if (!t.fit) return 0;
     h->slots = std::move(t);
     const ihm2::SlotTable &s = h->slots;
@@ -741,6 +760,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
             return -1;
     }
     if (h->inst_b) return scatter_instance_bounds(h);      // the per-instance values into the new table (or a refusal: ready() then reports it)
+    h->slots_full = ihm2::slot_table_full(s, 5);            // (5: the NSLOT of the catalogue's full-form pair)
     return 0;
 }
 
@@ -784,6 +804,7 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
         h->i_lbu.reset(); h->i_ubu.reset(); h->i_lg.reset(); h->i_ug.reset();
         h->ih_lb = std::vector<double>(); h->ih_ub = std::vector<double>();
         h->inst_b = false; h->inst_b_ok = false;
+        h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, 5);        // the batch-shared bounds again
         return 0;
     }
     if (!lbx || !ubx || !lbu || !ubu || !lg || !ug) return fail("lbx, ubx, lbu, ubu, lg, ug must all be given, or all be NULL (batch-shared bounds again)");

@@ -101,6 +101,7 @@ struct ihm2mpc_handle {
     // slots with at least one finite side that rebuild_slots lays out from them for the QP kernels (qp_tables.hpp)
     ihm2::ConstraintRows rows;
     ihm2::SlotTable slots;         // the last table that fitted, as the device holds it
+    bool slots_full;               // the table (with the per-instance bounds, if any) takes the full slot form (qp_tables.hpp: slot_table_full)
     bool slots_fit;                // false: the rows set so far fit no instantiation (reported by the next solve: a later setter may still change them)
     DevBuf<int32_t> slot_kc;             // (slots.per_lane*64) stage * 16 + row, -1 = padding
     DevBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
@@ -314,13 +315,14 @@ struct StepArgs {
 // void pointer: a function with the unnamed namespace's type in its signature could not be defined in another translation unit.)
 void ihm2_sens_args(const ihm2mpc_handle *h, void *out);
 
-// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0 .. 6) returns the table of the ones it
+// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0 .. 7) returns the table of the ones it
 // holds, in its order of preference (kernels_qp.hip: QP_INSTANCES).  A key holds the template parameters as the launch record gives them
 // (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.  nf is not in the record: the
 // form of the factor sweep (qp_wave_body: 0 the general form, 40 straight-line with the horizon 40 compiled in, -1 straight-line with the
-// run-time horizon) -- same results, so the record names the kernel by its other parameters.
+// run-time horizon) -- same results, so the record names the kernel by its other parameters.  full: the form of the slot phases alike
+// (qp_wave_body: FULL; 1 for the tables of qp_tables.hpp: slot_table_full), reported beside nf in the record's [15].
 enum { QP_WAVE = 1, QP_BLOCK = 2, QP_STEPS = 3 };
-struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens, nf; };
+struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens, nf, full; };
 struct QpInst { QpKey key; int threads; const void *kernel; };
 struct QpTable { const QpInst *inst; int n; };
-QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6();
+QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6(), ihm2_qp_set7();

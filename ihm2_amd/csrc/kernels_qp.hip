@@ -62,6 +62,10 @@ namespace {
 #define SWEEP_DL ((SWEEP_RING >= 8) ? 4 : 2)       // stages the LDS operands are fetched ahead
 
 __device__ __forceinline__ bool fin(double v) { return fabs(v) < INF_BOUND; }
+// A value the compiler takes as new wherever it is asked for: what is computed from it stays where it is used.  (The fields unpacked from a
+// slot's packed index are loop-invariant; hoisted out of the interior-point iteration they are held in registers of their own, more than the
+// packing saves.)
+__device__ __forceinline__ int here(int v) { asm volatile("" : "+v"(v)); return v; }
 
 // Lane exchanges at VALU speed (no LDS crossbar): DPP moves inside a 16-lane row (dpp_mov, riccati_mfma.hpp), v_permlane16_swap /
 // v_permlane32_swap (gfx950) across rows and halves.
@@ -191,10 +195,17 @@ __device__ __forceinline__ void stream_rows_v1(const double *rows, int N, int e_
 // NF != 0: the factor sweep in its straight-line form (riccati_mfma.hpp: PLAIN) -- for the launches api.hip selects it for: a table with
 // active rows (no p_k stores) of a model that needs no symmetrising tile.  NF > 0: with the horizon a.N == NF as a compile-time constant;
 // NF = -1: with the run-time horizon.  NF = 0 is the form every other instantiation keeps.
-template <int NSLOT, int NSOFT, int PATH, int UNI, int NW = 1, int LEAN = 1, int NF = 0>
+// FULL != 0: the slot phases in their straight-line form -- for the tables api.hip selects it for (qp_tables.hpp: slot_table_full): every one of
+// the 64 NSLOT entries is a hard row with both sides finite, no track or a_lat row among them.  The same operations in the same order on the
+// same values as the general form, without its questions: no validity or side test per slot, the row's word index and its general-row flag
+// formed once per solve where the slot is loaded, and cf / gam zeroed once per solve instead of in every coefficient pass (qp_lds.hpp:
+// qp_full_zeroes_kept).
+template <int NSLOT, int NSOFT, int PATH, int UNI, int NW = 1, int LEAN = 1, int NF = 0, int FULL = 0>
 __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, double *sm, const bool want_res = true)
 {
     static_assert(NF == 0 || NW == 1, "the straight-line factor sweep parks its idle lanes' stores in the tile the block reductions use");
+    static_assert(FULL == 0 || (NSOFT == 0 && PATH == 0 && UNI != 0 && NW == 1 && LEAN != 0 && NF > 0 && NSLOT <= 8),
+                  "the full slot form is written for the all-hard table of the batch-shared rows, one wave, the lean phases and the compiled-in horizon");
     // want_res = false (wave-uniform): the stationarity residual of the incoming iterate -- an output only (ihm2mpc_get_residuals), a third of
     // the QP set-up -- is skipped; the persistent RTI loop asks for it on its last step alone
     constexpr int NT = 64 * NW;
@@ -220,6 +231,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     static_assert(qp_sweeps_inside(qp_lds(40, CLS), 40, LEAN != 0, SWEEP_RING, SWEEP_DL) && (LEAN == 0 || qp_sweeps_inside(qp_lds(2, CLS), 2, true, SWEEP_RING, SWEEP_DL)),
                   "the sweeps' unclamped LDS prefetch leaves the block (the earlier form does below N = 4: api.hip refuses those launches)");
     static_assert(NW <= 4, "qp_factor_inside checks the block reductions for four waves");
+    static_assert(FULL == 0 || qp_full_zeroes_kept(qp_lds(NF > 0 ? NF : 2, CLS), NF > 0 ? NF : 2), "a store of the factor sweep reaches gam or cf: the full slot form zeroes them once per solve");
     // (the pointers as a chain, each array from its predecessor's end in the layout's order, by lengths evaluated here -- and not as sm + offset:
     // the same addresses, but the shape and the order of this arithmetic decide the register allocation of the whole kernel, qp_lds.hpp)
 #define LEN(id) qp_lds_len(id, N, NS, CLS)
@@ -364,6 +376,10 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     sg = blk_max(sg); sb = blk_max(sb);
 
     // constraint slots owned by this lane
+    // FULL: s_kc packs what the phases need of a slot into its one register (five more per lane tipped k_steps' allocation into scratch):
+    // bits 0..15 the byte offset 8 (k NCK + c) of its word in cf and gam, bits 16..29 the byte offset of its word in a stage-major vector
+    // v[NS][10] (8 (k * 10 + c) of a box row, 8 (k * 10) of a general row), bit 31 (the sign) a general row, bit 30 which of the two -- what
+    // row_dot works out of k NCK + c on every call
     int s_kc[NSLOT];
     double s_dl[NSLOT], s_du[NSLOT];      // bounds relative to the iterate (+-inf = absent)
     double lam_l[NSLOT], lam_u[NSLOT], t_l[NSLOT], t_u[NSLOT];
@@ -382,9 +398,14 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 // scheduler -- run to run different ones -- while the default build matched the CPU restatement on 4096 instances; the cause was not found
 // (NOTES.md R4.10), so that kernel keeps both sides' registers for every slot, the form that passes in both builds)
 #define ONE_SIDED(r) (NSOFT > 0 && PATH != 2 && (r) < NSOFT)
-#define HAS_L(r) (ONE_SIDED(r) ? true : fin(s_dl[r]))
-#define HAS_U(r) (ONE_SIDED(r) ? false : fin(s_du[r]))
-#define ROW_DOT(r, v) (ONE_SIDED(r) ? s_sg[(r) < NSOFT ? (r) : 0] * row_dot(s_kc[r], (v)) : row_dot(s_kc[r], (v)))
+#define HAS_L(r) (FULL ? true : ONE_SIDED(r) ? true : fin(s_dl[r]))
+#define HAS_U(r) (FULL ? true : ONE_SIDED(r) ? false : fin(s_du[r]))
+#define ROW_DOT(r, v) (FULL ? row_dot_full((r), (v)) : ONE_SIDED(r) ? s_sg[(r) < NSOFT ? (r) : 0] * row_dot(s_kc[r], (v)) : row_dot(s_kc[r], (v)))
+// FULL: every entry of the table is a row (no padding to skip)
+#define NO_SLOT(r) (!FULL && s_kc[r] < 0)
+#define SLOT_W(r) (FULL ? (s_kc[r] & 0xffff) >> 3 : s_kc[r])
+// the slot's word of cf or gam
+#define SLOT_AT(arr, r) (*(FULL ? reinterpret_cast<double *>(reinterpret_cast<char *>(arr) + (here(s_kc[r]) & 0xffff)) : &(arr)[s_kc[r]]))
 #define ROW_SIGN(r, c) (ONE_SIDED(r) ? s_sg[(r) < NSOFT ? (r) : 0] * (c) : (c))
     double s_sg[NSO];
 #pragma unroll
@@ -395,12 +416,13 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 #pragma unroll
     for (int r = 0; r < NSLOT; r++) {
         const int s = tid + NT * r;
-        s_kc[r] = -1; s_dl[r] = -INFINITY; s_du[r] = INFINITY;
+        s_kc[r] = FULL ? 0 : -1; s_dl[r] = -INFINITY; s_du[r] = INFINITY;      // (FULL: the table has no padding; offset 0 keeps a wrong one inside the LDS)
         lam_l[r] = lam_u[r] = 0.0; t_l[r] = t_u[r] = 1.0;
         const int kc = (s < a.nslots) ? a.slot_kc[s] : -1;
         if (kc >= 0) {
             const int k = kc >> 4, c = kc & 15;
             s_kc[r] = k * NCK + c;
+            if (FULL) s_kc[r] = ((k * NCK + c) * 8) | ((k * 10 + ((c < 10) ? c : 0)) << 19) | ((c >= 10) ? (int)(0x80000000u | ((unsigned)(c - 10) << 30)) : 0);
             double cz;
             if (c < 8) cz = xb[k * 8 + c];
             else if (c < 10) cz = ub[k * 2 + c - 8];
@@ -453,15 +475,28 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         for (int j = 0; j < 10; j++) acc = fma(CDV(k, c - 10, j), v[k * 10 + j], acc);
         return acc;
     };
+    // the same of slot r of a full table: a box row is its word, a general row the same chain of ten products in the same order
+    auto row_dot_full = [&](int r, const double *v) -> double {
+        const int pk = here(s_kc[r]);
+        const double *vk = reinterpret_cast<const double *>(reinterpret_cast<const char *>(v) + ((pk >> 16) & 0x3fff));
+        if (pk >= 0) return vk[0];
+        const double *cd = CDl + (((unsigned)pk >> 30) & 1) * 10;
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < 10; j++) acc = fma(cd[j], vk[j], acc);
+        return acc;
+    };
 
 /*@S:0*/
     // ------------------------------------------------------------------ initial point
     for (int e = tid; e < NS * 10; e += NT) z[e] = (e < 8) ? a.x0[(size_t)b * 8 + e] - xb[e] : 0.0;
     for (int e = tid; e < NS * 8; e += NT) pi[e] = 0.0;
+    // FULL: the one zeroing of cf and gam -- from here on a word is rewritten by its slot in every pass that reads it, or never written again
+    if (FULL) for (int e = tid; e < NS * NCK; e += NT) { cf[e] = 0.0; gam[e] = 0.0; }
     BSYNC();
 #pragma unroll
     for (int r = 0; r < NSLOT; r++) {
-        if (s_kc[r] < 0) continue;
+        if (NO_SLOT(r)) continue;
         const double rz = ROW_DOT(r, z);
         const bool al = HAS_L(r), au = HAS_U(r);
         double tau_c = a.tau0;
@@ -490,13 +525,15 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         // ---- slack residuals, complementarity; lam_l - lam_u -> cf (read by the exact stationarity residual only) ----
         bool exact = (it == 0) || exact_mode, finished = false;
         auto multipliers_to_cf = [&]() {
-            for (int e = tid; e < NS * NCK; e += NT) cf[e] = 0.0;
-            BSYNC();
+            if (!FULL) {
+                for (int e = tid; e < NS * NCK; e += NT) cf[e] = 0.0;
+                BSYNC();
+            }
 #pragma unroll
             for (int r = 0; r < NSLOT; r++) {
-                if (s_kc[r] < 0) continue;
+                if (NO_SLOT(r)) continue;
                 const bool al = HAS_L(r), au = HAS_U(r);
-                SLOT_ACC(cf[s_kc[r]], ROW_SIGN(r, (al ? lam_l[r] : 0.0) - (au ? lam_u[r] : 0.0)));     // the two halves of a split slot share a lane
+                SLOT_ACC(SLOT_AT(cf, r), ROW_SIGN(r, (al ? lam_l[r] : 0.0) - (au ? lam_u[r] : 0.0)));     // the two halves of a split slot share a lane
             }
             BSYNC();
         };
@@ -512,7 +549,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 #pragma unroll
         for (int r = 0; r < NSLOT; r++) {
             rd_l[r] = rd_u[r] = 0.0;
-            if (s_kc[r] < 0) continue;
+            if (NO_SLOT(r)) continue;
             const double rz = ROW_DOT(r, z);
             const bool al = HAS_L(r), au = HAS_U(r);
             const double sv = IS_SOFT(r) ? so_s[r < NSOFT ? r : 0] : 0.0;      // the slack enters its (single) side
@@ -529,7 +566,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 res_gs = nanmax(res_gs, fabs(so_rs[q]));
                 mu_acc += so_ls[q] * so_s[q]; res_m = nanmax(res_m, fabs(so_ls[q] * so_s[q]));
             }
-            if (LEAN == 0) SLOT_ACC(cf[s_kc[r]], ROW_SIGN(r, (al ? lam_l[r] : 0.0) - (au ? lam_u[r] : 0.0)));
+            if (LEAN == 0) SLOT_ACC(SLOT_AT(cf, r), ROW_SIGN(r, (al ? lam_l[r] : 0.0) - (au ? lam_u[r] : 0.0)));
         }
         if constexpr (NW > 1) {
             // several waves per instance: the slots' terms go to LDS (gam: dead between the factor sweep and the next coefficient phase) and every wave
@@ -627,12 +664,14 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         // ---- barrier weights and gradient coefficients of the owned slots -> LDS (pass 0: predictor; pass 1: corrector) ----
         auto slot_coeffs = [&](int pass) {
             // ---- barrier weights and gradient coefficients of the owned slots -> LDS ----
-            for (int e = tid; e < NS * NCK; e += NT) { cf[e] = 0.0; if (pass == 0) gam[e] = 0.0; }
-            BSYNC();
+            if (!FULL) {
+                for (int e = tid; e < NS * NCK; e += NT) { cf[e] = 0.0; if (pass == 0) gam[e] = 0.0; }
+                BSYNC();
+            }
             const double mu_t = fmax(sigma * mu, mu_floor);
 #pragma unroll
             for (int r = 0; r < NSLOT; r++) {
-                if (s_kc[r] < 0) continue;
+                if (NO_SLOT(r)) continue;
                 const bool al = HAS_L(r), au = HAS_U(r);
                 double c = 0.0;
                 if (IS_SOFT(r)) {
@@ -641,10 +680,10 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                     const double lm = al ? lam_l[r] : lam_u[r], tt = al ? t_l[r] : t_u[r], rdv = al ? rd_l[r] : rd_u[r];
                     const double gm = lm / tt, gs = so_ls[q] / so_s[q], D = so_Zw[q] + gm + gs;
                     double c1, c2, rsv;
-                    if (pass == 0) { c1 = (lm * tt + lm * rdv) / tt; c2 = so_ls[q]; rsv = so_rs[q]; gam[s_kc[r]] += gm * (so_Zw[q] + gs) / D; }
+                    if (pass == 0) { c1 = (lm * tt + lm * rdv) / tt; c2 = so_ls[q]; rsv = so_rs[q]; SLOT_AT(gam, r) += gm * (so_Zw[q] + gs) / D; }
                     else { c1 = ((al ? pa_l[r] : pa_u[r]) - mu_t) / tt; c2 = (so_pa[q] - mu_t) / so_s[q]; rsv = 0.0; }
                     c = c1 - gm * (rsv + c1 + c2) / D;
-                    cf[s_kc[r]] += ONE_SIDED(r) ? ROW_SIGN(r, c) : (al ? c : -c);
+                    SLOT_AT(cf, r) += ONE_SIDED(r) ? ROW_SIGN(r, c) : (al ? c : -c);
                     continue;
                 }
                 if (pass == 0) {
@@ -652,12 +691,12 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                     const double gl = al ? lam_l[r] / t_l[r] : 0.0, gu = au ? lam_u[r] / t_u[r] : 0.0;
                     if (al) c += fma(gl, rd_l[r], lam_l[r]);        // (lam t + lam rd) / t
                     if (au) c -= fma(gu, rd_u[r], lam_u[r]);
-                    SLOT_ACC(gam[s_kc[r]], gl + gu);
+                    SLOT_ACC(SLOT_AT(gam, r), gl + gu);
                 } else {
                     if (al) c += (pa_l[r] - mu_t) / t_l[r];
                     if (au) c -= (pa_u[r] - mu_t) / t_u[r];
                 }
-                SLOT_ACC(cf[s_kc[r]], ROW_SIGN(r, c));
+                SLOT_ACC(SLOT_AT(cf, r), ROW_SIGN(r, c));
             }
             BSYNC();
         };
@@ -887,7 +926,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 #pragma unroll
             for (int r = 0; r < NSLOT; r++) {
                 dlam_l[r] = dlam_u[r] = dt_l[r] = dt_u[r] = 0.0;
-                if (s_kc[r] < 0) continue;
+                if (NO_SLOT(r)) continue;
                 const double drz = ROW_DOT(r, dz);
                 if (IS_SOFT(r)) {
                     const int q = r < NSOFT ? r : 0;
@@ -948,7 +987,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 #pragma unroll
                 for (int r = 0; r < NSLOT; r++) {
                     pa_l[r] = dlam_l[r] * dt_l[r]; pa_u[r] = dlam_u[r] * dt_u[r];
-                    if (s_kc[r] < 0) continue;
+                    if (NO_SLOT(r)) continue;
                     mu_aff = __dadd_rn(mu_aff, __dadd_rn(HAS_L(r) ? __dmul_rn(fma(amax_d, dlam_l[r], lam_l[r]), fma(amax, dt_l[r], t_l[r])) : 0.0,
                                                          HAS_U(r) ? __dmul_rn(fma(amax_d, dlam_u[r], lam_u[r]), fma(amax, dt_u[r], t_u[r])) : 0.0));
                     if (IS_SOFT(r)) {
@@ -1024,7 +1063,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         for (int e = tid; e < NS * 8; e += NT) pi[e] = fma(alpha_d, pv[e], pi[e]);
 #pragma unroll
         for (int r = 0; r < NSLOT; r++) {
-            if (s_kc[r] < 0) continue;
+            if (NO_SLOT(r)) continue;
             if (HAS_L(r)) { lam_l[r] = fma(alpha_d, dlam_l[r], lam_l[r]); t_l[r] = fma(alpha, dt_l[r], t_l[r]); }
             if (HAS_U(r)) { lam_u[r] = fma(alpha_d, dlam_u[r], lam_u[r]); t_u[r] = fma(alpha, dt_u[r], t_u[r]); }
             if (IS_SOFT(r)) { const int q = r < NSOFT ? r : 0; so_s[q] = fma(alpha, so_ds[q], so_s[q]); so_ls[q] = fma(alpha_d, so_dls[q], so_ls[q]); }
@@ -1061,8 +1100,8 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < NSLOT; r++) {
-            if (s_kc[r] < 0) continue;
-            const int k = s_kc[r] / NCK, c = s_kc[r] % NCK;
+            if (NO_SLOT(r)) continue;
+            const int k = SLOT_W(r) / NCK, c = SLOT_W(r) % NCK;
             if (ONE_SIDED(r)) {        // the one side, kept in the lower side's registers: s_sg < 0 = it is the row's upper side
                 const int up = (s_sg[r < NSOFT ? r : 0] < 0.0) ? 1 : 0;
                 if (ALAT && c == 14) { lamab[k * 2 + up] = lam_l[r]; if (IS_SOFT(r)) slkab[k * 2 + up] = so_s[r < NSOFT ? r : 0]; }
@@ -1093,13 +1132,13 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 
 #undef BSYNC
 
-template <int NSLOT, int NSOFT, int PATH, int UNI, int NF = 0>
+template <int NSLOT, int NSOFT, int PATH, int UNI, int NF = 0, int FULL = 0>
 __global__ __launch_bounds__(64) void k_qp_wave(QpArgs a)
 {
     extern __shared__ double sm[];
     if ((int)blockIdx.x >= a.B) return;
     if (NF > 0 && a.N != NF) return;        // (api.hip selects by the handle's horizon)
-    qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, 1, NF>(a, blockIdx.x, sm);
+    qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, 1, NF, FULL>(a, blockIdx.x, sm);
 }
 
 // The latency kernel: NW wavefronts per instance (qp_wave_body with NW > 1), for batches that leave most of the chip idle -- the
@@ -1200,8 +1239,8 @@ __device__ __noinline__ void call_line_search(const LsArgs &ls, int b, int it, i
 // step's history row, in mode 2 the forward sweep over the horizon on the last step.  The body reuses the QP's LDS from offset 0 (the QP and
 // the linearisation write theirs before they read it).  A template parameter for the reason DYN is one: a run-time flag and the call it
 // guards would change the register allocation of the benchmarked kernels.
-// NF: the form of the QP's factor sweep and the compile-time horizon (qp_wave_body).
-template <int NSLOT, int NSOFT, int PATH, int UNI, int SQP, int IRK = 0, int DYN = 0, int SENS = 0, int NF = 0>
+// NF: the form of the QP's factor sweep and the compile-time horizon, FULL: the form of its slot phases (qp_wave_body).
+template <int NSLOT, int NSOFT, int PATH, int UNI, int SQP, int IRK = 0, int DYN = 0, int SENS = 0, int NF = 0, int FULL = 0>
 __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, const LsArgs *lsp)
 {
     // the loop's own arguments are read from device memory where they are used: as by-value kernel arguments they stayed in
@@ -1328,7 +1367,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
             }
             // LEAN (the sweeps and norm phases on a diet): measured per class of instantiation -- it gains 6-8 % in the all-hard RTI loops and costs the
             // SQP loops 13-17 % and the soft / track-row loops 2-9 % (their register allocation tips into scratch); the stand-alone QP kernels take it
-            qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, SQP ? 0 : 1, NF>(a, b, sm, SQP || step + 1 == s.n_steps);
+            qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, SQP ? 0 : 1, NF, FULL>(a, b, sm, SQP || step + 1 == s.n_steps);
             __syncthreads();
             if constexpr (SENS != 0) {
                 sens_body(*s.sens, b, sm, step);
@@ -1357,21 +1396,24 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 
 }  // namespace
 
-// This file is compiled SEVEN times (Makefile; QP_SET = 5, 6: the loops of IHM2MPC_INTEG_ERK_LAG, below): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
+// This file is compiled EIGHT times (Makefile; QP_SET = 5, 6: the loops of IHM2MPC_INTEG_ERK_LAG, QP_SET = 7: the pair of set 4 for the horizon 40 with the slot phases in their full form, below): QP_SET = 0 holds the all-hard instantiations (the reference's OCP), QP_SET = 1 the
 // soft / track-row instantiations, QP_SET = 2 the persistent loop of the dynamic OCP models (all tables), QP_SET = 3 the persistent loop
 // with x0 sensitivities (SENS = 1) for every RTI loop of the sets 0 and 1 -- same flags, same (default) scheduler -- and QP_SET = 4 the
 // benchmarked pair of set 0 with the straight-line factor sweep (NF).  Separate objects are separate device code images: the benchmarked kernels' image does not move when another set grows.  `make ilp` builds both again under
 // LLVM's iterative ILP scheduler into the test artefact libihm2mpc_ilp.so (tests/test_gpu_configs.py compares the two builds).
 #ifndef QP_SET
-#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities), -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep), -DQP_SET=5 or -DQP_SET=6 (the all-hard RTI loops with the closed-form actuator lags: general form / straight-line factor sweep)"
+#error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities), -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep), -DQP_SET=5 or -DQP_SET=6 (the all-hard RTI loops with the closed-form actuator lags: general form / straight-line factor sweep), -DQP_SET=7 (the pair of set 4 at the horizon 40 with the full slot form)"
 #endif
-// The instantiations of this object: its part of the catalogue api.hip selects from (qp_catalogue.hpp: QP_INSTANCES_0 .. QP_INSTANCES_6,
+// The instantiations of this object: its part of the catalogue api.hip selects from (qp_catalogue.hpp: QP_INSTANCES_0 .. QP_INSTANCES_7,
 // where the lists and the meaning of WAVE, BLOCK, STEPS are written down); below, the expansion of its entries to kernel pointers.
 #define QP_INSTANCES_(n) QP_INSTANCES_##n
 #define QP_INSTANCES_OF(n) QP_INSTANCES_(n)
 #define QP_INSTANCES QP_INSTANCES_OF(QP_SET)
 
-#if QP_SET == 4 || QP_SET == 6
+#if QP_SET == 7
+#define WAVE(NS, NO, PT, UN) {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, 40, 1}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, 40, 1>},
+#define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 0, 40, 1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 0, 40, 1>},
+#elif QP_SET == 4 || QP_SET == 6
 #define WAVE(NS, NO, PT, UN)                                                                          \
     {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, 40}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, 40>},     \
     {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, -1}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, -1>},

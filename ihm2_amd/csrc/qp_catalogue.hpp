@@ -1,6 +1,6 @@
-// qp_catalogue.hpp -- which instantiations of the QP kernels exist: the lists of the seven objects built from kernels_qp.hip (QP_SET = 0 .. 6),
+// qp_catalogue.hpp -- which instantiations of the QP kernels exist: the lists of the eight objects built from kernels_qp.hip (QP_SET = 0 .. 7),
 // entry for entry in their order of preference, and what they say about the slot tables the per-step QP takes.  Plain C++17, no HIP:
-// kernels_qp.hip expands its own list to kernel pointers, the host code (api.hip, tools/probes/check_slot_table.cpp) expands all seven to
+// kernels_qp.hip expands its own list to kernel pointers, the host code (api.hip, tools/probes/check_slot_table.cpp) expands them to
 // numbers.
 //
 // WAVE(NSLOT, NSOFT, PATH, UNI) k_qp_wave, BLOCK(NSLOT, UNI, NW) k_qp_block, STEPS(NSLOT, NSOFT, PATH, UNI, IRK, DYN) k_steps in both SQP
@@ -51,6 +51,10 @@
     STEPS(5, 0, 0, 0, 2, 0) STEPS(5, 0, 0, 1, 2, 0) STEPS(8, 0, 0, 0, 2, 0) STEPS(8, 0, 0, 1, 2, 0) STEPS(10, 0, 0, 1, 2, 0)
 // QP_SET = 6: ... and the benchmarked table's loop with the straight-line factor sweep, as QP_SET = 4 (Makefile: the same flags)
 #define QP_INSTANCES_6(WAVE, BLOCK, STEPS) STEPS(5, 0, 0, 1, 2, 0)
+// QP_SET = 7: the list of the set 4 once more -- the same pair, for the horizon 40 only, with the slot phases in their full form
+// (qp_wave_body: FULL; qp_tables.hpp: slot_table_full says which tables take it).  No further table fits through it: slot_limits
+// does not walk it.  An object of its own with the flags of the set 4, so that the four kernels of that set stay what they were.
+#define QP_INSTANCES_7 QP_INSTANCES_4
 
 namespace ihm2 {
 

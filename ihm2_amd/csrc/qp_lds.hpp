@@ -157,6 +157,27 @@ QP_LDS_FN QpReach qp_reach_plain_parking(const QpLds &l) { return {l.tile, l.til
 // ... and the next stage's C operand is read unconditionally: after stage 0 the rows "k = -1" of gt and gam, i.e. the words in front of
 // them (gt comes first); upwards the lane groups 2, 3 read the words 10, 11 of a row of 10 -- the next row's, at most row N-1's.
 QP_LDS_FN QpReach qp_reach_plain_operand(const QpLds &l, int N, int nck) { return {l.gt - 10, l.gam + N * nck}; }
+// ... and what it STORES to LDS: p_N into the terminal row of pv; P_{k+1} rb_k, Guu^-1, kff_k, K_k into their own rows 0 .. N-1; c_k into
+// the rows 1 .. N of dz (+ 4: the second register of a pair); everything else into the parking words of the tile.  The lowest of them
+// besides pv's row is dz + 10, the highest the end of the tile.
+QP_LDS_FN QpReach qp_reach_plain_stores(const QpLds &l) { return {l.dz + 10, l.tile.end()}; }
+QP_LDS_FN QpReach qp_reach_plain_store_pv(const QpLds &l, int N) { return {l.pv + N * 8, l.pv + N * 8 + 8}; }
+// The full slot form (kernels_qp.hip: qp_wave_body, FULL) zeroes gam and cf ONCE per solve, where the general form zeroes them in every
+// coefficient pass.  The writers of the two arrays, walked one by one:
+//   * the slot loops (multipliers_to_cf, slot_coeffs): slot (k, c) stores to the word k nck + c of cf in every pass, and of gam in the
+//     predictor's pass -- in a full table every slot of every lane, unconditionally, so an owned word is rewritten before each of its readers
+//     (the exact residual, add_coeffs, the factor sweep) as it is after the zeroing pass of the general form; the words no slot owns
+//     (stage 0's state boxes, stage N's input and general rows, unbounded states) are written by nobody;
+//   * the factor sweep: its stores are qp_reach_plain_stores and qp_reach_plain_store_pv, both outside [gam, cf.end); its "k = -1" operand
+//     (qp_reach_plain_operand) is a read;
+//   * the vector and forward sweeps store to pv and dz inside [0, N) only (their unclamped accesses are prefetches: reads);
+//   * the four-wave kernel parks its slot sums in gam: it has no full form.
+// So a word of gam or cf is either rewritten by its one owning slot in every pass or never written after the zeroing at the top.
+QP_LDS_FN bool qp_full_zeroes_kept(const QpLds &l, int N)
+{
+    const QpReach s = qp_reach_plain_stores(l), p = qp_reach_plain_store_pv(l, N);
+    return s.lo >= l.cf.end() && qp_inside(s, l.cf.end(), l.total) && qp_inside(p, 0, l.gam) && l.cf == l.gam.end();
+}
 // the four-wave kernel's block reductions: one word per wave, in the tile
 QP_LDS_FN QpReach qp_reach_block_reduce(const QpLds &l, int nw) { return {l.tile, l.tile + nw}; }
 

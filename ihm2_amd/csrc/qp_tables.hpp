@@ -237,6 +237,35 @@ inline SlotTable lay_out_slots(const ConstraintRows &c, const std::vector<std::p
     return t;
 }
 
+// ---- the full table ----
+// What the kernels' full slot form (kernels_qp.hip: qp_wave_body, FULL) takes WITHOUT asking, in every slot loop of every iteration: the
+// table is all-hard, holds no track or a_lat row, every lane owns exactly `nslot` entries (the instantiation's NSLOT) and none of the
+// 64 nslot entries is padding, and both bounds of every entry are finite -- by the kernel's own test, |v| < 1e20.  The reference's rows
+// are such a table at N = 40 (8 N = 320 = 64 x 5 two-sided rows) and at no other horizon.
+inline bool full_bound(double v) { return std::fabs(v) < 1e20; }
+inline bool slot_table_full(const SlotTable &t, int nslot)
+{
+    if (!t.fit || t.nsoft != 0 || t.per_lane != nslot || t.total != 64 * nslot || t.entries() != (size_t)64 * nslot) return false;
+    for (size_t e = 0; e < t.entries(); e++) {
+        const int kc = t.kc[e];
+        if (kc < 0 || (kc & 15) >= 12 || t.Zw[e] >= 0.0) return false;
+        if (!full_bound(t.lb[e]) || !full_bound(t.ub[e])) return false;
+    }
+    return true;
+}
+// ... and with per-instance bounds (scatter_slot_bounds: (B, entries) each): those of every instance.  A second line of defence: the
+// setter refuses per-instance values whose finite sides differ from the shared table's (find_pattern_mismatch) before anything is
+// scattered, so once slot_table_full holds no call of the library reaches this function with an infinite value -- only the CPU probe
+// (tools/probes/check_full_table.cpp) does.  It stays because the kernel asks nothing, and the pattern check may change.
+inline bool slot_bounds_full(const SlotTable &t, int B, const std::vector<double> &slb, const std::vector<double> &sub)
+{
+    const size_t n = (size_t)B * t.entries();
+    if (slb.size() != n || sub.size() != n) return false;
+    for (size_t i = 0; i < n; i++)
+        if (!full_bound(slb[i]) || !full_bound(sub[i])) return false;
+    return true;
+}
+
 // ---- per-instance bounds in the pattern of the batch-shared table ----
 // il, iu (B,NS,12): the values of the rows 0..11 per instance, +-inf = absent (box_rows with stride 12).
 

@@ -424,7 +424,9 @@ class BatchedOcpSolver:
         (``"k_linearize"``, ``"k_linearize_dyn"``, ``"k_linearize_cols"``, ``"k_linearize_irk"``, ``"k_linearize_lag"``; ``"k_sim_step_kin"``,
         ``"k_sim_step"``, ``"k_sim_irk"``, ``"k_sim_step_kin_lag"``; ``_lag``: the integrator ``"ERK_LAG"``); ``qp_form`` / ``steps_form``: the form of the factor sweep in those two launches, ``"general"``,
         ``"plain"`` (straight-line stage, run-time horizon) or ``"plain_n40"`` (the horizon 40 compiled in) -- same results, so the
-        kernel names above do not tell them apart.  ``None`` where nothing was launched yet."""
+        kernel names above do not tell them apart; ``qp_slots`` / ``steps_slots``: the form of the slot phases alike, ``"general"`` or
+        ``"full"`` (a table of 64 x 5 hard two-sided rows at the horizon 40: no validity or side test per slot).  ``None`` where nothing
+        was launched yet."""
         rec = np.zeros(16, dtype=np.int32)
         _lib.check(self.lib.ihm2mpc_get_launch_record(self._h, rec.ctypes.data_as(_lib.c_int32_p)))
         r = [int(v) for v in rec]
@@ -441,8 +443,10 @@ class BatchedOcpSolver:
         lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk", "k_linearize_lag")[r[15] & 15]
         sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk", "k_sim_step_kin_lag")[(r[15] >> 4) & 15]
         forms = ("general", "plain", "plain_n40", None)
+        slots = ("general", "full")
         return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim,
-                "qp_form": forms[(r[15] >> 8) & 3] if qp else None, "steps_form": forms[(r[15] >> 12) & 3] if r[5] == 1 else None}
+                "qp_form": forms[(r[15] >> 8) & 3] if qp else None, "steps_form": forms[(r[15] >> 12) & 3] if r[5] == 1 else None,
+                "qp_slots": slots[(r[15] >> 10) & 1] if qp else None, "steps_slots": slots[(r[15] >> 14) & 1] if r[5] == 1 else None}
 
     # ---- device-pointer variants (zero copy; dptr = integer device address, instance-major layout) ----
     def set_x0_device(self, dptr: int):

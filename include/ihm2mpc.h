@@ -294,7 +294,11 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *       form, 1 the straight-line stage with the run-time horizon, 2 the straight-line stage with the horizon compiled in (N = 40).  The
  *       forms give the same bits; a table without active rows and the model IHM2MPC_MODEL_FDYN6 take the general form, and so does every
  *       configuration without an instantiation in the other two.  IHM2MPC_QP_FORM in the environment (read once) limits the choice:
- *       1 keeps N = 40 on form 1, 0 keeps every launch on form 0. */
+ *       1 keeps N = 40 on form 1, 0 keeps every launch on form 0.
+ *       bit 10 the form of the slot phases in the QP of [0], bit 14 in the k_steps launch of [5] (0 when [5] != 1): 1 the full form -- for
+ *       a table of 64 x 5 hard rows with both bounds finite (per instance too) and no track or a_lat row, at N = 40 on form 2 of the factor
+ *       sweep: no validity or side test per slot -- 0 the general form.  The same bits again.  IHM2MPC_QP_FORM = 2 keeps N = 40 on form 2
+ *       with the general slot phases; one infinite bound anywhere does the same. */
 int ihm2mpc_get_launch_record(ihm2mpc_handle *h, int32_t *rec);
 
 /* ---- sensitivities of the solution with respect to the initial state (acados: eval_param_sens(index, 0, "ex"), then

@@ -11,7 +11,8 @@ QP = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 jobs = [(f, []) for f in ("kernels_misc.hip", "kernels_linearize.hip", "kernels_cart.hip", "kernels_dyn10.hip", "kernels_sqp.hip", "kernels_irk.hip", "kernels_sens.hip", "kernels_adj.hip")]
 jobs += [("kernels_qp.hip", ["-DQP_SET=0"] + QP), ("kernels_qp.hip", ["-DQP_SET=1"] + QP), ("kernels_qp.hip", ["-DQP_SET=2"] + QP),
          ("kernels_qp.hip", ["-DQP_SET=3"] + QP), ("kernels_qp.hip", ["-DQP_SET=4"] + QP + ["-fno-unroll-loops"]),
-         ("kernels_qp.hip", ["-DQP_SET=5"] + QP), ("kernels_qp.hip", ["-DQP_SET=6"] + QP + ["-fno-unroll-loops"])]
+         ("kernels_qp.hip", ["-DQP_SET=5"] + QP), ("kernels_qp.hip", ["-DQP_SET=6"] + QP + ["-fno-unroll-loops"]),
+         ("kernels_qp.hip", ["-DQP_SET=7"] + QP + ["-fno-unroll-loops"])]
 with ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0))))) as pool:       # the compilers run side by side, the table keeps the order of `jobs`
     outs = list(pool.map(lambda j: subprocess.run(BASE + j[1] + [j[0]], cwd=SRC, capture_output=True, text=True).stderr, jobs))
 for (f, extra), out in zip(jobs, outs):
