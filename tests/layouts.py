@@ -207,11 +207,12 @@ REFUSED = {
 }
 
 
-def make_ocp(lay: Layout):
-    """The OCP the layout edits: the reference's (conftest.make_ocp), with the track rows / a_lat row switched on as asked."""
+def make_ocp(lay: Layout, **opts):
+    """The OCP the layout edits: the reference's (conftest.make_ocp), with the track rows / a_lat row switched on as asked.  ``opts``
+    go to conftest.make_ocp: ``model``, ``M`` and the solver options (integrator, SQP mode, line search)."""
     from conftest import make_ocp as base
 
-    ocp = base(N=lay.N)
+    ocp = base(N=lay.N, **opts)
     if lay.path:
         ocp.model.con_h_expr = "track+a_lat" if lay.alat else "track"
         c = ocp.constraints

@@ -162,6 +162,12 @@ LIVE = dict(nlp_solver_type="SQP", nlp_solver_max_iter=2, globalization="MERIT_B
 IRK = dict(integrator_type="IRK", sim_method_num_steps=1)                                              # python/main.py:234-236
 
 
+# What run_steps must launch for the reference's table (8 rows on each of 40 stages: 5 slots per lane, whatever n_max) with batch-shared
+# weights and the kinematic model, by (SQP mode, collocation): api.hip::select_steps.  More than 4 x 256 instances are not resident.
+LOOP_OF = {(False, False): "k_steps<5,0,0,1,0,0,0>", (True, False): "k_steps<5,0,0,1,1,0,0>",
+           (False, True): "k_steps<5,0,0,1,0,1,0>", (True, True): "k_steps<5,0,0,1,1,1,0>"}
+
+
 @pytest.mark.parametrize("plant,n_max,B,opts", [(0, 2.0, 150, {}), (-1, 0.9, 150, {}), (0, 2.0, 1100, {}), (0, 2.0, 150, LIVE), (-1, 2.0, 70, LIVE),
                                                 (0, 2.0, 150, IRK), (-1, 0.9, 70, IRK), (0, 2.0, 150, {**LIVE, **IRK}), (-1, 2.0, 70, {**LIVE, **IRK})])
 def test_persistent_loop_equals_step_by_step(track, plant, n_max, B, opts, monkeypatch):
@@ -178,12 +184,17 @@ def test_persistent_loop_equals_step_by_step(track, plant, n_max, B, opts, monke
     x0 = sample_x0(track, B, seed=31)
     res = []
     for persistent in (False, True):
-        s = BatchedOcpSolver(make_ocp(n_max=n_max, **opts), B, track.s_ref, track.kappa_ref)     # n_max 0.9: the 8-slot table
+        s = BatchedOcpSolver(make_ocp(n_max=n_max, **opts), B, track.s_ref, track.kappa_ref)
         s.set_lap_wrap(True)
         s.set_x0(x0); s.init_guess()
         s.step(40.0, model=plant, M_sim=30)                    # a first solve: u0 and status exist
         if persistent:
             h = s.run_steps(40.0, steps, model=plant, M_sim=30, u0_hist=True, x0_hist=True, status_hist=True, qp_iter_hist=True)
+            rec = s.get_launch_record()          # the loop itself ran: a silent fallback would compare launches per step with themselves
+            if B == 1100:
+                assert (rec["steps"], rec["steps_fallback"]) == ("per_step", "not_resident")
+            else:
+                assert rec["steps"] == LOOP_OF["nlp_solver_type" in opts, "integrator_type" in opts], rec
         else:
             h = dict(u0=[], x0=[], status=[], qp_iter=[])
             for _ in range(steps):
@@ -294,6 +305,11 @@ def test_persistent_loop_with_soft_tables_equals_step_by_step(track, variant, op
         s.step(40.0, model=0, M_sim=25)
         if persistent:
             h = s.run_steps(40.0, steps, model=0, M_sim=25, u0_hist=True, x0_hist=True, status_hist=True, qp_iter_hist=True)
+            # both variants deal 80 rows with two soft sides out over 64 lanes: up to 4 soft sides on a lane, the NSOFT = 4 tables
+            # (qp_tables.hpp: lay_out_slots; 8 slots per lane for soft_bounds, 9 with the track rows)
+            loop = {("soft_bounds", False): "k_steps<10,4,0,1,0,0,0>", ("soft_track_rows", False): "k_steps<10,4,1,1,0,0,0>",
+                    ("soft_track_rows", True): "k_steps<10,4,1,1,1,0,0>"}[variant, bool(opts)]
+            assert s.get_launch_record()["steps"] == loop, s.get_launch_record()
         else:
             h = dict(u0=[], x0=[], status=[], qp_iter=[])
             for _ in range(steps):

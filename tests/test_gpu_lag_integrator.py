@@ -136,6 +136,7 @@ def test_rti_step_matches_the_oracle_qp_on_lag_ref_records(rti, track):
     """OracleProblem.build_qp at the iterate, its A, Bm, b replaced by lag_ref's, orc.qp_solve, the step applied: x, u to 1e-7 as in the
     GPU-oracle tests of tests/test_gpu_parity.py, status and interior-point iteration count equal."""
     from oracle import oracle as orc
+    from steps_cases import rti_status_of_qp
 
     B, N, x, u = rti["B"], rti["N"], rti["x"], rti["u"]
     desc = dict(rti["ocp"].flatten().as_dict(track.s_ref, track.kappa_ref))
@@ -149,7 +150,7 @@ def test_rti_step_matches_the_oracle_qp_on_lag_ref_records(rti, track):
         r = orc.qp_solve(qp["H"], qp["g"], A[i], Bm[i], b[i], qp["dx0"], qp["R"], qp["dl"], qp["du"], iter_max=P.p.ipm_iter_max, tol=P.p.ipm_tol,
                          mu0=P.p.ipm_mu0, tau0=P.p.ipm_tau0)
         iters[i] = r["iters"]
-        status[i] = 1 if r["status"] == 3 or not np.all(np.isfinite(r["dz"])) else 4 if r["status"] in (2, 4) else 0      # orc_rti_step's rule
+        status[i] = rti_status_of_qp(r)
         if status[i] == 0:
             xo[i] += r["dz"][:, :8]; uo[i] += r["dz"][:N, 8:]
     np.testing.assert_array_equal(rti["status"], status)

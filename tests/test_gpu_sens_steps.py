@@ -110,6 +110,22 @@ def test_nothing_else_moves(track, plant, n_max, B, opts, monkeypatch):
         np.testing.assert_array_equal(fb[k], fa[k], err_msg=k)
 
 
+# The table (NSLOT, NSOFT, PATH, UNI) of the loop each layout of the QP-layout suite takes (kinematic model, RK4, RTI), None where
+# api.hip::select_steps finds none and run_steps launches per step: stage-varying weights or rows (UNI = 0) on anything but the all-hard
+# tables of 5 and 8 slots, and the lateral-acceleration row.  The catalogue has every such loop with and without SENS.
+LOOP_ON = {
+    "hard_5_per_lane": "5,0,0,1", "hard_5_per_lane_stage_W": "5,0,0,0", "hard_6_per_lane": "8,0,0,1", "hard_8_per_lane_stage_rows": "8,0,0,0",
+    "hard_9_per_lane": "10,0,0,1", "hard_10_per_lane_all_boxes": "10,0,0,1", "hard_10_per_lane_stage_W": None,
+    "hard_random_one_sided": "5,0,0,1", "hard_narrow_rate_row": "5,0,0,1", "empty_table": "5,0,0,1",
+    "block_hard": "5,0,0,1", "block_hard_B1": "5,0,0,1", "block_hard_stage_W": "5,0,0,0",
+    "soft_2_per_lane": "8,2,0,1", "soft_2_per_lane_stage_W": None, "soft_2_per_lane_split_rows": "8,2,0,1", "soft_3_per_lane_asym": "10,4,0,1",
+    "soft_4_per_lane_mixed": "10,4,0,1", "soft_4_per_lane_stage_rows": None, "soft_one_sided_rows_padding": "8,2,0,1",
+    "path_hard": "8,0,1,1", "path_hard_stage_W": None, "path_soft_3_per_lane": "8,3,1,1", "path_soft_3_per_lane_stage_W": None,
+    "path_soft_both_sides": "10,4,1,1", "path_soft_4_per_lane": "10,4,1,1", "path_soft_4_per_lane_stage_W": None,
+    "alat_hard": None, "alat_soft": None,
+}
+
+
 @pytest.mark.parametrize("build", ["default", "ilp"])
 @pytest.mark.parametrize("name", list(TABLE))
 def test_gain_history_on_layout(track, name, build):
@@ -133,9 +149,11 @@ def test_gain_history_on_layout(track, name, build):
         if not persistent:
             s.run_steps(40.0, 1, model=0, M_sim=25)            # (what plain run_steps launches for the table, after the readings)
         rec = s.get_launch_record()
-        recs.append(rec["steps"] if rec["steps"] == "per_step" else rec["steps"][:-1])
+        recs.append(rec["steps"])
         s.free()
-    assert recs[1] == recs[0] or recs[1] == recs[0] + ",1", recs     # the SENS twin of plain run_steps' instantiation, or per step
+    # plain run_steps' instantiation and its SENS twin, or both per step
+    loop = LOOP_ON[name]
+    assert recs == (["per_step", "per_step"] if loop is None else [f"k_steps<{loop},0,0,0>", f"k_steps<{loop},0,0,0,1>"]), recs
     (sta, ka, sxa, sua), (stb, kb, sxb, sub) = res
     np.testing.assert_array_equal(stb, sta)
     ok = np.isin(sta, (0, 2))
