@@ -58,6 +58,41 @@ int alloc_all(DevBuf<T> &b, size_t n, Rest &&...rest)
     return 0;
 }
 
+// IHM2MPC_POISON_WORKSPACE (ihm2mpc_internal.h: WorkBuf): the handle's workspace buffers of doubles by member name.  The argument blocks
+// ls_args, step_args and sens_args are left out: they hold pointers and counts.  "track_work" names the local work buffers of
+// ihm2mpc_build_tracks / ihm2mpc_fit_tracks.
+struct Poisonable { const char *name; WorkBuf<double> ihm2mpc_handle::*buf; };
+#define PB(m) {#m, &ihm2mpc_handle::m}
+const Poisonable POISONABLE[] = {
+    PB(lin), PB(q_g), PB(q_rg), PB(q_P), PB(q_M), PB(scratch), PB(res), PB(qp_res), PB(dyn10), PB(ls_phi),
+    PB(ls_x), PB(ls_u), PB(ls_pi), PB(ls_lam), PB(ls_slk), PB(ls_wpi), PB(ls_wlam), PB(ls_alpha),
+    PB(hist_u0), PB(hist_x0), PB(hist_k),
+    PB(sens_xbar), PB(sens_ubar), PB(sens_u0), PB(sens_x), PB(sens_u),
+    PB(adj_sx), PB(adj_su), PB(adj_gx0), PB(adj_gy), PB(adj_gye), PB(adj_gW), PB(adj_gWe),
+};
+#undef PB
+
+// the switch names this buffer: "1" names all, a comma-separated list its entries
+bool poisoned(const ihm2mpc_handle *h, const char *name)
+{
+    const std::string &s = h->poison;
+    if (s.empty() || s == "0") return false;
+    if (s == "1") return true;
+    const size_t n = strlen(name);
+    for (size_t i = 0; i < s.size();) {
+        const size_t j = std::min(s.find(',', i), s.size());
+        if (j - i == n && s.compare(i, n, name) == 0) return true;
+        i = j + 1;
+    }
+    return false;
+}
+
+// before the first allocation: the fill of every workspace buffer the switch names
+void arm_poison(ihm2mpc_handle *h)
+{
+    for (const Poisonable &p : POISONABLE) (h->*p.buf).poison(poisoned(h, p.name));
+}
+
 // host (B, elems) <-> device (B, elems): same instance-major layout on both sides
 int upload(ihm2mpc_handle *h, const double *host, double *dev, int elems)
 {
@@ -524,6 +559,7 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
     h->NS = cfg->N + 1;
     h->n_cu = prop.multiProcessorCount;
     { const char *e = getenv("IHM2MPC_BLOCK_QP"); h->block_qp = !(e && e[0] == '0'); }
+    { const char *e = getenv("IHM2MPC_POISON_WORKSPACE"); h->poison = e ? e : ""; arm_poison(h.get()); }
     const size_t B = h->B, N = h->N, NS = h->NS, nt = (size_t)cfg->ntracks * cfg->nknots;
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
@@ -602,11 +638,13 @@ int ihm2mpc_build_tracks(ihm2mpc_handle *h, int32_t max_seg, const int32_t *nseg
     for (int t = 0; t < h->cfg.ntracks; t++)
         if (nseg[t] < 2 || nseg[t] > max_seg) return fail("track %d has %d spline segments (2 .. max_seg = %d)", t, nseg[t], max_seg);
     const size_t nc = (size_t)h->cfg.ntracks * max_seg;
-    DevBuf<double> dev;
-    DevBuf<int32_t> dseg;
-    HIP_TRY(dev.alloc(nc * 9));
-    if (dseg.alloc(h->cfg.ntracks) != hipSuccess) return fail("out of device memory");
-    double *cX = dev, *cY = dev + nc * 4, *work = dev + nc * 8;
+    StateBuf<double> dev;            // the uploaded coefficients
+    WorkBuf<double> dwork;           // "track_work": segment lengths, then their running sums
+    StateBuf<int32_t> dseg;
+    dwork.poison(poisoned(h, "track_work"));
+    HIP_TRY(dev.alloc(nc * 8));
+    if (dwork.alloc(nc) != hipSuccess || dseg.alloc(h->cfg.ntracks) != hipSuccess) return fail("out of device memory");
+    double *cX = dev, *cY = dev + nc * 4, *work = dwork;
     if (hipMemcpyAsync(cX, coeffs_X, nc * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(cY, coeffs_Y, nc * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(dseg, nseg, h->cfg.ntracks * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail("upload of the spline coefficients failed");
@@ -626,11 +664,13 @@ int ihm2mpc_fit_tracks(ihm2mpc_handle *h, int32_t max_pts, const int32_t *npts, 
     for (int t = 0; t < nt; t++)
         if (npts[t] < 3 || npts[t] > max_pts) return fail("track %d has %d centre-line points (3 .. max_pts = %d)", t, npts[t], max_pts);
     const size_t m = 7 * (size_t)max_pts, nwork = (size_t)nt * m * (m + 2), nxy = (size_t)nt * max_pts * 2, nc = (size_t)nt * max_pts * 4;
-    DevBuf<double> dev;          // zero-filled: cX, cY past a track's 4 npts coefficients stay 0
-    DevBuf<int32_t> di;
-    HIP_TRY(dev.alloc(nwork + nxy + 2 * nc));
-    if (di.alloc(2 * (size_t)nt) != hipSuccess) return fail("out of device memory");
-    double *work = dev, *dxy = dev + nwork, *cX = dxy + nxy, *cY = cX + nc;
+    StateBuf<double> dev;        // the uploaded points, then cX, cY: the rows past a track's npts are returned as 0 (include/ihm2mpc.h), the fill's value
+    WorkBuf<double> dwork;       // "track_work": the augmented KKT matrices (k_track_fit clears the part it uses)
+    StateBuf<int32_t> di;
+    dwork.poison(poisoned(h, "track_work"));
+    HIP_TRY(dev.alloc(nxy + 2 * nc));
+    if (dwork.alloc(nwork) != hipSuccess || di.alloc(2 * (size_t)nt) != hipSuccess) return fail("out of device memory");
+    double *work = dwork, *dxy = dev, *cX = dxy + nxy, *cY = cX + nc;
     std::vector<int32_t> flags(nt, 1);
     if (hipMemcpyAsync(dxy, xy, nxy * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(di, npts, nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail("upload of the centre lines failed");

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/ihm2mpc.h"
@@ -37,9 +38,14 @@ LagFac ihm2_lag_factors(double h);
 struct ihm2mpc_comm;      // comm.hip: RCCL communicator + staging buffers of a one-process-per-GPU job
 namespace ihm2 { struct IrkTab; }
 
-// The owner of one device array (host code only).  alloc(n) gives n elements, zero-filled: the fill runs on the null stream and is waited
-// for, since the handle's streams are non-blocking and an upload that overtook it would be zeroed afterwards.  It converts to T *, which
-// the argument blocks and the launches take.
+// The owner of one device array (host code only).  alloc(n) gives n elements, every byte set to the buffer's fill byte (0 unless the buffer
+// was poisoned, see WorkBuf): the fill runs on the null stream and is waited for, since the handle's streams are non-blocking and an upload
+// that overtook it would be overwritten afterwards.  It converts to T *, which the argument blocks and the launches take.
+//
+// Every buffer is declared through one of the two classes below (DESIGN.md "Data layout in HBM"; tests/test_buffer_classes.py fails for a
+// member of the handle declared as a bare DevBuf):
+//   StateBuf  state / problem data: the contents carry meaning from call to call, or zero is the documented default
+//   WorkBuf   workspace / outputs: a call must write what it, or a getter after it, reads
 template <typename T>
 class DevBuf {
 public:
@@ -53,7 +59,7 @@ public:
         reset();
         void *q = nullptr;
         hipError_t e = hipMalloc(&q, n * sizeof(T));
-        if (e == hipSuccess) e = hipMemset(q, 0, n * sizeof(T));
+        if (e == hipSuccess) e = hipMemset(q, fill_, n * sizeof(T));
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) { (void)hipFree(q); return e; }
         p_ = (T *)q; n_ = n;
@@ -67,9 +73,28 @@ public:
     size_t size() const { return n_; }     // elements
     T *get() const { return p_; }
     operator T *() const { return p_; }
+protected:
+    int fill_ = 0;      // the byte alloc() fills with
 private:
     T *p_ = nullptr;
     size_t n_ = 0;
+};
+
+template <typename T>
+class StateBuf : public DevBuf<T> {};
+
+// IHM2MPC_POISON_WORKSPACE (read when a handle is created, api.hip: arm_poison) poisons workspace: every later alloc() of a poisoned
+// buffer, regrowth included, fills with 0xFF bytes -- NaN -- instead of zeros, so that a read of a word no call wrote shows in the results.
+// Only a workspace of doubles can be poisoned: an integer read early may be an index, and an out-of-range index is a memory fault, where
+// a NaN is arithmetic only.
+template <typename T>
+class WorkBuf : public DevBuf<T> {
+public:
+    void poison(bool on)
+    {
+        static_assert(sizeof(T) == sizeof(double) && T(0.5) != T(0), "only a workspace of doubles is poisoned");
+        this->fill_ = on ? 0xFF : 0;
+    }
 };
 
 // Created by value-initialisation (std::make_unique<ihm2mpc_handle>() in ihm2mpc_create): there is no user-provided constructor, so every
@@ -89,83 +114,88 @@ struct ihm2mpc_handle {
     bool uniform_H, uniform_CD;    // stage Hessians / general rows identical for all k < N (QP kernel keeps them in LDS)
 
     // ---- shared problem data (device) ----
-    DevBuf<double> s_ref, kappa_ref;     // (ntracks, nknots)
-    DevBuf<int32_t> track_id;            // (B)
-    DevBuf<double> Hs;                   // (NS,10,10)  cost_scale * V'WV ; terminal: W_e padded with I
-    DevBuf<double> Gy;                   // (NS,10,12)  cost_scale * V'W  ; terminal: W_e in the first 8x8
-    DevBuf<double> lbx, ubx;             // (NS,8)
-    DevBuf<double> lbu, ubu;             // (N,2)
-    DevBuf<double> CD;                   // (N,2,10)  general rows [C D]
-    DevBuf<double> lg, ug;               // (N,2)
+    StateBuf<double> s_ref, kappa_ref;     // (ntracks, nknots)
+    StateBuf<int32_t> track_id;            // (B)
+    StateBuf<double> Hs;                   // (NS,10,10)  cost_scale * V'WV ; terminal: W_e padded with I
+    StateBuf<double> Gy;                   // (NS,10,12)  cost_scale * V'W  ; terminal: W_e in the first 8x8
+    StateBuf<double> lbx, ubx;             // (NS,8)
+    StateBuf<double> lbu, ubu;             // (N,2)
+    StateBuf<double> CD;                   // (N,2,10)  general rows [C D]
+    StateBuf<double> lg, ug;               // (N,2)
     // the constraint rows as the setters leave them (set_bounds / set_soft / ... may come in any order), and the compact table of the
     // slots with at least one finite side that rebuild_slots lays out from them for the QP kernels (qp_tables.hpp)
     ihm2::ConstraintRows rows;
     ihm2::SlotTable slots;         // the last table that fitted, as the device holds it
     bool slots_full;               // the table (with the per-instance bounds, if any) takes the full slot form (qp_tables.hpp: slot_table_full)
     bool slots_fit;                // false: the rows set so far fit no instantiation (reported by the next solve: a later setter may still change them)
-    DevBuf<int32_t> slot_kc;             // (slots.per_lane*64) stage * 16 + row, -1 = padding
-    DevBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
-    DevBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot
-    DevBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
-    DevBuf<double> slot_lb_blk, slot_ub_blk;
+    StateBuf<int32_t> slot_kc;             // (slots.per_lane*64) stage * 16 + row, -1 = padding
+    StateBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
+    StateBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot
+    StateBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
+    StateBuf<double> slot_lb_blk, slot_ub_blk;
+    std::string poison;            // IHM2MPC_POISON_WORKSPACE as read at creation: "" / "0" off, "1" every workspace of doubles, else a list of names
     bool block_qp;                 // use k_qp_block for batches of at most one instance per CU (IHM2MPC_BLOCK_QP=0 turns it off)
     // nonlinear track-boundary rows (rows 12, 13 of the stages 1..N); the lateral-acceleration row's switch is rows.alat_on
     int path_on;
     double car_L, car_W, lh[NH], uh[NH];
-    DevBuf<double> widths;               // (ntracks, 2) = (w_R, w_L)
+    StateBuf<double> widths;               // (ntracks, 2) = (w_R, w_L)
     // Cartesian side (ROS stack): centre-line geometry per track, Cartesian plant state and projection guess per instance
     bool geometry_set;
-    DevBuf<double> X_ref, Y_ref, phi_ref;   // (ntracks, nknots)
-    DevBuf<double> xc;                   // (B,8) (X, Y, phi, v_x, v_y, r, T, delta)
-    DevBuf<double> s_guess;              // (B)
+    StateBuf<double> X_ref, Y_ref, phi_ref;   // (ntracks, nknots)
+    StateBuf<double> xc;                   // (B,8) (X, Y, phi, v_x, v_y, r, T, delta)
+    StateBuf<double> s_guess;              // (B)
 
     // ---- per-instance state, instance-major ----
-    DevBuf<double> x;      // (B,NS,8)
-    DevBuf<double> u;      // (B,N,2)
-    DevBuf<double> x0;     // (B,8)
-    DevBuf<double> yref;   // (B,N,12)
-    DevBuf<double> yref_e; // (B,8)
-    DevBuf<double> pi;     // (B,NS,8)
-    DevBuf<double> lam;    // (B,NS,28)
-    DevBuf<double> slk;    // (B,NS,28) slack values of the soft sides after the last QP (0 for hard sides)
-    DevBuf<double> lam_a, slk_a;   // (B,NS,2) multipliers and slack values of the lateral-acceleration row: lower, upper side
-    DevBuf<double> res;    // (B,4)
+    StateBuf<double> x;      // (B,NS,8)
+    StateBuf<double> u;      // (B,N,2)
+    StateBuf<double> x0;     // (B,8)
+    StateBuf<double> yref;   // (B,N,12)
+    StateBuf<double> yref_e; // (B,8)
+    StateBuf<double> pi;     // (B,NS,8)
+    StateBuf<double> lam;    // (B,NS,28)
+    StateBuf<double> slk;    // (B,NS,28) slack values of the soft sides after the last QP (0 for hard sides)
+    StateBuf<double> lam_a, slk_a;   // (B,NS,2) multipliers and slack values of the lateral-acceleration row: lower, upper side
+    WorkBuf<double> res;    // (B,4)
     // (n_alpha, B, N, 8) IRK rollouts at the trial points of the line search (SQP mode with the IRK integrator), grown on demand: its
     // n_alpha (the ladder it was grown for, sqp_body.hpp: make_ls_args) is the stride the line search reads it with
-    DevBuf<double> ls_phi;
-    DevBuf<ihm2::IrkTab> irk_tab;       // the OCP integrator's collocation tableau, empty for ERK
-    DevBuf<ihm2::IrkTab> sim_irk_tab;   // the same for the plant steps of the persistent loop (step dt / sim_irk_M), allocated on first use
+    WorkBuf<double> ls_phi;
+    StateBuf<ihm2::IrkTab> irk_tab;       // the OCP integrator's collocation tableau, empty for ERK
+    StateBuf<ihm2::IrkTab> sim_irk_tab;   // the same for the plant steps of the persistent loop (step dt / sim_irk_M), allocated on first use
     int sim_irk_M;
-    DevBuf<double> dyn10;  // (B,35) staging of the fdyn10 plant: x (15), u (5), x_next (15); allocated on first use
-    DevBuf<double> qp_res; // (B,4) KKT residuals of the QP at its returned point, relative to the scales of its tolerances
-    DevBuf<int32_t> status, qp_iter;   // (B)
-    DevBuf<int32_t> active;            // (B) plant mask of the device-resident closed loop (nullptr-equivalent while !active_set)
+    WorkBuf<double> dyn10;  // (B,35) staging of the fdyn10 plant: x (15), u (5), x_next (15); allocated on first use
+    WorkBuf<double> qp_res; // (B,4) KKT residuals of the QP at its returned point, relative to the scales of its tolerances
+    StateBuf<int32_t> status, qp_iter;   // (B)
+    StateBuf<int32_t> active;            // (B) plant mask of the device-resident closed loop (nullptr-equivalent while !active_set)
     bool active_set;
     bool freeze_armed;           // a run_steps(freeze) call initialised the mask: later calls keep what the device made of it
     bool lap_wrap;               // prepare_step / step move cars that passed s = L back by one lap first
-    DevBuf<double> u0;     // (B,2) first control of the last solve
+    // (B,2) first control of the last solve.  State, not an output only: the plant of the next ihm2mpc_step / _sim_advance / _run_steps reads
+    // it, so it carries meaning from call to call, and before the first solve it is the documented default 0 (the car coasts)
+    StateBuf<double> u0;
 
-    DevBuf<double> lin;    // (B,N,96) linearisation records [A | B | b | rb], then B spare records (the kinematic plant's by-product)
+    WorkBuf<double> lin;    // (B,N,96) linearisation records [A | B | b | rb], then B spare records (the kinematic plant's by-product)
     // ---- QP workspace in HBM/L2 (everything else of the QP lives in LDS / registers) ----
-    DevBuf<double> q_g;    // (B,NS,10) QP gradient
-    DevBuf<double> q_rg;   // (B,NS,10) stationarity residual of the interior-point iterate (follows the step between two evaluations from the data)
-    DevBuf<double> q_P;    // (B,NS,64) Riccati matrices of the current factorisation
-    DevBuf<double> q_M;    // (QM_PAD + B*N + QM_PAD, 64) closed-loop matrices A - B K (row-major; the vector recursion reads them
+    WorkBuf<double> q_g;    // (B,NS,10) QP gradient
+    WorkBuf<double> q_rg;   // (B,NS,10) stationarity residual of the interior-point iterate (follows the step between two evaluations from the data)
+    WorkBuf<double> q_P;    // (B,NS,64) Riccati matrices of the current factorisation
+    WorkBuf<double> q_M;    // (QM_PAD + B*N + QM_PAD, 64) closed-loop matrices A - B K (row-major; the vector recursion reads them
                            // transposed), padded at both ends: the sweeps' prefetch rings run QM_PAD rows past an instance unclamped
-    DevBuf<double> scratch;   // (B, 3*8) plant scratch
+    WorkBuf<double> scratch;   // (B, 3*8) plant scratch
 
     // ---- SQP mode (cfg.nlp_solver_type == IHM2MPC_SQP): convergence test + merit line search, kernels_sqp.hip ----
     int sqp_globalization, sqp_use_suff, sqp_full_step_dual;   // globalization: 0 FIXED_STEP, 1 MERIT_BACKTRACKING
     double sqp_alpha_min, sqp_alpha_red, sqp_eps, sqp_tol[4];
-    DevBuf<double> Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
-    DevBuf<double> st_lb, st_ub;           // (NS,NC) device copies of rows.lb / rows.ub
-    DevBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of rows.sz / rows.sZ
+    StateBuf<double> Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
+    StateBuf<double> st_lb, st_ub;           // (NS,NC) device copies of rows.lb / rows.ub
+    StateBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of rows.sz / rows.sZ
     // allocated together by the first SQP solve (api.hip: sqp_buffers): the iterate the QP was built at, merit weights, per-solve bookkeeping
-    DevBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
-    DevBuf<int32_t> ls_done, ls_status, ls_iter, ls_qp_acc;
-    DevBuf<int32_t> ls_pending;            // (B) instances whose line search goes past the first rollouts (two-launch ladder)
-    DevBuf<double> ls_args;                // device copy of the line search's argument block for the persistent loop (512 B)
-    DevBuf<double> step_args;              // device copy of the persistent loop's own argument block (384 B), allocated with the handle
+    WorkBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
+    WorkBuf<int32_t> ls_done, ls_status, ls_iter, ls_qp_acc;
+    WorkBuf<int32_t> ls_pending;            // (B) instances whose line search goes past the first rollouts (two-launch ladder)
+    // The three argument blocks (ls_args, step_args, sens_args) are workspace that is never poisoned: they hold pointers, counts and loop
+    // bounds in the storage of doubles, so an early read would be an address, not arithmetic (api.hip: POISONABLE leaves them out)
+    WorkBuf<double> ls_args;                // device copy of the line search's argument block for the persistent loop (512 B)
+    WorkBuf<double> step_args;              // device copy of the persistent loop's own argument block (384 B), allocated with the handle
     void *args_host[2];             // pinned staging of both blocks (1 KB each), used alternately
     hipEvent_t args_ev[2];          // recorded after a slot's upload: the slot is free again once it has passed
     int args_idx;
@@ -176,15 +206,15 @@ struct ihm2mpc_handle {
     bool inst_w, inst_b;
     bool inst_b_ok;                // false: a later setter changed the shared pattern and the stored values no longer fit it
     bool shared_uniform_H;         // uniform_H of the batch-shared weights (restored when the per-instance weights go)
-    DevBuf<double> iHs, iGy, iWd;          // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
+    StateBuf<double> iHs, iGy, iWd;          // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
     std::vector<double> ih_lb, ih_ub;      // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
-    DevBuf<double> i_slot_lb, i_slot_ub;   // (B,slots.per_lane*64) the slot table's bounds per instance, grown on demand
-    DevBuf<double> i_st_lb, i_st_ub;       // (B,NS,NC) the SQP mode's bounds per instance
-    DevBuf<double> i_lbu, i_ubu, i_lg, i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
+    StateBuf<double> i_slot_lb, i_slot_ub;   // (B,slots.per_lane*64) the slot table's bounds per instance, grown on demand
+    StateBuf<double> i_st_lb, i_st_ub;       // (B,NS,NC) the SQP mode's bounds per instance
+    StateBuf<double> i_lbu, i_ubu, i_lg, i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
 
     // ---- history of ihm2mpc_run_steps, grown on demand ----
-    DevBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)
-    DevBuf<int32_t> hist_st, hist_it;      // (steps,B)
+    WorkBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)
+    WorkBuf<int32_t> hist_st, hist_it;      // (steps,B)
 
     // ---- what was last launched (ihm2mpc_get_launch_record), written from the catalogue's keys (api.hip: note_launch) ----
     int32_t launch_rec[16];
@@ -193,16 +223,16 @@ struct ihm2mpc_handle {
     int sens_mode;                  // 0 off, 1 the stage-0 gain, 2 the whole horizon
     int sens_state;                 // 0 nothing computed in this mode yet, 1 valid for the last solve / step, 2 the last step came from run_steps
     bool sens_quiet;                // run_steps' launches per step: no snapshot, no sensitivity launch (the persistent loop has none either)
-    DevBuf<double> sens_xbar, sens_ubar;   // (B,NS,8), (B,N,2) the point the last QP was linearised at
-    DevBuf<double> sens_u0;                // (B,2,8) du_0 / dx_0
-    DevBuf<double> sens_args;              // device copy of the persistent loop's SensArgs (512 B), allocated with the buffers above
-    DevBuf<double> sens_x, sens_u;         // (B,NS,8,8), (B,N,2,8) (mode 2)
-    DevBuf<double> hist_k;                 // (steps,B,2,8) du_0/dx0 of every step of ihm2mpc_run_steps_sens, grown on demand
+    WorkBuf<double> sens_xbar, sens_ubar;   // (B,NS,8), (B,N,2) the point the last QP was linearised at
+    WorkBuf<double> sens_u0;                // (B,2,8) du_0 / dx_0
+    WorkBuf<double> sens_args;              // device copy of the persistent loop's SensArgs (512 B), allocated with the buffers above
+    WorkBuf<double> sens_x, sens_u;         // (B,NS,8,8), (B,N,2,8) (mode 2)
+    WorkBuf<double> hist_k;                 // (steps,B,2,8) du_0/dx0 of every step of ihm2mpc_run_steps_sens, grown on demand
 
     // ---- adjoint sensitivities (ihm2mpc_eval_adjoint_sensitivities, kernels_adj.hip): grown on demand to the largest n_seeds seen ----
-    DevBuf<double> adj_sx, adj_su;         // (B,n_seeds,NS,8), (B,n_seeds,N,2) seeds
-    DevBuf<double> adj_gx0, adj_gy, adj_gye;   // (B,n_seeds,8), (B,n_seeds,N,12), (B,n_seeds,8) gradients
-    DevBuf<double> adj_gW, adj_gWe;        // (B,n_seeds,12,12), (B,n_seeds,8,8) gradients in the weights (ihm2mpc_eval_adjoint_sensitivities_w)
+    WorkBuf<double> adj_sx, adj_su;         // (B,n_seeds,NS,8), (B,n_seeds,N,2) seeds
+    WorkBuf<double> adj_gx0, adj_gy, adj_gye;   // (B,n_seeds,8), (B,n_seeds,N,12), (B,n_seeds,8) gradients
+    WorkBuf<double> adj_gW, adj_gWe;        // (B,n_seeds,12,12), (B,n_seeds,8,8) gradients in the weights (ihm2mpc_eval_adjoint_sensitivities_w)
 };
 
 // --- launchers (each defined in one .hip file) ---

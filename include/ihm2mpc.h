@@ -144,6 +144,14 @@ const char *ihm2mpc_version(void);
  * series of the 1 - e (...) terms.  h = 12.5 ms, tau = 1 ms: (0.37708781, 0.03225617, -0.02611426).  Non-zero: h or tau not positive and finite. */
 int ihm2mpc_lag_stage_factors(double h, double tau, double *out4);
 
+/* ---- handle lifetime ----
+ * ihm2mpc_create reads two environment variables, so that one process can hold handles of either kind: IHM2MPC_BLOCK_QP (ihm2mpc_run_steps
+ * below) and, for testing, IHM2MPC_POISON_WORKSPACE.  An output read before the call that forms it (the linearisation, the residuals, the
+ * sensitivities, the histories ...) is not defined: the getter returns whatever the workspace holds, zeros on a fresh handle.
+ * IHM2MPC_POISON_WORKSPACE=1 makes that visible: every workspace buffer of doubles is filled with NaN (0xFF bytes) instead of zeros when it is
+ * allocated or regrown; a comma-separated list of buffer names (the handle's WorkBuf members in csrc/ihm2mpc_internal.h, "track_work" for the
+ * work buffers of ihm2mpc_build_tracks / _fit_tracks) poisons only those; unset or 0: nothing changes.  State and problem data (iterates,
+ * multipliers, u0, every uploaded table) are never poisoned. */
 int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out);
 int ihm2mpc_free(ihm2mpc_handle *h);
 int ihm2mpc_synchronize(ihm2mpc_handle *h);
@@ -163,7 +171,7 @@ int ihm2mpc_build_tracks(ihm2mpc_handle *h, int32_t max_seg, const int32_t *nseg
  * min 1/2 p'Pp + q'p s.t. Ap = 0; here: its KKT system, one workgroup per track, sparse Gaussian elimination with partial pivoting).
  * xy (ntracks, max_pts, 2): centre-line points of every track, the first npts[t] rows used (closed path: the last point is NOT the first
  * again); curv_weight: weight of the curvature term (offline_motion_plan uses 2.0, :358); out coeffs_X, coeffs_Y (ntracks, max_pts, 4), host:
- * feed them to ihm2mpc_build_tracks.  3 <= npts[t] <= max_pts <= 182. */
+ * feed them to ihm2mpc_build_tracks; the rows past a track's npts[t] are returned as 0.  3 <= npts[t] <= max_pts <= 182. */
 int ihm2mpc_fit_tracks(ihm2mpc_handle *h, int32_t max_pts, const int32_t *npts, const double *xy, double curv_weight, double *coeffs_X,
                        double *coeffs_Y);
 /* read the tables back, (ntracks, nknots) each; any pointer may be NULL */
@@ -264,7 +272,7 @@ int ihm2mpc_get_linearization(ihm2mpc_handle *h, double *A, double *Bm, double *
 
 int ihm2mpc_get_x(ihm2mpc_handle *h, double *x);
 int ihm2mpc_get_u(ihm2mpc_handle *h, double *u);
-int ihm2mpc_get_u0(ihm2mpc_handle *h, double *u0);              /* (B,2) */
+int ihm2mpc_get_u0(ihm2mpc_handle *h, double *u0);              /* (B,2); 0 before the first solve: the plants of _step / _sim_advance / _run_steps read it */
 int ihm2mpc_get_status(ihm2mpc_handle *h, int32_t *status);     /* (B) */
 int ihm2mpc_get_qp_iter(ihm2mpc_handle *h, int32_t *qp_iter);   /* (B) */
 int ihm2mpc_get_residuals(ihm2mpc_handle *h, double *res);      /* (B,4): stat, eq, ineq, comp */
