@@ -78,10 +78,32 @@ __host__ __device__ constexpr int s_count(int mdl) { return s_pos(mdl, 10, 0); }
 // one RK4 stage of sensitivity column COL:  dX = S + ah*dK_prev ; dK = Jx dX + Ju[:,COL] ; Sacc += wh*dK
 // SL != nullptr: the sub-step's base sensitivities S live in LDS (entry-major, one word per lane: Sl[pos * 64]) instead of
 // registers -- the dynamic model's forward-AD evaluation needs the registers (it spilled 868 B per lane to scratch)
-template <int MODEL, int COL>
+// FACTORED (fkin6 only): J is the factored form of fkin6_eval, whose rows 2 and 5 are applied through rows 0 and 4 of the same stage --
+// the rows are taken in ascending order, so dK[0] and dK[4] are already the new values:
+//   dK[2] = dX[5] - kappa dK[0] - (kappa' s_dot) dX[0] ;  dK[5] = l_R dK[4] - dbd_dd dX[7] - (COL == 9 ? dbd_du : 0)
+// with the terms the column's mask leaves out left out (22 of the 153 products of a stage over the ten columns)
+template <int COL>
+__device__ __forceinline__ double fkin6_factored_row(int i, const double (&J)[8][10], const double (&dX)[8], const double (&dK)[8])
+{
+    constexpr unsigned cm = S_COL_MASK[0][COL];
+    double acc = 0.0;
+    if (i == 2) {
+        if ((cm >> 5) & 1u) acc = dX[5];
+        acc = fma(-J[FKIN6_F_ROW2][FKIN6_F_DKS], dX[0], acc);
+        acc = fma(-J[FKIN6_F_ROW2][FKIN6_F_KAP], dK[0], acc);
+    } else {
+        if (COL == 9) acc = -J[FKIN6_F_ROW5][FKIN6_F_DBD_DU];
+        if ((cm >> 4) & 1u) acc = fma(k_lR, dK[4], acc);
+        if ((cm >> 7) & 1u) acc = fma(-J[FKIN6_F_ROW5][FKIN6_F_DBD_DD], dX[7], acc);
+    }
+    return acc;
+}
+
+template <int MODEL, int COL, bool FACTORED = false>
 __device__ __forceinline__ void sens_col_stage(const double (&J)[8][10], const double (&S)[8], const double *Sl, double (&Sacc)[8],
                                                double (&dK)[8], double ah, double wh)
 {
+    static_assert(!FACTORED || MODEL == IHM2MPC_MODEL_FKIN6, "the factored Jacobian is fkin6's");
     constexpr unsigned cm = S_COL_MASK[MODEL ? 1 : 0][COL];
     double dX[8];
 #pragma unroll
@@ -90,6 +112,7 @@ __device__ __forceinline__ void sens_col_stage(const double (&J)[8][10], const d
 #pragma unroll
     for (int i = 0; i < 8; i++) {
         if (!((cm >> i) & 1u)) continue;
+        if (FACTORED && (i == 2 || i == 5)) { dK[i] = fkin6_factored_row<COL>(i, J, dX, dK); continue; }
         double acc = 0.0;
         if (COL >= 8 && ((JU_MASK[MODEL ? 1 : 0][i] >> (COL - 8)) & 1u)) acc = J[i][COL];
 #pragma unroll
@@ -114,7 +137,7 @@ __device__ __forceinline__ void sens_col_copy(const double (&src)[8], double (&d
 // IHM2MPC_INTEG_ERK_LAG: one RK4 stage of sensitivity column COL of the six vehicle states.  The actuator rows of the stage point are
 // X_a = u + (a - u) E (E: the lag's stage factor, ihm2mpc_lag_stage_factors), so their derivative is E * S_a for a state column and
 // E * S_a + (1 - E) for the lag's own input column; dK and Sacc carry the rows 0..5 only (the rows 6, 7 of S follow a+ in closed form)
-template <int COL>
+template <int COL, bool FACTORED = false>
 __device__ __forceinline__ void sens_col_stage_lag(const double (&J)[8][10], const double (&S)[8], double (&Sacc)[8], double (&dK)[8], double ah,
                                                    double wh, double E_T, double E_d)
 {
@@ -128,6 +151,7 @@ __device__ __forceinline__ void sens_col_stage_lag(const double (&J)[8][10], con
 #pragma unroll
     for (int i = 0; i < 6; i++) {
         if (!((cm >> i) & 1u)) continue;
+        if (FACTORED && (i == 2 || i == 5)) { dK[i] = fkin6_factored_row<COL>(i, J, dX, dK); continue; }
         double acc = 0.0;
         if (COL >= 8 && ((JU_MASK[0][i] >> (COL - 8)) & 1u)) acc = J[i][COL];
 #pragma unroll
@@ -196,7 +220,7 @@ __device__ __forceinline__ void dev_integrate_sens_fkin6(
             double X[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-            fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
+            fkin6_eval<FKIN6_JAC_FACTORED>(X, u_T, u_d, trk, K, J4[st]);
 #pragma unroll
             for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
         }
@@ -207,7 +231,7 @@ __device__ __forceinline__ void dev_integrate_sens_fkin6(
             double Sa[8], dKc[8];                                                                                        \
             _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                              \
             _Pragma("unroll") for (int st = 0; st < 4; st++)                                                             \
-                sens_col_stage<MODEL, c>(J4[st], S[c], nullptr, Sa, dKc, rk4_a(st, h), rk4_w(st, h));                    \
+                sens_col_stage<MODEL, c, true>(J4[st], S[c], nullptr, Sa, dKc, rk4_a(st, h), rk4_w(st, h));              \
             sens_col_copy<MODEL, c>(Sa, S[c]);                                                                           \
         }
         FOR_ALL_COLS(SUBSTEP_COL)
@@ -252,7 +276,7 @@ __device__ __forceinline__ void dev_integrate_sens_fkin6_lag(
             for (int i = 0; i < 6; i++) X[i] = fma(ah, K[i], x[i]);
             X[6] = fma(dT, ET[sf], u_T);
             X[7] = fma(dD, ED[sf], u_d);
-            fkin6_eval<true>(X, u_T, u_d, trk, K, J4[st]);
+            fkin6_eval<FKIN6_JAC_FACTORED>(X, u_T, u_d, trk, K, J4[st]);
 #pragma unroll
             for (int i = 0; i < 6; i++) xacc[i] = fma(wh, K[i], xacc[i]);
         }
@@ -267,7 +291,7 @@ __device__ __forceinline__ void dev_integrate_sens_fkin6_lag(
             _Pragma("unroll") for (int i = 0; i < 8; i++) { Sa[i] = S[c][i]; dKc[i] = 0.0; }                              \
             _Pragma("unroll") for (int st = 0; st < 4; st++) {                                                           \
                 const int sf = (st == 0) ? 0 : ((st == 3) ? 2 : 1);                                                      \
-                sens_col_stage_lag<c>(J4[st], S[c], Sa, dKc, rk4_a(st, h), rk4_w(st, h), ET[sf], ED[sf]);                \
+                sens_col_stage_lag<c, true>(J4[st], S[c], Sa, dKc, rk4_a(st, h), rk4_w(st, h), ET[sf], ED[sf]);          \
             }                                                                                                            \
             _Pragma("unroll") for (int i = 0; i < 6; i++)                                                                \
                 if ((cm >> i) & 1u) S[c][i] = Sa[i];                                                                     \
@@ -391,7 +415,7 @@ __device__ __forceinline__ void dev_sim_step(int b, int q, int model, int M, dou
             double X[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-            if (mdl == IHM2MPC_MODEL_FKIN6) fkin6_eval<false>(X, u_T, u_d, trk, K, J);
+            if (mdl == IHM2MPC_MODEL_FKIN6) fkin6_eval<FKIN6_JAC_NONE>(X, u_T, u_d, trk, K, J);
             else if (mdl == IHM2MPC_MODEL_FDYN6U) fdyn6_eval_quad<true>(q, X, u_T, u_d, trk, K);
             else fdyn6_eval_quad<false>(q, X, u_T, u_d, trk, K);
 #pragma unroll

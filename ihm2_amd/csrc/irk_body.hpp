@@ -106,7 +106,7 @@ template <int MODEL, bool ROW = false>
 __device__ __forceinline__ void eval_model(const double (&X)[8], double u_T, double u_d, TrackSeg &trk, double (&f)[8], double (&J)[8][10])
 {
     // (structural zeros of J are never written and never read: jnz)
-    if (MODEL == IHM2MPC_MODEL_FKIN6) fkin6_eval<true>(X, u_T, u_d, trk, f, J);
+    if (MODEL == IHM2MPC_MODEL_FKIN6) fkin6_eval<FKIN6_JAC_DENSE>(X, u_T, u_d, trk, f, J);
     else fdyn6_eval<true, MODEL == IHM2MPC_MODEL_FDYN6U, ROW>(X, u_T, u_d, trk, f, J);
 }
 

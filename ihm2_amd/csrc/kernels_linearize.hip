@@ -71,10 +71,10 @@ __device__ __forceinline__ void dev_integrate_col_fkin6(const double *xk, const 
             double X[8], J[8][10];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-            fkin6_eval<true>(X, u_T, u_d, trk, K, J);
+            fkin6_eval<FKIN6_JAC_FACTORED>(X, u_T, u_d, trk, K, J);
 #pragma unroll
             for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
-            sens_col_stage<MODEL, COL>(J, S, nullptr, Sacc, dK, ah, wh);
+            sens_col_stage<MODEL, COL, true>(J, S, nullptr, Sacc, dK, ah, wh);
         }
 #pragma unroll
         for (int i = 0; i < 8; i++) x[i] = xacc[i];

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(64) void k_init_guess(int B, int N, int M, double d
                     X[7] = fma(dD0, (st == 0) ? 1.0 : ((st == 3) ? eD : eD2), u_d);
                 }
                 if (MODEL == IHM2MPC_MODEL_FDYN6U) fdyn6_eval<false, true>(X, u_T, u_d, trk, K, J);
-                else fkin6_eval<false>(X, u_T, u_d, trk, K, J);
+                else fkin6_eval<FKIN6_JAC_NONE>(X, u_T, u_d, trk, K, J);
 #pragma unroll
                 for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
             }

@@ -118,10 +118,32 @@ __device__ __forceinline__ double tanh_e(double y)
     return copysign((1.0 - t) / (1.0 + t), y);
 }
 
+// Structural pattern of d f_i / d x_l (bit l of JX_MASK[model][i]) and of d f_i / d u (bit 0: u_T, bit 1: u_delta).
+// fdyn6: rows 3..5 (v_x_dot, v_y_dot, r_dot) depend on (v_x, v_y, r, T, delta) and on no input directly.
+__device__ constexpr unsigned JX_MASK[2][8] = {{0x1Fu, 0x1Cu, 0x3Fu, 0xD8u, 0xC8u, 0xC8u, 0x40u, 0x80u},
+                                               {0x1Fu, 0x1Cu, 0x3Fu, 0xF8u, 0xF8u, 0xF8u, 0x40u, 0x80u}};
+__device__ constexpr unsigned JU_MASK[2][8] = {{0u, 0u, 0u, 2u, 2u, 2u, 1u, 2u}, {0u, 0u, 0u, 0u, 0u, 0u, 1u, 2u}};
+// Rows of the sensitivity matrix S = d x_m / d (x_0, u) that can be non-zero in column j
+// (block-triangular structure): columns s0,n0,psi0 | v_x0,v_y0 | r0 | T0 | delta0 | u_T | u_delta
+__device__ constexpr unsigned S_COL_MASK[2][10] = {{0x07u, 0x07u, 0x07u, 0x3Fu, 0x3Fu, 0x27u, 0x7Fu, 0xBFu, 0x7Fu, 0xBFu},
+                                                   {0x07u, 0x07u, 0x07u, 0x3Fu, 0x3Fu, 0x3Fu, 0x7Fu, 0xBFu, 0x7Fu, 0xBFu}};
+// The factored form of fkin6's Jacobian (FKIN6_JAC_FACTORED, see fkin6_eval) keeps the four factors of its rows 2 and 5 in entries of those
+// rows that the dense form never writes (columns outside JX_MASK[0][2] / JX_MASK[0][5] and JU_MASK): J[2][6] = kappa, J[2][7] = kappa' s_dot,
+// J[5][0] = dbd_dd, J[5][1] = dbd_du.  Nothing else of the two rows is written or read in that form.
+constexpr int FKIN6_F_ROW2 = 2, FKIN6_F_KAP = 6, FKIN6_F_DKS = 7, FKIN6_F_ROW5 = 5, FKIN6_F_DBD_DD = 0, FKIN6_F_DBD_DU = 1;
+static_assert(!((0x3Fu >> FKIN6_F_KAP) & 1u) && !((0x3Fu >> FKIN6_F_DKS) & 1u) && !((0xC8u >> FKIN6_F_DBD_DD) & 1u) && !((0xC8u >> FKIN6_F_DBD_DU) & 1u),
+              "the factors sit outside the dense rows' patterns");
+
 // ---- fkin6: xdot and the 31 structural non-zeros of d xdot / d (x,u) ----
 // J[i][j], j < 8: d/dx_j ; j = 8: d/du_T ; j = 9: d/du_delta.  Entries that are structurally zero
 // are never written and never read.
-template <bool WITH_JAC>
+// WITH_JAC: FKIN6_JAC_NONE (xdot alone), FKIN6_JAC_DENSE (all 31 entries) or FKIN6_JAC_FACTORED: rows 2 and 5 are combinations of rows 0 and 4,
+//   J[2][l] = -kappa J[0][l] (l = 1..4), J[2][0] = -kappa' s_dot - kappa J[0][0], J[2][5] = 1 ;  J[5][.] = l_R J[4][.], less dbd_dd in column 7
+//   and dbd_du in column 9,
+// so the factored form does not assemble them (11 entries) and hands over their four factors instead, for the sensitivity stages to apply
+// to a column directly (device_steps.hpp: sens_col_stage).  Where the factors live is said once, beside JX_MASK above (FKIN6_F_*).
+constexpr int FKIN6_JAC_NONE = 0, FKIN6_JAC_DENSE = 1, FKIN6_JAC_FACTORED = 2;
+template <int WITH_JAC>
 __device__ __forceinline__ void fkin6_eval(const double (&x)[8], double u_T, double u_delta, TrackSeg &trk,
                                            double (&f)[8], double (&J)[8][10])
 {
@@ -138,13 +160,15 @@ __device__ __forceinline__ void fkin6_eval(const double (&x)[8], double u_T, dou
     // slip angle of the kinematic model (models.py:261-284): beta = atan(c tan(delta)).  One sincos(delta) and
     // one rsqrt replace tan, atan, sincos(beta) and sincos(delta - beta):
     //   cos(beta) = cd / sqrt(cd^2 + c^2 sd^2), sin(beta) = c sd / sqrt(cd^2 + c^2 sd^2)   (cd > 0 for |delta| < pi/2)
+    // and the derivatives of beta need no tangent either: with 1 + tan^2 = 1 / cd^2 and 1 + c^2 tan^2 = (cd^2 + c^2 sd^2) / cd^2
+    //   d beta / d delta = c / (cd^2 + c^2 sd^2),   d2 beta / d delta2 = 2 c (1 - c^2) sd cd / (cd^2 + c^2 sd^2)^2
+    // exactly -- one reciprocal, nothing that grows as cd -> 0
     double sd, cd;
     fast_sincos(delta, &sd, &cd);
-    const double td = sd / cd;
-    const double hyp = 1.0 / sqrt(cd * cd + c * c * sd * sd);
+    const double hyp2 = 1.0 / (cd * cd + c * c * sd * sd);
+    const double hyp = sqrt(hyp2);
     const double cb = cd * hyp, sb = c * sd * hyp;
-    const double den = 1.0 + c * c * td * td;
-    const double bp = c * (1.0 + td * td) / den;          // d beta / d delta
+    const double bp = c * hyp2;                           // d beta / d delta
     const double beta_dot = bp * delta_dot;
     const double cdb = cd * cb + sd * sb, sdb = sd * cb - cd * sb;      // cos / sin (delta - beta)
     const double v_dot = (F_Rx * cb + F_Fx * cdb) * (1.0 / k_m);
@@ -168,7 +192,7 @@ __device__ __forceinline__ void fkin6_eval(const double (&x)[8], double u_T, dou
     f[7] = delta_dot;
     if (WITH_JAC) {
         const double dFdrag = -(k_Cr1 + 2.0 * k_Cr2 * v_x) * sg - poly * 10.0 * (1.0 - sg * sg);
-        const double bpp = 2.0 * c * td * (1.0 + td * td) * (1.0 - c * c) / (den * den);
+        const double bpp = (2.0 * c * (1.0 - c * c)) * (sd * cd) * (hyp2 * hyp2);
         const double dbd_dd = bpp * delta_dot - bp * (1.0 / k_tdelta);
         const double dbd_du = bp * (1.0 / k_tdelta);
         const double dv_dvx = dFdrag * cb * (1.0 / k_m);
@@ -183,12 +207,19 @@ __device__ __forceinline__ void fkin6_eval(const double (&x)[8], double u_T, dou
         J[1][2] = num;
         J[1][3] = sp;
         J[1][4] = cp;
-        J[2][0] = -dk * s_dot - kap * J[0][0];
-        J[2][1] = -kap * J[0][1];
-        J[2][2] = -kap * J[0][2];
-        J[2][3] = -kap * J[0][3];
-        J[2][4] = -kap * J[0][4];
-        J[2][5] = 1.0;
+        if (WITH_JAC == FKIN6_JAC_FACTORED) {
+            J[FKIN6_F_ROW2][FKIN6_F_KAP] = kap;
+            J[FKIN6_F_ROW2][FKIN6_F_DKS] = (dk * num) * inv_dn;
+            J[FKIN6_F_ROW5][FKIN6_F_DBD_DD] = dbd_dd;
+            J[FKIN6_F_ROW5][FKIN6_F_DBD_DU] = dbd_du;
+        } else {
+            J[2][0] = -dk * s_dot - kap * J[0][0];
+            J[2][1] = -kap * J[0][1];
+            J[2][2] = -kap * J[0][2];
+            J[2][3] = -kap * J[0][3];
+            J[2][4] = -kap * J[0][4];
+            J[2][5] = 1.0;
+        }
         J[3][3] = dv_dvx * cb;
         J[3][4] = -beta_dot;
         J[3][6] = dv_dT * cb;
@@ -198,10 +229,12 @@ __device__ __forceinline__ void fkin6_eval(const double (&x)[8], double u_T, dou
         J[4][6] = dv_dT * sb;
         J[4][7] = dv_dd * sb + v_dot * cb * bp + dbd_dd * v_x;
         J[4][9] = dbd_du * v_x;
-        J[5][3] = k_lR * J[4][3];
-        J[5][6] = k_lR * J[4][6];
-        J[5][7] = k_lR * J[4][7] - dbd_dd;
-        J[5][9] = k_lR * J[4][9] - dbd_du;
+        if (WITH_JAC != FKIN6_JAC_FACTORED) {
+            J[5][3] = k_lR * J[4][3];
+            J[5][6] = k_lR * J[4][6];
+            J[5][7] = k_lR * J[4][7] - dbd_dd;
+            J[5][9] = k_lR * J[4][9] - dbd_du;
+        }
         J[6][6] = -1.0 / k_tT;
         J[6][8] = 1.0 / k_tT;
         J[7][7] = -1.0 / k_tdelta;
@@ -234,16 +267,6 @@ __device__ __forceinline__ double alat_eval(const double v_x, const double v_y, 
     g[3] = (-F_Rx * cb * bp + F_Fx * cdb * (1.0 - bp)) * (1.0 / k_m) + vv * cb * bp * (1.0 / k_lR);
     return (-F_Rx * sb + F_Fx * sdb) * (1.0 / k_m) + vv * sb * (1.0 / k_lR);
 }
-
-// Structural pattern of d f_i / d x_l (bit l of JX_MASK[model][i]) and of d f_i / d u (bit 0: u_T, bit 1: u_delta).
-// fdyn6: rows 3..5 (v_x_dot, v_y_dot, r_dot) depend on (v_x, v_y, r, T, delta) and on no input directly.
-__device__ constexpr unsigned JX_MASK[2][8] = {{0x1Fu, 0x1Cu, 0x3Fu, 0xD8u, 0xC8u, 0xC8u, 0x40u, 0x80u},
-                                               {0x1Fu, 0x1Cu, 0x3Fu, 0xF8u, 0xF8u, 0xF8u, 0x40u, 0x80u}};
-__device__ constexpr unsigned JU_MASK[2][8] = {{0u, 0u, 0u, 2u, 2u, 2u, 1u, 2u}, {0u, 0u, 0u, 0u, 0u, 0u, 1u, 2u}};
-// Rows of the sensitivity matrix S = d x_m / d (x_0, u) that can be non-zero in column j
-// (block-triangular structure): columns s0,n0,psi0 | v_x0,v_y0 | r0 | T0 | delta0 | u_T | u_delta
-__device__ constexpr unsigned S_COL_MASK[2][10] = {{0x07u, 0x07u, 0x07u, 0x3Fu, 0x3Fu, 0x27u, 0x7Fu, 0xBFu, 0x7Fu, 0xBFu},
-                                                   {0x07u, 0x07u, 0x07u, 0x3Fu, 0x3Fu, 0x3Fu, 0x7Fu, 0xBFu, 0x7Fu, 0xBFu}};
 
 // ---- transcendental functions of the dynamic model as CALLS ----
 // One body per function instead of one inlined copy per use (13 atan, 6 sincos, 5 tanh, 4 exp per evaluation of the force model):

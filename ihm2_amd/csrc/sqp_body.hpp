@@ -60,7 +60,7 @@ __device__ __forceinline__ void rollout(double (&x)[8], double u_T, double u_d, 
             double X[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) X[i] = fma(ah, K[i], x[i]);
-            if (MODEL == IHM2MPC_MODEL_FKIN6) fkin6_eval<false>(X, u_T, u_d, trk, K, J);
+            if (MODEL == IHM2MPC_MODEL_FKIN6) fkin6_eval<FKIN6_JAC_NONE>(X, u_T, u_d, trk, K, J);
             else fdyn6_eval<false, MODEL == IHM2MPC_MODEL_FDYN6U>(X, u_T, u_d, trk, K, J);
 #pragma unroll
             for (int i = 0; i < 8; i++) xacc[i] = fma(wh, K[i], xacc[i]);
