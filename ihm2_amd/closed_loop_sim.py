@@ -75,6 +75,16 @@ class Simulator:
         """Host arrays in, host arrays out: ``x`` (B,8), ``u`` (B,2) -> next state (B,8)."""
         return self.controller.solver.sim_step(x, u, model=_PLANT_CODE[self.variant], M_sim=self.config.num_steps)
 
+    def simulate_sens(self, x: np.ndarray, u: np.ndarray) -> dict:
+        """``simulate`` with the plant's Jacobians: ``dict(x=(B,8), Sx=(B,8,8), Su=(B,8,2), model_used=(B,))``
+        (``BatchedOcpSolver.sim_step_sens``; for the switched variants the derivative of the branch taken)."""
+        return self.controller.solver.sim_step_sens(x, u, model=_PLANT_CODE[self.variant], M_sim=self.config.num_steps)
+
+    def closed_loop_matrix(self) -> np.ndarray:
+        """``Sx + Su @ K0`` ``(B,8,8)`` of this plant at the controller's ``(x0, u0)`` with the gain of its last solve
+        (``IHM2Controller(x0_sensitivities=True)``)."""
+        return self.controller.solver.closed_loop_matrix(model=_PLANT_CODE[self.variant], M_sim=self.config.num_steps)
+
     def advance(self) -> None:
         """x0 <- plant(x0, u0 of the last solve) without leaving the device."""
         self.controller.solver.sim_advance(model=_PLANT_CODE[self.variant], M_sim=self.config.num_steps)

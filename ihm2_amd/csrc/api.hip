@@ -1388,6 +1388,59 @@ int ihm2mpc_sim_advance(ihm2mpc_handle *h, int32_t model, int32_t M_sim)
     return 0;
 }
 
+// ---- plant step with forward sensitivities (kernels_simsens.hip) ----
+static int check_plant_sens(const ihm2mpc_handle *h, int model, int M_sim, const void *x, const void *u)
+{
+    if (!h->tracks_set) return fail("ihm2mpc_set_tracks has not been called");
+    if (!x || !u) return fail("null argument");
+    return check_plant(h, model, M_sim);
+}
+
+int ihm2mpc_sim_step_sens_device(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const void *x, const void *u, void *x_next, void *S_x,
+                                 void *S_u, void *model_used)
+{
+    CHECK_H(h);
+    if (check_plant_sens(h, model, M_sim, x, u)) return -1;
+    // the kernels of a switched plant run under the mask: without the caller's array a local one, released (which waits for the device)
+    // when the call returns
+    StateBuf<int32_t> mask;
+    if (!model_used && model < 0) {
+        HIP_TRY(mask.alloc(h->B));
+        model_used = mask.get();
+    }
+    if (ihm2_launch_sim_sens(h, model, M_sim, (const double *)x, (const double *)u, (double *)x_next, (double *)S_x, (double *)S_u,
+                             (int32_t *)model_used, h->stream))
+        return fail("upload of the plant's collocation tableau failed");
+    HIP_TRY(hipGetLastError());
+    if (mask) HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int ihm2mpc_sim_step_sens(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const double *x, const double *u, double *x_next, double *S_x,
+                          double *S_u, int32_t *model_used)
+{
+    CHECK_H(h);
+    if (check_plant_sens(h, model, M_sim, x, u)) return -1;
+    const size_t B = h->B;
+    StateBuf<double> din;            // the uploaded pairs: x (B,8), u (B,2)
+    WorkBuf<double> dwork;           // "sim_sens_work": x_next (B,8), S_x (B,8,8), S_u (B,8,2)
+    WorkBuf<int32_t> dmodel;         // model_used (B)
+    dwork.poison(poisoned(h, "sim_sens_work"));
+    HIP_TRY(din.alloc(B * (NX + NU)));
+    if (dwork.alloc(B * (NX + NX * NX + NX * NU)) != hipSuccess || dmodel.alloc(B) != hipSuccess) return fail("out of device memory");
+    double *dx = din, *du = din + B * NX, *dxn = dwork, *dSx = dwork + B * NX, *dSu = dwork + B * (NX + NX * NX);
+    HIP_TRY(hipMemcpyAsync(dx, x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(du, u, B * NU * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (ihm2_launch_sim_sens(h, model, M_sim, dx, du, dxn, dSx, dSu, dmodel, h->stream)) return fail("upload of the plant's collocation tableau failed");
+    HIP_TRY(hipGetLastError());
+    if (x_next) HIP_TRY(hipMemcpyAsync(x_next, dxn, B * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (S_x) HIP_TRY(hipMemcpyAsync(S_x, dSx, B * NX * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (S_u) HIP_TRY(hipMemcpyAsync(S_u, dSu, B * NX * NU * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (model_used) HIP_TRY(hipMemcpyAsync(model_used, dmodel, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 int ihm2mpc_host_alloc(uint64_t nbytes, void **p)
 {
     if (!p || nbytes == 0) return fail("null argument");

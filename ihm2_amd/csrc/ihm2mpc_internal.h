@@ -257,6 +257,10 @@ void ihm2_launch_copy_iterate(ihm2mpc_handle *h);   // x, u, pi, lam, slk -> ls_
 void ihm2_launch_line_search(ihm2mpc_handle *h, int it, int last, int phase = 0, int j_limit = 0);
 void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, hipStream_t stream,
                      const int32_t *active);
+// kernels_simsens.hip: the plant step with forward sensitivities on `stream`; xn (B,8), Sx (B,8,8), Su (B,8,2), model_used (B) may each be
+// nullptr, model_used not for the switched plants (model < 0), whose kernels run under it; 0 ok
+int ihm2_launch_sim_sens(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, double *Sx, double *Su,
+                         int32_t *model_used, hipStream_t stream);
 void ihm2_launch_sim_cart(ihm2mpc_handle *h, int model, int M, double dt, int n_steps, double v_dyn, const double *x, const double *u,
                           double *xn, hipStream_t stream);
 void ihm2_launch_project(ihm2mpc_handle *h, double s_tol, const double *xc, double *s_guess, double *xf, hipStream_t stream);

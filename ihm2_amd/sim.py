@@ -5,7 +5,8 @@ The reference builds one ``AcadosSimSolver`` per plant model (``python/main.py:3
 ``T = dt``), hands it the track as parameter vector ``p = [s_ref; kappa_ref]`` (``:432-435``) and calls ``simulate(x, u)`` once per
 control period (``:476-502``).  Here the same object integrates a BATCH: ``x`` may be ``(8,)`` (the reference's call, returns ``(8,)``)
 or ``(B, 8)``.  Fields of ``set`` / ``get`` as used by the reference and by ``old/scripts/gen_sim.py:599-604``: ``"x"``, ``"u"``,
-``"p"``, ``"T"`` in, ``"x"`` (the state after ``solve``), ``"CPUtime"`` / ``"time_tot"`` (seconds of the last ``solve``) out.
+``"p"``, ``"T"`` in, ``"x"`` (the state after ``solve``), ``"CPUtime"`` / ``"time_tot"`` (seconds of the last ``solve``) out; with
+``AcadosSimOpts.sens_forw`` also ``"Sx"``, ``"Su"`` and ``"S_forw"`` = ``[Sx Su]`` (``ihm2mpc_sim_step_sens``).
 No code generation: ``gen_code_dir`` and the ``generate`` / ``build`` keywords are accepted and ignored.
 """
 from __future__ import annotations
@@ -28,6 +29,9 @@ class AcadosSimOpts:
     integrator_type: str = "IRK"
     collocation_type: str = "GAUSS_LEGENDRE"
     newton_iter: int = 3
+    # A named deviation: acados defaults to True.  False keeps solve() on ihm2mpc_sim_step, the kernel it has always run, bit for bit;
+    # True makes solve() call ihm2mpc_sim_step_sens and get("Sx" | "Su" | "S_forw") answer
+    sens_forw: bool = False
 
 
 @dataclass
@@ -58,10 +62,14 @@ class AcadosSimSolver:
         # fdyn10 (python/models.py:609-801; the DYN10 plant of python/main.py:490-502): 15 states, 5 inputs; "IRK" = the reference's
         # Radau IIA x num_steps solved to convergence (usable from rest, python/main.py:438-441), "ERK" = RK4 x num_steps (moving cars)
         self.dyn10 = sim.model.kind == "fdyn10"
+        self.sens_forw = bool(getattr(o, "sens_forw", False))
+        if self.sens_forw and self.dyn10:
+            raise ValueError("sens_forw=True: the fdyn10 sim model has no forward sensitivities (fkin6, fdyn6, fdyn6u have)")
         self.nx, self.nu = (15, 5) if self.dyn10 else (NX, NU)
         self._T = float(o.T)
         self._p = None if sim.parameter_values is None else np.asarray(sim.parameter_values, dtype=float).ravel()
         self._x = np.zeros((self.B, self.nx)); self._u = np.zeros((self.B, self.nu)); self._xn = np.zeros((self.B, self.nx))
+        self._Sx = self._Su = None
         self._time = 0.0
         self._solver = None
 
@@ -111,6 +119,9 @@ class AcadosSimSolver:
         t0 = time.perf_counter()
         if self.dyn10:
             self._xn = s.sim_step_dyn10(self._x, self._u, M_sim=int(self.sim.solver_options.num_steps))
+        elif self.sens_forw:
+            out = s.sim_step_sens(self._x, self._u, model=self.model_id, M_sim=int(self.sim.solver_options.num_steps))
+            self._xn, self._Sx, self._Su = out["x"], out["Sx"], out["Su"]
         else:
             self._xn = s.sim_step(self._x, self._u, model=self.model_id, M_sim=int(self.sim.solver_options.num_steps))
         self._time = time.perf_counter() - t0
@@ -121,6 +132,13 @@ class AcadosSimSolver:
             return self._xn[0].copy() if self.B == 1 else self._xn.copy()
         if field_ in ("CPUtime", "time_tot"):
             return self._time
+        if field_ in ("Sx", "Su", "S_forw"):
+            if not self.sens_forw:
+                raise ValueError(f"field {field_!r} needs AcadosSimOpts.sens_forw = True (off by default here: solve() then computes no sensitivities)")
+            if self._Sx is None:
+                raise ValueError(f"field {field_!r}: call solve() first")
+            v = {"Sx": self._Sx, "Su": self._Su}[field_] if field_ != "S_forw" else np.concatenate([self._Sx, self._Su], axis=2)
+            return v[0].copy() if self.B == 1 else v.copy()
         raise ValueError(f"unknown field {field_!r}: x, CPUtime")
 
     def simulate(self, x=None, u=None, p=None):

@@ -422,7 +422,7 @@ class BatchedOcpSolver:
         DYN, and an eighth 1 for the loop with x0 sensitivities) or ``"per_step"`` with ``steps_fallback`` ``"no_instantiation"`` /
         ``"not_resident"``; ``linearize`` / ``sim``: the kernel of the last linearisation / plant launch outside ``k_steps``
         (``"k_linearize"``, ``"k_linearize_dyn"``, ``"k_linearize_cols"``, ``"k_linearize_irk"``, ``"k_linearize_lag"``; ``"k_sim_step_kin"``,
-        ``"k_sim_step"``, ``"k_sim_irk"``, ``"k_sim_step_kin_lag"``; ``_lag``: the integrator ``"ERK_LAG"``); ``qp_form`` / ``steps_form``: the form of the factor sweep in those two launches, ``"general"``,
+        ``"k_sim_step"``, ``"k_sim_irk"``, ``"k_sim_step_kin_lag"``, ``"k_sim_sens"`` (``sim_step_sens``); ``_lag``: the integrator ``"ERK_LAG"``); ``qp_form`` / ``steps_form``: the form of the factor sweep in those two launches, ``"general"``,
         ``"plain"`` (straight-line stage, run-time horizon) or ``"plain_n40"`` (the horizon 40 compiled in) -- same results, so the
         kernel names above do not tell them apart; ``qp_slots`` / ``steps_slots``: the form of the slot phases alike, ``"general"`` or
         ``"full"`` (a table of 64 x 5 hard two-sided rows at the horizon 40: no validity or side test per slot).  ``None`` where nothing
@@ -441,7 +441,7 @@ class BatchedOcpSolver:
         elif r[5] == 2:
             steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
         lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk", "k_linearize_lag")[r[15] & 15]
-        sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk", "k_sim_step_kin_lag")[(r[15] >> 4) & 15]
+        sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk", "k_sim_step_kin_lag", "k_sim_sens")[(r[15] >> 4) & 15]
         forms = ("general", "plain", "plain_n40", None)
         slots = ("general", "full")
         return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim,
@@ -542,6 +542,34 @@ class BatchedOcpSolver:
         out = np.empty((self.B, NX))
         _lib.check(self.lib.ihm2mpc_sim_step(self._h, int(model), int(M_sim), _ptr(x), _ptr(u), _ptr(out)))
         return out
+
+    def sim_step_sens(self, x, u, model: int = 0, M_sim: int = 100):
+        """Plant step with forward sensitivities (acados: ``AcadosSimSolver.solve()`` with ``sens_forw``): ``dict(x=(B,8), Sx=(B,8,8),
+        Su=(B,8,2), model_used=(B,) int32)`` with ``Sx[b,i,j] = dx_next,i/dx_j``, ``Su[b,i,j] = dx_next,i/du_j`` -- the exact derivative
+        of the handle's plant integrator with ``M_sim`` steps -- and the model that integrated instance ``b`` (for the switched plants
+        ``model = -1 / -2`` the branch taken, whose derivative it is: the rule is piecewise).  ``ihm2mpc_sim_step_sens``; nothing else of
+        the solver changes."""
+        x = _f64(x, (self.B, NX), "x"); u = _f64(u, (self.B, NU), "u")
+        out = dict(x=np.empty((self.B, NX)), Sx=np.empty((self.B, NX, NX)), Su=np.empty((self.B, NX, NU)), model_used=np.empty(self.B, dtype=np.int32))
+        _lib.check(self.lib.ihm2mpc_sim_step_sens(self._h, int(model), int(M_sim), _ptr(x), _ptr(u), _ptr(out["x"]), _ptr(out["Sx"]), _ptr(out["Su"]),
+                                                  out["model_used"].ctypes.data_as(_lib.c_int32_p)))
+        return out
+
+    def sim_step_sens_device(self, x_dptr: int, u_dptr: int, model: int = 0, M_sim: int = 100, x_next: int = 0, Sx: int = 0, Su: int = 0,
+                             model_used: int = 0):
+        """The same on device (or pinned host) memory, stream-ordered: addresses as integers, 0 = that output is not wanted."""
+        ptr = [C.c_void_p(int(a)) if a else None for a in (x_next, Sx, Su, model_used)]
+        _lib.check(self.lib.ihm2mpc_sim_step_sens_device(self._h, int(model), int(M_sim), C.c_void_p(int(x_dptr)), C.c_void_p(int(u_dptr)), *ptr))
+
+    def closed_loop_matrix(self, model: int = 0, M_sim: int = 100):
+        """``A_cl = Sx + Su @ K0`` ``(B,8,8)``: the plant's Jacobian at the handle's ``(x0, u0)`` closed with the gain ``K0 = du_0/dx_0`` of
+        the last solve -- the linearised closed loop of one control period, whose spectral radius says whether a tuning is linearly
+        stable on that plant.  Needs ``set_x0_sensitivities(1 or 2)`` before the solve (refused otherwise, as ``get_x0_sensitivities``
+        is); NaN rows where ``K0`` has them (status neither 0 nor 2)."""
+        _, su = self.get_x0_sensitivities()
+        K0 = su[:, 0] if su.ndim == 4 else su
+        s = self.sim_step_sens(self.get_x0(), self.get_u0(), model=model, M_sim=M_sim)
+        return s["Sx"] + s["Su"] @ K0
 
     # ---- Cartesian side of the ROS stack (plants of sim_node.cpp, Track::project) ----
     def set_track_geometry(self, X_ref, Y_ref, phi_ref):

@@ -25,6 +25,7 @@
  *   ihm2mpc_get_status        <- return value of solve()                        python/main.py:325-328; dpc/main.py:287-293
  *   ihm2mpc_get_residuals     <- solver.get_stats("residuals") (acados)
  *   ihm2mpc_sim_step          <- AcadosSimSolver.simulate(x,u)                  python/main.py:476-502; python/sim.py:9-25
+ *   ihm2mpc_sim_step_sens <- AcadosSimSolver.solve() with sens_forw; get("Sx" | "Su" | "S_forw")
  *   ihm2mpc_compute_control   <- IHM2Controller.compute_control(x) as one call            python/main.py:297-334
  *   ihm2mpc_step              <- one iteration of the MiL loop (plant + compute_control)  python/main.py:476-517
  *   ihm2mpc_run_steps         <- n iterations of that loop in one launch                  python/main.py:448-517
@@ -297,7 +298,8 @@ int ihm2mpc_get_timings(ihm2mpc_handle *h, double *ms, int32_t n);
  *   [15] bits 0..3 the last linearisation launch (ihm2mpc_linearize, a solve, ihm2mpc_step): 0 none yet, 1 k_linearize, 2 k_linearize_dyn,
  *       3 k_linearize_cols, 4 k_linearize_irk, 5 k_linearize with the closed-form lags (ERK_LAG);  bits 4..7 the last plant launch
  *       (ihm2mpc_sim_step, ihm2mpc_sim_advance, ihm2mpc_step): 0 none yet, 1 k_sim_step_kin, 2 k_sim_step, 3 k_sim_irk, 4 k_sim_step_kin with
- *       the closed-form lags (ERK_LAG).  Launches inside k_steps are not recorded here.
+ *       the closed-form lags (ERK_LAG), 5 a plant step with sensitivities (ihm2mpc_sim_step_sens, ihm2mpc_sim_step_sens_device: the
+ *       kernels of kernels_simsens.hip).  Launches inside k_steps are not recorded here.
  *       bits 8..9 the form of the factor sweep in the QP of [0], bits 12..13 in the k_steps launch of [5] (0 when [5] != 1): 0 the general
  *       form, 1 the straight-line stage with the run-time horizon, 2 the straight-line stage with the horizon compiled in (N = 40).  The
  *       forms give the same bits; a table without active rows and the model IHM2MPC_MODEL_FDYN6 take the general form, and so does every
@@ -392,6 +394,33 @@ int ihm2mpc_sim_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const doub
  * switch with IHM2MPC_MODEL_FDYN6U as the dynamic model) */
 int ihm2mpc_sim_advance(ihm2mpc_handle *h, int32_t model, int32_t M_sim);
 int ihm2mpc_get_x0(ihm2mpc_handle *h, double *x0);
+/* Plant step with forward sensitivities (acados: AcadosSimSolver.solve() with sens_forw, then get("Sx" | "Su" | "S_forw")):
+ *   ihm2mpc_sim_step_sens <- AcadosSimSolver.solve() with sens_forw; get("Sx" | "Su" | "S_forw")
+ * x (B,8), u (B,2) -> x_next (B,8), S_x (B,8,8) with S_x[b][i][j] = d x_next,i / d x_j, S_u (B,8,2) with S_u[b][i][j] = d x_next,i / d u_j
+ * (S_forw = [S_x S_u]), and model_used (B) int32: the model that integrated instance b, 0, 1 or 2 (IHM2MPC_MODEL_*).  Any output may be
+ * NULL.
+ * model is 0, 1, 2, -1 or -2 as for ihm2mpc_sim_step; the integrator is the handle's sim_integrator_type with M_sim steps over the
+ * handle's dt, and the sensitivities are the exact derivative of that discrete map, in its three integrator families:
+ *   IHM2MPC_INTEG_ERK      the derivative of the RK4 x M_sim map, propagated through the same stages;
+ *   IHM2MPC_INTEG_ERK_LAG  model 0 only: the same with the actuator lags in closed form, stage factors of h = dt / M_sim;
+ *   IHM2MPC_INTEG_IRK_GL4 / _IRK_RADAU4  collocation: per step IHM2MPC_IRK_NEWTON_ITER Newton iterations from K = 0 and the
+ *                          implicit-function sensitivities at the final stage values (as the linearisation of the shooting intervals),
+ *                          with the plant's tableau for h = dt / M_sim; the steps are chained.
+ * For a switched plant (model -1 / -2) model_used is the branch the kin / dyn switch of python/main.py:482-489 took at x_b, decided
+ * once at the start of the period, and the derivative is that of the branch taken: the rule is PIECEWISE -- on the switching surface
+ * x_next itself jumps, and S_x, S_u say nothing about that jump.  An instance gets the bits of a call with its model fixed.
+ * Refused as ihm2mpc_sim_step refuses: an unknown model, ERK_LAG with a dynamic or switched plant, too few RK4 sub-steps for the
+ * actuator lags, tracks not set, NULL x or u.  The Cartesian plants (IHM2MPC_PLANT_*, ihm2mpc_sim_step_cart) and fdyn10
+ * (ihm2mpc_sim_step_dyn10) have no such entry: their model numbers are refused as unknown.
+ * Nothing else of the handle changes: x0, u0, the iterate, the linearisation records that ihm2mpc_get_linearization reads and every
+ * getter keep their values; of the launch record only [15] bits 4..7 move (code 5).  Staging is local to the call.
+ * The host variant blocks.  The device variant takes device memory of the handle's device (or pinned host memory) in the same layouts
+ * and is stream-ordered like the other _device entries: inputs and outputs must stay valid, and must not overlap, until the stream has
+ * passed; with model_used NULL on a switched plant it waits for the stream itself (the mask is then local to the call). */
+int ihm2mpc_sim_step_sens(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const double *x, const double *u,
+                          double *x_next, double *S_x, double *S_u, int32_t *model_used);
+int ihm2mpc_sim_step_sens_device(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const void *x, const void *u,
+                                 void *x_next, void *S_x, void *S_u, void *model_used);
 /* one iteration of the MiL loop (python/main.py:476-517) on the device: sim_advance(model, M_sim), prepare_step(s_target) and
  * one RTI iteration.  Same results as the three calls; the plant step and the reference ramp run beside the warm-start
  * shift and the linearisation (they only meet in the QP), which hides the plant's latency. */

@@ -14,7 +14,12 @@
       the handle's stream around the call with every output NULL (the seed upload and the kernel; for the default seeds the kernel alone).
   (e) --adjoint-weights: the same rows for ihm2mpc_eval_adjoint_sensitivities_w (k_adj<true>: the gradients in the cost weights W, W_e as
       well; the wall time holds its five downloads).
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights] > result.json"""
+  (f) --plant: the plant step with forward sensitivities (kernels_simsens.hip) beside the plant step the handle already has, B = 1024,
+      RK4 x 30, model 0 and model 2: HIP events on the handle's stream around ihm2mpc_sim_advance (the kernel of ihm2mpc_sim_step alone, on
+      the handle's x0, u0, which are restored before every call) and around ihm2mpc_sim_step_sens_device on the same pairs with every
+      output NULL (the kernel alone) and with all four outputs; wall time of the two blocking host calls.  --lib PATH times a library
+      that lacks the new entries (the parent's build) on the plant rows alone: ihm2mpc_sim_step's kernel is not to move.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --plant [--lib PATH]] > result.json"""
 import argparse
 import ctypes
 import json
@@ -166,6 +171,83 @@ def adjoint_timings(B, steps, warmup, weights=False):
     return out
 
 
+def plant_timings(B, steps, warmup, lib_path=None):
+    from ihm2_amd import _lib
+
+    new = ("ihm2mpc_sim_step_sens", "ihm2mpc_sim_step_sens_device")
+    if lib_path:
+        _lib.LIB_PATH, _lib._lib = os.path.abspath(lib_path), None
+        probe = ctypes.CDLL(_lib.LIB_PATH)
+        if not all(hasattr(probe, n) for n in new):          # the parent's build: bind what it has
+            for n in new:
+                _lib.SYMBOLS.pop(n, None)
+    have = all(n in _lib.SYMBOLS for n in new)
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    ocp, track = bench.build_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    s.set_x0(bench.sample_x0(track, B, 20240607))
+    s.init_guess()
+    s.prepare_step(40.0)
+    s.solve()
+    x0, u0 = s.get_x0(), s.get_u0()
+    stream = ctypes.c_void_p()
+    _lib.check(s.lib.ihm2mpc_get_stream(s._h, ctypes.byref(stream)))
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(ctypes.byref(e)) == 0
+    sizes = dict(x=x0.nbytes, u=u0.nbytes, xn=B * 64, Sx=B * 512, Su=B * 128, mu=B * 4)
+    buf = {}
+    for k, n in sizes.items():
+        buf[k] = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(buf[k]), ctypes.c_size_t(n)) == 0
+    assert hip.hipMemcpy(buf["x"], ctypes.c_void_p(x0.ctypes.data), ctypes.c_size_t(x0.nbytes), 1) == 0
+    assert hip.hipMemcpy(buf["u"], ctypes.c_void_p(u0.ctypes.data), ctypes.c_size_t(u0.nbytes), 1) == 0
+
+    def events(call, before=None):
+        ms_all = []
+        for _ in range(warmup + steps):
+            if before:
+                before()
+            assert hip.hipEventRecord(ev[0], stream) == 0
+            call()
+            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+            ms = ctypes.c_float()
+            assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) == 0
+            ms_all.append(ms.value)
+        t = ms_all[warmup:]
+        return dict(event_ms=float(np.median(t)), spread=float(np.ptp(t) / np.median(t)))
+
+    def wall(call):
+        t = []
+        for _ in range(warmup + steps):
+            t0 = time.perf_counter()
+            call()
+            t.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(t[warmup:]))
+
+    out = {}
+    for model in (0, 2):
+        r = {"sim_step_kernel": events(lambda: s.sim_advance(model=model, M_sim=30), before=lambda: s.set_x0(x0))}
+        r["sim_step_kernel"]["kernel"] = s.get_launch_record()["sim"]
+        r["sim_step_call_wall_ms"] = wall(lambda: s.sim_step(x0, u0, model=model, M_sim=30))
+        if have:
+            r["sim_step_sens_kernel"] = events(lambda: s.sim_step_sens_device(buf["x"].value, buf["u"].value, model=model, M_sim=30))
+            r["sim_step_sens_kernel_and_stores"] = events(lambda: s.sim_step_sens_device(
+                buf["x"].value, buf["u"].value, model=model, M_sim=30, x_next=buf["xn"].value, Sx=buf["Sx"].value, Su=buf["Su"].value,
+                model_used=buf["mu"].value))
+            r["sim_step_sens_call_wall_ms"] = wall(lambda: s.sim_step_sens(x0, u0, model=model, M_sim=30))
+            r["kernel_ratio"] = r["sim_step_sens_kernel"]["event_ms"] / r["sim_step_kernel"]["event_ms"]
+        out[f"model{model}"] = r
+    for e in ev:
+        hip.hipEventDestroy(e)
+    for b in buf.values():
+        hip.hipFree(b)
+    s.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
@@ -174,7 +256,12 @@ def main():
     ap.add_argument("--only-loops", action="store_true")
     ap.add_argument("--adjoint", action="store_true")
     ap.add_argument("--adjoint-weights", action="store_true")
+    ap.add_argument("--plant", action="store_true")
+    ap.add_argument("--lib", default=None, help="--plant: path of another build of libihm2mpc.so (one without the new entries times ihm2mpc_sim_step alone)")
     a = ap.parse_args()
+    if a.plant:
+        print(json.dumps({"plant": {"1024": plant_timings(1024, a.steps, a.warmup, a.lib)}, "lib": a.lib or "product"}))
+        return
     if a.adjoint or a.adjoint_weights:
         key = "adjoint_weights" if a.adjoint_weights else "adjoint"
         print(json.dumps({key: {str(B): adjoint_timings(B, a.steps, a.warmup, a.adjoint_weights) for B in (1024, 8192)}}))
