@@ -14,6 +14,7 @@
 
 #include "ihm2mpc_internal.h"
 #include "qp_catalogue.hpp"
+#include "qp_select.hpp"
 #include "sqp_body.hpp"
 
 static thread_local std::string g_err;
@@ -150,130 +151,51 @@ int scatter_instance_bounds(ihm2mpc_handle *h)
     if (n && (upload_shared(h, slb.data(), h->i_slot_lb, slb.size()) || upload_shared(h, sub.data(), h->i_slot_ub, sub.size()))) return -1;
     if (upload_shared(h, stl.data(), h->i_st_lb, stl.size()) || upload_shared(h, stu.data(), h->i_st_ub, stu.size())) return -1;
     h->inst_b_ok = true;
-    h->slots_full = ihm2::slot_table_full(h->slots, 5) && ihm2::slot_bounds_full(h->slots, B, slb, sub);
+    h->slots_full = ihm2::slot_table_full(h->slots, ihm2::full_form_nslot()) && ihm2::slot_bounds_full(h->slots, B, slb, sub);
     return 0;
 }
 
-// ---- the instantiations of the QP kernels and the persistent loop: catalogue, selection, launch ----
-// The catalogue is the eight objects' tables (ihm2mpc_internal.h).  An instantiation takes a slot table when its NSOFT is the table's
-// (the leading one-sided entries per lane rebuild_slots laid it out for) and its NSLOT holds the table's slots per lane; of those
-// that fit the configuration, the first in catalogue order is launched.
-const QpTable qp_catalogue[] = {ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6(), ihm2_qp_set7()};
+// ---- the instantiations of the QP kernels and the persistent loop: the handle's situation, the chosen instantiation, launch ----
+// The catalogue is the eight objects' tables laid end to end, in the order of qp_catalogue.hpp: catalogue_keys(), whose positions
+// qp_select.hpp: select_qp / select_steps return.  Built once.
+const QpInst *catalogue_inst(int pos)
+{
+    static const std::vector<const QpInst *> insts = [] {
+        std::vector<const QpInst *> v;
+#define QP_SET_INSTS(set) { const QpTable t = QP_SET_TABLE(set)(); for (int i = 0; i < t.n; i++) v.push_back(t.inst + i); }
+        QP_SETS(QP_SET_INSTS)
+#undef QP_SET_INSTS
+        return v;
+    }();
+    return pos < 0 ? nullptr : insts[pos];
+}
 
 // the PATH of the instantiations that take the handle's rows: 0 none, 1 the track rows, 2 the track rows and the lateral-acceleration row
 int path_class(const ihm2mpc_handle *h) { return h->rows.alat_on ? 2 : h->path_on ? 1 : 0; }
 
-// the first entry of the catalogue with the fields of `want` and at least its NSLOT; nullptr: none
-const QpInst *find_inst(const QpKey &want)
-{
-    for (const QpTable &t : qp_catalogue)
-        for (const QpInst *e = t.inst; e < t.inst + t.n; e++) {
-            const QpKey &k = e->key;
-            if (k.kind == want.kind && k.nsoft == want.nsoft && k.path == want.path && k.uni == want.uni && k.sqp == want.sqp &&
-                k.irk == want.irk && k.dyn == want.dyn && k.sens == want.sens && k.nf == want.nf && k.full == want.full && k.nslot >= want.nslot)
-                return e;
-        }
-    return nullptr;
-}
-
-// The form of the factor sweep the handle's QP may take (QpKey.nf; riccati_mfma.hpp: PLAIN).  The straight-line stage keeps neither the
-// symmetrising tile (the dynamic model as written needs it) nor the p_k stores (a table without active rows needs them): 0 then.  Otherwise
-// 40 for the horizon 40 -- the horizon as a compile-time constant -- and -1 for every other one.  IHM2MPC_QP_FORM (read once) makes the
-// forms comparable in one build: 2 keeps the slot phases on their general form (slot_form), 1 keeps the horizon 40 on the run-time form
-// as well, 0 keeps every launch on the general form.
+// IHM2MPC_QP_FORM (read once; qp_select.hpp: factor_form says what the values mean)
 int qp_form_limit()
 {
     static const int limit = [] { const char *e = getenv("IHM2MPC_QP_FORM"); return (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : (e && e[0] == '2') ? 2 : 3; }();
     return limit;
 }
-int factor_form(const ihm2mpc_handle *h)
-{
-    const int limit = qp_form_limit();
-    if (limit == 0 || h->cfg.model == IHM2MPC_MODEL_FDYN6 || h->slots.m_act == 0) return 0;
-    return (h->N == 40 && limit >= 2) ? 40 : -1;
-}
-// The form of the slot phases (QpKey.full; kernels_qp.hip: qp_wave_body, FULL): 1 where the handle's table -- with its per-instance bounds,
-// if it has any -- is full (qp_tables.hpp: slot_table_full, evaluated where the table is laid out and where bounds are uploaded) and the
-// factor sweep takes the compiled-in horizon, the one form the catalogue has it with.
-int slot_form(const ihm2mpc_handle *h) { return (qp_form_limit() == 3 && h->slots_full && factor_form(h) == 40) ? 1 : 0; }
 
-// find_inst with the factor sweep in the form the handle may take, where the catalogue has the instantiation in that form (the
-// full slot form first, then the compile-time horizon, then the run-time one), else in the general form
-const QpInst *find_form(const ihm2mpc_handle *h, QpKey want)
+// what the selection reads of the handle (qp_select.hpp)
+ihm2::QpSituation situation(const ihm2mpc_handle *h)
 {
-    if (slot_form(h)) {
-        want.nf = 40; want.full = 1;
-        if (const QpInst *e = find_inst(want)) return e;
-        want.full = 0;
-    }
-    for (int nf = factor_form(h); nf != 0; nf = (nf > 0) ? -1 : 0) {
-        want.nf = nf;
-        if (const QpInst *e = find_inst(want)) return e;
-    }
-    want.nf = 0;
-    return find_inst(want);
-}
-
-// the LDS layout of the QP that takes the handle's rows and weights (qp_lds.hpp): what the kernels carve up is what the launch asks for
-ihm2::QpLds qp_layout(const ihm2mpc_handle *h) { return ihm2::qp_lds(h->N, ihm2::qp_lds_class(path_class(h), h->uniform_H && h->uniform_CD)); }
-size_t qp_lds_bytes(const ihm2mpc_handle *h) { return sizeof(double) * (size_t)qp_layout(h).total; }
-// the persistent loop's: the QP's with its guests (sens: k_sens' body after every QP)
-ihm2::StepsLds steps_lds(const ihm2mpc_handle *h, int sens)
-{
-    const bool dyn_rk4 = h->cfg.model != IHM2MPC_MODEL_FKIN6 && h->cfg.integrator_type == IHM2MPC_INTEG_ERK;
-    return ihm2::steps_lds_doubles(qp_layout(h).total, sens ? (int)(ihm2_sens_lds_bytes(h) / sizeof(double)) : 0, dyn_rk4);
-}
-
-// The per-step QP for the handle's table; nullptr: none takes it (or not in the LDS)
-const QpInst *select_qp(const ihm2mpc_handle *h, size_t lds)
-{
-    if (lds > 160 * 1024) return nullptr;
-    const int uni = h->uniform_H && h->uniform_CD;
-    // few instances (at most one per CU): four wavefronts per instance, slots from the 256-lane table
-    // (per-instance bounds: the 64-lane table alone carries them -- k_qp_wave's results are the four-wave kernel's bit for bit)
-    if (h->block_qp && !h->inst_b && h->slots.per_blk >= 1 && h->B <= h->n_cu && h->slots.per_lane * 64 <= (h->N + 1) * 12)
-        if (const QpInst *e = find_inst({QP_BLOCK, h->slots.per_blk, h->slots.nsoft, path_class(h), uni, 0, 0, 0})) return e;
-    return find_form(h, {QP_WAVE, h->slots.per_lane, h->slots.nsoft, path_class(h), uni, 0, 0, 0});
-}
-
-// The persistent loop for the handle's configuration; nullptr: none (ihm2mpc_run_steps then launches per step, which gives the same
-// results).  The catalogue has it for the kinematic and the dynamic OCP models, not for the lateral-acceleration row; with soft sides,
-// track rows, the collocation integrator or a dynamic model for batch-shared tables only (UNI = 1).  sens = 1 (ihm2mpc_run_steps_sens):
-// the loop with x0 sensitivities, for the kinematic OCP model in the RTI mode.
-const QpInst *select_steps(const ihm2mpc_handle *h, int sens = 0)
-{
-    const ihm2::StepsLds lds = steps_lds(h, sens);
-    const bool sqp = h->cfg.nlp_solver_type == IHM2MPC_SQP;
-    // QpKey.irk: 0 RK4, 1 collocation, 2 RK4 with the closed-form lags
-    const int irk = ihm2_is_irk(h->cfg.integrator_type) ? 1 : (h->cfg.integrator_type == IHM2MPC_INTEG_ERK_LAG) ? 2 : 0;
-    const bool dyn = h->cfg.model != IHM2MPC_MODEL_FKIN6;
-    if (irk == 1 && (!h->irk_tab || (sqp && h->sqp_globalization && !h->ls_phi))) return nullptr;
-    // a plant with the closed-form lags rides on lane N of the loop that linearises with them; the other loops have no such plant
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG && irk != 2) return nullptr;
-    if (sqp && !h->ls_x) return nullptr;        // the caller allocates the line-search buffers first
-    if (lds.total() * sizeof(double) > 160 * 1024) return nullptr;
-    // the dynamic models' RK4 integrator parks its base sensitivities in the QP's LDS
-    if (!lds.guests_fit()) return nullptr;
-    // the SQP instantiations keep the sweeps' earlier form, whose unclamped prefetch of LDS operands starts in front of the block's LDS at
-    // N = 2 and N = 3 (by 60 and 24 words; the values are never used): those horizons are launched per step
-    if (sqp && !ihm2::qp_sweeps_inside(qp_layout(h), h->N, false, 0, 0)) return nullptr;
-    return find_form(h, {QP_STEPS, h->slots.per_lane, h->slots.nsoft, path_class(h), h->uniform_H && h->uniform_CD, sqp, irk, dyn, sens});
-}
-
-// the launch record (ihm2mpc_get_launch_record) from the key of what was launched; a k_steps key with `per_step` != 0: run_steps
-// launched per step instead (1 no instantiation, 2 the batch is not resident), the key's fields are 0
-void note_launch(ihm2mpc_handle *h, const QpKey &k, int per_step = 0)
-{
-    int32_t *r = h->launch_rec;
-    const int form = (k.nf > 0) ? 2 : (k.nf < 0) ? 1 : 0;       // [15] bits 8..9 / 12..13: the factor sweep's form (QpKey.nf)
-    if (k.kind != QP_STEPS) {
-        r[0] = k.kind; r[1] = k.nslot; r[2] = k.nsoft; r[3] = k.path; r[4] = k.uni;
-        r[15] = (r[15] & ~0x700) | (form << 8) | ((k.full ? 1 : 0) << 10);        // bit 10 / 14: the slot phases' form (QpKey.full)
-    } else {
-        r[15] = (r[15] & ~0x7000) | ((per_step ? 0 : form) << 12) | ((!per_step && k.full ? 1 : 0) << 14);
-        r[5] = per_step ? 2 : 1; r[6] = k.nslot; r[7] = k.nsoft; r[8] = k.path; r[9] = k.uni; r[10] = k.sqp; r[11] = k.irk; r[12] = k.dyn;
-        r[13] = per_step; r[14] = k.sens;
-    }
+    ihm2::QpSituation s;
+    s.N = h->N; s.B = h->B; s.n_cu = h->n_cu;
+    s.model = h->cfg.model; s.integrator_type = h->cfg.integrator_type; s.sim_integrator_type = h->cfg.sim_integrator_type;
+    s.nlp_solver_type = h->cfg.nlp_solver_type; s.sqp_globalization = h->sqp_globalization;
+    s.per_lane = h->slots.per_lane; s.per_blk = h->slots.per_blk; s.nsoft = h->slots.nsoft; s.m_act = h->slots.m_act;
+    s.slots_full = h->slots_full;
+    s.path = path_class(h);
+    s.uni = h->uniform_H && h->uniform_CD;
+    s.inst_b = h->inst_b; s.block_qp = h->block_qp;
+    s.qp_form = qp_form_limit();
+    s.irk_tab = !!h->irk_tab; s.ls_x = !!h->ls_x; s.ls_phi = !!h->ls_phi;
+    s.sens_lds = (int)(ihm2_sens_lds_bytes(h) / sizeof(double));
+    return s;
 }
 
 QpArgs qp_args(ihm2mpc_handle *h)
@@ -301,19 +223,19 @@ void launch_inst(ihm2mpc_handle *h, const QpInst *e, void **args, size_t lds)
 {
     (void)hipFuncSetAttribute(e->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipLaunchKernel(e->kernel, dim3(h->B), dim3(e->threads), args, lds, h->stream);
-    note_launch(h, e->key);
+    ihm2::encode_launch(h->launch_rec, e->key);
 }
 
 // The per-step QP; non-zero: no instantiation takes the table (ready() has refused the tables without one), or not in the LDS
 int launch_qp(ihm2mpc_handle *h)
 {
-    const size_t lds = qp_lds_bytes(h);
-    const QpInst *e = select_qp(h, lds);
+    const ihm2::QpChoice c = ihm2::select_qp(situation(h));
+    const QpInst *e = catalogue_inst(c.pos);
     if (!e) return 1;
     QpArgs a = qp_args(h);
     if (e->key.kind == QP_BLOCK) { a.slot_kc = h->slot_kc_blk; a.slot_lb = h->slot_lb_blk; a.slot_ub = h->slot_ub_blk; a.nslots = h->slots.per_blk * 256; }
     void *args[] = {&a};
-    launch_inst(h, e, args, lds);
+    launch_inst(h, e, args, c.lds);
     return 0;
 }
 
@@ -322,8 +244,8 @@ int launch_qp(ihm2mpc_handle *h)
 // (k_steps<..., SENS = 1>), their history into h->hist_k; its LDS is the larger of the QP's and k_sens' (the body reuses the QP's).
 int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop, int sens = 0)
 {
-    const size_t lds = sizeof(double) * (size_t)steps_lds(h, sens).total();
-    const QpInst *e = select_steps(h, sens);
+    const ihm2::QpChoice c = ihm2::select_steps(situation(h), sens);
+    const QpInst *e = catalogue_inst(c.pos);
     if (!e) return 1;
     const bool irk_plant = ihm2_is_irk(h->cfg.sim_integrator_type);     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
     if (irk_plant && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;
@@ -375,7 +297,7 @@ int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n
     const StepArgs *sdev = (const StepArgs *)h->step_args.get();
     const ihm2::LsArgs *ls = (const ihm2::LsArgs *)h->ls_args.get();
     void *args[] = {&sdev, &a, &ls};
-    launch_inst(h, e, args, lds);
+    launch_inst(h, e, args, c.lds);
     return 0;
 }
 
@@ -800,7 +722,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
             return -1;
     }
     if (h->inst_b) return scatter_instance_bounds(h);      // the per-instance values into the new table (or a refusal: ready() then reports it)
-    h->slots_full = ihm2::slot_table_full(s, 5);            // (5: the NSLOT of the catalogue's full-form pair)
+    h->slots_full = ihm2::slot_table_full(s, ihm2::full_form_nslot());
     return 0;
 }
 
@@ -844,7 +766,7 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
         h->i_lbu.reset(); h->i_ubu.reset(); h->i_lg.reset(); h->i_ug.reset();
         h->ih_lb = std::vector<double>(); h->ih_ub = std::vector<double>();
         h->inst_b = false; h->inst_b_ok = false;
-        h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, 5);        // the batch-shared bounds again
+        h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, ihm2::full_form_nslot());        // the batch-shared bounds again
         return 0;
     }
     if (!lbx || !ubx || !lbu || !ubu || !lg || !ug) return fail("lbx, ubx, lbu, ubu, lg, ug must all be given, or all be NULL (batch-shared bounds again)");
@@ -1591,7 +1513,7 @@ static int run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_t
     }
     if (rc != 0) {
         if (freeze) return fail("no persistent loop for this configuration (needs batch-shared weights and rows for soft tables or the collocation integrator, and a batch of at most %d): call ihm2mpc_step per control period", 4 * h->n_cu);
-        note_launch(h, QpKey{QP_STEPS}, resident ? 1 : 2);      // the per-step QP launches below update [0..4]
+        ihm2::encode_launch(h->launch_rec, QpKey{QP_STEPS}, resident ? 1 : 2);      // the per-step QP launches below update [0..4]
         for (size_t i = 0; i < n; i++) {      // launches per step, histories by device-to-device copies in stream order
             if (ihm2mpc_step(h, model, M_sim, s_target)) return -1;
             HIP_TRY(hipMemcpyAsync(h->hist_u0 + i * B * 2, h->u0, B * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));

@@ -216,7 +216,7 @@ struct ihm2mpc_handle {
     WorkBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)
     WorkBuf<int32_t> hist_st, hist_it;      // (steps,B)
 
-    // ---- what was last launched (ihm2mpc_get_launch_record), written from the catalogue's keys (api.hip: note_launch) ----
+    // ---- what was last launched (ihm2mpc_get_launch_record), written from the catalogue's keys (qp_select.hpp: encode_launch, note_lin, note_sim) ----
     int32_t launch_rec[16];
 
     // ---- x0 sensitivities of the last RTI QP (ihm2mpc_set_x0_sensitivities, kernels_sens.hip): allocated on first use ----
@@ -349,14 +349,6 @@ struct StepArgs {
 // void pointer: a function with the unnamed namespace's type in its signature could not be defined in another translation unit.)
 void ihm2_sens_args(const ihm2mpc_handle *h, void *out);
 
-// The catalogue of their instantiations: each object built from kernels_qp.hip (QP_SET = 0 .. 7) returns the table of the ones it
-// holds, in its order of preference (kernels_qp.hip: QP_INSTANCES).  A key holds the template parameters as the launch record gives them
-// (include/ihm2mpc.h), kind first; k_qp_block's NSLOT counts the slots per thread of its 256-lane table.  nf is not in the record: the
-// form of the factor sweep (qp_wave_body: 0 the general form, 40 straight-line with the horizon 40 compiled in, -1 straight-line with the
-// run-time horizon) -- same results, so the record names the kernel by its other parameters.  full: the form of the slot phases alike
-// (qp_wave_body: FULL; 1 for the tables of qp_tables.hpp: slot_table_full), reported beside nf in the record's [15].
-enum { QP_WAVE = 1, QP_BLOCK = 2, QP_STEPS = 3 };
-struct QpKey { int kind, nslot, nsoft, path, uni, sqp, irk, dyn, sens, nf, full; };
-struct QpInst { QpKey key; int threads; const void *kernel; };
-struct QpTable { const QpInst *inst; int n; };
-QpTable ihm2_qp_set0(), ihm2_qp_set1(), ihm2_qp_set2(), ihm2_qp_set3(), ihm2_qp_set4(), ihm2_qp_set5(), ihm2_qp_set6(), ihm2_qp_set7();
+// The catalogue of their instantiations -- QpKey, QpInst, QpTable and the tables ihm2_qp_set0() .. ihm2_qp_set7() of the objects built from
+// kernels_qp.hip -- is qp_catalogue.hpp's; qp_select.hpp chooses from it.
+#include "qp_catalogue.hpp"

@@ -20,6 +20,7 @@
 #include "ihm2mpc_internal.h"
 #include "model.hpp"
 #include "device_steps.hpp"
+#include "qp_select.hpp"     // note_lin, note_sim: the launch record's last linearisation / plant kernel
 
 using namespace ihm2;
 
@@ -235,11 +236,6 @@ __global__ __launch_bounds__(64) void k_sim_step_kin(int B, int M, double dt, in
 
 }  // namespace
 
-// the launch record's [15] (ihm2mpc_get_launch_record): low four bits the last linearisation kernel, the next four the last plant kernel
-// (5 / 4: k_linearize / k_sim_step_kin with the closed-form actuator lags, IHM2MPC_INTEG_ERK_LAG)
-static void note_lin(ihm2mpc_handle *h, int code) { h->launch_rec[15] = (h->launch_rec[15] & ~0xF) | code; }
-static void note_sim(ihm2mpc_handle *h, int code) { h->launch_rec[15] = (h->launch_rec[15] & ~0xF0) | (code << 4); }
-
 // The stage factors of both actuator lags for sub-steps of h (include/ihm2mpc.h: ihm2mpc_lag_stage_factors), on the host: no exp on the device
 LagFac ihm2_lag_factors(double h)
 {
@@ -251,12 +247,12 @@ LagFac ihm2_lag_factors(double h)
 
 void ihm2_launch_linearize(ihm2mpc_handle *h)
 {
-    if (ihm2_is_irk(h->cfg.integrator_type)) { note_lin(h, 4); ihm2_launch_linearize_irk(h); return; }
+    if (ihm2_is_irk(h->cfg.integrator_type)) { note_lin(h->launch_rec, LIN_K_LINEARIZE_IRK); ihm2_launch_linearize_irk(h); return; }
     const long total = (long)h->B * h->N;
     const int blocks = (int)((total + 63) / 64);
     if (h->cfg.integrator_type == IHM2MPC_INTEG_ERK_LAG) {
         // one kernel at every batch size: with sub-steps sized for the car (M = 4) the column-parallel latency path has nothing left to hide
-        note_lin(h, 5);
+        note_lin(h->launch_rec, LIN_K_LINEARIZE_LAG);
         hipLaunchKernelGGL((k_linearize<1, LagFac>), dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
                            h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin, ihm2_lag_factors(h->cfg.dt / h->cfg.M));
         return;
@@ -264,7 +260,7 @@ void ihm2_launch_linearize(ihm2mpc_handle *h)
     // diagnostic (tools/bench_linearize.py --cols): the column-parallel kernel -- one sensitivity column per wavefront, ten wavefronts
     // per block of 64 intervals -- at any batch size, to measure it against the lane-per-interval kernel
     static const bool force_cols = getenv("IHM2MPC_LINEARIZE_COLS") && getenv("IHM2MPC_LINEARIZE_COLS")[0] == '1';
-    note_lin(h, h->cfg.model != IHM2MPC_MODEL_FKIN6 ? 2 : (blocks <= 2 || force_cols) ? 3 : 1);
+    note_lin(h->launch_rec, h->cfg.model != IHM2MPC_MODEL_FKIN6 ? LIN_K_LINEARIZE_DYN : (blocks <= 2 || force_cols) ? LIN_K_LINEARIZE_COLS : LIN_K_LINEARIZE);
     if (h->cfg.model == IHM2MPC_MODEL_FDYN6U)
         hipLaunchKernelGGL(k_linearize_dyn<IHM2MPC_MODEL_FDYN6U>, dim3(blocks), dim3(64), (s_count(1) + dk_count()) * 64 * sizeof(double), h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
                            h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
@@ -281,16 +277,16 @@ void ihm2_launch_linearize(ihm2mpc_handle *h)
 
 void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, hipStream_t stream, const int32_t *active)
 {
-    if (ihm2_is_irk(h->cfg.sim_integrator_type)) { note_sim(h, 3); ihm2_launch_sim_irk(h, model, M_sim, x, u, xn, stream, active); return; }
+    if (ihm2_is_irk(h->cfg.sim_integrator_type)) { note_sim(h->launch_rec, SIM_K_SIM_IRK); ihm2_launch_sim_irk(h, model, M_sim, x, u, xn, stream, active); return; }
     const int blocks = (h->B + 63) / 64;
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG) {      // (the callers have refused every plant but model 0)
-        note_sim(h, 4);
+        note_sim(h->launch_rec, SIM_K_SIM_STEP_KIN_LAG);
         hipLaunchKernelGGL((k_sim_step_kin<1, LagFac>), dim3(blocks), dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref,
                            h->track_id, x, u, xn, active, h->lin + (size_t)h->B * h->N * LIN_REC, ihm2_lag_factors(h->cfg.dt / M_sim));
         return;
     }
     const bool shared = model == IHM2MPC_MODEL_FKIN6 && (long)h->B * h->N > 128 && h->cfg.integrator_type == IHM2MPC_INTEG_ERK;
-    note_sim(h, shared ? 1 : 2);
+    note_sim(h->launch_rec, shared ? SIM_K_SIM_STEP_KIN : SIM_K_SIM_STEP);
     // the plain kinematic plant shares the integrator of the shooting intervals (bit-identical to lane N of the persistent loop); for
     // the few instances of a real-time controller (the batches that also take the column-parallel linearisation) its discarded
     // sensitivities would put 0.1 ms on the critical path of ihm2mpc_step: those take the state-only rollout, and so does a handle whose

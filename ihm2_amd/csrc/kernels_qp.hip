@@ -192,10 +192,10 @@ __device__ __forceinline__ void stream_rows_v1(const double *rows, int N, int e_
 // are parallel over stages / rows run over all NT = 64 NW threads, the constraint slots are spread over NT lanes (NSLOT is then the
 // count per lane of THAT table), reductions go wave -> LDS -> block, hand-offs are s_barriers; the three sequential sweeps run on
 // wave 0 while the others wait.  NW == 1 compiles to exactly the single-wave code (tid == lane, BSYNC == WSYNC).
-// NF != 0: the factor sweep in its straight-line form (riccati_mfma.hpp: PLAIN) -- for the launches api.hip selects it for: a table with
+// NF != 0: the factor sweep in its straight-line form (riccati_mfma.hpp: PLAIN) -- for the launches qp_select.hpp selects it for: a table with
 // active rows (no p_k stores) of a model that needs no symmetrising tile.  NF > 0: with the horizon a.N == NF as a compile-time constant;
 // NF = -1: with the run-time horizon.  NF = 0 is the form every other instantiation keeps.
-// FULL != 0: the slot phases in their straight-line form -- for the tables api.hip selects it for (qp_tables.hpp: slot_table_full): every one of
+// FULL != 0: the slot phases in their straight-line form -- for the tables qp_select.hpp selects it for (qp_tables.hpp: slot_table_full): every one of
 // the 64 NSLOT entries is a hard row with both sides finite, no track or a_lat row among them.  The same operations in the same order on the
 // same values as the general form, without its questions: no validity or side test per slot, the row's word index and its general-row flag
 // formed once per solve where the slot is loaded, and cf / gam zeroed once per solve instead of in every coefficient pass (qp_lds.hpp:
@@ -1137,7 +1137,7 @@ __global__ __launch_bounds__(64) void k_qp_wave(QpArgs a)
 {
     extern __shared__ double sm[];
     if ((int)blockIdx.x >= a.B) return;
-    if (NF > 0 && a.N != NF) return;        // (api.hip selects by the handle's horizon)
+    if (NF > 0 && a.N != NF) return;        // (qp_select.hpp selects by the handle's horizon)
     qp_wave_body<NSLOT, NSOFT, PATH, UNI, 1, 1, NF, FULL>(a, blockIdx.x, sm);
 }
 
@@ -1251,7 +1251,7 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
     extern __shared__ double sm[];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.B) return;
-    if (NF > 0 && a.N != NF) return;        // (api.hip selects by the handle's horizon)
+    if (NF > 0 && a.N != NF) return;        // (qp_select.hpp selects by the handle's horizon)
     const int N = (NF > 0) ? NF : a.N;
     const size_t B = a.B;
     // a car that stops (freeze) keeps its state: the rest of the history repeats it with zero inputs
@@ -1404,39 +1404,15 @@ __global__ __launch_bounds__(64) void k_steps(const StepArgs *sp, QpArgs a, cons
 #ifndef QP_SET
 #error "compile with -DQP_SET=0 (all-hard instantiations), -DQP_SET=1 (soft / track-row instantiations), -DQP_SET=2 (dynamic OCP models in the persistent loop), -DQP_SET=3 (the persistent loop with x0 sensitivities), -DQP_SET=4 (the benchmarked all-hard pair with the straight-line factor sweep), -DQP_SET=5 or -DQP_SET=6 (the all-hard RTI loops with the closed-form actuator lags: general form / straight-line factor sweep), -DQP_SET=7 (the pair of set 4 at the horizon 40 with the full slot form)"
 #endif
-// The instantiations of this object: its part of the catalogue api.hip selects from (qp_catalogue.hpp: QP_INSTANCES_0 .. QP_INSTANCES_7,
-// where the lists and the meaning of WAVE, BLOCK, STEPS are written down); below, the expansion of its entries to kernel pointers.
-#define QP_INSTANCES_(n) QP_INSTANCES_##n
-#define QP_INSTANCES_OF(n) QP_INSTANCES_(n)
-#define QP_INSTANCES QP_INSTANCES_OF(QP_SET)
-
-#if QP_SET == 7
-#define WAVE(NS, NO, PT, UN) {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, 40, 1}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, 40, 1>},
-#define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 0, 40, 1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 0, 40, 1>},
-#elif QP_SET == 4 || QP_SET == 6
-#define WAVE(NS, NO, PT, UN)                                                                          \
-    {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, 40}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, 40>},     \
-    {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0, 0, -1}, 64, (const void *)k_qp_wave<NS, NO, PT, UN, -1>},
-#define STEPS(NS, NO, PT, UN, IR, DY)                                                                                    \
-    {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 0, 40}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 0, 40>},         \
-    {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 0, -1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 0, -1>},
-#else
-#define WAVE(NS, NO, PT, UN) {{QP_WAVE, NS, NO, PT, UN, 0, 0, 0}, 64, (const void *)k_qp_wave<NS, NO, PT, UN>},
-#define BLOCK(NS, UN, NW) {{QP_BLOCK, NS, 0, 0, UN, 0, 0, 0}, 64 * NW, (const void *)k_qp_block<NS, UN, NW>},
-#if QP_SET == 3
-#define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY, 1}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY, 1>},
-#elif QP_SET == 5
-#define STEPS(NS, NO, PT, UN, IR, DY) {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>},
-#else
-#define STEPS(NS, NO, PT, UN, IR, DY)                                                                  \
-    {{QP_STEPS, NS, NO, PT, UN, 0, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 0, IR, DY>}, \
-    {{QP_STEPS, NS, NO, PT, UN, 1, IR, DY}, 64, (const void *)k_steps<NS, NO, PT, UN, 1, IR, DY>},
-#endif
-#endif
-#define QP_TABLE_(n) ihm2_qp_set##n
-#define QP_TABLE(n) QP_TABLE_(n)
-QpTable QP_TABLE(QP_SET)()      // (a host function's table stays out of the device code image)
+// The instantiations of this object: its part of the catalogue (qp_catalogue.hpp: QP_INSTANCES_0 .. QP_INSTANCES_7 with the forms
+// QP_FORMS_0 .. QP_FORMS_7 each entry is built in; qp_select.hpp selects from it).  Below, the one expansion of an entry: its key and its
+// kernel from the same arguments.
+#define QP_EMIT_WAVE(NS, NO, PT, UN, NF, FU) {QP_KEY_WAVE(NS, NO, PT, UN, NF, FU), 64, (const void *)k_qp_wave<NS, NO, PT, UN, NF, FU>},
+#define QP_EMIT_BLOCK(NS, UN, NW) {QP_KEY_BLOCK(NS, UN, NW), 64 * NW, (const void *)k_qp_block<NS, UN, NW>},
+#define QP_EMIT_STEPS(NS, NO, PT, UN, SQ, IR, DY, SE, NF, FU) \
+    {QP_KEY_STEPS(NS, NO, PT, UN, SQ, IR, DY, SE, NF, FU), 64, (const void *)k_steps<NS, NO, PT, UN, SQ, IR, DY, SE, NF, FU>},
+QpTable QP_SET_TABLE(QP_SET)()      // (a host function's table stays out of the device code image)
 {
-    static const QpInst inst[] = {QP_INSTANCES(WAVE, BLOCK, STEPS)};
+    static const QpInst inst[] = {QP_ENTRIES(QP_SET)};
     return {inst, (int)(sizeof(inst) / sizeof(inst[0]))};
 }

@@ -33,13 +33,9 @@ __global__ __launch_bounds__(64) void k_sens(SensArgs a)
 
 }  // namespace
 
-// LDS of one instance (doubles): the factorisation's arrays and the forward sweep's dX_k (64), dU_k (16) behind them (sens_body's carve-up)
-static constexpr size_t sens_lds_doubles(size_t N) { return sens_factor_lds_doubles(N) + 64 + 16; }
-static_assert(sens_lds_doubles(40) == 1989 && sens_lds_doubles(1) == 546, "k_sens: launch LDS at N = 40 and N = 1");
-
 size_t ihm2_sens_lds_bytes(const ihm2mpc_handle *h)
 {
-    return sizeof(double) * sens_lds_doubles((size_t)h->N);
+    return sizeof(double) * ihm2::sens_lds_doubles((size_t)h->N);      // (qp_lds.hpp)
 }
 
 void ihm2_sens_args(const ihm2mpc_handle *h, void *out)

@@ -21,6 +21,7 @@
 #include "device_steps.hpp"
 #include "riccati_mfma.hpp"
 #include "irk_body.hpp"
+#include "qp_select.hpp"
 
 using namespace ihm2;
 
@@ -205,13 +206,13 @@ __global__ __launch_bounds__(64) void k_sim_sens_irk(int B, int M, const IrkTab 
 
 // Launches on `stream`: the switch into model_used (when given; required for model < 0), then the kernel of each model family the call can
 // reach.  The callers (api.hip) have run check_plant: model -2 .. 2, ERK_LAG with model 0 only.  Returns 0, or 1 if the plant's collocation
-// tableau could not be uploaded.  The launch record's plant code becomes 5.
+// tableau could not be uploaded.  The launch record's plant kernel becomes SIM_K_SIM_SENS.
 int ihm2_launch_sim_sens(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, double *Sx, double *Su,
                          int32_t *model_used, hipStream_t stream)
 {
     const int B = h->B, integ = h->cfg.sim_integrator_type;
     const int lanes = (B + 63) / 64, quads = (B + 15) / 16;
-    h->launch_rec[15] = (h->launch_rec[15] & ~0xF0) | (5 << 4);
+    note_sim(h->launch_rec, SIM_K_SIM_SENS);
     if (ihm2_is_irk(integ) && ihm2_upload_sim_irk_tab(h, M_sim)) return 1;
     if (model_used) hipLaunchKernelGGL(k_sim_sens_switch, dim3(lanes), dim3(64), 0, stream, B, model, x, model_used);
     const int32_t *mask = model < 0 ? model_used : nullptr;

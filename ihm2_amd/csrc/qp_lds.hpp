@@ -1,8 +1,10 @@
 // qp_lds.hpp -- the LDS of one instance of the interior-point QP (kernels_qp.hip: qp_wave_body), described once: the arrays with their
-// offsets and lengths in doubles, the total the launch asks for (api.hip: qp_lds_bytes), the integer offsets the factor sweep takes
+// offsets and lengths in doubles, the total the launch asks for (qp_select.hpp: select_qp, select_steps), the integer offsets the factor sweep takes
 // (riccati_mfma.hpp: RicLds; qp_lds_ric), and -- as checked statements -- how far the code that relies on an array's neighbours reaches.
 // Plain C++17 with no HIP header: tools/probes/check_qp_lds.cpp builds it with g++ and walks every class over N = 2..64.
 #pragma once
+
+#include <cstddef>
 
 #ifdef __HIPCC__
 #define QP_LDS_FN __host__ __device__ constexpr
@@ -193,6 +195,14 @@ QP_LDS_FN bool qp_factor_inside(const QpLds &l, int N, int nck)
     return qp_inside(qp_reach_plain_parking(l), l.tile, l.tile.end()) && qp_inside(qp_reach_block_reduce(l, 4), l.tile, l.tile.end()) &&
            qp_inside(qp_reach_plain_operand(l, N, nck), 0, l.total);
 }
+
+// ---- the x0-sensitivity body (sens_body.hpp): k_sens' whole LDS, and the persistent loop's guest with SENS = 1 ----
+constexpr int SENS_ROWS = 15;       // rows per stage: 8 state boxes, 2 input boxes, 2 general rows, 2 track rows, the lateral-acceleration row
+// LDS of the factorisation (doubles): the arrays w .. Q that sens_body and k_adj carve out in front of their own; sens_factor_body.hpp fills them
+QP_LDS_FN size_t sens_factor_lds_doubles(size_t N) { return (N + 1) * (SENS_ROWS + 6) + N * 16 + 64 + 64 + 16 + 100 + 64 + 16 + 84; }
+// LDS of one instance (doubles): the factorisation's arrays and the forward sweep's dX_k (64), dU_k (16) behind them (sens_body's carve-up)
+QP_LDS_FN size_t sens_lds_doubles(size_t N) { return sens_factor_lds_doubles(N) + 64 + 16; }
+static_assert(sens_lds_doubles(40) == 1989 && sens_lds_doubles(1) == 546, "k_sens: launch LDS at N = 40 and N = 1");
 
 // ---- k_steps: the QP's LDS and its guests ----
 // qp: the QP's own; sens: sens_body's, from offset 0 (0 without SENS); dyn_rk4: the dynamic models' RK4 integrator, QP_DYN_RK4_WORDS per

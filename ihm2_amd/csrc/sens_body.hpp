@@ -7,14 +7,16 @@
 
 #include "ihm2mpc_internal.h"
 #include "model.hpp"
+#include "qp_lds.hpp"
 #include "wave_sync.hpp"
 
 namespace {
 
 #define SENS_INF 1e20
 #define SENS_NR 15      // rows per stage: 8 state boxes, 2 input boxes, 2 general rows, 2 track rows, the lateral-acceleration row
-// LDS of the factorisation (doubles): the arrays w .. Q that sens_body and k_adj carve out in front of their own; sens_factor_body.hpp fills them
-__host__ __device__ constexpr size_t sens_factor_lds_doubles(size_t N) { return (N + 1) * (SENS_NR + 6) + N * 16 + 64 + 64 + 16 + 100 + 64 + 16 + 84; }
+// the LDS of the factorisation and of the whole body in doubles: qp_lds.hpp, where the launches' sizes are chosen
+static_assert(SENS_NR == ihm2::SENS_ROWS, "sens_factor_lds_doubles counts other rows than the carve-up");
+using ihm2::sens_factor_lds_doubles;
 
 #define SSYNC() WSYNC()      // (the name the 16 hand-offs of sens_body, sens_factor_body.hpp and kernels_adj.hip were written with)
 

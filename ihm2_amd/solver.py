@@ -39,6 +39,29 @@ def _ptr(a):
     return a.ctypes.data_as(_lib.c_double_p)
 
 
+def decode_launch_record(rec) -> dict:
+    """The dictionary of ``BatchedOcpSolver.get_launch_record`` from the sixteen integers of ``ihm2mpc_get_launch_record``
+    (``csrc/qp_select.hpp``: ``encode_launch``, ``note_lin``, ``note_sim`` write them)."""
+    r = [int(v) for v in rec]
+    qp = None
+    if r[0] == 1:
+        qp = "k_qp_wave<%d,%d,%d,%d>" % tuple(r[1:5])
+    elif r[0] == 2:
+        qp = "k_qp_block<%d,%d,4>" % (r[1], r[4])
+    steps, fallback = None, None
+    if r[5] == 1:
+        steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13]) if r[14] == 0 else "k_steps<%d,%d,%d,%d,%d,%d,%d,1>" % tuple(r[6:13])
+    elif r[5] == 2:
+        steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
+    lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk", "k_linearize_lag")[r[15] & 15]
+    sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk", "k_sim_step_kin_lag", "k_sim_sens")[(r[15] >> 4) & 15]
+    forms = ("general", "plain", "plain_n40", None)
+    slots = ("general", "full")
+    return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim,
+            "qp_form": forms[(r[15] >> 8) & 3] if qp else None, "steps_form": forms[(r[15] >> 12) & 3] if r[5] == 1 else None,
+            "qp_slots": slots[(r[15] >> 10) & 1] if qp else None, "steps_slots": slots[(r[15] >> 14) & 1] if r[5] == 1 else None}
+
+
 class BatchedOcpSolver:
     """B independent instances of the bicycle NMPC on one MI355X."""
 
@@ -429,24 +452,7 @@ class BatchedOcpSolver:
         was launched yet."""
         rec = np.zeros(16, dtype=np.int32)
         _lib.check(self.lib.ihm2mpc_get_launch_record(self._h, rec.ctypes.data_as(_lib.c_int32_p)))
-        r = [int(v) for v in rec]
-        qp = None
-        if r[0] == 1:
-            qp = "k_qp_wave<%d,%d,%d,%d>" % tuple(r[1:5])
-        elif r[0] == 2:
-            qp = "k_qp_block<%d,%d,4>" % (r[1], r[4])
-        steps, fallback = None, None
-        if r[5] == 1:
-            steps = "k_steps<%d,%d,%d,%d,%d,%d,%d>" % tuple(r[6:13]) if r[14] == 0 else "k_steps<%d,%d,%d,%d,%d,%d,%d,1>" % tuple(r[6:13])
-        elif r[5] == 2:
-            steps, fallback = "per_step", {1: "no_instantiation", 2: "not_resident"}.get(r[13])
-        lin = (None, "k_linearize", "k_linearize_dyn", "k_linearize_cols", "k_linearize_irk", "k_linearize_lag")[r[15] & 15]
-        sim = (None, "k_sim_step_kin", "k_sim_step", "k_sim_irk", "k_sim_step_kin_lag", "k_sim_sens")[(r[15] >> 4) & 15]
-        forms = ("general", "plain", "plain_n40", None)
-        slots = ("general", "full")
-        return {"qp": qp, "steps": steps, "steps_fallback": fallback, "linearize": lin, "sim": sim,
-                "qp_form": forms[(r[15] >> 8) & 3] if qp else None, "steps_form": forms[(r[15] >> 12) & 3] if r[5] == 1 else None,
-                "qp_slots": slots[(r[15] >> 10) & 1] if qp else None, "steps_slots": slots[(r[15] >> 14) & 1] if r[5] == 1 else None}
+        return decode_launch_record(rec)
 
     # ---- device-pointer variants (zero copy; dptr = integer device address, instance-major layout) ----
     def set_x0_device(self, dptr: int):

@@ -12,7 +12,7 @@ import layouts as L  # noqa: E402
 import poison_cases as PC  # noqa: E402
 
 QP, STEPS = "k_qp_wave<5,0,0,1>", "k_steps<5,0,0,1,0,0,0>"
-# IHM2MPC_QP_FORM -> (form of the factor sweep, form of the slot phases) both launch records must report (api.hip: qp_form_limit)
+# IHM2MPC_QP_FORM -> (form of the factor sweep, form of the slot phases) both launch records must report (qp_select.hpp: factor_form, slot_form; tests/test_qp_select.py runs them on this layout without a GPU)
 FORMS = {"0": ("general", "general"), "1": ("plain", "general"), "2": ("plain_n40", "general"), "unset": ("plain_n40", "full")}
 
 

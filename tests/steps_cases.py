@@ -3,7 +3,8 @@
 no configuration reaches.  A helper: tests/test_steps_catalogue.py checks the table against the catalogue without a GPU,
 tests/test_gpu_steps_catalogue.py launches every entry.
 
-Each case is derived by reading api.hip::select_steps, which asks find_form for the key
+Each case is derived by reading csrc/qp_select.hpp: select_steps -- and tests/test_steps_catalogue.py runs that function on every
+case, without a GPU (tools/probes/check_qp_select.cpp).  It asks find_form for the key
 
     {QP_STEPS, slots.per_lane, slots.nsoft, path_class, uniform_H && uniform_CD, sqp, irk, dyn, sens}
 
@@ -169,7 +170,7 @@ def steps_name(table, sqp, irk, dyn, sens=0):
 # The sample_x0 seed of a case is 700 + the layout's own seed, as tests/test_gpu_qp_layouts.py starts its loops.  From these starts the oracle
 # solves every instance's first step (tests/test_steps_catalogue.py asserts 60 %), so no case needed another seed.
 
-# Two names exist in further forms (api.hip::find_form; the launch record tells them apart in steps_form / steps_slots), and the cases
+# Two names exist in further forms (qp_select.hpp: find_form; the launch record tells them apart in steps_form / steps_slots), and the cases
 # assert the one they run:
 #   k_steps<5,0,0,1,0,0,0>  on the reference layout at N = 40 the table is full (qp_tables.hpp: slot_table_full): the set-7 object, horizon
 #                           40 compiled in and straight-line slot phases.  The ILP library links that object from the default build, so
@@ -227,8 +228,8 @@ assert len(BY_NAME) == len(CASES)
 ILP_CASES = {"k_steps<5,0,0,1,0,0,0>": dataclasses.replace(BY_NAME["k_steps<5,0,0,1,0,0,0>"], layout="hard_random_one_sided", seed=703,
                                                            form=("plain_n40", "general"))}
 
-# Configurations ihm2mpc_run_steps must launch per step, with the steps_fallback of the launch record (api.hip::select_steps returns
-# nullptr: "no_instantiation"; the other reason, "not_resident", needs more than 4 x 256 instances and is asserted in
+# Configurations ihm2mpc_run_steps must launch per step, with the steps_fallback of the launch record (qp_select.hpp: select_steps chooses
+# none: "no_instantiation"; the other reason, "not_resident", needs more than 4 x 256 instances and is asserted in
 # tests/test_gpu_closed_loop.py and tests/test_gpu_sens_steps.py at B = 1100).  id -> case
 _NO = "no_instantiation"
 FALLBACK = {

@@ -163,7 +163,7 @@ IRK = dict(integrator_type="IRK", sim_method_num_steps=1)                       
 
 
 # What run_steps must launch for the reference's table (8 rows on each of 40 stages: 5 slots per lane, whatever n_max) with batch-shared
-# weights and the kinematic model, by (SQP mode, collocation): api.hip::select_steps.  More than 4 x 256 instances are not resident.
+# weights and the kinematic model, by (SQP mode, collocation): csrc/qp_select.hpp: select_steps (run on the CPU by tests/test_steps_catalogue.py).  More than 4 x 256 instances are not resident.
 LOOP_OF = {(False, False): "k_steps<5,0,0,1,0,0,0>", (True, False): "k_steps<5,0,0,1,1,0,0>",
            (False, True): "k_steps<5,0,0,1,0,1,0>", (True, True): "k_steps<5,0,0,1,1,1,0>"}
 

@@ -2,7 +2,7 @@
 
 Which instantiation runs is decided by the slot table api.hip::rebuild_slots lays out from the rows (csrc/qp_tables.hpp: lay_out_slots --
 slots per lane, leading one-sided entries per lane; tests/test_slot_table.py checks the tables themselves without a GPU) and by the
-catalogue of instantiations it is selected from (csrc/qp_catalogue.hpp: QP_INSTANCES_0 .. 6).  Each layout below is
+catalogue of instantiations it is selected from (csrc/qp_catalogue.hpp: the lists of the sets 0 .. 6).  Each layout below is
 named for the table it is meant to give; the launch record (BatchedOcpSolver.get_launch_record) says what actually ran, and the last test checks
 that the module as a whole launched exactly the list of instantiations written there.
 

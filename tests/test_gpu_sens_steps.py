@@ -111,7 +111,7 @@ def test_nothing_else_moves(track, plant, n_max, B, opts, monkeypatch):
 
 
 # The table (NSLOT, NSOFT, PATH, UNI) of the loop each layout of the QP-layout suite takes (kinematic model, RK4, RTI), None where
-# api.hip::select_steps finds none and run_steps launches per step: stage-varying weights or rows (UNI = 0) on anything but the all-hard
+# csrc/qp_select.hpp: select_steps finds none and run_steps launches per step: stage-varying weights or rows (UNI = 0) on anything but the all-hard
 # tables of 5 and 8 slots, and the lateral-acceleration row.  The catalogue has every such loop with and without SENS.
 LOOP_ON = {
     "hard_5_per_lane": "5,0,0,1", "hard_5_per_lane_stage_W": "5,0,0,0", "hard_6_per_lane": "8,0,0,1", "hard_8_per_lane_stage_rows": "8,0,0,0",

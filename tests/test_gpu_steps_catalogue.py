@@ -1,7 +1,7 @@
 """Every instantiation of the persistent control-step loop, by name, against launches per step.
 
 tests/steps_cases.py holds one configuration per k_steps<NSLOT, NSOFT, PATH, UNI, SQP, IRK, DYN[, SENS]> of csrc/qp_catalogue.hpp (read
-from api.hip::select_steps; tests/test_steps_catalogue.py checks the table against the catalogue, the layouts' slot tables and the
+from csrc/qp_select.hpp: select_steps, which tests/test_steps_catalogue.py runs on every case without a GPU; that test also checks the table against the catalogue, the layouts' slot tables and the
 oracle's first step on the CPU), and the configurations that must fall back.  Each instantiation is a register allocation of its own
 of the same loop body, inlined next to another integrator, line search or sensitivity guest; here each is launched, the launch record
 is compared with the name, and the results with those of ihm2mpc_step call by call, bit for bit.  That equality is worth what step()

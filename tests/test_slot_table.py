@@ -10,16 +10,13 @@ digests against tests/golden/slot_tables.json -- recorded from the tables the li
 header (tests/golden/make_slot_tables.py), so they pin the entry order every bit of the QP's results depends on."""
 import json
 import os
-import re
 import subprocess
 
-import numpy as np
 import pytest
 
 import layouts as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
+import select_probe as P
+from select_probe import ROOT, problem_text
 
 # the smallest shapes: the horizons 2 and 3 of the reference layout (fewer rows than lanes), and no row at all
 SMALL = {
@@ -47,41 +44,19 @@ NAMED_FOR = {
 }
 
 
-def problem_text(lay) -> str:
-    """The problem of a layout as check_slot_table.cpp reads it: what test_gpu_qp_layouts.py::_solver leaves in the handle."""
-    data = L.make_ocp(lay).flatten()
-    arr = L.apply(data, lay)
-
-    def nums(a):
-        return " ".join(repr(float(v)) for v in np.asarray(a, dtype=np.float64).ravel())
-
-    out = [lay.name, str(lay.N)] + [nums(arr[n]) for n in ("lbx", "ubx", "lbu", "ubu", "C", "D", "lg", "ug")]
-    soft = data.soft_Z is not None and bool(np.any(np.asarray(data.soft_Z) >= 0.0))         # BatchedOcpSolver._push_soft
-    out.append("1 " + nums(data.soft_z) + " " + nums(data.soft_Z) if soft else "0")
-    out.append("1 " + nums(data.lh) + " " + nums(data.uh) if data.path_on else "0")
-    if data.path_on and data.alat_on:
-        out.append("1 " + nums([data.alat_lb, data.alat_ub]))
-        out.append("0" if data.alat_soft_Z is None else "1 " + nums(np.zeros(2) if data.alat_soft_z is None else data.alat_soft_z) + " " + nums(data.alat_soft_Z))
-    else:
-        out.append("0")
-    return "\n".join(out) + "\n"
-
-
-def wave_entries():
-    """(NSLOT, NSOFT, PATH) of the WAVE entries of the catalogue, in its order."""
-    text = open(os.path.join(CSRC, "qp_catalogue.hpp")).read()
-    lists = re.findall(r"#define QP_INSTANCES_(\d)\(WAVE, BLOCK, STEPS\)((?:.*\\\n)*.*)\n", text)
-    assert [n for n, _ in lists] == list("0123456")
-    return [tuple(int(v) for v in m[:3]) for _, body in lists for m in re.findall(r"\bWAVE\((\d+), (\d+), (\d+), (\d+)\)", body)]
+@pytest.fixture(scope="module")
+def waves(tmp_path_factory):
+    """(NSLOT, NSOFT, PATH) of the WAVE entries of the catalogue, in its order: from the probe's dump of csrc/qp_catalogue.hpp:
+    catalogue_keys, one per entry of the lists (the set 4's entry is built twice, NF = 40 and NF = -1; the set 7 is that list once more)."""
+    exe = P.build_probe(tmp_path_factory.mktemp("catalogue"))
+    return [(k["nslot"], k["nsoft"], k["path"]) for k in P.catalogue(exe) if k["kind"] == P.WAVE and k["nf"] != -1 and not k["full"]]
 
 
 @pytest.fixture(scope="module")
 def tables(tmp_path_factory):
     """name -> (fit, per_lane, nsoft, total, m_act, digest) of every layout, from one run of the probe."""
     tmp = tmp_path_factory.mktemp("slot_table")
-    exe = str(tmp / "check_slot_table")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tools", "probes", "check_slot_table.cpp")])
+    exe = P.build_probe(tmp, "check_slot_table")
     files = []
     for name, lay in LAYOUTS.items():
         files.append(str(tmp / (name + ".txt")))
@@ -97,14 +72,13 @@ def tables(tmp_path_factory):
     return res
 
 
-def test_catalogue_lists_are_the_ones_the_layouts_are_named_for():
-    waves = wave_entries()
+def test_catalogue_lists_are_the_ones_the_layouts_are_named_for(waves):
     assert len(waves) == 19 and set(NAMED_FOR) == set(FIT)
     assert set(NAMED_FOR.values()) == set(waves)          # every per-step instantiation has a layout
 
 
 @pytest.mark.parametrize("name", list(LAYOUTS))
-def test_layout_fits_the_instantiation_it_is_named_for(tables, name):
+def test_layout_fits_the_instantiation_it_is_named_for(tables, waves, name):
     fit, per_lane, nsoft, _, _, _ = tables[name]
     if name in L.REFUSED:
         assert fit == 0
@@ -112,7 +86,7 @@ def test_layout_fits_the_instantiation_it_is_named_for(tables, name):
     assert fit == 1
     lay = LAYOUTS[name]
     path = 2 if lay.alat else 1 if lay.path else 0
-    first = next(w for w in wave_entries() if w[2] == path and w[1] == nsoft and w[0] >= per_lane)
+    first = next(w for w in waves if w[2] == path and w[1] == nsoft and w[0] >= per_lane)
     assert first == NAMED_FOR[name], (per_lane, nsoft)
 
 

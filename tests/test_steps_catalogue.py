@@ -1,49 +1,38 @@
-"""The case table of the persistent loop (tests/steps_cases.py) against the catalogue (csrc/qp_catalogue.hpp), without a GPU:
+"""The case table of the persistent loop (tests/steps_cases.py) against the catalogue (csrc/qp_catalogue.hpp) and the selection
+(csrc/qp_select.hpp), without a GPU, through the sanitizer-built tools/probes/check_qp_select.cpp (run as a stand-alone program):
 
-* the names the STEPS entries expand to are exactly CASES + UNREACHED, so that an entry added without a case fails here;
-* every case's layout gives the slot table (slots per lane -> NSLOT, NSOFT, PATH) its name says, through the sanitizer-built
-  tools/probes/check_slot_table.cpp (run as a stand-alone program, as tests/test_slot_table.py does);
+* the names of the catalogue's k_steps keys are exactly CASES + UNREACHED, so that an entry added without a case fails here;
+* for every case, select_steps on the case's layout and options chooses the instantiation the case is named for, in the form the case
+  lists -- the choice itself runs here, not a restatement of it -- and for every fallback it chooses none, with the fallback's reason;
 * from every case's start the oracle solves at least 60 % of the instances in its first step, so that the comparison of
   tests/test_gpu_steps_catalogue.py is one of solved problems."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import layouts as L
 import rollout_ref as R
+import select_probe as P
 import steps_cases as S
-from test_slot_table import CSRC, ROOT, problem_text
+from ihm2_amd.solver import decode_launch_record
 
 N_NAMES = 87            # 16 + 20 + 28 + 18 + 5
 
 
-def steps_entries():
-    """set -> [(NSLOT, NSOFT, PATH, UNI, IRK, DYN)] of the STEPS entries of the catalogue, in its order."""
-    text = open(os.path.join(CSRC, "qp_catalogue.hpp")).read()
-    lists = re.findall(r"#define QP_INSTANCES_(\d)\(WAVE, BLOCK, STEPS\)((?:.*\\\n)*.*)\n", text)
-    assert [n for n, _ in lists] == list("0123456")
-    sets = {int(n): [tuple(int(v) for v in m) for m in re.findall(r"\bSTEPS\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\)", body)] for n, body in lists}
-    assert re.search(r"#define QP_INSTANCES_7 QP_INSTANCES_4\n", text)
-    sets[7] = sets[4]
-    return sets
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("steps_catalogue")
+    return P.build_probe(tmp), tmp
 
 
-def expand(sets):
-    """The k_steps names of the catalogue, name -> the sets that hold it.  THE EXPANSION RULE (kernels_qp.hip: the STEPS macro per QP_SET):
-
-    sets 0, 1, 2   every entry in both SQP modes, SENS = 0
-    set 3          RTI only, SENS = 1 (the eighth field of the name)
-    set 5          RTI only, SENS = 0
-    sets 4, 6, 7   RTI only, SENS = 0, other forms of the factor sweep / the slot phases: the launch record's name does not carry the
-                   form, so these add no name -- each must already be one of the sets 0 and 5"""
+def steps_names(exe):
+    """The k_steps names of the catalogue, name -> the sets that hold it (the record's name does not carry the form of the factor sweep
+    and the slot phases: the keys of the sets 4, 6 and 7 repeat names)."""
     names = {}
-    for n, entries in sets.items():
-        for (ns, no, pt, un, irk, dyn) in entries:
-            for sqp in ((0, 1) if n in (0, 1, 2) else (0,)):
-                names.setdefault(S.steps_name((ns, no, pt, un), sqp, irk, dyn, sens=1 if n == 3 else 0), []).append(n)
+    for k in P.catalogue(exe):
+        if k["kind"] == P.STEPS:
+            names.setdefault(P.key_name(k), []).append(k["set"])
     return names
 
 
@@ -52,8 +41,8 @@ def parse_name(name):
     return dict(nslot=f[0], nsoft=f[1], path=f[2], uni=f[3], sqp=f[4], irk=f[5], dyn=f[6], sens=f[7] if len(f) == 8 else 0)
 
 
-def test_case_table_is_the_catalogue():
-    names = expand(steps_entries())
+def test_case_table_is_the_catalogue(probe):
+    names = steps_names(probe[0])
     other_forms = {k for k, v in names.items() if set(v) <= {4, 6, 7}}
     assert not other_forms, other_forms                   # the sets 4, 6 and 7 repeat names of the sets 0 and 5
     cases, unreached = set(S.BY_NAME), set(S.UNREACHED)
@@ -80,46 +69,52 @@ def test_case_fields_say_what_the_name_says():
         assert 0 in plants and plants - {0}, (cls, plants)
 
 
-@pytest.fixture(scope="module")
-def tables(tmp_path_factory):
-    """layout -> (fit, per_lane, nsoft) of every layout of the cases and fallbacks, from one run of the probe."""
-    tmp = tmp_path_factory.mktemp("steps_catalogue")
-    exe = str(tmp / "check_slot_table")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tools", "probes", "check_slot_table.cpp")])
-    used = sorted({c.layout for c in list(S.CASES) + list(S.FALLBACK.values()) + list(S.ILP_CASES.values())})
-    files = []
-    for name in used:
-        files.append(str(tmp / (name + ".txt")))
-        with open(files[-1], "w") as f:
-            f.write(problem_text(S.LAYOUTS[name]))
-    out = subprocess.run([exe] + files, capture_output=True, text=True)
-    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-4000:] + out.stderr[-4000:]
-    res = {}
-    for line in out.stdout.splitlines()[:len(files)]:
-        name, fit, per_lane, nsoft = line.split()[:4]
-        res[name] = (int(fit), int(per_lane), int(nsoft))
-    assert list(res) == used
-    return res
-
-
 def _case(name):
     return S.FALLBACK[name[9:]] if name.startswith("fallback:") else S.ILP_CASES[name[4:]] if name.startswith("ilp:") else S.BY_NAME[name]
 
 
-@pytest.mark.parametrize("name", list(S.BY_NAME) + ["ilp:" + k for k in S.ILP_CASES])
-def test_layout_gives_the_table_of_the_name(tables, name):
-    """find_inst: the first STEPS entry, in catalogue order over the sets, whose other fields are the key's and whose NSLOT holds the
-    table's slots per lane."""
+CASE_IDS = list(S.BY_NAME) + ["ilp:" + k for k in S.ILP_CASES]
+FALLBACK_IDS = ["fallback:" + k for k in S.FALLBACK]
+
+
+def case_facts(case, **more):
+    """What the handle of a case is configured with (tests/test_gpu_steps_catalogue.py builds it from the same options)."""
+    lay = S.LAYOUTS[case.layout]
+    return lay, P.facts_of_data(L.make_ocp(lay, **case.ocp_opts()).flatten(), **{"B": case.B, "sens": case.sens, **more})
+
+
+@pytest.fixture(scope="module")
+def selected(probe):
+    """id -> the launch record ihm2mpc_run_steps leaves for the case, decoded: one run of the probe over all cases and fallbacks."""
+    ids = CASE_IDS + FALLBACK_IDS
+    res = P.select(*probe, [case_facts(_case(i)) for i in ids])
+    return {i: decode_launch_record(r["rec"]) for i, r in zip(ids, res)}
+
+
+@pytest.mark.parametrize("name", CASE_IDS)
+def test_layout_gives_the_table_of_the_name(selected, name):
+    """select_steps (csrc/qp_select.hpp) on the case's layout and options: the loop the case is named for, in the form it lists."""
     c = _case(name)
-    name = c.name
-    k = parse_name(name)
-    fit, per_lane, nsoft = tables[c.layout]
-    assert fit == 1
-    sets = steps_entries()
-    first = next(e for n in sorted(sets) if (n == 3) == (k["sens"] != 0) and (k["sqp"] == 0 or n in (0, 1, 2)) for e in sets[n]
-                 if e[1:] == (nsoft, k["path"], k["uni"], k["irk"], k["dyn"]) and e[0] >= per_lane)
-    assert first[0] == k["nslot"] and nsoft == k["nsoft"], (per_lane, nsoft, first)
+    rec = selected[name]
+    assert rec["steps"] == c.name, rec
+    assert (rec["steps_form"], rec["steps_slots"]) == c.form, rec
+
+
+@pytest.mark.parametrize("name", FALLBACK_IDS)
+def test_fallback_selects_no_loop(selected, name):
+    c = _case(name)
+    rec = selected[name]
+    assert rec["steps"] == "per_step" == c.name and rec["steps_fallback"] == c.reason, rec
+    assert rec["steps_form"] is None and rec["steps_slots"] is None
+
+
+def test_batch_above_four_per_cu_is_not_resident(probe):
+    """B = 1100 on 256 compute units (tests/test_gpu_closed_loop.py and tests/test_gpu_sens_steps.py assert it on hardware)."""
+    c = S.BY_NAME["k_steps<5,0,0,1,0,0,0>"]
+    for sens in (0, 1):
+        rec = decode_launch_record(P.select(*probe, [case_facts(c, B=1100, n_cu=256, sens=sens)])[0]["rec"])
+        assert (rec["steps"], rec["steps_fallback"]) == ("per_step", "not_resident"), rec
+        assert rec["qp"] == "k_qp_wave<5,0,0,1>"
 
 
 def problem(track, case):
@@ -142,7 +137,7 @@ def oracle_first_step(track, case):
     return S.oracle_rti_step(P, data, track, x, u, x0, yref, yref_e)["status"]
 
 
-@pytest.mark.parametrize("name", list(S.BY_NAME) + ["ilp:" + k for k in S.ILP_CASES] + ["fallback:" + k for k in S.FALLBACK])
+@pytest.mark.parametrize("name", CASE_IDS + FALLBACK_IDS)
 def test_oracle_solves_the_first_step_of_the_case(track, name):
     """At least 60 % of the instances end the first step accepted (0; in the SQP mode 0 or 2)."""
     case = _case(name)

@@ -12,7 +12,7 @@
 
 using namespace ihm2;
 
-static const int NSLOT_FULL = 5;        // the NSLOT of the catalogue's full-form pair (api.hip)
+static const int NSLOT_FULL = full_form_nslot();        // the NSLOT of the catalogue's full-form pair, as api.hip takes it
 static int fails = 0;
 #define CHECK(c) do { if (!(c)) { fails++; std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); } } while (0)
 

@@ -4,7 +4,7 @@
 //   * the total and the factor sweep's integer offsets equal the closed forms api.hip and kernels_qp.hip held before the layout was
 //     written down (copied here as the independent statement);
 //   * the sweeps' reaches equal what a replay of stream_rows' fetch sequence touches, and every consumer's reach is inside the block --
-//     except exactly the sweeps' earlier form at N = 2 and N = 3, whose reach is printed (api.hip: select_steps refuses those).
+//     except exactly the sweeps' earlier form at N = 2 and N = 3, whose reach is printed (qp_select.hpp: select_steps refuses those).
 // Build: g++ -std=c++17 -I ihm2_amd/csrc tools/probes/check_qp_lds.cpp   (SWEEP_RING as in kernels_qp.hip; also with -fsanitize=address,undefined)
 #include <algorithm>
 #include <cstdio>
@@ -54,7 +54,7 @@ int main()
                 p += a.len;
             }
             CHECK(p == l.total, "sum %d total %d", p, l.total);
-            // ---- the closed forms held before (api.hip: qp_lds_bytes; kernels_qp.hip: the RicLds block) ----
+            // ---- the closed forms held before (the launch's LDS bytes, qp_select.hpp: select_qp; kernels_qp.hip: the RicLds block) ----
             const int nck = path ? (path == 2 ? 15 : 14) : 12;
             const int total = NS * (10 + 10 + 8 + 8 + 2 * nck + 10 + (path ? (path == 2 ? 6 : 2) : 0)) + N * (8 + 4 + 16 + 8 + 8) + 136 + (uni ? 20 + (path ? 0 : 200 + 90) : 0);
             CHECK(l.total == total && c.nck == nck, "path %d uni %d N %d: %d against %d", path, uni, N, l.total, total);
