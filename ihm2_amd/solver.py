@@ -632,7 +632,9 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_set_lap_wrap(self._h, int(bool(enable))))
 
     def set_active(self, active=None):
-        """Plant mask for ``sim_advance`` / ``step``: instances with ``active[b] == 0`` keep their ``x0``; ``None`` = all."""
+        """Plant mask for ``sim_advance`` / ``step``: instances with ``active[b] == 0`` keep their ``x0``; ``None`` = all.
+        ``run_steps(freeze=True)`` clears entries of this mask as cars stop; without a mask from here it keeps one of its own, which
+        only later ``run_steps(freeze=True)`` calls read (``step`` / ``sim_advance`` / ``freeze=False`` do not), until ``set_active(None)``."""
         if active is None:
             _lib.check(self.lib.ihm2mpc_set_active(self._h, None))
         else:

@@ -457,8 +457,12 @@ int ihm2mpc_reserve_history(ihm2mpc_handle *h, int32_t n_steps);
  * and pays off while every instance has a wavefront of its own (batch <= 4 per compute unit); any other case runs
  * n_steps x ihm2mpc_step internally (freeze == 0) or is refused (freeze != 0).
  * freeze != 0: the rules of the reference's loop per car -- a solve status other than 0 / 2 (python/main.py:326-328) or a NaN
- * plant state (:503-504) stops the car where it is, s > lap_stop ends its run (:514-517); the plant mask of
- * ihm2mpc_set_active is updated accordingly and kept across calls until ihm2mpc_set_active(NULL).  freeze == 0: a car masked
+ * plant state (:503-504) stops the car where it is, s > lap_stop ends its run (:514-517).  A stopped car's rows hold u0 = 0, its x0 and
+ * its last status repeated, and 0 QP iterations.  The loop keeps the stopped cars in a plant mask for later calls with freeze != 0, until
+ * ihm2mpc_set_active(NULL): after ihm2mpc_set_active(mask) that is the caller's mask, whose entries the loop clears (ihm2mpc_step and
+ * ihm2mpc_sim_advance then see them cleared); otherwise a mask of its own that starts with every car driving, and that one is read by
+ * later ihm2mpc_run_steps / ihm2mpc_run_steps_sens calls with freeze != 0 ONLY -- ihm2mpc_step, ihm2mpc_sim_advance and freeze == 0 read
+ * a mask only after ihm2mpc_set_active(mask), and move a car again that a frozen loop had stopped.  freeze == 0: a car masked
  * by ihm2mpc_set_active keeps solving, only its plant stands still (as in ihm2mpc_step).  Histories (any may be NULL): u0 (n_steps,B,2), x0 after the plant
  * (n_steps,B,8), status and QP iterations (n_steps,B); copied in stream order (pinned destinations do not block).  ihm2mpc_get_residuals
  * afterwards: the NLP residuals of the iterate the LAST step started from, as after n_steps calls of ihm2mpc_step (in the RTI mode the
