@@ -180,23 +180,8 @@ int qp_form_limit()
     return limit;
 }
 
-// what the selection reads of the handle (qp_select.hpp)
-ihm2::QpSituation situation(const ihm2mpc_handle *h)
-{
-    ihm2::QpSituation s;
-    s.N = h->N; s.B = h->B; s.n_cu = h->n_cu;
-    s.model = h->cfg.model; s.integrator_type = h->cfg.integrator_type; s.sim_integrator_type = h->cfg.sim_integrator_type;
-    s.nlp_solver_type = h->cfg.nlp_solver_type; s.sqp_globalization = h->sqp_globalization;
-    s.per_lane = h->slots.per_lane; s.per_blk = h->slots.per_blk; s.nsoft = h->slots.nsoft; s.m_act = h->slots.m_act;
-    s.slots_full = h->slots_full;
-    s.path = path_class(h);
-    s.uni = h->uniform_H && h->uniform_CD;
-    s.inst_b = h->inst_b; s.block_qp = h->block_qp;
-    s.qp_form = qp_form_limit();
-    s.irk_tab = !!h->irk_tab; s.ls_x = !!h->ls_x; s.ls_phi = !!h->ls_phi;
-    s.sens_lds = (int)(ihm2_sens_lds_bytes(h) / sizeof(double));
-    return s;
-}
+// the switches that are on with the value 1 (read once each)
+bool switch_on(const char *name) { const char *e = getenv(name); return e && e[0] == '1'; }
 
 QpArgs qp_args(ihm2mpc_handle *h)
 {
@@ -229,7 +214,7 @@ void launch_inst(ihm2mpc_handle *h, const QpInst *e, void **args, size_t lds)
 // The per-step QP; non-zero: no instantiation takes the table (ready() has refused the tables without one), or not in the LDS
 int launch_qp(ihm2mpc_handle *h)
 {
-    const ihm2::QpChoice c = ihm2::select_qp(situation(h));
+    const ihm2::QpChoice c = ihm2::select_qp(ihm2_situation(h));
     const QpInst *e = catalogue_inst(c.pos);
     if (!e) return 1;
     QpArgs a = qp_args(h);
@@ -239,12 +224,12 @@ int launch_qp(ihm2mpc_handle *h)
     return 0;
 }
 
-// n_steps control steps in one launch (k_steps), histories into h->hist_*.  Returns 0 launched, 1 the configuration has no persistent
-// instantiation (the caller then runs ihm2mpc_step n_steps times, which gives the same results).  sens: the loop with x0 sensitivities
-// (k_steps<..., SENS = 1>), their history into h->hist_k; its LDS is the larger of the QP's and k_sens' (the body reuses the QP's).
-int launch_steps(ihm2mpc_handle *h, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop, int sens = 0)
+// n_steps control steps in one launch (k_steps) of the instantiation `c` (qp_select.hpp: select_run), histories into h->hist_*.  Returns
+// 0 launched, 1 not launched -- no instantiation, or the plant's tableau could not be uploaded (the caller then runs ihm2mpc_step n_steps
+// times, which gives the same results).  sens: the loop with x0 sensitivities (k_steps<..., SENS = 1>), their history into h->hist_k;
+// its LDS is the larger of the QP's and k_sens' (the body reuses the QP's).
+int launch_steps(ihm2mpc_handle *h, const ihm2::QpChoice &c, int model, int M_sim, double s_target, int n_steps, int freeze, double lap_stop, int sens)
 {
-    const ihm2::QpChoice c = ihm2::select_steps(situation(h), sens);
     const QpInst *e = catalogue_inst(c.pos);
     if (!e) return 1;
     const bool irk_plant = ihm2_is_irk(h->cfg.sim_integrator_type);     // the plants by collocation (python/main.py:395-400: Radau IIA x M_sim)
@@ -374,6 +359,27 @@ int field_info(ihm2mpc_handle *h, const char *field, FieldInfo *fi)
 
 }  // namespace
 
+// what the selection reads of the handle (qp_select.hpp); IHM2MPC_BLOCK_QP is the handle's from its creation, the other switches are
+// read when the process' first situation is filled
+ihm2::QpSituation ihm2_situation(const ihm2mpc_handle *h)
+{
+    static const bool linearize_cols = switch_on("IHM2MPC_LINEARIZE_COLS"), persistent_rounds = switch_on("IHM2MPC_PERSISTENT_ROUNDS");
+    ihm2::QpSituation s;
+    s.N = h->N; s.B = h->B; s.n_cu = h->n_cu;
+    s.model = h->cfg.model; s.integrator_type = h->cfg.integrator_type; s.sim_integrator_type = h->cfg.sim_integrator_type;
+    s.nlp_solver_type = h->cfg.nlp_solver_type; s.sqp_globalization = h->sqp_globalization;
+    s.per_lane = h->slots.per_lane; s.per_blk = h->slots.per_blk; s.nsoft = h->slots.nsoft; s.m_act = h->slots.m_act;
+    s.slots_full = h->slots_full;
+    s.path = path_class(h);
+    s.uni = h->uniform_H && h->uniform_CD;
+    s.inst_b = h->inst_b; s.block_qp = h->block_qp;
+    s.qp_form = qp_form_limit();
+    s.irk_tab = !!h->irk_tab; s.ls_x = !!h->ls_x; s.ls_phi = !!h->ls_phi;
+    s.sens_lds = (int)(ihm2_sens_lds_bytes(h) / sizeof(double));
+    s.linearize_cols = linearize_cols; s.persistent_rounds = persistent_rounds;
+    return s;
+}
+
 // Runs with the handle's device current.  Nothing of the handle's may still run when its streams and buffers go; the buffers release
 // themselves after this body.
 ihm2mpc_handle::~ihm2mpc_handle()
@@ -396,13 +402,13 @@ static int check_sim_substeps(const ihm2mpc_handle *h, int M_sim, const char *la
                     (int)ceil(h->cfg.dt / (2.78 * 1e-3)));
     return 0;
 }
-// the plant arguments of ihm2mpc_sim_step, _sim_advance, _step and the step loops: sub-steps, plant model -2 .. 2, and
-// sim_integrator_type ERK_LAG integrates the plain kinematic plant only
+// the plant arguments of ihm2mpc_sim_step, _sim_advance, _step and the step loops: sub-steps, plant model -2 .. 2, and a kernel for it
+// (qp_select.hpp: select_sim has none where sim_integrator_type ERK_LAG meets another plant than the plain kinematic one)
 static int check_plant(const ihm2mpc_handle *h, int model, int M_sim)
 {
     if (check_sim_substeps(h, M_sim, "actuator lags")) return -1;
     if (model < -2 || model > IHM2MPC_MODEL_FDYN6U) return fail("unknown plant model %d", model);
-    if (h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK_LAG || model == IHM2MPC_MODEL_FKIN6) return 0;
+    if (ihm2::select_sim(ihm2_situation(h), model) != ihm2::SIM_KERNEL_NONE) return 0;
     return fail("the plant integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic plant (model 0) only, not for plant "
                 "model %d: create the handle with another sim_integrator_type", model);
 }
@@ -991,22 +997,12 @@ static int sqp_buffers(ihm2mpc_handle *h)
                      h->ls_iter, B, h->ls_qp_acc, B, h->ls_pending, B);
 }
 
-// SQP mode with the collocation integrator: room for the line search's trial-point rollouts (every step length of the ladder)
-// Trial step lengths of the backtracking ladder 1, rho, rho^2, ... >= alpha_min -- the same floating-point sequence as the loop of
-// line_search_body (sqp_body.hpp).  ihm2mpc_set_sqp_options refuses option pairs whose ladder is longer than IHM2MPC_LS_MAX_TRIALS:
-// one length everywhere (the buffer of the collocation rollouts, the rollout launches, the line search).
-#define IHM2MPC_LS_MAX_TRIALS 64
-static int ladder_length(double alpha_min, double alpha_red)
-{
-    int n = 1;
-    for (double al = alpha_red; al >= alpha_min && n <= IHM2MPC_LS_MAX_TRIALS; al *= alpha_red) n++;
-    return n;
-}
-
+// SQP mode with the collocation integrator: room for the line search's trial-point rollouts (every step length of the ladder,
+// qp_select.hpp: ladder_length)
 static int sqp_phi_buffer(ihm2mpc_handle *h, int *n_alpha_out)
 {
     const size_t B = h->B, N = h->N;
-    const int n_alpha = ladder_length(h->sqp_alpha_min, h->sqp_alpha_red);
+    const int n_alpha = ihm2::ladder_length(h->sqp_alpha_min, h->sqp_alpha_red);
     if (n_alpha > IHM2MPC_LS_MAX_TRIALS) return fail("backtracking ladder longer than %d trial steps", IHM2MPC_LS_MAX_TRIALS);
     if (h->ls_phi.size() < (size_t)n_alpha * B * N * 8) {
         HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old one
@@ -1021,7 +1017,7 @@ static int sqp_phi_buffer(ihm2mpc_handle *h, int *n_alpha_out)
 static int sqp_iterations(ihm2mpc_handle *h, int n_iter, bool join)
 {
     if (sqp_buffers(h)) return -1;
-    const size_t B = h->B, N = h->N;
+    const size_t B = h->B;
     HIP_TRY(hipMemsetAsync(h->ls_done, 0, B * sizeof(int32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->ls_iter, 0, B * sizeof(int32_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->ls_qp_acc, 0, B * sizeof(int32_t), h->stream));
@@ -1032,14 +1028,13 @@ static int sqp_iterations(ihm2mpc_handle *h, int n_iter, bool join)
         if (it == 0 && join) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
         if (it == n_iter - 1) HIP_TRY(hipEventRecord(h->ev[1], h->stream));
         if (launch_qp(h)) return fail("problem exceeds the QP kernel limits (LDS or constraint slots)");
-        if (h->cfg.integrator_type != IHM2MPC_INTEG_ERK && h->sqp_globalization) {
-            // collocation integrator: the rollouts of the line search's trial points (all step lengths of the ladder) in their own launch
+        if (const ihm2::QpSituation s = ihm2_situation(h); ihm2::ladder_rollouts(s)) {
+            // collocation integrator: the rollouts of the line search's trial points (all step lengths of the ladder) in their own launch,
+            // or in two (qp_select.hpp: ladder_first): the rest of the ladder only for the instances the first line-search launch leaves
+            // open, which then redo their ladder -- same arithmetic as one launch
             int n_alpha = 1;
             if (sqp_phi_buffer(h, &n_alpha)) return -1;
-            // most instances accept one of the first step lengths: those rollouts for everybody, the rest of the ladder only for the
-            // instances the first line-search launch leaves open (which then redo their ladder: same arithmetic as one launch)
-            // (a few instances -- the whole ladder is one round of wavefronts on the chip -- keep the single launch: two launches less per iteration)
-            const int j_first = (n_alpha < 3 || (long)n_alpha * (long)B * (long)N <= 16384) ? n_alpha : 3;
+            const int j_first = ihm2::ladder_first(s, n_alpha);
             ihm2_launch_rollout_irk(h, 0, j_first, h->ls_phi, nullptr);
             if (j_first < n_alpha) {
                 ihm2_launch_line_search(h, it, it == n_iter - 1, 1, j_first);
@@ -1088,7 +1083,7 @@ int ihm2mpc_set_sqp_options(ihm2mpc_handle *h, int32_t globalization, double alp
     if (!(alpha_min > 0.0 && alpha_min <= 1.0)) return fail("alpha_min must be in (0, 1]");
     if (!(alpha_reduction > 0.0 && alpha_reduction < 1.0)) return fail("alpha_reduction must be in (0, 1)");
     if (!(eps_sufficient_descent >= 0.0 && eps_sufficient_descent < 1.0)) return fail("eps_sufficient_descent must be in [0, 1)");
-    if (globalization == IHM2MPC_MERIT_BACKTRACKING && ladder_length(alpha_min, alpha_reduction) > IHM2MPC_LS_MAX_TRIALS)
+    if (globalization == IHM2MPC_MERIT_BACKTRACKING && ihm2::ladder_length(alpha_min, alpha_reduction) > IHM2MPC_LS_MAX_TRIALS)
         return fail("alpha_reduction %g with alpha_min %g makes a backtracking ladder of more than %d trial steps", alpha_reduction, alpha_min, IHM2MPC_LS_MAX_TRIALS);
     h->sqp_globalization = globalization; h->sqp_alpha_min = alpha_min; h->sqp_alpha_red = alpha_reduction; h->sqp_eps = eps_sufficient_descent;
     h->sqp_use_suff = use_sufficient_descent ? 1 : 0; h->sqp_full_step_dual = full_step_dual ? 1 : 0;
@@ -1489,31 +1484,27 @@ static int run_steps(ihm2mpc_handle *h, int32_t model, int32_t M_sim, double s_t
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->freeze_armed = true;
     }
-    // The persistent loop pays off while every instance has a wavefront slot of its own (the QP's 40 KB of LDS allow 4 per CU):
-    // a larger batch would run in rounds of whole n_steps-long loops, whereas launches per step backfill the slots of finished
-    // QPs with the next instances.
-    // (IHM2MPC_PERSISTENT_ROUNDS=1: take the one-launch loop for larger batches too -- the workgroups then run in rounds of whole histories;
-    // measured round 4 against launches per step for the dynamic models, NOTES.md R4)
-    static const bool rounds = [] { const char *e = getenv("IHM2MPC_PERSISTENT_ROUNDS"); return e && e[0] == '1'; }();
-    const bool resident = B <= (size_t)4 * h->n_cu || (rounds && !freeze);
-    int rc = 1;
     // x0 sensitivities: without `sens` none from the persistent loop, and none from its launches per step either (the same results
     // either way); with it, the last step's are readable afterwards
     if (h->sens_mode) h->sens_state = sens ? 0 : 2;
     struct Quiet { ihm2mpc_handle *h; bool was; ~Quiet() { h->sens_quiet = was; } } quiet{h, h->sens_quiet};
     h->sens_quiet = !sens;
     if (h->cfg.nlp_solver_type == IHM2MPC_SQP && sqp_buffers(h)) return -1;
-    if (h->cfg.nlp_solver_type == IHM2MPC_SQP && h->cfg.integrator_type != IHM2MPC_INTEG_ERK && h->sqp_globalization && sqp_phi_buffer(h, nullptr)) return -1;
-    if (resident) {
+    if (h->cfg.nlp_solver_type == IHM2MPC_SQP && ihm2::ladder_rollouts(ihm2_situation(h)) && sqp_phi_buffer(h, nullptr)) return -1;
+    // the loop or launches per step (qp_select.hpp: select_run), with the buffers above in place
+    const ihm2::RunChoice run = ihm2::select_run(ihm2_situation(h), sens ? 1 : 0, freeze != 0);
+    int per_step = run.how;
+    if (run.how == ihm2::RUN_PERSISTENT) {
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        rc = launch_steps(h, model, M_sim, s_target, n_steps, freeze ? 1 : 0, lap_stop, sens ? 1 : 0);
-        if (rc == 0) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-        if (rc == 0 && sens) h->sens_state = 1;
+        // (not launched after all: the plant's tableau could not be uploaded)
+        per_step = launch_steps(h, run.steps, model, M_sim, s_target, n_steps, freeze ? 1 : 0, lap_stop, sens ? 1 : 0) ? ihm2::RUN_PER_STEP_NO_INSTANTIATION : 0;
+        if (!per_step) HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        if (!per_step && sens) h->sens_state = 1;
     }
-    if (rc != 0) {
+    if (per_step) {
         if (freeze) return fail("no persistent loop for this configuration (needs batch-shared weights and rows for soft tables or the collocation integrator, and a batch of at most %d): call ihm2mpc_step per control period", 4 * h->n_cu);
-        ihm2::encode_launch(h->launch_rec, QpKey{QP_STEPS}, resident ? 1 : 2);      // the per-step QP launches below update [0..4]
+        ihm2::encode_launch(h->launch_rec, QpKey{QP_STEPS}, per_step);      // the per-step QP launches below update [0..4]
         for (size_t i = 0; i < n; i++) {      // launches per step, histories by device-to-device copies in stream order
             if (ihm2mpc_step(h, model, M_sim, s_target)) return -1;
             HIP_TRY(hipMemcpyAsync(h->hist_u0 + i * B * 2, h->u0, B * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -1590,7 +1581,7 @@ int ihm2mpc_sim_step_dyn10(ihm2mpc_handle *h, int32_t M_sim, const double *x, co
     if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG)
         return fail("the plant integrator ERK_LAG (closed-form actuator lags) is implemented for the kinematic plant (model 0) only, not for the "
                     "fdyn10 plant: create the handle with another sim_integrator_type");
-    const bool irk = h->cfg.sim_integrator_type != IHM2MPC_INTEG_ERK;
+    const bool irk = ihm2_is_irk(h->cfg.sim_integrator_type);          // (ERK_LAG is refused above)
     if (!h->dyn10) HIP_TRY(h->dyn10.alloc((size_t)h->B * 35));
     double *xs = h->dyn10, *us = h->dyn10 + (size_t)h->B * 15, *xn = h->dyn10 + (size_t)h->B * 20;
     if (upload(h, x, xs, 15) || upload(h, u, us, 5)) return -1;

@@ -28,8 +28,10 @@
 #define QM_PAD 24    // >= 3 x ring depth of the vector / forward sweeps: their unclamped prefetch overshoots an instance by < 3 D rows
 #define LIN_REC 96   // doubles per (instance, interval) linearisation record: A (64) | B (16) | b (8) | rb (8: the QP's dynamics residual, riccati_mfma.hpp)
 
-// the collocation integrators among IHM2MPC_INTEG_* (ERK and ERK_LAG are the explicit ones)
-static inline bool ihm2_is_irk(int type) { return type == IHM2MPC_INTEG_IRK_GL4 || type == IHM2MPC_INTEG_IRK_RADAU4; }
+#include "qp_select.hpp"      // the launch decisions, host-only: QpSituation and the selectors that read it, the launch record
+
+// the collocation integrators among IHM2MPC_INTEG_* (qp_select.hpp: is_irk, the one spelling of it)
+static inline bool ihm2_is_irk(int type) { return ihm2::is_irk(type); }
 // IHM2MPC_INTEG_ERK_LAG: the stage factors {E_0, E_1, E_2, e} of the torque lag, then of the steering lag, for sub-steps of h
 // (ihm2mpc_lag_stage_factors on the model's two time constants; kernels_linearize.hip) -- computed on the host, a kernel argument
 struct LagFac { double f[8]; };
@@ -235,6 +237,9 @@ struct ihm2mpc_handle {
     WorkBuf<double> adj_gW, adj_gWe;        // (B,n_seeds,12,12), (B,n_seeds,8,8) gradients in the weights (ihm2mpc_eval_adjoint_sensitivities_w)
 };
 
+// api.hip: what the selection reads of the handle -- the only function that turns a handle into a QpSituation.  Allocates nothing.
+ihm2::QpSituation ihm2_situation(const ihm2mpc_handle *h);
+
 // --- launchers (each defined in one .hip file) ---
 // mode: bit 0 = reference ramp (needs x0), bit 1 = warm-start shift
 void ihm2_launch_prepare(ihm2mpc_handle *h, double s_target, int mode, hipStream_t stream);
@@ -246,7 +251,7 @@ void ihm2_launch_sim_dyn10_irk(ihm2mpc_handle *h, int integ, int M, int newton_i
 void ihm2_launch_wrap_lap(ihm2mpc_handle *h);
 void ihm2_launch_init_guess(ihm2mpc_handle *h, double v_ref_scale, int only_failed);
 void ihm2_launch_linearize(ihm2mpc_handle *h);
-// kernels_irk.hip: the collocation integrators (cfg.integrator_type / cfg.sim_integrator_type != IHM2MPC_INTEG_ERK)
+// kernels_irk.hip: the collocation integrators (ihm2_is_irk of cfg.integrator_type / cfg.sim_integrator_type)
 void ihm2_launch_linearize_irk(ihm2mpc_handle *h);
 int ihm2_upload_sim_irk_tab(ihm2mpc_handle *h, int M_sim);      // 0 ok (h->sim_irk_tab holds the plant tableau for M_sim steps)
 int ihm2_upload_irk_tab(ihm2mpc_handle *h);      // (re)builds h->irk_tab for the configured integrator and step; 0 ok
@@ -350,5 +355,4 @@ struct StepArgs {
 void ihm2_sens_args(const ihm2mpc_handle *h, void *out);
 
 // The catalogue of their instantiations -- QpKey, QpInst, QpTable and the tables ihm2_qp_set0() .. ihm2_qp_set7() of the objects built from
-// kernels_qp.hip -- is qp_catalogue.hpp's; qp_select.hpp chooses from it.
-#include "qp_catalogue.hpp"
+// kernels_qp.hip -- is qp_catalogue.hpp's; qp_select.hpp (included above) chooses from it.

@@ -15,12 +15,9 @@
 // Sensitivities are held column-wise in registers; only the structurally non-zero entries of the
 // 8x10 matrix are stored (52 for fkin6, 55 for fdyn6) and only the non-zeros of the model Jacobian (31 / 37) are multiplied
 // (model.hpp: JX_MASK / S_COL_MASK).  Algorithmic traffic per pair: read 10 + 8 doubles, write 88.
-#include <cstdlib>
-
-#include "ihm2mpc_internal.h"
+#include "ihm2mpc_internal.h"     // (with qp_select.hpp: select_linearize, select_sim, and note_lin, note_sim for the launch record)
 #include "model.hpp"
 #include "device_steps.hpp"
-#include "qp_select.hpp"     // note_lin, note_sim: the launch record's last linearisation / plant kernel
 
 using namespace ihm2;
 
@@ -245,56 +242,53 @@ LagFac ihm2_lag_factors(double h)
     return l;
 }
 
+// Which kernel: qp_select.hpp: select_linearize.  One lane per (instance, interval) in blocks of 64; the column kernel ten wavefronts per block.
 void ihm2_launch_linearize(ihm2mpc_handle *h)
 {
-    if (ihm2_is_irk(h->cfg.integrator_type)) { note_lin(h->launch_rec, LIN_K_LINEARIZE_IRK); ihm2_launch_linearize_irk(h); return; }
-    const long total = (long)h->B * h->N;
-    const int blocks = (int)((total + 63) / 64);
-    if (h->cfg.integrator_type == IHM2MPC_INTEG_ERK_LAG) {
-        // one kernel at every batch size: with sub-steps sized for the car (M = 4) the column-parallel latency path has nothing left to hide
-        note_lin(h->launch_rec, LIN_K_LINEARIZE_LAG);
-        hipLaunchKernelGGL((k_linearize<1, LagFac>), dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
-                           h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin, ihm2_lag_factors(h->cfg.dt / h->cfg.M));
-        return;
+    const LinKernel kernel = select_linearize(ihm2_situation(h));
+    note_lin(h->launch_rec, kernel);
+    const dim3 blocks((unsigned)(((long)h->B * h->N + 63) / 64));
+    const size_t dyn_lds = (s_count(1) + dk_count()) * 64 * sizeof(double);
+#define LINEARIZE(k, grid, lds, ...)                                                                                                  \
+    hipLaunchKernelGGL(k, grid, dim3(64), lds, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref,  \
+                       h->track_id, h->x, h->u, h->lin, ##__VA_ARGS__)
+    switch (kernel) {
+    case LIN_K_LINEARIZE_IRK: ihm2_launch_linearize_irk(h); break;
+    case LIN_K_LINEARIZE_LAG: LINEARIZE((k_linearize<1, LagFac>), blocks, 0, ihm2_lag_factors(h->cfg.dt / h->cfg.M)); break;
+    case LIN_K_LINEARIZE_DYN:
+        if (h->cfg.model == IHM2MPC_MODEL_FDYN6U) LINEARIZE(k_linearize_dyn<IHM2MPC_MODEL_FDYN6U>, blocks, dyn_lds);
+        else LINEARIZE(k_linearize_dyn<IHM2MPC_MODEL_FDYN6>, blocks, dyn_lds);
+        break;
+    case LIN_K_LINEARIZE_COLS: LINEARIZE(k_linearize_cols, dim3(blocks.x, 10), 0); break;
+    case LIN_K_LINEARIZE: LINEARIZE(k_linearize<>, blocks, 0); break;
+    case LIN_KERNEL_NONE: break;
     }
-    // diagnostic (tools/bench_linearize.py --cols): the column-parallel kernel -- one sensitivity column per wavefront, ten wavefronts
-    // per block of 64 intervals -- at any batch size, to measure it against the lane-per-interval kernel
-    static const bool force_cols = getenv("IHM2MPC_LINEARIZE_COLS") && getenv("IHM2MPC_LINEARIZE_COLS")[0] == '1';
-    note_lin(h->launch_rec, h->cfg.model != IHM2MPC_MODEL_FKIN6 ? LIN_K_LINEARIZE_DYN : (blocks <= 2 || force_cols) ? LIN_K_LINEARIZE_COLS : LIN_K_LINEARIZE);
-    if (h->cfg.model == IHM2MPC_MODEL_FDYN6U)
-        hipLaunchKernelGGL(k_linearize_dyn<IHM2MPC_MODEL_FDYN6U>, dim3(blocks), dim3(64), (s_count(1) + dk_count()) * 64 * sizeof(double), h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
-                           h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
-    else if (h->cfg.model == IHM2MPC_MODEL_FDYN6)
-        hipLaunchKernelGGL(k_linearize_dyn<IHM2MPC_MODEL_FDYN6>, dim3(blocks), dim3(64), (s_count(1) + dk_count()) * 64 * sizeof(double), h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
-                           h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
-    else if (blocks <= 2 || force_cols)      // one or a few real-time controllers: the latency path (not bit-identical to the batch kernel, see above)
-        hipLaunchKernelGGL(k_linearize_cols, dim3(blocks, 10), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
-                           h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
-    else
-        hipLaunchKernelGGL(k_linearize<>, dim3(blocks), dim3(64), 0, h->stream, h->B, h->N, h->cfg.M, h->cfg.dt,
-                           h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, h->x, h->u, h->lin);
+#undef LINEARIZE
 }
 
+// Which kernel: qp_select.hpp: select_sim; none (ERK_LAG with another plant than model 0) launches nothing -- api.hip: check_plant has
+// refused the call.  k_sim_step_kin leaves its discarded linearisation record behind the handle's B N records.
 void ihm2_launch_sim(ihm2mpc_handle *h, int model, int M_sim, const double *x, const double *u, double *xn, hipStream_t stream, const int32_t *active)
 {
-    if (ihm2_is_irk(h->cfg.sim_integrator_type)) { note_sim(h->launch_rec, SIM_K_SIM_IRK); ihm2_launch_sim_irk(h, model, M_sim, x, u, xn, stream, active); return; }
-    const int blocks = (h->B + 63) / 64;
-    if (h->cfg.sim_integrator_type == IHM2MPC_INTEG_ERK_LAG) {      // (the callers have refused every plant but model 0)
-        note_sim(h->launch_rec, SIM_K_SIM_STEP_KIN_LAG);
-        hipLaunchKernelGGL((k_sim_step_kin<1, LagFac>), dim3(blocks), dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref,
-                           h->track_id, x, u, xn, active, h->lin + (size_t)h->B * h->N * LIN_REC, ihm2_lag_factors(h->cfg.dt / M_sim));
-        return;
-    }
-    const bool shared = model == IHM2MPC_MODEL_FKIN6 && (long)h->B * h->N > 128 && h->cfg.integrator_type == IHM2MPC_INTEG_ERK;
-    note_sim(h->launch_rec, shared ? SIM_K_SIM_STEP_KIN : SIM_K_SIM_STEP);
-    // the plain kinematic plant shares the integrator of the shooting intervals (bit-identical to lane N of the persistent loop); for
-    // the few instances of a real-time controller (the batches that also take the column-parallel linearisation) its discarded
-    // sensitivities would put 0.1 ms on the critical path of ihm2mpc_step: those take the state-only rollout, and so does a handle whose
-    // shooting intervals use the collocation integrator (nothing to share: the loop runs the plant as a phase of its own on one lane)
-    if (shared)
-        hipLaunchKernelGGL(k_sim_step_kin<>, dim3(blocks), dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id,
-                           x, u, xn, active, h->lin + (size_t)h->B * h->N * LIN_REC);
-    else        // four lanes per instance
+    const SimKernel kernel = select_sim(ihm2_situation(h), model);
+    note_sim(h->launch_rec, kernel);
+    const dim3 blocks((h->B + 63) / 64);
+    double *spare_rec = h->lin + (size_t)h->B * h->N * LIN_REC;
+    switch (kernel) {
+    case SIM_K_SIM_IRK: ihm2_launch_sim_irk(h, model, M_sim, x, u, xn, stream, active); break;
+    case SIM_K_SIM_STEP_KIN_LAG:
+        hipLaunchKernelGGL((k_sim_step_kin<1, LagFac>), blocks, dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref,
+                           h->track_id, x, u, xn, active, spare_rec, ihm2_lag_factors(h->cfg.dt / M_sim));
+        break;
+    case SIM_K_SIM_STEP_KIN:
+        hipLaunchKernelGGL(k_sim_step_kin<>, blocks, dim3(64), 0, stream, h->B, M_sim, h->cfg.dt, h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id,
+                           x, u, xn, active, spare_rec);
+        break;
+    case SIM_K_SIM_STEP:        // four lanes per instance
         hipLaunchKernelGGL(k_sim_step, dim3((4 * h->B + 63) / 64), dim3(64), 0, stream, h->B, model, M_sim, h->cfg.dt,
                            h->cfg.nknots, h->s_ref, h->kappa_ref, h->track_id, x, u, xn, active);
+        break;
+    case SIM_K_SIM_SENS: case SIM_KERNEL_NONE: break;
+    }
 }
+

@@ -344,7 +344,7 @@ static inline LsArgs make_ls_args(ihm2mpc_handle *h)
     a.res = h->res; a.status = h->status; a.qp_iter = h->qp_iter;
     a.done = h->ls_done; a.sqp_status = h->ls_status; a.sqp_iter = h->ls_iter; a.qp_acc = h->ls_qp_acc;
     a.alpha = h->ls_alpha; a.u0 = h->u0;
-    a.phi = (h->cfg.integrator_type != IHM2MPC_INTEG_ERK) ? h->ls_phi.get() : nullptr; a.n_alpha = (int)(h->ls_phi.size() / ((size_t)h->B * h->N * 8));
+    a.phi = ihm2_is_irk(h->cfg.integrator_type) ? h->ls_phi.get() : nullptr; a.n_alpha = (int)(h->ls_phi.size() / ((size_t)h->B * h->N * 8));
     a.phase = 0; a.j_limit = 0; a.pending = h->ls_pending; a.irk_tab = h->irk_tab;
     return a;
 }

@@ -1,6 +1,6 @@
 """tools/probes/check_qp_select.cpp from Python: the stand-alone program that runs csrc/qp_select.hpp (the choice of the QP and step-loop
-instantiations, and the launch record) on the CPU.  A helper of tests/test_qp_select.py, tests/test_steps_catalogue.py and
-tests/test_slot_table.py: each builds the probe once, with the address and undefined-behaviour sanitizers, and reads its lines."""
+instantiations and of the linearisation and plant kernels, how run_steps proceeds, the line search's ladder, and the launch record) on the
+CPU.  A helper of tests/test_qp_select.py, tests/test_steps_catalogue.py, tests/test_launch_select.py and tests/test_slot_table.py: each builds the probe once, with the address and undefined-behaviour sanitizers, and reads its lines."""
 import dataclasses
 import os
 import subprocess
@@ -61,7 +61,7 @@ def records(exe):
 
 @dataclasses.dataclass(frozen=True)
 class Facts:
-    """The configuration a handle is in, beside its problem: what api.hip::situation reads.  The defaults: the reference's OCP, one
+    """The configuration a handle is in, beside its problem: what api.hip: ihm2_situation reads, and the arguments of the call.  The defaults: the reference's OCP, one
     controller's worth of buffers, an MI355X."""
     model: int = 0                  # IHM2MPC_MODEL_*
     integrator: int = 0             # IHM2MPC_INTEG_* of the shooting intervals
@@ -75,6 +75,10 @@ class Facts:
     block_qp: bool = True
     qp_form: int = 3                # IHM2MPC_QP_FORM; 3: unset
     buffers: int = None             # None: what ihm2mpc_create and ihm2mpc_run_steps allocate for this configuration
+    plant: int = 0                  # the plant model of ihm2mpc_step / ihm2mpc_run_steps / ihm2mpc_sim_step: -2 .. 2
+    freeze: bool = False            # ihm2mpc_run_steps' freeze
+    linearize_cols: bool = False    # IHM2MPC_LINEARIZE_COLS=1
+    persistent_rounds: bool = False  # IHM2MPC_PERSISTENT_ROUNDS=1
 
     def tokens(self):
         irk = self.integrator in (1, 2)
@@ -82,7 +86,8 @@ class Facts:
         if buffers is None:     # the tableau with a collocation integrator; the line search's buffers in the SQP mode, its rollouts with collocation
             buffers = (1 if irk else 0) | (2 if self.sqp else 0) | (4 if self.sqp and self.integrator != 0 and self.globalization else 0)
         return [self.model, self.integrator, self.sim_integrator, int(self.sqp), self.globalization, self.B, self.n_cu, int(self.sens != 0),
-                int(self.inst_b), int(self.block_qp), self.qp_form, buffers]
+                int(self.inst_b), int(self.block_qp), self.qp_form, buffers, self.plant, int(self.freeze), int(self.linearize_cols),
+                int(self.persistent_rounds)]
 
 
 def facts_of_data(data, **more):
@@ -118,7 +123,8 @@ def problem_text(lay, data=None) -> str:
 
 def select(exe, tmp, jobs):
     """Runs the probe on jobs = [(layout, Facts)], one argument each.  Returns per job a dict: `qp` / `steps` the position of the chosen key
-    in catalogue() or None, `qp_lds` / `steps_lds` the LDS bytes of the launch, `rec` the sixteen integers of the launch record."""
+    in catalogue() or None, `qp_lds` / `steps_lds` the LDS bytes of the launch, `lin` / `sim` the enumerators of select_linearize / select_sim,
+    `run` select_run's outcome (persistent, no_instantiation, not_resident, refused), `rec` the sixteen integers of the launch record."""
     files, args = {}, []
     for lay, facts in jobs:
         if lay.name not in files:
@@ -131,7 +137,17 @@ def select(exe, tmp, jobs):
     out = []
     for (lay, _), line in zip(jobs, lines):
         t = line.split()
-        assert t[0] == lay.name and t[1] == "qp" and t[4] == "steps" and t[7] == "rec" and len(t) == 24, line
+        assert t[0] == lay.name and (t[1], t[4], t[7], t[9], t[11], t[13]) == ("qp", "steps", "lin", "sim", "run", "rec") and len(t) == 30, line
         pos = lambda v: None if v == "none" else int(v)       # noqa: E731
-        out.append(dict(qp=pos(t[2]), qp_lds=int(t[3]), steps=pos(t[5]), steps_lds=int(t[6]), rec=[int(v) for v in t[8:]]))
+        out.append(dict(qp=pos(t[2]), qp_lds=int(t[3]), steps=pos(t[5]), steps_lds=int(t[6]), lin=t[8], sim=t[10], run=t[12],
+                        rec=[int(v) for v in t[14:]]))
     return out
+
+
+def ladder(exe, alpha_min, alpha_red, B, N):
+    """(`--ladder`) (ladder_length, ladder_first) of the SQP options on a collocation handle of B instances and the horizon N; the length
+    is None where it exceeds IHM2MPC_LS_MAX_TRIALS (ihm2mpc_set_sqp_options refuses the pair)."""
+    (line,) = _lines(exe, "--ladder", repr(float(alpha_min)), repr(float(alpha_red)), str(B), str(N))
+    t = line.split()
+    assert t[0] == "ladder"
+    return (None, None) if t[1:] == ["too_long"] else (int(t[1]), int(t[2]))

@@ -59,7 +59,7 @@ LIVE = dict(nlp_solver_type="SQP", nlp_solver_max_iter=2, globalization="MERIT_B
 INTEG = {0: ("ERK", dict(integrator_type="ERK")), 1: ("IRK", dict(integrator_type="IRK", sim_method_num_steps=1)),       # python/main.py:234-236
          2: ("ERK_LAG", dict(integrator_type="ERK_LAG", sim_method_num_steps=4))}
 MODEL_CODE = {"fkin6": 0, "fdyn6u": 2}          # include/ihm2mpc.h: IHM2MPC_MODEL_*, also the plant argument of step / run_steps
-B = 5           # x N = 40: 200 intervals, above the 128-interval switch to k_linearize_cols and the state-only plant; a ragged last wave
+B = 5           # x N = 40: 200 intervals, no latency batch (launch_cases.latency_batch: k_linearize_cols and the state-only plant); a ragged last wave
 
 
 @dataclasses.dataclass(frozen=True)

@@ -8,14 +8,15 @@ import pytest
 from conftest import make_ocp, sample_x0
 
 import edge_states as E
+import launch_cases as LC
 
 pytestmark = pytest.mark.gpu
 
 MODELS = ["fkin6", "fdyn6", "fdyn6u"]
 INTEG = {"ERK": dict(M=25), "IRK_GL": dict(M=1, integrator_type="IRK", collocation_type="GAUSS_LEGENDRE"),
          "IRK_RADAU": dict(M=1, integrator_type="IRK", collocation_type="GAUSS_RADAU_IIA")}
-# (B, N, two tracks): > 128 intervals with a ragged last wave (k_linearize / k_linearize_dyn / k_linearize_irk); <= 128 intervals
-# (k_linearize_cols for fkin6 with ERK); N + 1 no multiple of 4 (a ragged tail in the three-pass tiling of the collocation quads);
+# (B, N, two tracks): no latency batch (launch_cases.latency_batch), with a ragged last wave (k_linearize / k_linearize_dyn /
+# k_linearize_irk); a latency batch (k_linearize_cols for fkin6 with ERK); N + 1 no multiple of 4 (a ragged tail in the three-pass tiling of the collocation quads);
 # the same track tabulated twice with every instance but the first on the second table, so that every entry reads the tid * nknots base
 # and the last knot of the last table
 SHAPES = {"batch": (5, 40, False), "columns": (3, 40, False), "odd_horizon": (27, 5, False), "two_tracks": (5, 40, True)}
@@ -91,7 +92,8 @@ def test_linearisation_matches_oracle_at_edge_states(track, entries, model, inte
     idx = E.grid(entries, B, N, first=7 * list(SHAPES).index(shape))
     on_last_table = slice(None) if tid is None else tid == tid.max()
     assert np.unique(idx[on_last_table][:, :N]).size == len(entries)          # every entry is linearised (two tracks: on the second table)
-    kernel = "k_linearize_irk" if integ != "ERK" else "k_linearize_dyn" if model != "fkin6" else "k_linearize_cols" if shape == "columns" else "k_linearize"
+    kernel = LC.names(s)[0]
+    assert LC.latency_batch(B, N) == (shape == "columns")
     X, U = E.arrays(entries)
     for parity in (0, 1):
         x, u = np.ascontiguousarray(X[idx]), np.ascontiguousarray(U[idx[:, :N]])
@@ -132,7 +134,7 @@ def test_plant_step_matches_oracle_at_edge_states(track, entries, plant, config)
             "RADAU_4": dict(sim_integrator_type="IRK", sim_collocation_type="GAUSS_RADAU_IIA")}[config]
     s, P, _ = _handles(track, "fkin6", "ERK", B, 40, **opts)
     xn = s.sim_step(x, u, model=plant, M_sim=M_sim)
-    assert s.get_launch_record()["sim"] == ("k_sim_irk" if config == "RADAU_4" else "k_sim_step_kin" if (plant == 0 and config != "ERK_25_rollout") else "k_sim_step")
+    assert s.get_launch_record()["sim"] == LC.names(s, plant)[1]
     s.free()
     xo, kin = _plant_reference(P, x, u, plant, M_sim, orc.INTEG_IRK_RADAU4 if config == "RADAU_4" else orc.INTEG_RK4)
     if kin is not None:

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 from conftest import make_ocp, sample_x0
 
+import launch_cases as LC
+
 pytestmark = pytest.mark.gpu
 
 B = 8
@@ -66,7 +68,7 @@ def _solve(track, ocp, x0, ref=None):
 @pytest.mark.parametrize("N", sorted(SEEDS))
 def test_horizons_around_the_ring_depth(track, N, monkeypatch):
     """k_qp_wave against the oracle (status, iteration count, x and u to 1e-9), then two control steps per step (k_qp_wave) and in one
-    launch (k_steps).  (The kin/dyn switch plant, model -1: k_sim_step on both sides; at B N <= 128 the per-step path integrates the
+    launch (k_steps).  (The kin/dyn switch plant, model -1: k_sim_step on both sides; on a latency batch the per-step path integrates the
     kinematic plant with another kernel than the loop, tests/test_gpu_qp_layouts.py: KNOWN DIFFERENCE.)"""
     from ihm2_amd.solver import BatchedOcpSolver
 
@@ -85,11 +87,11 @@ def test_horizons_around_the_ring_depth(track, N, monkeypatch):
     rec = s.get_launch_record()
     assert rec["qp"] == "k_qp_wave<5,0,0,1>" and rec["qp_form"] == "plain"
     s.free()
-    # The two GPU paths.  ihm2mpc_step linearises batches of up to 128 intervals with the latency kernel k_linearize_cols, whose records
-    # agree with the loop's to 1e-15 and not bit for bit (include/ihm2mpc.h, ihm2mpc_run_steps): at B = 8 the two paths are compared
-    # as tests/test_gpu_qp_layouts.py compares them there (status and iteration counts equal, the rest to 1e-9), and bit for bit on the
-    # smallest batch that takes the batch linearisation on both sides (B N > 128).
-    for Bp in (B, max(B, 129 // N + 1)):
+    # The two GPU paths.  ihm2mpc_step linearises a latency batch (launch_cases.latency_batch) with the kernel k_linearize_cols, whose
+    # records agree with the loop's to 1e-15 and not bit for bit (include/ihm2mpc.h, ihm2mpc_run_steps): at B = 8 the two paths are compared
+    # as tests/test_gpu_qp_layouts.py compares them there (status and iteration counts equal, the rest to 1e-9), and bit for bit on a
+    # batch just past the switch, which takes the batch linearisation on both sides.
+    for Bp in (B, LC.PAST_THE_SWITCH[N]):
         xp = sample_x0(track, Bp, seed=SEEDS[N]); xp[:, 3] = np.clip(xp[:, 3], 4.0, 12.0)
         res = []
         for persistent in (False, True):
@@ -110,14 +112,14 @@ def test_horizons_around_the_ring_depth(track, N, monkeypatch):
                 h = {k: np.array(v) for k, v in h.items()}
                 rec = s.get_launch_record()
                 assert rec["qp"] == "k_qp_wave<5,0,0,1>" and rec["qp_form"] == "plain"
-                assert rec["linearize"] == ("k_linearize" if Bp * N > 128 else "k_linearize_cols")
+                assert (rec["linearize"], rec["sim"]) == LC.names(s, plant=-1)
             res.append((h, s.get_x(), s.get_u(), s.get_multipliers()))
             s.free()
         (ha, xa, ua, ma), (hb, xb, ub, mb) = res
         np.testing.assert_array_equal(ha["status"], hb["status"]); np.testing.assert_array_equal(ha["qp_iter"], hb["qp_iter"])
         pairs = [(ha["x0"], hb["x0"], "x0"), (ha["u0"], hb["u0"], "u0"), (xa, xb, "x"), (ua, ub, "u"), (ma[0], mb[0], "pi"), (ma[1], mb[1], "lam")]
         for a, b, k in pairs:
-            if Bp * N > 128:
+            if not LC.latency_batch(Bp, N):
                 np.testing.assert_array_equal(a, b, err_msg=f"B={Bp}: {k}")
             else:
                 d = _rel(a, b)
@@ -130,7 +132,7 @@ def test_sqp_loop_is_refused_where_its_sweeps_leave_the_lds(track, N, loop, monk
     """The SQP instantiations of the persistent loop keep the sweeps' earlier form (kernels_qp.hip: stream_rows_v1), whose unclamped prefetch
     of LDS operands starts in front of the block's LDS at N = 2, 3 (csrc/qp_lds.hpp: qp_reach_v1_vector; 60 / 24 words): run_steps launches
     those horizons per step and says so, and runs the loop from N = 4.  Three control steps, bit for bit against three calls of step().
-    (The collocation integrator: at B N <= 128 it is the one configuration in which step() and the loop linearise and simulate with the
+    (The collocation integrator: on a latency batch it is the one configuration in which step() and the loop linearise and simulate with the
     same code -- see test_horizons_around_the_ring_depth.)"""
     from ihm2_amd.solver import BatchedOcpSolver
 

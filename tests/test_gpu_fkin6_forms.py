@@ -20,13 +20,13 @@ from conftest import make_ocp, random_state
 
 import edge_states as E
 import lag_ref
+import launch_cases as LC
 
 pytestmark = pytest.mark.gpu
 
 N, B_BIG, B_SMALL = 5, 67, 3
 OFFSET = 1e-3 * np.array([1.0, -1.0, 2.0, -2.0, 3.0, -3.0, 4.0, -4.0])
 KS = np.arange(0, N, 2)          # the compared intervals
-KERNELS = {("ERK", B_BIG): "k_linearize", ("ERK", B_SMALL): "k_linearize_cols", ("ERK_LAG", B_BIG): "k_linearize_lag", ("ERK_LAG", B_SMALL): "k_linearize_lag"}
 
 
 def _states(track):
@@ -78,7 +78,7 @@ def case(request, track):
         s = BatchedOcpSolver(ocp, B, s_ref, k_ref, track_id=tid[:B])
         s.set_x0(x[:B, 0]); s.set_x(x[:B]); s.set_u(u[:B])
         s.linearize()
-        got[B] = (s.get_linearization(), s.get_launch_record())
+        got[B] = (s.get_linearization(), s.get_launch_record(), LC.names(s)[0])
         s.free()
     return dict(integ=integ, M=M, idx=idx, tol_ab=tol_ab, tol_b=tol_b, names=np.array(names), ref=ref, got=got)
 
@@ -92,8 +92,8 @@ def _errors(got, ref):
 
 @pytest.mark.parametrize("B", [B_BIG, B_SMALL])
 def test_records_match_the_reference(case, B):
-    (A, Bm, b), rec = case["got"][B]
-    assert rec["linearize"] == KERNELS[case["integ"], B]
+    (A, Bm, b), rec, kernel = case["got"][B]
+    assert rec["linearize"] == kernel and (kernel == "k_linearize_cols") == (case["integ"] == "ERK" and B == B_SMALL)
     ref = tuple(r[:B] for r in case["ref"])
     assert np.all(np.isfinite(A)) and np.all(np.isfinite(Bm)) and np.all(np.isfinite(b))
     assert np.abs(ref[2][:, KS]).max() < 0.01          # the defects are the offset
@@ -109,9 +109,10 @@ def test_records_match_the_reference(case, B):
 
 def test_small_batch_matches_the_batch_kernel(case):
     """The first three instances alone (ERK: the column kernel, whose Jacobian is dense) and inside the large batch (factored rows)."""
-    (A, Bm, b), rec_big = case["got"][B_BIG]
-    (As, Bms, bs), rec_small = case["got"][B_SMALL]
-    assert (rec_big["linearize"], rec_small["linearize"]) == (KERNELS[case["integ"], B_BIG], KERNELS[case["integ"], B_SMALL])
+    (A, Bm, b), rec_big, kernel_big = case["got"][B_BIG]
+    (As, Bms, bs), rec_small, kernel_small = case["got"][B_SMALL]
+    assert (rec_big["linearize"], rec_small["linearize"]) == (kernel_big, kernel_small)
+    assert (kernel_big == kernel_small) == (case["integ"] == "ERK_LAG")
     ea, eb, ec = _errors((As, Bms, bs), (A[:B_SMALL], Bm[:B_SMALL], b[:B_SMALL]))
     print(f"{case['integ']} M={case['M']}: small batch against the batch kernel A {ea.max():.2e} B {eb.max():.2e} b {ec.max():.2e}")
     assert ea.max() < 1e-13 and eb.max() < 1e-13 and ec.max() < 1e-13

@@ -23,7 +23,7 @@ from test_gpu_steps_catalogue import _sens, _solver, _start
 
 pytestmark = pytest.mark.gpu
 
-B = 8               # x N >= 40: 320 intervals and more, above the 128-interval switch to k_linearize_cols and the state-only plant
+B = 8               # x N >= 40: 320 intervals and more, no latency batch (launch_cases.latency_batch: k_linearize_cols and the state-only plant)
 STEPS = 6
 HIST = ("u0", "x0", "status", "qp_iter")
 FAILED_CAR, NAN_CAR = 0, 1          # the cars the causes (a) and (b) are planted in; the lap rule acts among the cars 2 .. B - 1

@@ -154,7 +154,7 @@ def test_forms_give_the_same_bits(tmp_path):
     """Three control steps through step() and the same three in one run_steps launch, in the full form and in the general slot form
     (IHM2MPC_QP_FORM=2: the straight-line factor sweep with the horizon compiled in, the default before the full form) -- one process
     each, the variable is read once.  Between the forms everything is equal byte for byte; inside a form the two paths are too: B N = 320
-    is above the 128 intervals up to which step() linearises and integrates the plant with other kernels than the loop
+    is no latency batch (tests/launch_cases.py), which step() linearises and whose plant it integrates with other kernels than the loop
     (tests/test_gpu_factor_sweep_forms.py, tests/test_gpu_qp_layouts.py: KNOWN DIFFERENCE)."""
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "slot_forms_child.py")
     got = {}

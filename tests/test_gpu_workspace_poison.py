@@ -21,6 +21,7 @@ import sys
 import numpy as np
 import pytest
 
+import launch_cases as LC
 import layouts as L
 import poison_cases as PC
 import steps_cases as S
@@ -279,7 +280,7 @@ def test_single_instance_control(track):
         xc = x0.copy()
         for _ in range(3):
             u0, st = s.compute_control(xc, 40.0)
-            assert s.get_launch_record()["linearize"] == "k_linearize_cols"
+            assert s.get_launch_record()["linearize"] == LC.names(s)[0] == "k_linearize_cols"
             out.append(dict(PC.outputs(s), u0_returned=u0, status_returned=st))
             xc = s.sim_step(xc, u0, model=0, M_sim=20)
         return out

@@ -11,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import launch_cases as LC
 import layouts as L
 import rollout_ref as R
 import select_probe as P
@@ -62,7 +63,7 @@ def test_case_fields_say_what_the_name_says():
         assert (k["sqp"], k["irk"], k["dyn"], k["sens"] != 0) == (int(c.sqp), c.irk, int(c.model != "fkin6"), c.sens != 0), c
         assert k["uni"] == (0 if lay.stage_W or lay.grows == "stagevary" else 1), c
         assert k["path"] == (2 if lay.alat else 1 if lay.path else 0), c
-        assert c.B * lay.N > 128 and (c.B * lay.N) % 64 != 0          # past the switch to k_linearize_cols / the state-only plant; a ragged last wave
+        assert not LC.latency_batch(c.B, lay.N) and (c.B * lay.N) % 64 != 0          # k_linearize_cols / the state-only plant are not run; a ragged last wave
     # the plants rotate within every (IRK, DYN) class: the kinematic plant on lane N and a called dynamic plant both occur
     for cls in {(c.irk, c.model) for c in S.CASES}:
         plants = {c.plant for c in S.CASES if (c.irk, c.model) == cls}
