@@ -25,7 +25,8 @@
 
 #include "qp_tables.hpp"      // ConstraintRows, SlotTable: the handle holds one of each
 
-#define QM_PAD 24    // >= 3 x ring depth of the vector / forward sweeps: their unclamped prefetch overshoots an instance by < 3 D rows
+#define QM_PAD 24    // >= 3 x ring depth of the vector / forward sweeps: their unclamped prefetch overshoots an instance by < 3 D rows (stage-major rows;
+                     // the stage-pair-major rows of the compiled-in horizon: D pair rows = 2 D stage rows, qp_mrows.hpp: qm_pair_inside)
 #define LIN_REC 96   // doubles per (instance, interval) linearisation record: A (64) | B (16) | b (8) | rb (8: the QP's dynamics residual, riccati_mfma.hpp)
 
 #include "qp_select.hpp"      // the launch decisions, host-only: QpSituation and the selectors that read it, the launch record
@@ -181,7 +182,8 @@ struct ihm2mpc_handle {
     WorkBuf<double> q_rg;   // (B,NS,10) stationarity residual of the interior-point iterate (follows the step between two evaluations from the data)
     WorkBuf<double> q_P;    // (B,NS,64) Riccati matrices of the current factorisation
     WorkBuf<double> q_M;    // (QM_PAD + B*N + QM_PAD, 64) closed-loop matrices A - B K (row-major; the vector recursion reads them
-                           // transposed), padded at both ends: the sweeps' prefetch rings run QM_PAD rows past an instance unclamped
+                           // transposed), padded at both ends: the sweeps' prefetch rings run QM_PAD rows past an instance unclamped.
+                           // An instance's N x 512 bytes are stage-major or stage-pair-major by the kernel that writes and reads them (qp_mrows.hpp)
     WorkBuf<double> scratch;   // (B, 3*8) plant scratch
 
     // ---- SQP mode (cfg.nlp_solver_type == IHM2MPC_SQP): convergence test + merit line search, kernels_sqp.hip ----

@@ -42,6 +42,7 @@
 #include "riccati_mfma.hpp"
 #include "sens_body.hpp"
 #include "qp_lds.hpp"
+#include "qp_mrows.hpp"
 #include "qp_catalogue.hpp"
 #include "wave_sync.hpp"
 
@@ -120,7 +121,8 @@ __device__ __forceinline__ double sum_stride8(double v)
     return __hiloint2double(b32[0], a32[0]) + __hiloint2double(b32[1], a32[1]);
 }
 
-// Ring of D coalesced 512-byte loads running D-1 stages ahead of a sequential sweep over a (N,64) array.
+// Ring of D coalesced 512-byte loads running D-1 stages ahead of a sequential sweep over a (N,64) array: the stage-major M_k rows of
+// qp_mrows.hpp (PAIR, below: the stage-pair-major rows of the compiled-in horizon, D 1024-byte loads covering 2 D stages).
 // DIR = -1: k = N-1 .. 0 ; DIR = +1: k = 0 .. N-1.  body(k, value of element `lane` of row k).
 // The element a lane takes alternates with the step: e_even on steps 0, 2, ... and e_odd on steps 1, 3, ... (D is even).
 // pre(k, odd, x0, x1) fetches the LDS operands of a step DL steps ahead of its use (the body's own LDS stores would otherwise
@@ -129,10 +131,60 @@ __device__ __forceinline__ double sum_stride8(double v)
 // BUF: how a row is loaded.  true: buffer loads on a scalar row offset; false: global loads with per-lane 64-bit addresses, the sweeps' row
 // streaming as it was before the diet -- kept (stream_rows_v1) for the SQP instantiations of the persistent loop, whose register allocation the
 // leaner form tips into scratch (live options: 449 k control steps/s with this form, 380 k with the other).
-template <int DIR, int D, int DL, bool BUF = true, typename P, typename F>
+// PAIR: the rows in the stage-pair-major layout of qp_mrows.hpp (the compiled-in even horizon): the lane's 16 bytes hold its values of two
+// consecutive steps, so ONE 16-byte buffer load per two stages (e_even, e_odd are not used: every lane takes its own slot).  Same pass of 2 D
+// stages, i.e. D pairs; the ring is the D pairs r2[.], each refilled -- with the pair D pairs further on -- behind the body of its second stage,
+// when both of its values are dead: again nothing to copy at the back edge, and 2 D - 2 stages between a load and its first use.
+template <int DIR, int D, int DL, bool BUF = true, bool PAIR = false, typename P, typename F>
 __device__ __forceinline__ void stream_rows(const double *rows, int N, int e_even, int e_odd, P &&pre, F &&body)
 {
     static_assert(D % 2 == 0 && DL % 2 == 0 && D % DL == 0 && 3 * D <= QM_PAD, "the element index alternates with the step parity");
+    if constexpr (PAIR) {
+        static_assert(BUF, "the paired rows come through buffer loads");
+        // the unclamped prefetch in pair rows (qp_mrows.hpp: qm_pair_reach), checked by the caller for its horizon against QM_PAD; the
+        // descriptor covers the instance's block and the padding on both sides, as below
+        typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+        u4_t r2[D];
+        double x0[DL], x1[DL];
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(rows) - (size_t)QM_PAD * 64, 0, (N + 2 * QM_PAD) * QM_STAGE_BYTES, 0x00020000);
+        const unsigned vl = (unsigned)qm_pair_slot(2, 0, (int)threadIdx.x & 63);
+        auto load_pair = [&](const int pstep) -> u4_t {                     // pstep: wave-uniform, the pair's place in the sweep's order
+            const int prow = (DIR < 0) ? (N >> 1) - 1 - pstep : pstep;
+            return __builtin_amdgcn_raw_buffer_load_b128(rsrc, vl, QM_PAD * QM_STAGE_BYTES + prow * QM_PAIR_BYTES, 0);
+        };
+        // the half a step takes (qm_pair_read): forward the first on even steps, backward the second
+        auto half = [&](const u4_t v, const bool odd) -> double {
+            const bool second = (DIR < 0) ? !odd : odd;
+            return second ? __hiloint2double((int)v.w, (int)v.z) : __hiloint2double((int)v.y, (int)v.x);
+        };
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            r2[p] = load_pair(p);
+            __builtin_amdgcn_sched_barrier(0);          // ring order, as below
+            if (p < DL) pre((DIR < 0) ? N - 1 - p : p, (p & 1) != 0, x0[p], x1[p]);
+        }
+        for (int s0 = 0; s0 < N; s0 += 2 * D) {
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    const int s = s0 + 2 * p + t;
+                    const int k = (DIR < 0) ? N - 1 - s : s;
+                    const double v = half(r2[p], t != 0), y0 = x0[(2 * p + t) % DL], y1 = x1[(2 * p + t) % DL];
+                    pre((DIR < 0) ? k - DL : k + DL, t != 0, x0[(2 * p + t) % DL], x1[(2 * p + t) % DL]);
+                    if (s < N) body(k, v, t != 0, y0, y1);
+                    if (t == 1) {
+                        r2[p] = load_pair((s0 >> 1) + p + D);
+                        // the load stays behind its pair (fence): left alone, the scheduler sank three of the forward sweep's four loads to
+                        // the end of the pass, two and four stages in front of their use (per stage, 16 instances' stamps: forward sweep
+                        // 173 cycles without the fence, 153 with it; vector sweep 170 and 154; NOTES R16)
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+        }
+        return;
+    }
     // The prefetches run UNCLAMPED past the instance, by at most ceil(N / 2D) 2D + D - N < 3 D rows (D + DL stages of LDS
     // operands): the streamed array is padded by QM_PAD >= 3 D rows at both ends and the LDS operands sit inside the kernel's LDS with other
     // arrays on both sides (qp_lds.hpp: qp_sweeps_inside -- asserted in qp_wave_body, and where it fails the launch is refused, api.hip),
@@ -209,6 +261,11 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     // want_res = false (wave-uniform): the stationarity residual of the incoming iterate -- an output only (ihm2mpc_get_residuals), a third of
     // the QP set-up -- is skipped; the persistent RTI loop asks for it on its last step alone
     constexpr int NT = 64 * NW;
+    // M_k of the compiled-in horizon is kept stage-pair-major (qp_mrows.hpp): the factor sweep's straight-line stage writes it so, the lean vector and
+    // forward sweeps take one 16-byte load per two stages.  Every other form keeps the stage-major RIC_IDX rows.
+    constexpr bool PAIRM = NF > 0;
+    static_assert(!PAIRM || (NF % 4 == 0 && LEAN != 0 && NW == 1 && qm_pair_inside(NF > 0 ? NF : 2, SWEEP_RING, QM_PAD)),
+                  "the paired rows: an even horizon in whole factor passes, the lean sweeps, and their unclamped prefetch inside q_M's padding");
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #define BSYNC() do { if (NW == 1) WSYNC(); else __syncthreads(); } while (0)
     const int N = (NF > 0) ? NF : a.N, NS = N + 1;
@@ -772,7 +829,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 const double *be = (w == 0) ? pv + (N - 1) * 8 + g : dz, *bo = (g == 0) ? pv + (N - 2) * 8 + w : dz;
                 const double *qe = Prb + (N - 1) * 8 + w, *qo = Prb + (N - 2) * 8 + g;      // P_{k+1} rb_k, same order
                 double *oe = pv + (N - 1) * 8 + g, *oo = pv + (N - 2) * 8 + w;               // results: k = N-1, N-3, ... and N-2, N-4, ...
-                stream_rows<-1, SWEEP_RING, SWEEP_DL>(Mg, N, RIC_IDX(w, g), RIC_IDX(g, w),
+                stream_rows<-1, SWEEP_RING, SWEEP_DL, true, PAIRM>(Mg, N, RIC_IDX(w, g), RIC_IDX(g, w),
                     [&](int k, bool odd, double &prb, double &base) {
                         if (odd) { prb = *qo; qo -= 16; base = *bo; bo -= so2; } else { prb = *qe; qe -= 16; base = *be; be -= se2; }
                     },
@@ -848,7 +905,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 // (running pointers with a per-lane increment: the fetches come in the order k = 0, 1, ... with even and odd steps alternating)
                 const int se2 = (w == 0) ? 20 : 0, so2 = (g == 0) ? 20 : 0;
                 const double *ce = (w == 0) ? dz + 10 + g : dz, *co = (g == 0) ? dz + 20 + w : dz;
-                stream_rows<+1, SWEEP_RING, SWEEP_DL>(Mg, N, RIC_IDX(g, w), RIC_IDX(w, g),
+                stream_rows<+1, SWEEP_RING, SWEEP_DL, true, PAIRM>(Mg, N, RIC_IDX(g, w), RIC_IDX(w, g),
                     [&](int k, bool odd, double &c, double &unused) {
                         if (odd) { c = *co; co += so2; } else { c = *ce; ce += se2; }
                         unused = 0.0;

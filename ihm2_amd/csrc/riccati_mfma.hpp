@@ -38,6 +38,7 @@ __device__ long long ric_dbg[8];
 #include <hip/hip_runtime.h>
 
 #include "qp_lds.hpp"
+#include "qp_mrows.hpp"
 #include "wave_sync.hpp"
 
 namespace ihm2 {
@@ -147,7 +148,9 @@ __device__ __forceinline__ void dyn_residual(const int N, const int lane, double
 }
 
 // Backward sweep.  In (LDS): gam, hc, gt = the predictor's gradient incl. [A B]'pi; in the records: A, B and rb (slot 88).
-// Out: LDS arrays of RicLds; HBM: Pg (NS,64), Mg (N,64) in the RIC_IDX layout.  store_p (wave-uniform): also keep p_k, k < N.
+// Out: LDS arrays of RicLds; HBM: Pg (NS,64) in the RIC_IDX layout; Mg, the instance's N x 512 bytes, in the RIC_IDX layout too (stage-major)
+// except with NF > 0, which writes it stage-pair-major for the sweeps that read it back (qp_mrows.hpp states both layouts and who takes
+// which).  store_p (wave-uniform): also keep p_k, k < N.
 // Hs (NS,10,10), CD (N,2,10): batch-shared; UNI: the same for all k < N (only stage 0 is read).  HsT: the terminal stage's 10x10.  D: depth of the record prefetch ring.
 // ALAT: a fifteenth row per stage, gam[k][14] a a' with a = the four non-zeros in L.ha (stages 1..N-1).
 //
@@ -156,7 +159,8 @@ __device__ __forceinline__ void dyn_residual(const int N, const int lane, double
 // bits; what goes is the bookkeeping around them, which at one wave per SIMD costs an issue slot like any product:
 //   * the records come through buffer loads -- per-lane element offsets fixed, the stage as a scalar byte offset that steps down by one
 //     record and is clamped at stage 0 -- instead of addresses rebuilt from k;
-//   * P_k and M_k leave through one running 32-bit offset per lane (both arrays are (., 64): the same entry of the same row);
+//   * P_k and M_k leave through one running 32-bit offset per lane (both arrays are (., 64): the same entry of the same row; the pair-major
+//     M_k of NF > 0 adds a constant of the lane at odd stages and splits the 16-byte store into the two owners' 8 bytes);
 //   * the LDS results leave through running per-lane addresses, in ALL lanes: a lane that owns no entry of an array keeps a fixed address in
 //     the transpose tile, which is idle in this form, and a step of zero (the vector sweep's dz[0] trick, for stores) -- no exec-mask region
 //     but the one around the two global stores.  kff_k and K_k are the same register (Kf) in different lanes: one store;
@@ -264,6 +268,9 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lan
     // PLAIN: the running state of the stage's loads and stores (stage k = N - 1 first)
     int rs = (N - 1 - D) * rec_bytes;                                  // record k - D, clamped where it is used
     unsigned gofs = (unsigned)((N - 1) * 64 + RIC_IDX(g, j)) * 8u;     // entry of P_k and M_k (lanes j < 8)
+    // NF > 0: M_k leaves pair-major (qp_mrows.hpp).  An even stage's byte is gofs itself, an odd stage's is gofs plus this constant of the lane
+    static_assert(NF <= 0 || (NF % D == 0 && D % 2 == 0 && qm_pair_horizon(NF)), "the stage's parity is a constant of the straight-line pass");
+    const unsigned mdel = (NF > 0) ? (unsigned)qm_pair_odd_delta(NF > 0 ? NF : 2, g, j & 7) : 0u;
     const bool own10 = j == 10, ownK = j < 8 && g < 2;
     const int dead = L.tile + lane;                                    // (+ 4 at most: inside the tile, qp_lds.hpp: qp_reach_plain_parking)
     int a_hv = own10 ? L.hv + (N - 1) * 8 + g : dead, a_dz = own10 ? L.dz + N * 10 + g : dead, a_gi = own10 ? L.Ginv + (N - 1) * 8 + 2 * g : dead;
@@ -361,6 +368,17 @@ __device__ __forceinline__ void riccati_sweep_mfma(const int N_rt, const int lan
                         double2 mm, pp;
                         mm.x = S[2]; mm.y = S[3];
                         pp.x = S[0]; pp.y = S[1];
+                        if constexpr (NF > 0) {
+                            // pair-major M_k: rows g and g + 4 of column j go to their two owners' slots as two 8-byte stores.  The stage's
+                            // parity is a constant of the pass (NF % D == 0, D even: k is odd where d is even), so the offset stays the
+                            // running one plus the lane's constant plus an immediate.  The two halves of a 16-byte slot are written by two
+                            // stages of this wave and read by this wave behind the caller's barrier after the sweep, as the double2
+                            // rows were: no ordering beyond what was there.
+                            const bool odd_k = ((NF - 1 - d) & 1) != 0;        // a constant once the pass is unrolled
+                            char *const mp = (char *)Mg + (odd_k ? gofs + mdel : gofs);
+                            *(double *)mp = mm.x;
+                            *(double *)(mp + qm_pair_row4_step(NF, odd_k)) = mm.y;
+                        } else
                         *(double2 *)((char *)Mg + gofs) = mm;
                         *(double2 *)((char *)Pg + gofs) = pp;
                     }

@@ -23,8 +23,8 @@ s = s.replace("    double car_L, car_W;\n", "    double car_L, car_W;\n    long 
 open(p, "w").write(s)
 p = os.path.join(dst, "api.hip"); s = open(p).read()
 s = s.replace("    a.lin = h->lin;", "    static long long *dbg = nullptr; if (!dbg) (void)hipMalloc((void**)&dbg, 16 * %d * sizeof(long long)); a.dbg = dbg;\n    a.lin = h->lin;" % (NS + 1))
-assert "    launch_inst(h, e, args, lds);\n    return 0;" in s
-s = s.replace("    launch_inst(h, e, args, lds);\n    return 0;", "    launch_inst(h, e, args, lds);\n    { long long hb[16 * NSP]; (void)hipMemcpy(hb, a.dbg, sizeof hb, hipMemcpyDeviceToHost); static int cnt = 0; if (cnt++ % 10 == 5) for (int w = 0; w < 16; w++) { printf(\"[stamps b=%d it=%lld]\", w, hb[w * NSP + NSP - 1]); for (int q = 0; q < NSP - 1; q++) printf(\" %lld\", hb[w * NSP + q]); printf(\"\\n\"); } }\n    return 0;".replace("NSP", str(NS + 1)), 1)
+assert "    launch_inst(h, e, args, c.lds);\n    return 0;" in s
+s = s.replace("    launch_inst(h, e, args, c.lds);\n    return 0;", "    launch_inst(h, e, args, c.lds);\n    { long long hb[16 * NSP]; (void)hipMemcpy(hb, a.dbg, sizeof hb, hipMemcpyDeviceToHost); static int cnt = 0; if (cnt++ % 10 == 5) for (int w = 0; w < 16; w++) { printf(\"[stamps b=%d it=%lld]\", w, hb[w * NSP + NSP - 1]); for (int q = 0; q < NSP - 1; q++) printf(\" %lld\", hb[w * NSP + q]); printf(\"\\n\"); } }\n    return 0;".replace("NSP", str(NS + 1)), 1)
 open(p, "w").write(s)
 mk = os.path.join(dst, "Makefile"); m = open(mk).read().replace("OUT     = ../libihm2mpc.so", "OUT     = libihm2mpc_dbg.so")
 if os.environ.get("STAMP_SOFT"): m = m.replace("-DQP_SET=1", "-DQP_SET=1 -DSTAMP_SOFT")      # stamps in the soft / track-row set as well
