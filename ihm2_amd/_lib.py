@@ -122,6 +122,8 @@ SYMBOLS = {
     "ihm2mpc_get_sens_u0_device": (C.c_int, [_H, C.c_void_p]),
     "ihm2mpc_eval_adjoint_sensitivities": (C.c_int, [_H, C.c_int32] + [c_double_p] * 5),
     "ihm2mpc_eval_adjoint_sensitivities_w": (C.c_int, [_H, C.c_int32] + [c_double_p] * 7),
+    "ihm2mpc_eval_cost": (C.c_int, [_H] + [c_double_p] * 3),
+    "ihm2mpc_eval_cost_gradient": (C.c_int, [_H] + [c_double_p] * 8),
 }
 
 _lib = None

@@ -313,6 +313,12 @@ class IHM2Controller(Controller):
         _, K = self.solver.get_x0_sensitivities()
         return K[0] if self.B == 1 else K
 
+    def cost(self):
+        """The objective of the last ``compute_control`` at its solution (``BatchedOcpSolver.get_cost``): a float for a batch of
+        one, else ``(B,)``."""
+        J = self.solver.get_cost()
+        return float(J[0]) if self.B == 1 else J
+
     def warm_start(self, x0: np.ndarray, v_ref_scale: float = 1.0) -> None:
         """Replace the cold-start prediction (a car at rest at s = -6, ``python/main.py:242-246``) by a rollout of the
         model from ``x0`` under Stanley feedback -- for batches that start anywhere on the track at speed."""

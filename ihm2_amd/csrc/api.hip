@@ -1208,14 +1208,32 @@ int ihm2mpc_get_x0_sensitivities(ihm2mpc_handle *h, double *sens_x, double *sens
     return 0;
 }
 
+// the adjoint entries' refusal in the SQP mode
+static int adjoint_refused_in_sqp(const ihm2mpc_handle *h)
+{
+    if (h->cfg.nlp_solver_type == IHM2MPC_SQP)
+        return fail("adjoint sensitivities are implemented for SQP_RTI: in the SQP mode the line search scales the step and the multipliers, "
+                    "which leaves no QP solution to differentiate");
+    return 0;
+}
+
+// the handle's seed and gradient buffers of the adjoint entries for S seeds (weights: and the two gradients in the weights), grown on demand
+static int adjoint_buffers(ihm2mpc_handle *h, size_t S, bool weights)
+{
+    const size_t B = h->B, N = h->N, NS = h->NS;
+    if (h->adj_gx0.size() < B * S * NX &&
+        alloc_all(h->adj_sx, B * S * NS * NX, h->adj_su, B * S * N * NU, h->adj_gx0, B * S * NX, h->adj_gy, B * S * N * NY, h->adj_gye, B * S * NX))
+        return -1;
+    if (weights && h->adj_gW.size() < B * S * NY * NY && alloc_all(h->adj_gW, B * S * NY * NY, h->adj_gWe, B * S * NX * NX)) return -1;
+    return 0;
+}
+
 // ihm2mpc_eval_adjoint_sensitivities and ihm2mpc_eval_adjoint_sensitivities_w (weights: grad_W / grad_W_e are computed and may be asked for)
 static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0, double *grad_yref,
                         double *grad_yref_e, bool weights, double *grad_W, double *grad_W_e)
 {
     CHECK_H(h);
-    if (h->cfg.nlp_solver_type == IHM2MPC_SQP)
-        return fail("adjoint sensitivities are implemented for SQP_RTI: in the SQP mode the line search scales the step and the multipliers, "
-                    "which leaves no QP solution to differentiate");
+    if (adjoint_refused_in_sqp(h)) return -1;
     if (n_seeds < 1 || n_seeds > 8) return fail("adjoint sensitivities: n_seeds = %d, one call takes 1 to 8 seeds", n_seeds);
     const bool unit_u0 = !seed_x && !seed_u;
     if (unit_u0 && n_seeds != 2)
@@ -1223,10 +1241,7 @@ static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x
     // the factorisation is that of the x0 sensitivities: their snapshot of (xbar, ubar) must belong to the last solve
     if (sens_readable(h)) return -1;
     const size_t B = h->B, N = h->N, NS = h->NS, S = n_seeds;
-    if (h->adj_gx0.size() < B * S * NX &&
-        alloc_all(h->adj_sx, B * S * NS * NX, h->adj_su, B * S * N * NU, h->adj_gx0, B * S * NX, h->adj_gy, B * S * N * NY, h->adj_gye, B * S * NX))
-        return -1;
-    if (weights && h->adj_gW.size() < B * S * NY * NY && alloc_all(h->adj_gW, B * S * NY * NY, h->adj_gWe, B * S * NX * NX)) return -1;
+    if (adjoint_buffers(h, S, weights)) return -1;
     if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (seed_u) HIP_TRY(hipMemcpyAsync(h->adj_su, seed_u, B * S * N * NU * sizeof(double), hipMemcpyHostToDevice, h->stream));
     ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0, weights ? 1 : 0);
@@ -1250,6 +1265,70 @@ int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, con
                                          double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e)
 {
     return eval_adjoint(h, n_seeds, seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
+}
+
+// ---- the objective and its total gradient (kernels_cost.hip) ----
+// a finite side of the constraint rows carries a slack (the lateral-acceleration row: stages 1 .. N-1)
+static bool any_soft_side(const ihm2mpc_handle *h)
+{
+    const ihm2::ConstraintRows &r = h->rows;
+    for (int k = 0; k < r.NS; k++)
+        for (int c = 0; c < NC; c++)
+            if ((std::isfinite(r.lb[k * NC + c]) && r.sZ[k * NLAM + c] >= 0.0) || (std::isfinite(r.ub[k * NC + c]) && r.sZ[k * NLAM + NC + c] >= 0.0))
+                return true;
+    return r.alat_on && r.NS > 2 &&
+           ((std::isfinite(r.alat_lb) && r.alat_sZ[0] >= 0.0) || (std::isfinite(r.alat_ub) && r.alat_sZ[1] >= 0.0));
+}
+
+int ihm2mpc_eval_cost(ihm2mpc_handle *h, double *cost, double *stage_cost, double *slack_cost)
+{
+    CHECK_H(h);
+    if (ready(h)) return -1;
+    const size_t B = h->B, NS = h->NS;
+    WorkBuf<double> dwork;           // "cost_work": cost (B), slack_cost (B), stage_cost (B,NS)
+    dwork.poison(poisoned(h, "cost_work"));
+    if (dwork.alloc(B * (2 + NS)) != hipSuccess) return fail("out of device memory");
+    double *dc = dwork, *dsl = dwork + B, *dst = dwork + 2 * B;
+    ihm2_launch_cost(h, 0, dc, stage_cost ? dst : nullptr, dsl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, dc, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (stage_cost) HIP_TRY(hipMemcpyAsync(stage_cost, dst, B * NS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (slack_cost) HIP_TRY(hipMemcpyAsync(slack_cost, dsl, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                               double *grad_W_e, double *seed_x, double *seed_u)
+{
+    CHECK_H(h);
+    if (adjoint_refused_in_sqp(h)) return -1;
+    if (sens_readable(h)) return -1;
+    if (any_soft_side(h))
+        return fail("the cost gradient is defined for all-hard constraint tables: with a soft side the objective depends on slacks that the "
+                    "adjoint system has eliminated and that carry no seed (ihm2mpc_eval_cost evaluates the cost of any table)");
+    const size_t B = h->B, N = h->N, NS = h->NS;
+    if (adjoint_buffers(h, 1, true)) return -1;
+    // "cost_work": cost (B), then the explicit partials, which the epilogue turns into the totals: yref (B,N,12), yref_e (B,8), W (B,12,12), W_e (B,8,8)
+    WorkBuf<double> dwork;
+    dwork.poison(poisoned(h, "cost_work"));
+    if (dwork.alloc(B * (1 + N * NY + NX + NY * NY + NX * NX)) != hipSuccess) return fail("out of device memory");
+    double *dc = dwork, *dgy = dc + B, *dgye = dgy + B * N * NY, *dgW = dgye + B * NX, *dgWe = dgW + B * NY * NY;
+    // the seeds dJ/dz straight into the adjoint entries' seed buffers, k_adj<true> on them, the explicit partials added: no host round trip
+    ihm2_launch_cost(h, 1, dc, nullptr, nullptr, h->adj_sx, h->adj_su, dgy, dgye, dgW, dgWe);
+    ihm2_launch_adj(h, 1, h->adj_sx, h->adj_su, 0, 1);
+    ihm2_launch_cost_epilogue(h, dgy, dgye, dgW, dgWe);
+    HIP_TRY(hipGetLastError());
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, dc, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, dgy, B * N * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, dgye, B * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_W) HIP_TRY(hipMemcpyAsync(grad_W, dgW, B * NY * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, dgWe, B * NX * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (seed_x) HIP_TRY(hipMemcpyAsync(seed_x, h->adj_sx, B * NS * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (seed_u) HIP_TRY(hipMemcpyAsync(seed_u, h->adj_su, B * N * NU * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)

@@ -278,6 +278,13 @@ size_t ihm2_sens_lds_bytes(const ihm2mpc_handle *h);
 // seeds in device memory (nullptr = zero), unit_u0: the two unit seeds on u_0 instead; weights: also the gradients in W, W_e into
 // h->adj_gW, adj_gWe (the other three are the same bits either way)
 void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights);
+// kernels_cost.hip: the objective at the handle's (x, u) into cost (B), stage_cost (B,NS), slack_cost (B), each may be nullptr; grad: also
+// its seeds dJ/dz into seed_x (B,NS,8), seed_u (B,N,2) and its explicit partials in yref, yref_e, W, W_e into ex_* ((B,N,12), (B,8),
+// (B,12,12), (B,8,8); NaN for instances whose status is neither 0 nor 2).  The epilogue adds h->adj_gy, adj_gye, adj_gW, adj_gWe of one
+// seed to ex_*, in place
+void ihm2_launch_cost(ihm2mpc_handle *h, int grad, double *cost, double *stage_cost, double *slack_cost, double *seed_x, double *seed_u,
+                      double *ex_yref, double *ex_yref_e, double *ex_W, double *ex_We);
+void ihm2_launch_cost_epilogue(ihm2mpc_handle *h, double *ex_yref, double *ex_yref_e, double *ex_W, double *ex_We);
 
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'

@@ -534,6 +534,36 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_w(self._h, 2, None, None, None, None, None, _ptr(out["W"]), _ptr(out["W_e"])))
         return out
 
+    # ---- the objective and its total gradient (acados: get_cost, eval_and_get_optimal_value_gradient) ----
+    def get_cost(self, stagewise: bool = False):
+        """The objective at the current iterate (after a solve: at the returned solution), as acados documents ``get_cost`` with the
+        stage terms scaled by ``cost_scale_stage``: ``J = sum_k (c_s/2) e_k' W_k e_k + 1/2 e_N' W_e e_N`` plus the slack penalties
+        ``z s + 1/2 Z s^2`` of the soft sides.  ``(B,)``, or with ``stagewise`` the terms of the stages ``(B, N+1)``, whose sum it is.
+        Works in both solver modes, on every constraint table and at any time (``ihm2mpc_eval_cost``)."""
+        out = np.empty((self.B, self.N + 1)) if stagewise else np.empty(self.B)
+        _lib.check(self.lib.ihm2mpc_eval_cost(self._h, None if stagewise else _ptr(out), _ptr(out) if stagewise else None, None))
+        return out
+
+    def get_slack_cost(self):
+        """``(B,)``: the part of :meth:`get_cost` that comes from the slack penalties of the soft sides."""
+        out = np.empty(self.B)
+        _lib.check(self.lib.ihm2mpc_eval_cost(self._h, None, None, _ptr(out)))
+        return out
+
+    def eval_cost_gradient(self):
+        """The cost of the last RTI solve and its total derivative through the QP-solution map: ``dict(cost=(B,), x0=(B,8),
+        yref=(B,N,12), yref_e=(B,8), W=(B,12,12), W_e=(B,8,8), seed_x=(B,N+1,8), seed_u=(B,N,2))``.  ``seed_x``, ``seed_u`` are
+        ``dJ/dx_k``, ``dJ/du_k`` -- the seeds ``eval_adjoint_weight_sensitivities`` would be given -- and the five gradients are its
+        outputs for them plus the explicit partials of ``J`` (``x0``: the value-function gradient of the RTI step, no explicit part).
+        ``W`` is the derivative in a change common to all stages; ``W`` and ``W_e`` are exactly symmetric.  NaN gradients for
+        instances whose status is neither 0 nor 2.  Preconditions of ``eval_adjoint_sensitivities``; all-hard constraint tables only
+        (``ihm2mpc_eval_cost_gradient``)."""
+        B, N = self.B, self.N
+        out = dict(cost=np.empty(B), x0=np.empty((B, NX)), yref=np.empty((B, N, NY)), yref_e=np.empty((B, NX)), W=np.empty((B, NY, NY)),
+                   W_e=np.empty((B, NX, NX)), seed_x=np.empty((B, N + 1, NX)), seed_u=np.empty((B, N, NU)))
+        _lib.check(self.lib.ihm2mpc_eval_cost_gradient(self._h, *[_ptr(v) for v in out.values()]))
+        return out
+
     def du0_ds_target(self):
         """``(B,2)``: the reaction of the first control of the last solve to ``prepare_step``'s ``s_target`` -- the reference ramp puts
         ``(j / N) s_target`` into ``yref_j[0]`` and ``s_target`` into ``yref_e[0]``, so it is
@@ -806,6 +836,23 @@ class AcadosOcpSolver:
         sx, su = self._adjoint_seeds(seed_x, seed_u, "eval_adjoint_weight_sensitivity")
         g = self.batch.eval_adjoint_weight_sensitivities(sx, su)
         return g["W"][self.i].copy(), g["W_e"][self.i].copy()
+
+    def get_cost(self) -> float:
+        """acados' ``get_cost``: the objective at this instance's current iterate, stage terms scaled by ``cost_scale_stage``
+        (``BatchedOcpSolver.get_cost``)."""
+        return float(self.batch.get_cost()[self.i])
+
+    def eval_and_get_optimal_value_gradient(self, with_respect_to: str = "initial_state") -> np.ndarray:
+        """acados' ``eval_and_get_optimal_value_gradient``: ``(8,)``, the gradient of this instance's cost in the initial state.  Named
+        difference: acados differentiates the optimal value of a converged NLP, this is the derivative of the cost of the last RTI
+        step's solution through that step's QP (``BatchedOcpSolver.eval_cost_gradient``)."""
+        if with_respect_to == "p_global":
+            raise Exception("AcadosOcpSolver.eval_and_get_optimal_value_gradient(): this OCP has no p_global (the track tables are batch "
+                            "data, not parameters); with_respect_to = 'initial_state' is supported")
+        if with_respect_to != "initial_state":
+            raise Exception(f"AcadosOcpSolver.eval_and_get_optimal_value_gradient(): with_respect_to '{with_respect_to}' is not supported "
+                            "('initial_state')")
+        return self.batch.eval_cost_gradient()["x0"][self.i].copy()
 
     def get(self, stage: int, field: str) -> np.ndarray:
         if field in ("sens_x", "sens_u"):

@@ -34,6 +34,9 @@
  *   ihm2mpc_eval_adjoint_sensitivities <- solver.eval_adjoint_solution_sensitivity(seed_x, seed_u) (acados)
  *   ihm2mpc_eval_adjoint_sensitivities_w <- the same, and the gradients in the cost weights W, W_e (acados has no counterpart: one
  *                                           re-solve per weight entry and direction)
+ *   ihm2mpc_eval_cost         <- solver.get_cost() (acados), stage terms scaled by cost_scale_stage
+ *   ihm2mpc_eval_cost_gradient <- solver.eval_and_get_optimal_value_gradient("initial_state") (acados), of the RTI step's cost, and the
+ *                                 gradients of that cost in yref, yref_e, W, W_e
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -378,6 +381,40 @@ int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const
 int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
                                          double *grad_x0, double *grad_yref, double *grad_yref_e,
                                          double *grad_W, double *grad_W_e);   /* (B,n_seeds,12,12), (B,n_seeds,8,8) */
+
+/* ---- the objective and its total gradient (kernels_cost.hip) ----
+ * The objective at the handle's current (x, u) -- after a solve the returned solution z+ -- as acados documents get_cost, stage terms
+ * scaled by cost_scale_stage:
+ *     J = sum_{k<N} (c_s/2) e_k' W_k e_k + 1/2 e_N' W_e e_N + J_slack,     J_slack = sum over the soft sides of z_i s_i + 1/2 Z_i s_i^2
+ * with e_k = V z_k - yref_k (k < N), e_N = x_N - yref_e, V the 12 x 10 selector y = (x, u, x[6:8] - u), c_s the configuration's
+ * cost_scale_stage, W_k the weights as set (per-instance weights are honoured), s_i the slack values of ihm2mpc_get_slacks (and of
+ * ihm2mpc_get_alat_multipliers for the lateral-acceleration row), z_i, Z_i the penalties of ihm2mpc_set_soft /
+ * ihm2mpc_set_alat_constraint: what the merit function of the SQP mode sums at the full step.
+ * Outputs, any may be NULL: cost (B); stage_cost (B,N+1), the terms of the stages with their slack terms (cost is their sum);
+ * slack_cost (B) = J_slack.  Works on any ready handle at any time -- both solver modes, soft tables, the lateral-acceleration row,
+ * after ihm2mpc_init_guess, after ihm2mpc_run_steps -- and for every status; it reads state only and changes no output.  Every sum is
+ * taken in a fixed order: the value does not depend on the batch.  Blocking. */
+int ihm2mpc_eval_cost(ihm2mpc_handle *h, double *cost, double *stage_cost, double *slack_cost);
+/* The cost and its total derivative through the QP-solution map that ihm2mpc_eval_adjoint_sensitivities differentiates.  With
+ * t_k = W_k e_k the seeds dJ/dz_k, in the layout of ihm2mpc_eval_adjoint_sensitivities with n_seeds = 1, are
+ *     seed_z,k = c_s V' t_k  (k < N):  seed_x,k = c_s (t[0:8] + (0,..,0, t[10], t[11])),  seed_u,k = c_s (t[8:10] - t[10:12]);   seed_x,N = W_e e_N
+ * and with grad_* the outputs of ihm2mpc_eval_adjoint_sensitivities_w for those seeds
+ *     dJ/dx0 = grad_x0,     dJ/dyref_k = grad_yref_k - c_s t_k,     dJ/dyref_e = grad_yref_e - W_e e_N,
+ *     dJ/dW = grad_W + (c_s/2) sum_{k<N} e_k e_k',     dJ/dW_e = grad_W_e + 1/2 e_N e_N'
+ * -- the explicit partials of J added to the part that reaches J through the solution.  dJ/dW is the derivative in a change common to
+ * all stages, as grad_W is; dJ/dW and dJ/dW_e are exactly symmetric.  This is the derivative of the cost of the RTI step's solution, not of
+ * a converged NLP's optimal value (acados: eval_and_get_optimal_value_gradient differentiates the latter); bounds are not differentiated.
+ * The kernel writes the seeds into the adjoint entries' device buffers, the adjoint kernel runs on them and one more kernel adds the
+ * explicit partials: no host round trip.  Outputs, any may be NULL: cost (B), grad_x0 (B,8), grad_yref (B,N,12), grad_yref_e (B,8),
+ * grad_W (B,12,12), grad_W_e (B,8,8), seed_x (B,N+1,8), seed_u (B,N,2); the five gradients are NaN for instances whose status is
+ * neither 0 nor 2, cost and the seeds are plain evaluations and stay finite.  Same preconditions and refusals as
+ * ihm2mpc_eval_adjoint_sensitivities: x0 sensitivity mode 1 or 2 on for the solve; refused while the mode is off, before a solve with the
+ * mode on, after ihm2mpc_run_steps (after ihm2mpc_run_steps_sens: the last step's) and in the SQP mode; it must follow the solve directly.
+ * Refused on a handle with a soft side: J_slack depends on slacks that the adjoint system has eliminated and that carry no seed, so
+ * the gradient is defined for all-hard tables only (ihm2mpc_eval_cost takes every table).  It changes no other output, but overwrites
+ * the seed and gradient buffers of the adjoint entries, as every call of those does.  Blocking. */
+int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e,
+                               double *grad_W, double *grad_W_e, double *seed_x, double *seed_u);
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */

@@ -19,7 +19,11 @@
       the handle's x0, u0, which are restored before every call) and around ihm2mpc_sim_step_sens_device on the same pairs with every
       output NULL (the kernel alone) and with all four outputs; wall time of the two blocking host calls.  --lib PATH times a library
       that lacks the new entries (the parent's build) on the plant rows alone: ihm2mpc_sim_step's kernel is not to move.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --plant [--lib PATH]] > result.json"""
+  (g) --value: the cost and its total gradient (kernels_cost.hip) after one RTI step, B = 1024 and 8192 (--batches): wall time of the
+      blocking calls ihm2mpc_eval_cost and ihm2mpc_eval_cost_gradient with every output, HIP events around them with every output NULL
+      (the call-local allocation and the kernels; a kernel profiler run on this mode gives k_cost alone), and in the same process the
+      rows of (e), whose eight-seed call the whole gradient call is set against.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --plant [--lib PATH]] > result.json"""
 import argparse
 import ctypes
 import json
@@ -171,6 +175,54 @@ def adjoint_timings(B, steps, warmup, weights=False):
     return out
 
 
+def value_timings(B, steps, warmup):
+    """ihm2mpc_eval_cost and ihm2mpc_eval_cost_gradient after one RTI step: wall time of the whole blocking call with every output, and
+    HIP events on the handle's stream around the call with every output NULL (no download: the call-local allocation on the host, then
+    k_cost alone / k_cost<1>, k_adj<true> with one seed and k_cost_epilogue)."""
+    from ihm2_amd import _lib
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    ocp, track = bench.build_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    s.set_x0_sensitivities(1)
+    s.set_x0(bench.sample_x0(track, B, 20240607))
+    s.init_guess()
+    s.prepare_step(40.0)
+    st = s.solve()
+    stream = ctypes.c_void_p()
+    _lib.check(s.lib.ihm2mpc_get_stream(s._h, ctypes.byref(stream)))
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(ctypes.byref(e)) == 0
+    N = s.N
+    ptr = lambda a: a.ctypes.data_as(_lib.c_double_p)      # noqa: E731
+    cost_out = [np.empty(B), np.empty((B, N + 1)), np.empty(B)]
+    grad_out = [np.empty(B), np.empty((B, 8)), np.empty((B, N, 12)), np.empty((B, 8)), np.empty((B, 12, 12)), np.empty((B, 8, 8)),
+                np.empty((B, N + 1, 8)), np.empty((B, N, 2))]
+    out = {"status0": float((st == 0).mean())}
+    for name, fn, bufs in (("cost", s.lib.ihm2mpc_eval_cost, cost_out), ("gradient", s.lib.ihm2mpc_eval_cost_gradient, grad_out)):
+        wall, dev = [], []
+        for i in range(warmup + steps):
+            t0 = time.perf_counter()
+            _lib.check(fn(s._h, *[ptr(a) for a in bufs]))
+            wall.append((time.perf_counter() - t0) * 1e3)
+        for i in range(warmup + steps):
+            assert hip.hipEventRecord(ev[0], stream) == 0
+            _lib.check(fn(s._h, *[None] * len(bufs)))
+            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+            ms = ctypes.c_float()
+            assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) == 0
+            dev.append(ms.value)
+        out[name] = dict(call_wall_ms=float(np.median(wall[warmup:])), alloc_and_kernel_event_ms=float(np.median(dev[warmup:])),
+                         event_ms_spread=float(np.ptp(dev[warmup:]) / np.median(dev[warmup:])))
+    out["finite_rows"] = float(np.isfinite(grad_out[4]).all(axis=(1, 2)).mean())
+    for e in ev:
+        hip.hipEventDestroy(e)
+    s.free()
+    return out
+
+
 def plant_timings(B, steps, warmup, lib_path=None):
     from ihm2_amd import _lib
 
@@ -258,7 +310,14 @@ def main():
     ap.add_argument("--adjoint-weights", action="store_true")
     ap.add_argument("--plant", action="store_true")
     ap.add_argument("--lib", default=None, help="--plant: path of another build of libihm2mpc.so (one without the new entries times ihm2mpc_sim_step alone)")
+    ap.add_argument("--value", action="store_true")
+    ap.add_argument("--batches", default="1024,8192", help="--value: the batch sizes (one at a time under a kernel profiler)")
     a = ap.parse_args()
+    if a.value:
+        batches = [int(v) for v in a.batches.split(",")]
+        print(json.dumps({"value": {str(B): value_timings(B, a.steps, a.warmup) for B in batches},
+                          "adjoint_weights": {str(B): adjoint_timings(B, a.steps, a.warmup, True) for B in batches}}))
+        return
     if a.plant:
         print(json.dumps({"plant": {"1024": plant_timings(1024, a.steps, a.warmup, a.lib)}, "lib": a.lib or "product"}))
         return
