@@ -43,6 +43,7 @@
 #include "sens_body.hpp"
 #include "qp_lds.hpp"
 #include "qp_mrows.hpp"
+#include "qp_reduce.hpp"
 #include "qp_catalogue.hpp"
 #include "wave_sync.hpp"
 
@@ -94,6 +95,10 @@ __device__ __forceinline__ double wave_max(double v) { return wave_reduce(v, [](
 __device__ __forceinline__ double wave_min(double v) { return wave_reduce(v, [](double a, double b) { return fmin(a, b); }); }
 __device__ __forceinline__ double wave_sum(double v) { return wave_reduce(v, [](double a, double b) { return a + b; }); }
 __device__ __forceinline__ double wave_nanmax(double v) { return wave_reduce(v, [](double a, double b) { return nanmax(a, b); }); }
+// res <- max(res, v) of a norm whose NaNs must surface, in the full slot form (qp_reduce.hpp): the maximum by fmax and the NaN as a flag of the
+// lane -- a compare and a mask operation beside the chain of maxima, where nanmax puts a compare and two selects into it; the flags are
+// gathered by one ballot per norm where the norm is reduced
+__device__ __forceinline__ void norm_max(double &res, bool &bad, double v) { bad |= v != v; res = fmax(res, v); }
 
 // Sum over aligned groups of 8 consecutive lanes with DPP moves (VALU speed, no LDS crossbar):
 // quad_perm(1,0,3,2), quad_perm(2,3,0,1), row_half_mirror.  Every lane of the group gets the total.
@@ -430,7 +435,8 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         sb = fmax(sb, fabs(d));
         r_eq = fmax(r_eq, fabs(d));
     }
-    sg = blk_max(sg); sb = blk_max(sb);
+    if constexpr (FULL != 0) { double sg2 = sg, sb2 = sb; wave_max4(lane, sg, sb, sg2, sb2); }      // (both >= 1, no NaN: fmax dropped them lane by lane)
+    else { sg = blk_max(sg); sb = blk_max(sb); }
 
     // constraint slots owned by this lane
     // FULL: s_kc packs what the phases need of a slot into its one register (five more per lane tipped k_steps' allocation into scratch):
@@ -510,7 +516,10 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             if (ONE_SIDED(r) && fin(ubd)) { s_sg[r < NSOFT ? r : 0] = -1.0; s_dl[r] = -s_du[r]; }      // R z <= ub  as  -R z >= -ub
         }
     }
-    if (want_res) { r_stat = blk_max(r_stat); r_eq = blk_max(r_eq); r_ineq = blk_max(r_ineq); r_comp = blk_max(r_comp); }
+    if (want_res) {
+        if constexpr (FULL != 0) wave_max4(lane, r_stat, r_eq, r_ineq, r_comp);      // (all >= +0, no NaN)
+        else { r_stat = blk_max(r_stat); r_eq = blk_max(r_eq); r_ineq = blk_max(r_ineq); r_comp = blk_max(r_comp); }
+    }
     if (want_res && tid == 0) {
         double *rs = a.res + (size_t)b * 4;
         rs[0] = r_stat; rs[1] = r_eq; rs[2] = r_ineq; rs[3] = r_comp;
@@ -603,6 +612,10 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         }
         double mu_acc = 0.0, res_gs = 0.0;
         res_d = 0.0; res_m = 0.0;
+        // FULL: this lane's maxima over its NaN-free values are kept beside the reduced norms (the packed reduction below takes them in both passes),
+        // and whether the lane met a NaN is a flag per norm
+        double lane_d = 0.0, lane_m = 0.0;
+        bool bad_d = false, bad_m = false, bad_gs = false;
 #pragma unroll
         for (int r = 0; r < NSLOT; r++) {
             rd_l[r] = rd_u[r] = 0.0;
@@ -613,15 +626,27 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             // (the complementarity products are summed as rounded products, in slot order: the sum is then the same number whichever
             // lanes hold the slots -- one wave per instance or four, SLOT_SUM below)
             double pl = 0.0, pu = 0.0;
+            if constexpr (FULL != 0) {      // (every slot has both sides)
+                rd_l[r] = rz - t_l[r] - s_dl[r] + sv; pl = __dmul_rn(lam_l[r], t_l[r]); norm_max(lane_m, bad_m, fabs(pl));
+                rd_u[r] = s_du[r] - rz - t_u[r] + sv; pu = __dmul_rn(lam_u[r], t_u[r]); norm_max(lane_m, bad_m, fabs(pu));
+            } else {
             if (al) { rd_l[r] = rz - t_l[r] - s_dl[r] + sv; pl = __dmul_rn(lam_l[r], t_l[r]); res_m = nanmax(res_m, fabs(pl)); }
             if (au) { rd_u[r] = s_du[r] - rz - t_u[r] + sv; pu = __dmul_rn(lam_u[r], t_u[r]); res_m = nanmax(res_m, fabs(pu)); }
+            }
             mu_acc = __dadd_rn(mu_acc, __dadd_rn(pl, pu));
+            if constexpr (FULL != 0) { bad_d |= __builtin_isunordered(rd_l[r], rd_u[r]); lane_d = fmax(lane_d, fmax(fabs(rd_l[r]), fabs(rd_u[r]))); }
+            else
             res_d = nanmax(res_d, nanmax(fabs(rd_l[r]), fabs(rd_u[r])));
             if (IS_SOFT(r)) {
                 const int q = r < NSOFT ? r : 0;
                 so_rs[q] = so_Zw[q] * so_s[q] + so_zw[q] - (al ? lam_l[r] : lam_u[r]) - so_ls[q];
+                if constexpr (FULL != 0) {      // (for the form's sake: a full table has no soft slot)
+                    norm_max(res_gs, bad_gs, fabs(so_rs[q]));
+                    mu_acc += so_ls[q] * so_s[q]; norm_max(lane_m, bad_m, fabs(so_ls[q] * so_s[q]));
+                } else {
                 res_gs = nanmax(res_gs, fabs(so_rs[q]));
                 mu_acc += so_ls[q] * so_s[q]; res_m = nanmax(res_m, fabs(so_ls[q] * so_s[q]));
+                }
             }
             if (LEAN == 0) SLOT_ACC(SLOT_AT(cf, r), ROW_SIGN(r, (al ? lam_l[r] : 0.0) - (au ? lam_u[r] : 0.0)));
         }
@@ -695,9 +720,20 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 }
                 for (int e = tid; e < N * 8; e += NT) res_b = nanmax(res_b, fabs(rb[e]));
             } else { res_g = fol_g; res_b = fol_b; }        // the update that wrote the followed residuals took their norms (masked entries are stored as zeros)
+            if constexpr (FULL != 0) {
+                // the four norms in one butterfly and mu's sum beside it, straight-line in both passes (the second pass repeats res_d, res_m and mu from
+                // the same lane values: the same numbers); a NaN surfaces through the ballots exactly where nanmax let it through (qp_reduce.hpp)
+                const bool nan_g = wave_any(res_g != res_g || bad_gs), nan_b = wave_any(res_b != res_b), nan_d = wave_any(bad_d), nan_m = wave_any(bad_m);
+                res_g = fmax(res_g, res_gs);
+                res_d = lane_d; res_m = lane_m;
+                wave_max4(lane, res_g, res_b, res_d, res_m);
+                mu = wave_sum(mu_acc) * inv_m;
+                res_g = nan_g ? NAN : res_g; res_b = nan_b ? NAN : res_b; res_d = nan_d ? NAN : res_d; res_m = nan_m ? NAN : res_m;
+            } else {
             res_g = nanmax(res_g, res_gs);
             res_g = blk_nanmax(res_g); res_b = blk_nanmax(res_b);
             if (rpass == 0) { res_d = blk_nanmax(res_d); res_m = blk_nanmax(res_m); mu = ((NW == 1) ? blk_sum(mu_acc) : wave_sum(mu_acc)) * inv_m; }
+            }
             // not-a-number in the data of the QP (first pass over them): status 1; a QP that diverges on the way: a failed QP, status 4 --
             // the same two codes as the reference restatement, wherever the overflow first shows
             if (!(res_g == res_g) || !(res_b == res_b) || !(res_d == res_d) || !(res_m == res_m)) { qstatus = (it == 0) ? 3 : 4; finished = true; break; }
@@ -1038,7 +1074,8 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 /*@S:15*/
             // hard sides collect max(-dt/t), max(-dlam/lam) (>= 1 matters only); soft sides the step bounds themselves
             if (NSOFT == 0) { amax = fmin(amax, 1.0 / rmax); amax_d = fmin(amax_d, 1.0 / rmax_d); }
-            amax = blk_min(amax); amax_d = blk_min(amax_d);
+            if constexpr (FULL != 0) wave_min2(lane, amax, amax_d);      // (in [0, 1], never NaN: rmax = fmax(1, .) dropped them)
+            else { amax = blk_min(amax); amax_d = blk_min(amax_d); }
             if (pass == 0) {
                 if (a.m_act == 0) { alpha = alpha_d = 1.0; break; }
 #pragma unroll
