@@ -26,10 +26,9 @@ DIRECTIONS = tuple(EPS)
 
 def start(track, B, seed, N):
     """x0 (B,8), yref (B,N,12), yref_e (B,8): test_gpu_qp_layouts._start's."""
-    from conftest import sample_x0
+    import drive
 
-    x0 = sample_x0(track, B, seed=seed)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, seed)
     yref = np.zeros((B, N, 12)); yref[:, :, 0] = x0[:, 0:1] + S_TARGET * np.arange(N)[None] / N
     yref_e = np.zeros((B, 8)); yref_e[:, 0] = x0[:, 0] + S_TARGET
     return x0, yref, yref_e

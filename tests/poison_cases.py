@@ -221,11 +221,10 @@ QP_CASES = {c[0]: c for c in qp_cases()}
 
 def qp_start(track, lay, B, seed):
     """(x0, yref, yref_e) of tests/test_gpu_qp_layouts.py::_start."""
-    from conftest import sample_x0
+    import drive
 
     N = lay.N
-    x0 = sample_x0(track, B, seed=seed)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, seed)
     yref = np.zeros((B, N, 12)); yref[:, :, 0] = x0[:, 0:1] + 40.0 * np.arange(N)[None] / N
     yref_e = np.zeros((B, 8)); yref_e[:, 0] = x0[:, 0] + 40.0
     return x0, yref, yref_e

@@ -10,10 +10,7 @@ import conftest  # noqa: E402,F401  (puts the repository root on the path)
 
 import layouts as L  # noqa: E402
 import poison_cases as PC  # noqa: E402
-
-QP, STEPS = "k_qp_wave<5,0,0,1>", "k_steps<5,0,0,1,0,0,0>"
-# IHM2MPC_QP_FORM -> (form of the factor sweep, form of the slot phases) both launch records must report (qp_select.hpp: factor_form, slot_form; tests/test_qp_select.py runs them on this layout without a GPU)
-FORMS = {"0": ("general", "general"), "1": ("plain", "general"), "2": ("plain_n40", "general"), "unset": ("plain_n40", "full")}
+import qp_forms as QF  # noqa: E402  (the forms both launch records must report; tests/test_qp_select.py runs them on this layout without a GPU)
 
 
 def main(form):
@@ -21,6 +18,7 @@ def main(form):
     from ihm2_amd.track import track_table
 
     track = track_table("fsds_competition_1")
+    level = QF.NAMES[form]
     lay, B = PC.MISC_LAYOUT, PC.MISC_B
     x0, yref, yref_e = PC.qp_start(track, lay, B, PC.MISC_SEED)
 
@@ -42,13 +40,13 @@ def main(form):
         for _ in range(3):
             s.solve_async()
             rec = s.get_launch_record()
-            assert (rec["qp"], rec["qp_form"], rec["qp_slots"]) == (QP,) + FORMS[form], rec
+            assert (rec["qp"], rec["qp_form"], rec["qp_slots"]) == QF.qp_record(level), rec
             out.append(PC.outputs(s))
         s.step(40.0, model=0, M_sim=25)
         out.append(PC.outputs(s))
         h = s.run_steps(40.0, 3, model=0, M_sim=25, u0_hist=True, x0_hist=True, status_hist=True, qp_iter_hist=True)
         rec = s.get_launch_record()
-        assert (rec["steps"], rec["steps_form"], rec["steps_slots"]) == (STEPS,) + FORMS[form], rec
+        assert (rec["steps"], rec["steps_form"], rec["steps_slots"]) == QF.steps_record(level), rec
         out += [{"hist_" + k: v for k, v in h.items()}, PC.outputs(s)]
         return out
 

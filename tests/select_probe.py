@@ -2,16 +2,13 @@
 instantiations and of the linearisation and plant kernels, how run_steps proceeds, the line search's ladder, and the launch record) on the
 CPU.  A helper of tests/test_qp_select.py, tests/test_steps_catalogue.py, tests/test_launch_select.py and tests/test_slot_table.py: each builds the probe once, with the address and undefined-behaviour sanitizers, and reads its lines."""
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 
+import host_probe as HP
 import layouts as L
+from host_probe import ROOT  # noqa: F401  (tests/test_slot_table.py and tests/test_qp_select.py take it from here)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
-GXX = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", CSRC]
 KEY_FIELDS = ("set", "kind", "nslot", "nsoft", "path", "uni", "sqp", "irk", "dyn", "sens", "nf", "full")
 WAVE, BLOCK, STEPS = 1, 2, 3            # QpKey.kind (csrc/qp_catalogue.hpp)
 N_CU = 256                              # compute units of the MI355X
@@ -19,14 +16,12 @@ N_CU = 256                              # compute units of the MI355X
 
 def build_probe(tmp, name="check_qp_select"):
     """The sanitizer build of tools/probes/<name>.cpp in the directory tmp; returns the program's path."""
-    exe = str(tmp / name)
-    subprocess.check_call(GXX + ["-o", exe, os.path.join(ROOT, "tools", "probes", name + ".cpp")])
-    return exe
+    return HP.build(name, tmp)
 
 
 def _lines(exe, *args):
-    out = subprocess.run([exe, *args], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-4000:]
+    out = HP.run(exe, *args)
+    assert out.returncode == 0, HP.tail(out)
     return out.stdout.splitlines()
 
 

@@ -99,12 +99,12 @@ def s_target(lay) -> float:
 def start(track, case):
     """(x0, yref, yref_e) of a case: the start of tests/test_gpu_qp_layouts.py::_start, with the lead of s_target."""
     import numpy as np
-    from conftest import sample_x0
+
+    import drive
 
     N = LAYOUTS[case.layout].N
     lead = s_target(LAYOUTS[case.layout])
-    x0 = sample_x0(track, case.B, seed=case.seed)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, case.B, case.seed)
     yref = np.zeros((case.B, N, 12)); yref[:, :, 0] = x0[:, 0:1] + lead * np.arange(N)[None] / N
     yref_e = np.zeros((case.B, 8)); yref_e[:, 0] = x0[:, 0] + lead
     return x0, yref, yref_e

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import host_probe as HP
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -77,12 +79,8 @@ def test_sensitivity_factorisation_is_written_once():
 def test_lean_trig_functions_of_the_models_match_libm(tmp_path):
     """The models' sincos / tanh (csrc/model.hpp: fast_sincos, tanh_e) restated in C with the same constants and operation order:
     within 2.5e-16 absolute of libm over +-64 rad / +-200 (tools/probes/check_fast_trig.c)."""
-    import subprocess
-
     src = os.path.join(ROOT, "tools", "probes", "check_fast_trig.c")
-    exe = str(tmp_path / "check_fast_trig")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-o", exe, src, "-lm"])
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = HP.run(HP.build("check_fast_trig", tmp_path, extra=("-O2", "-ffp-contract=off", "-lm"), lang="c"))
     assert out.returncode == 0, out.stdout
     # the constants in the header are the ones the C check uses
     hdr = open(os.path.join(ROOT, "ihm2_amd", "csrc", "model.hpp")).read()
@@ -95,15 +93,9 @@ def test_qp_lds_layout_holds_its_arrays_and_its_neighbour_assumptions(tmp_path):
     """The LDS layout of the interior-point QP (csrc/qp_lds.hpp) as host C++ (tools/probes/check_qp_lds.cpp, N = 2..64, every class of the
     catalogue): arrays disjoint and in order, total and factor-sweep offsets equal to the closed forms held before, every consumer's
     reach inside the block -- except the sweeps' earlier form at N = 2, 3, which starts 60 / 24 words in front of it."""
-    import subprocess
-
-    csrc = os.path.join(ROOT, "ihm2_amd", "csrc")
-    ring = re.search(r"#define SWEEP_RING (\d+)", open(os.path.join(csrc, "kernels_qp.hip")).read()).group(1)
-    exe = str(tmp_path / "check_qp_lds")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-DSWEEP_RING=" + ring, "-I", csrc, "-o", exe,
-                           os.path.join(ROOT, "tools", "probes", "check_qp_lds.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout
+    ring = re.search(r"#define SWEEP_RING (\d+)", open(os.path.join(HP.CSRC, "kernels_qp.hip")).read()).group(1)
+    out = HP.run(HP.build("check_qp_lds", tmp_path, defines=("SWEEP_RING=" + ring,)))
+    assert HP.passed(out, "qp_lds: "), HP.tail(out)
     for path, uni in ((0, 0), (0, 1), (1, 0), (1, 1), (2, 1)):
         assert f"path {path} uni {uni} N 2: the earlier form's vector sweep reaches word -60" in out.stdout
         assert f"path {path} uni {uni} N 3: the earlier form's vector sweep reaches word -24" in out.stdout

@@ -13,16 +13,15 @@ form writes 25 entries, none of them where the dense form writes one of rows 2 a
 The probe's formulas are copies of the headers' (device code); the statements are compared with the headers' text here."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import edge_states as E
+import host_probe as HP
+from host_probe import CSRC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
-PROBE = os.path.join(ROOT, "tools", "probes", "check_fkin6_algebra.cpp")
+PROBE = os.path.join(HP.ROOT, "tools", "probes", "check_fkin6_algebra.cpp")
 
 
 def _steering_values(track):
@@ -32,11 +31,9 @@ def _steering_values(track):
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory, track):
-    exe = str(tmp_path_factory.mktemp("fkin6_algebra") / "check_fkin6_algebra")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-o", exe, PROBE])
+    exe = HP.build("check_fkin6_algebra", tmp_path_factory.mktemp("fkin6_algebra"), extra=("-ffp-contract=off",))
     values = _steering_values(track)
-    out = subprocess.run([exe] + [repr(v) for v in values], capture_output=True, text=True)
+    out = HP.run(exe, *[repr(v) for v in values])
     return out, values
 
 
@@ -49,7 +46,7 @@ def test_edge_state_steering_values_are_in_the_grid(track):
 def test_probe_passes(probe):
     out, _ = probe
     print(out.stdout[-3000:])
-    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-4000:] + out.stderr[-4000:]
+    assert HP.passed(out), HP.tail(out)
 
 
 def test_steering_block_is_no_worse_than_twice_the_earlier_form(probe):

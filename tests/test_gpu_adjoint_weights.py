@@ -12,6 +12,7 @@ from conftest import make_ocp, sample_x0
 
 import adj_ref as R
 import adjw_ref as RW
+import drive
 import layouts as L
 import sens_ref as S
 from test_gpu_adjoint import _finite_where_solved, _seeds
@@ -344,8 +345,7 @@ def test_per_instance_weights(track):
     assign = np.arange(B) % 3
     W0, We0 = O.default_weights()
     var = [(W0 * (1.0 + 0.5 * j), We0 * (1.0 + 0.25 * j)) for j in range(3)]
-    x0 = sample_x0(track, B, seed=4343)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, 4343)
     seed_x, seed_u = _seeds(B, 3, lay.N, 99)
 
     def run(s, rows):

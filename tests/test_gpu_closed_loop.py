@@ -3,6 +3,8 @@ import numpy as np
 import pytest
 from conftest import make_ocp, sample_x0
 
+import drive
+
 pytestmark = pytest.mark.gpu
 
 N = 40
@@ -196,11 +198,7 @@ def test_persistent_loop_equals_step_by_step(track, plant, n_max, B, opts, monke
             else:
                 assert rec["steps"] == LOOP_OF["nlp_solver_type" in opts, "integrator_type" in opts], rec
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(steps):
-                s.step(40.0, model=plant, M_sim=30)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 40.0, steps, model=plant, M_sim=30)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers(), s.get_sqp_stats() if "nlp_solver_type" in opts else None))
         s.free()
     (ha, xa, ua, ma, sa), (hb, xb, ub, mb, sb) = res
@@ -311,11 +309,7 @@ def test_persistent_loop_with_soft_tables_equals_step_by_step(track, variant, op
                     ("soft_track_rows", True): "k_steps<10,4,1,1,1,0,0>"}[variant, bool(opts)]
             assert s.get_launch_record()["steps"] == loop, s.get_launch_record()
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(steps):
-                s.step(40.0, model=0, M_sim=25)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 40.0, steps, model=0, M_sim=25)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers()[1], s.get_slacks()))
         s.free()
     (ha, xa, ua, la, sa), (hb, xb, ub, lb, sb) = res
@@ -425,11 +419,7 @@ def test_persistent_loop_with_collocation_soft_tables_and_radau_plants(track, na
         if persistent:
             h = s.run_steps(40.0, steps, model=plant, M_sim=M_sim, u0_hist=True, x0_hist=True, status_hist=True, qp_iter_hist=True)
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(steps):
-                s.step(40.0, model=plant, M_sim=M_sim)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 40.0, steps, model=plant, M_sim=M_sim)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers()))
         s.free()
     (ha, xa, ua, ma), (hb, xb, ub, mb) = res
@@ -480,11 +470,7 @@ def test_persistent_loop_with_the_dynamic_ocp_models(track, name, model, plant, 
         if persistent:
             h = s.run_steps(40.0, steps, model=plant, M_sim=M_sim, u0_hist=True, x0_hist=True, status_hist=True, qp_iter_hist=True)
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(steps):
-                s.step(40.0, model=plant, M_sim=M_sim)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 40.0, steps, model=plant, M_sim=M_sim)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers()))
         s.free()
     (ha, xa, ua, ma), (hb, xb, ub, mb) = res

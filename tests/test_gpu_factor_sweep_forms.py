@@ -5,15 +5,13 @@ stores through running addresses, D = 4 stages to a pass: the horizons below are
 
 The general stage without active rows (m_act == 0: the p_k stores) is what tests/test_gpu_qp_layouts.py runs on its layout "empty_table"
 (test_layout_matches_oracle_and_kkt and test_persistent_loop_equals_step_by_step_on_layout, both builds)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
-from conftest import make_ocp, sample_x0
+from conftest import make_ocp
 
+import drive
 import launch_cases as LC
+import qp_forms as QF
 
 pytestmark = pytest.mark.gpu
 
@@ -24,9 +22,7 @@ SEED_FDYN6 = 7
 
 
 def _x0(track, seed):
-    x0 = sample_x0(track, B, seed=seed)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
-    return x0
+    return drive.clipped_start(track, B, seed)
 
 
 def _rel(a, b):
@@ -92,7 +88,7 @@ def test_horizons_around_the_ring_depth(track, N, monkeypatch):
     # as tests/test_gpu_qp_layouts.py compares them there (status and iteration counts equal, the rest to 1e-9), and bit for bit on a
     # batch just past the switch, which takes the batch linearisation on both sides.
     for Bp in (B, LC.PAST_THE_SWITCH[N]):
-        xp = sample_x0(track, Bp, seed=SEEDS[N]); xp[:, 3] = np.clip(xp[:, 3], 4.0, 12.0)
+        xp = drive.clipped_start(track, Bp, SEEDS[N])
         res = []
         for persistent in (False, True):
             s = BatchedOcpSolver(ocp, Bp, track.s_ref, track.kappa_ref)
@@ -105,11 +101,7 @@ def test_horizons_around_the_ring_depth(track, N, monkeypatch):
                 rec = s.get_launch_record()
                 assert rec["steps"] == "k_steps<5,0,0,1,0,0,0>" and rec["steps_form"] == "plain"
             else:
-                h = dict(u0=[], x0=[], status=[], qp_iter=[])
-                for _ in range(2):
-                    s.step(40.0, model=-1, M_sim=30)
-                    h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-                h = {k: np.array(v) for k, v in h.items()}
+                h = drive.per_step(s, 40.0, 2, model=-1, M_sim=30)
                 rec = s.get_launch_record()
                 assert rec["qp"] == "k_qp_wave<5,0,0,1>" and rec["qp_form"] == "plain"
                 assert (rec["linearize"], rec["sim"]) == LC.names(s, plant=-1)
@@ -153,11 +145,7 @@ def test_sqp_loop_is_refused_where_its_sweeps_leave_the_lds(track, N, loop, monk
             else:
                 assert rec["steps"] == "per_step" and rec["steps_fallback"] == "no_instantiation"
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(3):
-                s.step(40.0, model=-1, M_sim=30)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 40.0, 3, model=-1, M_sim=30)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers(), s.get_sqp_stats()))
         s.free()
     (ha, xa, ua, ma, sa), (hb, xb, ub, mb, sb) = res
@@ -178,23 +166,15 @@ def test_general_form_with_the_symmetrising_tile(track, monkeypatch):
     s.free()
 
 
-def test_three_forms_give_the_same_bits_at_n40(tmp_path):
+def test_three_forms_give_the_same_bits_at_n40():
     """N = 40: the general stage, the straight-line stage and the straight-line stage with the horizon compiled in -- one process each
-    (IHM2MPC_QP_FORM is read once) -- after one solve and after three persistent steps."""
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "factor_sweep_child.py")
-    got = {}
-    for form, env_form in (("general", "0"), ("plain", "1"), ("plain_n40", None)):
-        env = dict(os.environ)
-        env.pop("IHM2MPC_QP_FORM", None)
-        if env_form is not None:
-            env["IHM2MPC_QP_FORM"] = env_form
-        out = str(tmp_path / f"{form}.npz")
-        subprocess.run([sys.executable, child, out], env=env, check=True, timeout=300)
-        got[form] = dict(np.load(out))
-        assert got[form]["kernels"].tolist() == ["k_qp_wave<5,0,0,1>", form, "k_steps<5,0,0,1,0,0,0>", form]
-    ref = got["general"]
-    assert np.all(ref["a_status"] == 0) and (ref["b_status"] == 0).mean() > 0.9
-    for form in ("plain", "plain_n40"):
-        for k, v in ref.items():
-            if k != "kernels":
-                np.testing.assert_array_equal(got[form][k], v, err_msg=f"{form}: {k}")
+    (IHM2MPC_QP_FORM is read once; tests/qp_forms.py) -- after one solve and after three persistent steps, B = 8 from the unclipped start."""
+    for level in ("0", "1", None):
+        sweep = QF.FORMS[level][0]
+        assert QF.runs(level)["sweep_kernels"].tolist() == [QF.QP, sweep, QF.STEPS, sweep]
+    ref = QF.runs("0")
+    keys = [k for k in ref if k.startswith(("sweep_a_", "sweep_b_"))]
+    assert len(keys) == 14
+    assert np.all(ref["sweep_a_status"] == 0) and (ref["sweep_b_status"] == 0).mean() > 0.9
+    for level in ("1", None):
+        QF.compare(QF.runs(level), ref, keys, what=f"{QF.FORMS[level][0]} against general")

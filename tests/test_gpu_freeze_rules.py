@@ -17,6 +17,7 @@ import dataclasses
 import numpy as np
 import pytest
 
+import drive
 import freeze_ref as F
 import steps_cases as S
 from test_gpu_steps_catalogue import _sens, _solver, _start
@@ -25,7 +26,6 @@ pytestmark = pytest.mark.gpu
 
 B = 8               # x N >= 40: 320 intervals and more, no latency batch (launch_cases.latency_batch: k_linearize_cols and the state-only plant)
 STEPS = 6
-HIST = ("u0", "x0", "status", "qp_iter")
 FAILED_CAR, NAN_CAR = 0, 1          # the cars the causes (a) and (b) are planted in; the lap rule acts among the cars 2 .. B - 1
 MASKED = (3, 6)                     # the cars a user's mask stops in test_user_mask_without_freeze
 
@@ -82,22 +82,11 @@ def _state(s, case):
     return f
 
 
-def _gain(s):
-    su = s.get_x0_sensitivities()[1]
-    return su if su.ndim == 3 else su[:, 0]
-
-
 def _per_step(s, case, n):
     """n step() calls: the histories, and the handle's state after every one of them."""
-    h = {k: [] for k in HIST + (("sens_u0",) if case.sens else ())}
     states = []
-    for _ in range(n):
-        s.step(_tgt(case), model=case.plant, M_sim=case.M_sim)
-        h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-        if case.sens:
-            h["sens_u0"].append(_gain(s))
-        states.append(_state(s, case))
-    return {k: np.array(v) for k, v in h.items()}, states
+    h = drive.per_step(s, _tgt(case), n, model=case.plant, M_sim=case.M_sim, sens=bool(case.sens), after=lambda s: states.append(_state(s, case)))
+    return h, states
 
 
 def _run(s, case, n, freeze, lap_stop=np.inf):
@@ -178,7 +167,7 @@ def _reference(track, name, build):
 
 
 def _assert_hist(got, want, msg=""):
-    assert set(got) == {k for k in want if k in HIST + ("sens_u0",)}
+    assert set(got) == {k for k in want if k in drive.HIST + ("sens_u0",)}
     for k in got:
         np.testing.assert_array_equal(got[k], want[k], err_msg=f"{msg}{k}")
 

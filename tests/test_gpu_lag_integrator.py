@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 from conftest import make_ocp, random_state, sample_x0
 
+import drive
 import lag_ref
 
 pytestmark = pytest.mark.gpu
@@ -210,11 +211,7 @@ def test_persistent_loop_equals_step_by_step(track, name, sim, M_sim, soft, monk
             else:
                 assert rec[5] == 1 and rec[11] == 2 and rec[13] == 0 and rec[10] == 0 and rec[12] == 0
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(steps):
-                s.step(10.0, model=0, M_sim=M_sim)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 10.0, steps, model=0, M_sim=M_sim)
             rec = _record(s)
             assert rec[15] & 15 == 5 and (rec[15] >> 4) & 15 == (4 if sim == "ERK_LAG" else 2)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers()))

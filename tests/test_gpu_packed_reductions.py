@@ -5,7 +5,7 @@ nanmax, and is the bit-for-bit partner: everything a solve leaves behind is equa
 runs the butterfly on software lanes.)
 
 N = 40 (the full form takes no other horizon), the reference's table.  B = 3: fewer instances than the four of a compute unit; B = 67: more
-than one block, an odd count.  One process per form (the library reads the variable once); each runs both batch sizes.
+than one block, an odd count.  One process per form (the library reads the variable once; tests/qp_forms.py); each runs both batch sizes.
 
 NaN surfacing -- instance 1 of the batch gets a NaN through a public input, and which norm it reaches:
   * yref[1, 7, 3]: the QP gradient g of stage 7, so the stationarity residual r_g of the first iterate: res_g.  Nothing else: z, the
@@ -17,67 +17,43 @@ NaN surfacing -- instance 1 of the batch gets a NaN through a public input, and 
     complementarity, taken with fmax: the NaN is dropped there, in both forms and in the oracle) -- the QP starts from its own multipliers,
     so no input reaches res_m, which is formed from lam t of the iteration's own positive values.  The solve is the clean one.
 The oracle (CPU) confirms the codes; between the forms status, qp_iter, the residuals' bit patterns and the neighbours are equal."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 from conftest import make_ocp
+
+import qp_forms as QF
 
 pytestmark = pytest.mark.gpu
 
 BATCHES = (3, 67)
 NAN_AT = 1
-QP, STEPS = "k_qp_wave<5,0,0,1>", "k_steps<5,0,0,1,0,0,0>"
-FORMS = {"2": "general", None: "full"}
-PATH_KEYS = ("status", "qp_iter", "x", "u", "pi", "lam", "qp_res", "res", "u0", "hist_u0", "hist_x0", "hist_status", "hist_qp_iter")
-SOLVE_KEYS = ("status", "qp_iter", "x", "u", "pi", "lam", "qp_res", "res", "u0")
+LEVELS = ("2", None)        # the general slot form, the bit-for-bit partner, and the full form
+PATH_KEYS, SOLVE_KEYS = QF.PATH_KEYS, QF.SOLVE_KEYS         # everything the child stores
 INPUTS = ("x", "u", "x0", "yref", "yref_e", "pi", "lam")
-
-
-@pytest.fixture(scope="module")
-def runs(tmp_path_factory):
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "packed_reductions_child.py")
-    tmp = tmp_path_factory.mktemp("packed_reductions")
-    got = {}
-    for form in FORMS:
-        env = dict(os.environ)
-        env.pop("IHM2MPC_QP_FORM", None)
-        if form is not None:
-            env["IHM2MPC_QP_FORM"] = form
-        out = str(tmp / f"form_{form}.npz")
-        subprocess.run([sys.executable, child, out] + [str(b) for b in BATCHES], env=env, check=True, timeout=300)
-        got[form] = dict(np.load(out))
-    return got
 
 
 _ORACLE = {}
 
 
-def _oracle(track, runs, B, case):
+def _oracle(track, B, case):
     """the oracle's rti_step on the inputs the child pushed, once per (B, case), left unchanged"""
     if (B, case) not in _ORACLE:
         from oracle import oracle as orc
 
         P = orc.OracleProblem(make_ocp().flatten().as_dict(track.s_ref, track.kappa_ref))
-        i = {k: runs[None][f"b{B}_{case}_in_{k}"].copy() for k in INPUTS}
+        i = {k: QF.runs(None)[f"b{B}_{case}_in_{k}"].copy() for k in INPUTS}
         out = P.rti_step(i["x"], i["u"], i["x0"], i["yref"], i["yref_e"], pi=i["pi"], lam=i["lam"])
         _ORACLE[(B, case)] = (out, i["x"], i["u"])
     return _ORACLE[(B, case)]
 
 
-def _same_bytes(a, b, msg):
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), msg
-
-
 @pytest.mark.parametrize("B", BATCHES)
-def test_the_forms_ran_and_the_solves_are_real(runs, B):
-    for form, slots in FORMS.items():
-        assert runs[form][f"b{B}_kernels"].tolist() == [QP, "plain_n40", slots, STEPS, "plain_n40", slots], form
+def test_the_forms_ran_and_the_solves_are_real(B):
+    for level in LEVELS:
+        assert QF.runs(level)[f"b{B}_kernels"].tolist() == QF.kernels(level), level
         for case in ("clean", "yref", "x0", "lam"):
-            assert runs[form][f"b{B}_{case}_kernels"].tolist() == [QP, "plain_n40", slots], (form, case)
-    ref = runs["2"]
+            assert QF.runs(level)[f"b{B}_{case}_kernels"].tolist() == list(QF.qp_record(level)), (level, case)
+    ref = QF.runs("2")
     for path in ("step", "loop"):
         st, it = ref[f"b{B}_{path}_hist_status"], ref[f"b{B}_{path}_hist_qp_iter"]
         lam = ref[f"b{B}_{path}_lam"].reshape(B, 41, 2, -1)
@@ -87,24 +63,21 @@ def test_the_forms_ran_and_the_solves_are_real(runs, B):
 
 
 @pytest.mark.parametrize("B", BATCHES)
-def test_clean_batch_gives_the_general_forms_bits(runs, B):
+def test_clean_batch_gives_the_general_forms_bits(B):
     """three step() calls and one run_steps launch of three: everything equal byte for byte, NaN payloads of failed instances included"""
-    for path in ("step", "loop"):
-        for k in PATH_KEYS:
-            name = f"b{B}_{path}_{k}"
-            _same_bytes(runs[None][name], runs["2"][name], f"full against IHM2MPC_QP_FORM=2: {name}")
+    names = [f"b{B}_{path}_{k}" for path in ("step", "loop") for k in PATH_KEYS]
+    QF.compare(QF.runs(None), QF.runs("2"), names, QF.same_bytes, what="full against IHM2MPC_QP_FORM=2")
 
 
 @pytest.mark.parametrize("B", BATCHES)
 @pytest.mark.parametrize("case", ["yref", "x0", "lam"])
-def test_a_nan_surfaces_as_before(runs, track, B, case):
-    full, gen = runs[None], runs["2"]
+def test_a_nan_surfaces_as_before(track, B, case):
+    full, gen = QF.runs(None), QF.runs("2")
     at = min(NAN_AT, B - 1)
-    for k in INPUTS:
-        _same_bytes(full[f"b{B}_{case}_in_{k}"], gen[f"b{B}_{case}_in_{k}"], f"the two processes were given different inputs: {k}")
+    QF.compare(full, gen, [f"b{B}_{case}_in_{k}" for k in INPUTS], QF.same_bytes, what="the two processes were given different inputs")
     assert np.isnan(full[f"b{B}_{case}_in_{case}"][at]).sum() == 1 and np.isnan(np.delete(full[f"b{B}_{case}_in_{case}"], at, axis=0)).sum() == 0
-    out, _, _ = _oracle(track, runs, B, case)
-    clean, _, _ = _oracle(track, runs, B, "clean")
+    out, _, _ = _oracle(track, B, case)
+    clean, _, _ = _oracle(track, B, "clean")
     st, res = gen[f"b{B}_{case}_status"], gen[f"b{B}_{case}_qp_res"]
     print(f"B {B} NaN in {case} of instance {at}: oracle status {out['status'][at]}, general form status {st[at]} qp_iter {gen[f'b{B}_{case}_qp_iter'][at]} qp_res {res[at]}")
     # the reference's codes: not-a-number in the QP's data is status 1, found in the first iteration; the neighbours solve as in the clean batch
@@ -120,20 +93,18 @@ def test_a_nan_surfaces_as_before(runs, track, B, case):
         assert nan_norms == [False, True, True, False], res[at]
     else:
         assert not any(nan_norms), res[at]
-    for k in SOLVE_KEYS:
-        name = f"b{B}_{case}_{k}"
-        _same_bytes(full[name], gen[name], f"full against IHM2MPC_QP_FORM=2: {name}")
+    QF.compare(full, gen, [f"b{B}_{case}_{k}" for k in SOLVE_KEYS], QF.same_bytes, what="full against IHM2MPC_QP_FORM=2")
     # the untouched neighbours: what the clean batch gave them, byte for byte
     for k in SOLVE_KEYS:
-        _same_bytes(np.delete(full[f"b{B}_{case}_{k}"], at, axis=0), np.delete(full[f"b{B}_clean_{k}"], at, axis=0), f"a neighbour of the NaN instance moved: {k}")
+        QF.same_bytes(np.delete(full[f"b{B}_{case}_{k}"], at, axis=0), np.delete(full[f"b{B}_clean_{k}"], at, axis=0), f"a neighbour of the NaN instance moved: {k}")
 
 
-def test_full_form_against_the_oracle(runs, track):
+def test_full_form_against_the_oracle(track):
     """B = 3, one solve from the oracle's own inputs: status and qp_iter equal, x and u to 1e-9 (the tolerance of tests/test_gpu_slot_forms.py),
     with an active box and an active rate row in the oracle's solution"""
     B = BATCHES[0]
-    out, x, u = _oracle(track, runs, B, "clean")
-    got = runs[None]
+    out, x, u = _oracle(track, B, "clean")
+    got = QF.runs(None)
     lam = out["lam"].reshape(B, 41, 2, -1)
     assert np.any(out["status"] == 0) and lam[..., 10:12].max() > 1e-3 and lam[..., 0:10].max() > 1e-3, "a solved instance, an active rate row and an active box"
     np.testing.assert_array_equal(got[f"b{B}_clean_status"], out["status"])

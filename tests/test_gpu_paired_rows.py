@@ -6,50 +6,31 @@ run_steps launch of three steps.  (tests/test_qp_mrows.py walks the offsets on t
 
 N = 40, because the paired forms take no other horizon.  B = 3: fewer instances than a lane group, the first instance's backward prefetch
 runs into the padding in front of the workspace and the last one's forward prefetch into the padding behind it; B = 67: more than one
-block per compute unit's four, an odd count.  The start is that of tests/slot_forms_child.py (rate rows and boxes active, most solves
+block per compute unit's four, an odd count.  The start is the clipped one of tests/qp_forms_child.py (rate rows and boxes active, most solves
 converge in 7 to 12 iterations), asserted below on what was run.
 
-One process per form (the library reads the variable once); each runs both batch sizes."""
-import os
-import subprocess
-import sys
-
+One process per form (the library reads the variable once; tests/qp_forms.py); each runs both batch sizes."""
 import numpy as np
 import pytest
-from conftest import make_ocp, sample_x0
+from conftest import make_ocp
+
+import drive
+import qp_forms as QF
+from qp_forms import QP, STEPS
 
 pytestmark = pytest.mark.gpu
 
 BATCHES = (3, 67)
-QP, STEPS = "k_qp_wave<5,0,0,1>", "k_steps<5,0,0,1,0,0,0>"
-# IHM2MPC_QP_FORM -> (form of the factor sweep, form of the slot phases) of both launch records (tests/poison_child.py: FORMS)
-FORMS = {"0": ("general", "general"), "1": ("plain", "general"), "2": ("plain_n40", "general"), None: ("plain_n40", "full")}
 PAIRED, STAGE_MAJOR = (None, "2"), ("1", "0")
 KEYS = ("status", "qp_iter", "x", "u", "pi", "lam", "hist_u0", "hist_x0", "hist_status", "hist_qp_iter")
 OPEN = (17, 3)      # the row of tests/test_gpu_slot_forms.py whose upper side the last case takes away
 
 
-@pytest.fixture(scope="module")
-def runs(tmp_path_factory):
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "paired_rows_child.py")
-    tmp = tmp_path_factory.mktemp("paired_rows")
-    got = {}
-    for form in FORMS:
-        env = dict(os.environ)
-        env.pop("IHM2MPC_QP_FORM", None)
-        if form is not None:
-            env["IHM2MPC_QP_FORM"] = form
-        out = str(tmp / f"form_{form}.npz")
-        subprocess.run([sys.executable, child, out] + [str(b) for b in BATCHES], env=env, check=True, timeout=300)
-        got[form] = dict(np.load(out))
-    return got
-
-
 @pytest.mark.parametrize("B", BATCHES)
-def test_the_forms_ran_and_the_solves_are_real(runs, B):
-    for form, (sweep, slots) in FORMS.items():
-        assert runs[form][f"b{B}_kernels"].tolist() == [QP, sweep, slots, STEPS, sweep, slots], form
-    ref = runs["0"]
+def test_the_forms_ran_and_the_solves_are_real(B):
+    for level in QF.FORMS:
+        assert QF.runs(level)[f"b{B}_kernels"].tolist() == QF.kernels(level), level
+    ref = QF.runs("0")
     for path in ("step", "loop"):
         st, it = ref[f"b{B}_{path}_hist_status"], ref[f"b{B}_{path}_hist_qp_iter"]
         lam = ref[f"b{B}_{path}_lam"].reshape(B, 41, 2, -1)
@@ -61,11 +42,9 @@ def test_the_forms_ran_and_the_solves_are_real(runs, B):
 @pytest.mark.parametrize("B", BATCHES)
 @pytest.mark.parametrize("paired", PAIRED, ids=["full_slots", "general_slots"])
 @pytest.mark.parametrize("stage_major", STAGE_MAJOR, ids=["plain", "general_sweep"])
-def test_paired_rows_give_the_stage_major_bits(runs, B, paired, stage_major):
-    for path in ("step", "loop"):
-        for k in KEYS:
-            name = f"b{B}_{path}_{k}"
-            np.testing.assert_array_equal(runs[paired][name], runs[stage_major][name], err_msg=f"IHM2MPC_QP_FORM {paired} against {stage_major}: {name}")
+def test_paired_rows_give_the_stage_major_bits(B, paired, stage_major):
+    names = [f"b{B}_{path}_{k}" for path in ("step", "loop") for k in KEYS]
+    QF.compare(QF.runs(paired), QF.runs(stage_major), names, what=f"IHM2MPC_QP_FORM {paired} against {stage_major}")
 
 
 def test_a_table_that_is_not_full_takes_the_paired_general_slot_kernel(track, monkeypatch):
@@ -79,8 +58,7 @@ def test_a_table_that_is_not_full_takes_the_paired_general_slot_kernel(track, mo
     monkeypatch.delenv("IHM2MPC_QP_FORM", raising=False)
     s = BatchedOcpSolver(make_ocp(), B, track.s_ref, track.kappa_ref)
     s.set_lap_wrap(True)
-    x0 = sample_x0(track, B, seed=0)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, 0)
 
     def solve(slots):
         s.set_x0(x0); s.init_guess()

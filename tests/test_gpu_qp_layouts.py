@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 from conftest import sample_x0
 
+import drive
 import launch_cases as LC
 import layouts as L
 
@@ -79,8 +80,7 @@ def _solver(track, lay, B, build, block="1"):
 
 
 def _start(s, track, B, seed):
-    x0 = sample_x0(track, B, seed=seed)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, seed)
     s.set_x0(x0); s.init_guess()
     N = s.N
     yref = np.zeros((B, N, 12)); yref[:, :, 0] = x0[:, 0:1] + 40.0 * np.arange(N)[None] / N
@@ -196,11 +196,7 @@ def test_persistent_loop_equals_step_by_step_on_layout(track, name, build):
             RECORDS.add((build, rec["steps"] if rec["steps"] != "per_step" else "per_step:" + rec["steps_fallback"]))
             assert rec["steps"] is not None
         else:
-            h = dict(u0=[], x0=[], status=[], qp_iter=[])
-            for _ in range(steps):
-                s.step(40.0, model=0, M_sim=25)
-                h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            h = {k: np.array(v) for k, v in h.items()}
+            h = drive.per_step(s, 40.0, steps, model=0, M_sim=25)
         res.append((h, s.get_x(), s.get_u(), s.get_multipliers(), s.get_slacks()))
         s.free()
     (ha, xa, ua, ma, sa), (hb, xb, ub, mb, sb) = res
@@ -254,8 +250,7 @@ def test_instance_bounds_on_layout_equal_homogeneous_handles(track, name, build)
             out.append(dict(x=s.get_x(), u=s.get_u(), pi=pi, lam=lam, slk=s.get_slacks(), status=st, qp_iter=s.get_qp_iter()))
         return out
 
-    x0 = sample_x0(track, B, seed=4242)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, 4242)
     s = _solver(track, lay, B, build, "0")
     per = {n: np.stack([var[assign[b]][n] for b in range(B)]) for n in var[0]}
     s.set_instance_bounds(**per)

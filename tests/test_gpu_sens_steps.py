@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 from conftest import make_ocp, sample_x0
 
+import drive
 import launch_cases as LC
 
 from test_gpu_qp_layouts import TABLE, _solver, _start
@@ -14,27 +15,13 @@ pytestmark = pytest.mark.gpu
 IRK = dict(integrator_type="IRK", sim_method_num_steps=1)                                              # python/main.py:234-236
 
 
-def _gain(s):
-    _, su = s.get_x0_sensitivities()
-    return su if su.ndim == 3 else su[:, 0]
-
-
-def _step_by_step(s, steps, plant, M_sim):
-    h = dict(u0=[], x0=[], status=[], qp_iter=[], sens_u0=[])
-    for _ in range(steps):
-        s.step(40.0, model=plant, M_sim=M_sim)
-        h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-        h["sens_u0"].append(_gain(s))
-    return {k: np.array(v) for k, v in h.items()}
-
-
 def _final(s, mode):
     pi, lam = s.get_multipliers()
     out = dict(x=s.get_x(), u=s.get_u(), pi=pi, lam=lam, slk=s.get_slacks())
     if mode == 2:
         out["sens_x"], out["sens_u"] = s.get_x0_sensitivities()
     else:
-        out["sens_u0"] = _gain(s)
+        out["sens_u0"] = drive.gain(s)
     return out
 
 
@@ -64,7 +51,7 @@ def test_gain_history_equals_step_by_step(track, plant, n_max, B, opts, mode, mo
             else:
                 assert rec.startswith("k_steps<") and rec.endswith(",1>") and rec.count(",") == 7, rec
         else:
-            h = _step_by_step(s, steps, plant, 30)
+            h = drive.per_step(s, 40.0, steps, model=plant, M_sim=30, sens=True)
         res.append((h, _final(s, mode)))
         s.free()
     (ha, fa), (hb, fb) = res
@@ -145,7 +132,7 @@ def test_gain_history_on_layout(track, name, build):
         if persistent:
             h = s.run_steps(40.0, steps, model=0, M_sim=25, status_hist=True, sens_u0_hist=True)
         else:
-            h = _step_by_step(s, steps, 0, 25)
+            h = drive.per_step(s, 40.0, steps, model=0, M_sim=25, sens=True)
         sx, su = s.get_x0_sensitivities()
         res.append((h["status"], h["sens_u0"], sx, su))
         if not persistent:
@@ -270,7 +257,7 @@ def test_gain_history_without_waiting_and_in_pieces(track):
             s.synchronize()
         else:
             s.run_steps(40.0, n1 + n2, sens_u0_hist=k)
-        out.append((np.array(k), _gain(s)))
+        out.append((np.array(k), drive.gain(s)))
         s.free()
     for a, b in zip(*out):
         np.testing.assert_array_equal(a, b)

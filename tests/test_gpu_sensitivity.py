@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 from conftest import make_ocp, sample_x0
 
+import drive
 import layouts as L
 import sens_ref as S
 from test_gpu_qp_layouts import TABLE, _solver, _start, _widen
@@ -148,8 +149,7 @@ def test_per_instance_weights_and_bounds(track):
     for j, f in enumerate(facs):
         v = {n: np.where(np.abs(arr[n]) < L.BIG, arr[n] * f, arr[n]) for n in ("lbx", "ubx", "lbu", "ubu", "lg", "ug")}
         var.append((v, W0 * (1.0 + 0.5 * j), We0 * (1.0 + 0.25 * j)))
-    x0 = sample_x0(track, B, seed=4343)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
+    x0 = drive.clipped_start(track, B, 4343)
 
     def run(s, x0s):
         s.set_x0_sensitivities(2)

@@ -15,28 +15,25 @@ a shared table that has the infinite side itself.
 tests/test_gpu_factor_sweep_forms.py is unchanged: its "plain_n40" leg (environment unset) now runs the full slot form, which reports the
 same qp_form.  The general-slot kernels with the horizon compiled in are compared here, IHM2MPC_QP_FORM=2 against the full form, and there
 the full form against the general factor sweep."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
-from conftest import make_ocp, sample_x0
+from conftest import make_ocp
+
+import drive
+import qp_forms as QF
+from qp_forms import QP, STEPS
 
 pytestmark = pytest.mark.gpu
 
 B = 8
 SEED_PLAIN, SEED_ACTIVE = 0, 1
-QP, STEPS = "k_qp_wave<5,0,0,1>", "k_steps<5,0,0,1,0,0,0>"
 # the row whose upper side the fallback cases take away: v_x of stage 17 (far from the iterate: the solution is that of the full table
 # to rounding, the table is not full)
 OPEN = (17, 3)
 
 
 def _x0(track, seed):
-    x0 = sample_x0(track, B, seed=seed)
-    x0[:, 3] = np.clip(x0[:, 3], 4.0, 12.0)
-    return x0
+    return drive.clipped_start(track, B, seed)
 
 
 def _rel(a, b):
@@ -150,30 +147,20 @@ def test_per_instance_bounds(track, monkeypatch):
     s.free()
 
 
-def test_forms_give_the_same_bits(tmp_path):
+def test_forms_give_the_same_bits():
     """Three control steps through step() and the same three in one run_steps launch, in the full form and in the general slot form
     (IHM2MPC_QP_FORM=2: the straight-line factor sweep with the horizon compiled in, the default before the full form) -- one process
-    each, the variable is read once.  Between the forms everything is equal byte for byte; inside a form the two paths are too: B N = 320
-    is no latency batch (tests/launch_cases.py), which step() linearises and whose plant it integrates with other kernels than the loop
-    (tests/test_gpu_factor_sweep_forms.py, tests/test_gpu_qp_layouts.py: KNOWN DIFFERENCE)."""
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "slot_forms_child.py")
-    got = {}
-    for slots, env_form in (("general", "2"), ("full", None)):
-        env = dict(os.environ)
-        env.pop("IHM2MPC_QP_FORM", None)
-        if env_form is not None:
-            env["IHM2MPC_QP_FORM"] = env_form
-        out = str(tmp_path / f"{slots}.npz")
-        subprocess.run([sys.executable, child, out], env=env, check=True, timeout=300)
-        got[slots] = dict(np.load(out))
-        assert got[slots]["kernels"].tolist() == [QP, "plain_n40", slots, STEPS, "plain_n40", slots]
-    ref = got["general"]
-    keys = ("x", "u", "pi", "lam", "slk", "qp_iter", "status", "qp_res", "u0", "hist_u0", "hist_x0", "hist_status", "hist_qp_iter")
-    assert sorted(ref) == sorted([f"{p}_{k}" for p in ("step", "loop") for k in keys] + ["kernels"])
-    assert (ref["step_hist_status"] == 0).mean() > 0.9
-    for k, v in ref.items():
-        if k != "kernels":
-            np.testing.assert_array_equal(got["full"][k], v, err_msg=f"full against general: {k}")
-    for slots in got:
-        for k in keys:
-            np.testing.assert_array_equal(got[slots][f"step_{k}"], got[slots][f"loop_{k}"], err_msg=f"{slots}: step() against run_steps: {k}")
+    each, the variable is read once (tests/qp_forms.py).  Between the forms everything is equal byte for byte; inside a form the two paths
+    are equal too: B N = 320 is no latency batch (tests/launch_cases.py), which step() linearises and whose plant it integrates with other
+    kernels than the loop (tests/test_gpu_factor_sweep_forms.py, tests/test_gpu_qp_layouts.py: KNOWN DIFFERENCE)."""
+    got = {level: QF.runs(level) for level in ("2", None)}
+    for level, run in got.items():
+        assert run[f"b{B}_kernels"].tolist() == QF.kernels(level)
+    ref = got["2"]
+    keys = [f"b{B}_{p}_{k}" for p in ("step", "loop") for k in QF.PATH_KEYS]
+    assert sorted(k for k in ref if k.startswith(f"b{B}_")) == sorted(keys + [f"b{B}_kernels"])
+    assert (ref[f"b{B}_step_hist_status"] == 0).mean() > 0.9
+    QF.compare(got[None], ref, keys, QF.same_bytes, what="full against general")
+    paths = [(f"b{B}_step_{k}", f"b{B}_loop_{k}") for k in QF.PATH_KEYS if k != "res"]         # (the NLP residuals: between the forms only)
+    for level, run in got.items():
+        QF.compare(run, run, paths, what=f"{QF.FORMS[level][1]}: step() against run_steps")

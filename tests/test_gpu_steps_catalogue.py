@@ -12,6 +12,7 @@ batches sums in another order."""
 import numpy as np
 import pytest
 
+import drive
 import layouts as L
 import steps_cases as S
 from test_gpu_configs import _build
@@ -69,16 +70,7 @@ def _closed_loop(track, case, build, persistent, **more):
                         sens_u0_hist=True if case.sens else None)
         rec = s.get_launch_record()
     else:
-        h = dict(u0=[], x0=[], status=[], qp_iter=[], sens_u0=[])
-        for _ in range(STEPS):
-            s.step(tgt, model=case.plant, M_sim=case.M_sim)
-            h["u0"].append(s.get_u0()); h["x0"].append(s.get_x0()); h["status"].append(s.get_status()); h["qp_iter"].append(s.get_qp_iter())
-            if case.sens:
-                su = s.get_x0_sensitivities()[1]
-                h["sens_u0"].append(su if su.ndim == 3 else su[:, 0])
-        if not case.sens:
-            del h["sens_u0"]
-        h = {k: np.array(v) for k, v in h.items()}
+        h = drive.per_step(s, tgt, STEPS, model=case.plant, M_sim=case.M_sim, sens=bool(case.sens))
     pi, lam = s.get_multipliers()
     f = dict(x=s.get_x(), u=s.get_u(), pi=pi, lam=lam, slk=s.get_slacks())
     if lay.alat:

@@ -24,6 +24,7 @@ import pytest
 import launch_cases as LC
 import layouts as L
 import poison_cases as PC
+import qp_forms as QF
 import steps_cases as S
 from test_gpu_configs import _build
 from test_gpu_qp_layouts import EXPECTED_QP
@@ -140,13 +141,10 @@ def test_persistent_loop(track, name, build):
 
 # ---- the forms of the factor sweep and the slot phases: IHM2MPC_QP_FORM is read once per process ----
 
-@pytest.mark.parametrize("form", ["0", "1", "2", "unset"])
+@pytest.mark.parametrize("form", list(QF.NAMES))
 def test_qp_forms(form):
     """The reference layout at N = 40 (poison_child.py: three solves, a step and a persistent run on a poisoned and a clean handle)."""
-    env = dict(os.environ)
-    env.pop("IHM2MPC_QP_FORM", None)           # (IHM2MPC_POISON_WORKSPACE, if the caller narrows it to a list of buffers, goes through)
-    if form != "unset":
-        env["IHM2MPC_QP_FORM"] = form
+    env = QF.environ(QF.NAMES[form])           # (IHM2MPC_POISON_WORKSPACE, if the caller narrows it to a list of buffers, goes through)
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "poison_child.py")
     r = subprocess.run([sys.executable, child, form], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

@@ -4,20 +4,15 @@ every even horizon in 2..64, and checks that the offset functions refuse the odd
 are built with, read from their sources."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
+import host_probe as HP
 
 
 def test_paired_rows_layout(tmp_path):
-    ring = re.search(r"#define SWEEP_RING (\d+)", open(os.path.join(CSRC, "kernels_qp.hip")).read()).group(1)
-    pad = re.search(r"#define QM_PAD (\d+)", open(os.path.join(CSRC, "ihm2mpc_internal.h")).read()).group(1)
-    exe = str(tmp_path / "check_qp_mrows")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-DSWEEP_RING=" + ring, "-DQM_PAD=" + pad, "-I", CSRC, "-o", exe, os.path.join(ROOT, "tools", "probes", "check_qp_mrows.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and out.stdout.splitlines()[-1] == "all checks passed", out.stdout[-4000:] + out.stderr[-4000:]
+    ring = re.search(r"#define SWEEP_RING (\d+)", open(os.path.join(HP.CSRC, "kernels_qp.hip")).read()).group(1)
+    pad = re.search(r"#define QM_PAD (\d+)", open(os.path.join(HP.CSRC, "ihm2mpc_internal.h")).read()).group(1)
+    out = HP.run(HP.build("check_qp_mrows", tmp_path, defines=("SWEEP_RING=" + ring, "QM_PAD=" + pad)))
+    assert HP.passed(out), HP.tail(out)
     # the shipped case: N = 40 fetches 4 pair rows (8 stage rows) past either end of the block, inside the padding
     m = re.search(r"N 40 ring %s: fetches \[(-?\d+), (\d+)\) of a block of 20480 bytes, padding (\d+)" % ring, out.stdout)
     assert m and -int(m.group(3)) <= int(m.group(1)) < 0 and 20480 < int(m.group(2)) <= 20480 + int(m.group(3)), out.stdout

@@ -2,7 +2,7 @@
 tools/probes/check_qp_select.cpp.  The expectations are the tables the GPU tests assert on hardware -- a wrong choice gives the same
 results there, only slower, so the choice is tested here as well:
 
-* the forms of the factor sweep and the slot phases under IHM2MPC_QP_FORM, as tests/poison_child.py lists them for both records;
+* the forms of the factor sweep and the slot phases under IHM2MPC_QP_FORM, as tests/qp_forms.py lists them for both records;
 * the per-step QP of every layout of tests/layouts.py (tests/test_slot_table.py: NAMED_FOR), and the four-wave kernel's conditions as
   tests/test_gpu_closed_loop.py and tests/test_gpu_qp_layouts.py see them;
 * the record of every key of the catalogue, and of every linearisation and plant kernel, through BatchedOcpSolver's decoder.
@@ -15,7 +15,7 @@ import pytest
 
 import layouts as L
 import poison_cases as PC
-import poison_child
+import qp_forms as QF
 import select_probe as P
 import steps_cases as S
 from ihm2_amd.solver import decode_launch_record
@@ -37,7 +37,7 @@ def _records(probe, jobs):
 
 # ---- forms under the switch ----
 
-QP_FORMS = {"0": 0, "1": 1, "2": 2, "unset": 3}         # the switch's value as tests/poison_child.py names it -> QpSituation.qp_form
+QP_FORMS = QF.SITUATION          # the switch's level -> QpSituation.qp_form
 
 
 def _both(rec):
@@ -50,14 +50,14 @@ def test_forms_of_the_reference_layout_under_the_switch(probe):
     assert lay.N == 40
     recs = _records(probe, [(lay, P.Facts(B=PC.MISC_B, block_qp=False, qp_form=f)) for f in QP_FORMS.values()])
     for form, rec in zip(QP_FORMS, recs):
-        assert _both(rec) == ((poison_child.QP,) + poison_child.FORMS[form], (poison_child.STEPS,) + poison_child.FORMS[form]), (form, rec)
+        assert _both(rec) == (QF.qp_record(form), QF.steps_record(form)), (form, rec)
 
 
 def test_fdyn6_stays_on_the_general_form(probe):
     """The dynamic model as written needs the symmetrising tile, which the straight-line stage does not keep."""
     recs = _records(probe, [(PC.MISC_LAYOUT, P.Facts(model=1, B=PC.MISC_B, block_qp=False, qp_form=f)) for f in QP_FORMS.values()])
     for rec in recs:
-        assert _both(rec) == ((poison_child.QP, "general", "general"), ("k_steps<5,0,0,1,0,0,1>", "general", "general")), rec
+        assert _both(rec) == ((QF.QP, "general", "general"), ("k_steps<5,0,0,1,0,0,1>", "general", "general")), rec
 
 
 def test_other_horizons_take_the_run_time_form(probe):
@@ -66,7 +66,7 @@ def test_other_horizons_take_the_run_time_form(probe):
     recs = _records(probe, [(lay, P.Facts(B=PC.MISC_B, block_qp=False, qp_form=f)) for f in QP_FORMS.values()])
     for form, rec in zip(QP_FORMS, recs):
         want = ("general", "general") if form == "0" else ("plain", "general")
-        assert _both(rec) == ((poison_child.QP,) + want, (poison_child.STEPS,) + want), (form, rec)
+        assert _both(rec) == ((QF.QP,) + want, (QF.STEPS,) + want), (form, rec)
 
 
 # ---- the per-step QP ----

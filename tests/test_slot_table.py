@@ -10,10 +10,10 @@ digests against tests/golden/slot_tables.json -- recorded from the tables the li
 header (tests/golden/make_slot_tables.py), so they pin the entry order every bit of the QP's results depends on."""
 import json
 import os
-import subprocess
 
 import pytest
 
+import host_probe as HP
 import layouts as L
 import select_probe as P
 from select_probe import ROOT, problem_text
@@ -62,8 +62,8 @@ def tables(tmp_path_factory):
         files.append(str(tmp / (name + ".txt")))
         with open(files[-1], "w") as f:
             f.write(problem_text(lay))
-    out = subprocess.run([exe] + files, capture_output=True, text=True)
-    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-4000:] + out.stderr[-4000:]
+    out = HP.run(exe, *files)
+    assert HP.passed(out, "slot tables: "), HP.tail(out)
     res = {}
     for line in out.stdout.splitlines()[:len(files)]:
         name, fit, per_lane, nsoft, total, m_act, digest = line.split()

@@ -5,13 +5,9 @@ undefined-behaviour sanitizers, lays the reference's rows out through the functi
 The kernel asks nothing about a slot in that form, so the predicate has to: the reference's rows are full at N = 40 (8 N = 64 x 5 two-sided
 rows) and at no other horizon, and one infinite side anywhere -- in the shared table or in one instance's bounds -- a soft side or a track
 row takes the form away."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
+import host_probe as HP
 
 # case -> (full, slots per lane, rows in the table)
 EXPECTED = {
@@ -31,11 +27,8 @@ EXPECTED = {
 
 @pytest.fixture(scope="module")
 def cases(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("full_table") / "check_full_table")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tools", "probes", "check_full_table.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and out.stdout.splitlines()[-1] == "all checks passed", out.stdout[-4000:] + out.stderr[-4000:]
+    out = HP.run(HP.build("check_full_table", tmp_path_factory.mktemp("full_table")))
+    assert HP.passed(out), HP.tail(out)
     res = {}
     for line in out.stdout.splitlines()[:-1]:
         name, full, per_lane, total = line.split()
