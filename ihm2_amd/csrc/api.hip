@@ -1228,14 +1228,16 @@ static int adjoint_buffers(ihm2mpc_handle *h, size_t S, bool weights)
     return 0;
 }
 
-// ihm2mpc_eval_adjoint_sensitivities and ihm2mpc_eval_adjoint_sensitivities_w (weights: grad_W / grad_W_e are computed and may be asked for)
-static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0, double *grad_yref,
-                        double *grad_yref_e, bool weights, double *grad_W, double *grad_W_e)
+// ihm2mpc_eval_adjoint_sensitivities, ihm2mpc_eval_adjoint_sensitivities_w (weights: grad_W / grad_W_e are computed and may be asked for) and
+// ihm2mpc_eval_adjoint_sensitivities_s (seed_s / seed_sa: seeds on the soft slacks, folded onto the stage seeds by k_slack_fold first)
+static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, const double *seed_s, const double *seed_sa,
+                        double *grad_x0, double *grad_yref, double *grad_yref_e, bool weights, double *grad_W, double *grad_W_e)
 {
     CHECK_H(h);
     if (adjoint_refused_in_sqp(h)) return -1;
     if (n_seeds < 1 || n_seeds > 8) return fail("adjoint sensitivities: n_seeds = %d, one call takes 1 to 8 seeds", n_seeds);
-    const bool unit_u0 = !seed_x && !seed_u;
+    const bool slack = seed_s || seed_sa;
+    const bool unit_u0 = !seed_x && !seed_u && !slack;
     if (unit_u0 && n_seeds != 2)
         return fail("adjoint sensitivities: seed_x and seed_u both NULL stands for the two unit seeds on u_0 and needs n_seeds = 2, not %d", n_seeds);
     // the factorisation is that of the x0 sensitivities: their snapshot of (xbar, ubar) must belong to the last solve
@@ -1244,27 +1246,48 @@ static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x
     if (adjoint_buffers(h, S, weights)) return -1;
     if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (seed_u) HIP_TRY(hipMemcpyAsync(h->adj_su, seed_u, B * S * N * NU * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0, weights ? 1 : 0);
+    WorkBuf<double> slack_seed_work;    // "slack_seed_work": seed_s (B,S,NS,28), then seed_sa (B,S,NS,2); the part of a NULL seed is not read
+    if (slack) {
+        slack_seed_work.poison(poisoned(h, "slack_seed_work"));
+        if (slack_seed_work.alloc(B * S * NS * (NLAM + 2)) != hipSuccess) return fail("out of device memory");
+        double *ds = slack_seed_work, *dsa = ds + B * S * NS * NLAM;
+        if (seed_s) HIP_TRY(hipMemcpyAsync(ds, seed_s, B * S * NS * NLAM * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (seed_sa) HIP_TRY(hipMemcpyAsync(dsa, seed_sa, B * S * NS * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        // the fold adds to the stage seeds: a NULL one is zero first
+        if (!seed_x) HIP_TRY(hipMemsetAsync(h->adj_sx, 0, B * S * NS * NX * sizeof(double), h->stream));
+        if (!seed_u) HIP_TRY(hipMemsetAsync(h->adj_su, 0, B * S * N * NU * sizeof(double), h->stream));
+        ihm2_launch_slack_fold(h, 0, n_seeds, seed_s ? ds : nullptr, seed_sa ? dsa : nullptr, h->adj_sx, h->adj_su);
+        ihm2_launch_adj(h, n_seeds, h->adj_sx, h->adj_su, 0, weights ? 1 : 0);
+    } else {
+        ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0, weights ? 1 : 0);
+    }
     HIP_TRY(hipGetLastError());
     if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, h->adj_gy, B * S * N * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, h->adj_gye, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_W) HIP_TRY(hipMemcpyAsync(grad_W, h->adj_gW, B * S * NY * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, h->adj_gWe, B * S * NX * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));      // the seeds may be reused and the gradients read as soon as we return
+    HIP_TRY(hipStreamSynchronize(h->stream));      // the seeds may be reused and the gradients read as soon as we return; slack_seed_work is released behind it
     return 0;
 }
 
 int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0,
                                        double *grad_yref, double *grad_yref_e)
 {
-    return eval_adjoint(h, n_seeds, seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, false, nullptr, nullptr);
+    return eval_adjoint(h, n_seeds, seed_x, seed_u, nullptr, nullptr, grad_x0, grad_yref, grad_yref_e, false, nullptr, nullptr);
 }
 
 int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, double *grad_x0,
                                          double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e)
 {
-    return eval_adjoint(h, n_seeds, seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
+    return eval_adjoint(h, n_seeds, seed_x, seed_u, nullptr, nullptr, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
+}
+
+int ihm2mpc_eval_adjoint_sensitivities_s(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, const double *seed_s,
+                                         const double *seed_sa, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                                         double *grad_W_e)
+{
+    return eval_adjoint(h, n_seeds, seed_x, seed_u, seed_s, seed_sa, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
 }
 
 // ---- the objective and its total gradient (kernels_cost.hip) ----
@@ -1298,13 +1321,16 @@ int ihm2mpc_eval_cost(ihm2mpc_handle *h, double *cost, double *stage_cost, doubl
     return 0;
 }
 
-int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
-                               double *grad_W_e, double *seed_x, double *seed_u)
+// ihm2mpc_eval_cost_gradient and ihm2mpc_eval_cost_gradient_soft (soft: every table is taken, and on one with a soft side k_slack_fold<true>
+// carries dJ_slack/ds onto the seeds between the cost kernel and the adjoint)
+static int eval_cost_gradient(ihm2mpc_handle *h, bool soft, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                              double *grad_W_e, double *seed_x, double *seed_u)
 {
     CHECK_H(h);
     if (adjoint_refused_in_sqp(h)) return -1;
     if (sens_readable(h)) return -1;
-    if (any_soft_side(h))
+    const bool fold = any_soft_side(h);
+    if (fold && !soft)
         return fail("the cost gradient is defined for all-hard constraint tables: with a soft side the objective depends on slacks that the "
                     "adjoint system has eliminated and that carry no seed (ihm2mpc_eval_cost evaluates the cost of any table)");
     const size_t B = h->B, N = h->N, NS = h->NS;
@@ -1316,6 +1342,7 @@ int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0,
     double *dc = dwork, *dgy = dc + B, *dgye = dgy + B * N * NY, *dgW = dgye + B * NX, *dgWe = dgW + B * NY * NY;
     // the seeds dJ/dz straight into the adjoint entries' seed buffers, k_adj<true> on them, the explicit partials added: no host round trip
     ihm2_launch_cost(h, 1, dc, nullptr, nullptr, h->adj_sx, h->adj_su, dgy, dgye, dgW, dgWe);
+    if (fold) ihm2_launch_slack_fold(h, 1, 1, nullptr, nullptr, h->adj_sx, h->adj_su);
     ihm2_launch_adj(h, 1, h->adj_sx, h->adj_su, 0, 1);
     ihm2_launch_cost_epilogue(h, dgy, dgye, dgW, dgWe);
     HIP_TRY(hipGetLastError());
@@ -1329,6 +1356,18 @@ int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0,
     if (seed_u) HIP_TRY(hipMemcpyAsync(seed_u, h->adj_su, B * N * NU * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                               double *grad_W_e, double *seed_x, double *seed_u)
+{
+    return eval_cost_gradient(h, false, cost, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e, seed_x, seed_u);
+}
+
+int ihm2mpc_eval_cost_gradient_soft(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                                    double *grad_W_e, double *seed_x, double *seed_u)
+{
+    return eval_cost_gradient(h, true, cost, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e, seed_x, seed_u);
 }
 
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)

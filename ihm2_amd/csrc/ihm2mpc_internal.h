@@ -285,6 +285,9 @@ void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const
 void ihm2_launch_cost(ihm2mpc_handle *h, int grad, double *cost, double *stage_cost, double *slack_cost, double *seed_x, double *seed_u,
                       double *ex_yref, double *ex_yref_e, double *ex_W, double *ex_We);
 void ihm2_launch_cost_epilogue(ihm2mpc_handle *h, double *ex_yref, double *ex_yref_e, double *ex_W, double *ex_We);
+// kernels_slackseed.hip: seeds on the soft slacks folded onto seed_x (B,n_seeds,NS,8), seed_u (B,n_seeds,N,2) in place, before ihm2_launch_adj.
+// cost: the slack terms' own dJ/ds (one seed, seed_s / seed_sa not read); else seed_s (B,n_seeds,NS,28), seed_sa (B,n_seeds,NS,2), nullptr = zero
+void ihm2_launch_slack_fold(ihm2mpc_handle *h, int cost, int n_seeds, const double *seed_s, const double *seed_sa, double *seed_x, double *seed_u);
 
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'

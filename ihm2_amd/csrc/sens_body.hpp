@@ -33,6 +33,17 @@ __device__ __forceinline__ double side_sigma(double lm, double gap, double sl, d
     return lm * rho / (t * rho + lm);          // 1 / (t / lm + 1 / rho), finite for rho = 0
 }
 
+// gamma of one soft side (arguments as side_sigma's, Zw >= 0): the share sigma / rho of a move of the row that its slack takes, which is what
+// carries a seed on the slack onto the stage variables (kernels_slackseed.hip) -- t, nu and rho as side_sigma forms them
+__device__ __forceinline__ double side_slack_share(double lm, double gap, double sl, double zw, double Zw, double tau)
+{
+    if (!(lm > 0.0)) return 0.0;
+    const double t = fmax(gap, tau);
+    const double nu = fmax(zw + Zw * sl - lm, 0.0);
+    const double rho = Zw + nu / fmax(sl, tau);
+    return lm / (t * rho + lm);                // finite for rho = 0, where it is 1
+}
+
 // The body of k_sens for instance b on the calling wavefront (lane = threadIdx.x), sm the block's dynamic LDS (written before it is
 // read).  step: the control step of the persistent loop (k_sens: 0) -- the row of a.hist it writes, and the forward sweep of mode 2 runs
 // on a.sweep_step only.  Not inlined: k_sens and k_steps<..., SENS = 1> run the same code, whatever their translation units contract.

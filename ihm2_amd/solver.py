@@ -564,6 +564,41 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_eval_cost_gradient(self._h, *[_ptr(v) for v in out.values()]))
         return out
 
+    def eval_cost_gradient_soft(self):
+        """:meth:`eval_cost_gradient` on every constraint table: the slack penalties' own seed ``dJ/ds_i = z_i + Z_i s_i`` is folded
+        onto the stage seeds before the adjoint runs, so ``seed_x``, ``seed_u`` come back as the seeds the adjoint saw.  The same dict;
+        on a table without a soft side the same bits (``ihm2mpc_eval_cost_gradient_soft``)."""
+        B, N = self.B, self.N
+        out = dict(cost=np.empty(B), x0=np.empty((B, NX)), yref=np.empty((B, N, NY)), yref_e=np.empty((B, NX)), W=np.empty((B, NY, NY)),
+                   W_e=np.empty((B, NX, NX)), seed_x=np.empty((B, N + 1, NX)), seed_u=np.empty((B, N, NU)))
+        _lib.check(self.lib.ihm2mpc_eval_cost_gradient_soft(self._h, *[_ptr(v) for v in out.values()]))
+        return out
+
+    def eval_adjoint_slack_sensitivities(self, seed_x=None, seed_u=None, seed_s=None, seed_sa=None):
+        """``eval_adjoint_weight_sensitivities`` for functions ``L`` that also depend on the soft slacks: ``seed_s`` ``(B,S,N+1,28)`` =
+        ``dL/ds`` in the layout of ``get_slacks`` (14 lower sides, 14 upper sides), ``seed_sa`` ``(B,S,N+1,2)`` for the slacks of the
+        lateral-acceleration row (``get_alat_multipliers``); the ``S`` axis may be dropped on all of them, as there.  A seed on a side
+        without a slack is ignored.  Any seed may be ``None`` = zero; all four ``None``: the two unit seeds on ``u_0``.  Returns the
+        dict of ``eval_adjoint_weight_sensitivities``; without slack seeds the same bits (``ihm2mpc_eval_adjoint_sensitivities_s``)."""
+        B, N = self.B, self.N
+        shapes = dict(seed_x=(N + 1, NX), seed_u=(N, NU), seed_s=(N + 1, 28), seed_sa=(N + 1, 2))
+        seeds = dict(seed_x=seed_x, seed_u=seed_u, seed_s=seed_s, seed_sa=seed_sa)
+        given = next((v for v in seeds.values() if v is not None), None)
+        if given is None:
+            S, squeeze = 2, False
+        else:
+            squeeze = np.ndim(given) == 3
+            S = 1 if squeeze else int(np.shape(given)[1])
+        ptrs = []
+        for name, v in seeds.items():
+            shape = (B, S) + shapes[name]
+            ptrs.append(None if v is None else _f64(np.asarray(v, dtype=np.float64).reshape(shape), shape, name))
+        out = dict(x0=np.empty((B, S, NX)), yref=np.empty((B, S, N, NY)), yref_e=np.empty((B, S, NX)), W=np.empty((B, S, NY, NY)),
+                   W_e=np.empty((B, S, NX, NX)))
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_s(self._h, S, *[None if p is None else _ptr(p) for p in ptrs],
+                                                                 *[_ptr(v) for v in out.values()]))
+        return {k: v[:, 0] for k, v in out.items()} if squeeze else out
+
     def du0_ds_target(self):
         """``(B,2)``: the reaction of the first control of the last solve to ``prepare_step``'s ``s_target`` -- the reference ramp puts
         ``(j / N) s_target`` into ``yref_j[0]`` and ``s_target`` into ``yref_e[0]``, so it is
@@ -853,6 +888,13 @@ class AcadosOcpSolver:
             raise Exception(f"AcadosOcpSolver.eval_and_get_optimal_value_gradient(): with_respect_to '{with_respect_to}' is not supported "
                             "('initial_state')")
         return self.batch.eval_cost_gradient()["x0"][self.i].copy()
+
+    def eval_and_get_optimal_value_gradient_soft(self, with_respect_to: str = "initial_state") -> np.ndarray:
+        """:meth:`eval_and_get_optimal_value_gradient` on every constraint table, soft sides included
+        (``BatchedOcpSolver.eval_cost_gradient_soft``)."""
+        if with_respect_to != "initial_state":
+            return self.eval_and_get_optimal_value_gradient(with_respect_to)        # raises
+        return self.batch.eval_cost_gradient_soft()["x0"][self.i].copy()
 
     def get(self, stage: int, field: str) -> np.ndarray:
         if field in ("sens_x", "sens_u"):

@@ -37,6 +37,7 @@
  *   ihm2mpc_eval_cost         <- solver.get_cost() (acados), stage terms scaled by cost_scale_stage
  *   ihm2mpc_eval_cost_gradient <- solver.eval_and_get_optimal_value_gradient("initial_state") (acados), of the RTI step's cost, and the
  *                                 gradients of that cost in yref, yref_e, W, W_e
+ *   ihm2mpc_eval_adjoint_sensitivities_s, ihm2mpc_eval_cost_gradient_soft <- the same two on tables with soft sides: seeds on the slacks
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -381,6 +382,22 @@ int ihm2mpc_eval_adjoint_sensitivities(ihm2mpc_handle *h, int32_t n_seeds, const
 int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
                                          double *grad_x0, double *grad_yref, double *grad_yref_e,
                                          double *grad_W, double *grad_W_e);   /* (B,n_seeds,12,12), (B,n_seeds,8,8) */
+/* The same call with seeds on the soft slacks: L may also depend on the slack values s_i of ihm2mpc_get_slacks (seed_s (B,n_seeds,N+1,28)
+ * = dL/ds_i, 14 lower sides then 14 upper sides per stage) and on those of the lateral-acceleration row (seed_sa (B,n_seeds,N+1,2),
+ * lower, upper; ihm2mpc_get_alat_multipliers).  The system above has every soft slack eliminated in series; with the slack kept, its row
+ * reads (lam_i / t_i) (s + sgn_i r_i z) + rho_i s = c_i for a seed c_i, and eliminating it moves the right-hand side:
+ *     seed_z,k  <-  seed_z,k - sum over the soft sides i of stage k with lam_i > 0 of  c_i gamma_i sgn_i r_i,
+ *     gamma_i = lam_i / (t_i rho_i + lam_i),   sgn_i = +1 on a lower side and -1 on an upper side
+ * (gamma_i = sigma_i / rho_i: the share of a move of the row that the slack takes; 1 for rho_i = 0).  One more kernel folds the slack
+ * seeds onto seed_x / seed_u in device memory; everything behind it is ihm2mpc_eval_adjoint_sensitivities_w, unchanged.  A seed on a side
+ * without a slack -- a hard side, or one with no finite bound -- is ignored, as is one on a side whose multiplier is zero.  Any of the
+ * four seeds may be NULL (= zero); all four NULL with n_seeds == 2: the two unit seeds on u_0.  With seed_s and seed_sa NULL no fold
+ * runs and the outputs are the bits of ihm2mpc_eval_adjoint_sensitivities_w.  Outputs, preconditions, refusals and NaN rows are that
+ * entry's; instances whose status is neither 0 nor 2 are not folded.  Gradients in the soft penalties and in the bounds are not computed.
+ * Blocking. */
+int ihm2mpc_eval_adjoint_sensitivities_s(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
+                                         const double *seed_s, const double *seed_sa,
+                                         double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e);
 
 /* ---- the objective and its total gradient (kernels_cost.hip) ----
  * The objective at the handle's current (x, u) -- after a solve the returned solution z+ -- as acados documents get_cost, stage terms
@@ -411,10 +428,19 @@ int ihm2mpc_eval_cost(ihm2mpc_handle *h, double *cost, double *stage_cost, doubl
  * ihm2mpc_eval_adjoint_sensitivities: x0 sensitivity mode 1 or 2 on for the solve; refused while the mode is off, before a solve with the
  * mode on, after ihm2mpc_run_steps (after ihm2mpc_run_steps_sens: the last step's) and in the SQP mode; it must follow the solve directly.
  * Refused on a handle with a soft side: J_slack depends on slacks that the adjoint system has eliminated and that carry no seed, so
- * the gradient is defined for all-hard tables only (ihm2mpc_eval_cost takes every table).  It changes no other output, but overwrites
+ * the gradient is defined for all-hard tables only (ihm2mpc_eval_cost takes every table; ihm2mpc_eval_cost_gradient_soft gives the
+ * slacks their seed and takes every table).  It changes no other output, but overwrites
  * the seed and gradient buffers of the adjoint entries, as every call of those does.  Blocking. */
 int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e,
                                double *grad_W, double *grad_W_e, double *seed_x, double *seed_u);
+/* ihm2mpc_eval_cost_gradient on every constraint table.  On a table with a soft side J_slack depends on the slacks, whose seed
+ * c_i = dJ_slack/ds_i = z_i + Z_i s_i is folded onto the stage seeds as ihm2mpc_eval_adjoint_sensitivities_s folds seed_s, between the
+ * cost kernel and the adjoint; x0, yref and the weights do not enter a slack's row, so the explicit partials are those above.  seed_x and
+ * seed_u come back as the seeds the adjoint saw, after the fold: the five gradients are those of ihm2mpc_eval_adjoint_sensitivities_w for
+ * them plus the explicit partials.  On a handle without a soft side no fold runs and every output is the bits of
+ * ihm2mpc_eval_cost_gradient.  Same arguments, shapes, preconditions, refusals (but the soft-side one) and NaN rows.  Blocking. */
+int ihm2mpc_eval_cost_gradient_soft(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e,
+                                    double *grad_W, double *grad_W_e, double *seed_x, double *seed_u);
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */

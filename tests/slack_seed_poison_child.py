@@ -1,0 +1,60 @@
+"""Child process of tests/test_gpu_slack_seeds.py::test_workspace_poison: ihm2mpc_eval_cost_gradient_soft and
+ihm2mpc_eval_adjoint_sensitivities_s on a poisoned and a clean handle and replayed on each (poison_cases.run_twin), bit for bit -- their
+call-local workspaces ("cost_work", "slack_seed_work", of which the part of a NULL slack seed is never uploaded) and the adjoint entries'
+seed buffers, which the entry zero-fills for NULL stage seeds before the fold adds to them, are NaN instead of zero on the poisoned
+handle.  A soft table and the lateral-acceleration row.  usage: slack_seed_poison_child.py"""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__))))
+import conftest  # noqa: E402,F401  (puts the repository root on the path)
+
+import numpy as np  # noqa: E402
+
+import layouts as L  # noqa: E402
+import poison_cases as PC  # noqa: E402
+
+
+def main():
+    from ihm2_amd.solver import BatchedOcpSolver
+    from ihm2_amd.track import track_table
+
+    track = track_table("fsds_competition_1")
+    B = 5
+    for lay in (L.TABLE["soft_2_per_lane"][0], L.TABLE["alat_soft"][0]):
+        N = lay.N
+        x0, yref, yref_e = PC.qp_start(track, lay, B, 77)
+        rng = np.random.default_rng(12)
+        seed_x, seed_u = rng.standard_normal((B, 3, N + 1, 8)), rng.standard_normal((B, 3, N, 2))
+        seed_s, seed_sa = rng.standard_normal((B, 3, N + 1, 28)), rng.standard_normal((B, 3, N + 1, 2))
+
+        def make():
+            s = BatchedOcpSolver(L.make_ocp(lay), B, track.s_ref, track.kappa_ref, track_widths=L.track_widths(lay))
+            L.apply(s.data, lay)
+            s._push_bounds()
+            s.set_x0_sensitivities(1)
+            return s
+
+        def start(s):
+            s.set_x0(x0); s.init_guess()
+            s.set_yref(yref); s.set_yref_e(yref_e); s.set_multipliers(None, None)
+            return yref, yref_e
+
+        def calls(s, tag):
+            out = []
+            for _ in range(2):
+                s.solve_async()
+                out.append(s.eval_adjoint_slack_sensitivities(seed_s=seed_s))            # NULL stage seeds, NULL seed_sa
+                out.append(s.eval_adjoint_slack_sensitivities(seed_x, None, None, seed_sa))
+                out.append(s.eval_cost_gradient_soft())
+                out.append(s.eval_adjoint_slack_sensitivities(None, seed_u[:, :1], seed_s[:, :1], seed_sa[:, :1]))
+                out.append(PC.outputs(s, sens=True, adjoint=True))
+            return out
+
+        first = PC.run_twin(make, start, calls, accepted=(0, 2))
+        assert np.isfinite(first[2]["cost"]).all() and np.abs(first[0]["x0"][np.isfinite(first[0]["x0"])]).max() > 0.0
+    print("slack seed poison ok")
+
+
+if __name__ == "__main__":
+    main()

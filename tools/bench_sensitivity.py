@@ -23,7 +23,11 @@
       blocking calls ihm2mpc_eval_cost and ihm2mpc_eval_cost_gradient with every output, HIP events around them with every output NULL
       (the call-local allocation and the kernels; a kernel profiler run on this mode gives k_cost alone), and in the same process the
       rows of (e), whose eight-seed call the whole gradient call is set against.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --plant [--lib PATH]] > result.json"""
+  (h) --value-soft: the rows of (g) for ihm2mpc_eval_cost_gradient_soft on a soft table -- the same workload with the two track rows soft
+      100 / 100 on both sides (bench.py's track_rows="soft") -- where k_slack_fold<true> (kernels_slackseed.hip) runs between k_cost<1>
+      and k_adj<true>, and in the same process the eight-seed rows of (e) on that handle's table; a kernel profiler run on this mode
+      sets the fold against k_adj<true>.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --plant [--lib PATH]] > result.json"""
 import argparse
 import ctypes
 import json
@@ -126,13 +130,25 @@ def loop_throughput(B, n, warmup, how):
     return dict(solves_per_s=B * n / el, ms_per_step=el * 1e3 / n, launch=rec, finite_gain_rows=ok)
 
 
-def adjoint_timings(B, steps, warmup, weights=False):
+def soft_track_problem(B):
+    """bench.build_problem with the track rows of bench.rti_throughput(track_rows="soft"): (ocp, track, track_widths)."""
+    ocp, track = bench.build_problem(B)
+    ocp.model.con_h_expr = "track"
+    c = ocp.constraints
+    c.lh = c.lh_e = np.array([-1e3, -1e3]); c.uh = c.uh_e = np.array([0.0, 0.0])
+    c.idxsh, c.idxsh_e = np.arange(2), np.arange(2)
+    ocp.cost.zl = ocp.cost.zu = ocp.cost.Zl = ocp.cost.Zu = np.full(2, 100.0)
+    ocp.cost.zl_e = ocp.cost.zu_e = ocp.cost.Zl_e = ocp.cost.Zu_e = np.full(2, 100.0)
+    return ocp, track, np.array([[track.right_widths.min(), track.left_widths.min()]])
+
+
+def adjoint_timings(B, steps, warmup, weights=False, soft=False):
     from ihm2_amd import _lib
     from ihm2_amd.solver import BatchedOcpSolver
 
     hip = ctypes.CDLL("libamdhip64.so")
-    ocp, track = bench.build_problem(B)
-    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    ocp, track, widths = soft_track_problem(B) if soft else bench.build_problem(B) + (None,)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref, track_widths=widths)
     s.set_x0_sensitivities(1)
     s.set_x0(bench.sample_x0(track, B, 20240607))
     s.init_guess()
@@ -175,16 +191,17 @@ def adjoint_timings(B, steps, warmup, weights=False):
     return out
 
 
-def value_timings(B, steps, warmup):
+def value_timings(B, steps, warmup, soft=False):
     """ihm2mpc_eval_cost and ihm2mpc_eval_cost_gradient after one RTI step: wall time of the whole blocking call with every output, and
     HIP events on the handle's stream around the call with every output NULL (no download: the call-local allocation on the host, then
-    k_cost alone / k_cost<1>, k_adj<true> with one seed and k_cost_epilogue)."""
+    k_cost alone / k_cost<1>, k_adj<true> with one seed and k_cost_epilogue).  soft: ihm2mpc_eval_cost_gradient_soft on the soft track
+    rows of soft_track_problem, with k_slack_fold<true> in front of k_adj<true>."""
     from ihm2_amd import _lib
     from ihm2_amd.solver import BatchedOcpSolver
 
     hip = ctypes.CDLL("libamdhip64.so")
-    ocp, track = bench.build_problem(B)
-    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    ocp, track, widths = soft_track_problem(B) if soft else bench.build_problem(B) + (None,)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref, track_widths=widths)
     s.set_x0_sensitivities(1)
     s.set_x0(bench.sample_x0(track, B, 20240607))
     s.init_guess()
@@ -201,7 +218,11 @@ def value_timings(B, steps, warmup):
     grad_out = [np.empty(B), np.empty((B, 8)), np.empty((B, N, 12)), np.empty((B, 8)), np.empty((B, 12, 12)), np.empty((B, 8, 8)),
                 np.empty((B, N + 1, 8)), np.empty((B, N, 2))]
     out = {"status0": float((st == 0).mean())}
-    for name, fn, bufs in (("cost", s.lib.ihm2mpc_eval_cost, cost_out), ("gradient", s.lib.ihm2mpc_eval_cost_gradient, grad_out)):
+    if soft:
+        out["status_0_or_2"] = float(np.isin(st, (0, 2)).mean())
+        out["slack_cost_in_use"] = float((s.get_slack_cost() > 1e-6).mean())
+    grad_fn = s.lib.ihm2mpc_eval_cost_gradient_soft if soft else s.lib.ihm2mpc_eval_cost_gradient
+    for name, fn, bufs in (("cost", s.lib.ihm2mpc_eval_cost, cost_out), ("gradient", grad_fn, grad_out)):
         wall, dev = [], []
         for i in range(warmup + steps):
             t0 = time.perf_counter()
@@ -311,12 +332,13 @@ def main():
     ap.add_argument("--plant", action="store_true")
     ap.add_argument("--lib", default=None, help="--plant: path of another build of libihm2mpc.so (one without the new entries times ihm2mpc_sim_step alone)")
     ap.add_argument("--value", action="store_true")
-    ap.add_argument("--batches", default="1024,8192", help="--value: the batch sizes (one at a time under a kernel profiler)")
+    ap.add_argument("--value-soft", action="store_true")
+    ap.add_argument("--batches", default="1024,8192", help="--value, --value-soft: the batch sizes (one at a time under a kernel profiler)")
     a = ap.parse_args()
-    if a.value:
+    if a.value or a.value_soft:
         batches = [int(v) for v in a.batches.split(",")]
-        print(json.dumps({"value": {str(B): value_timings(B, a.steps, a.warmup) for B in batches},
-                          "adjoint_weights": {str(B): adjoint_timings(B, a.steps, a.warmup, True) for B in batches}}))
+        print(json.dumps({"value_soft" if a.value_soft else "value": {str(B): value_timings(B, a.steps, a.warmup, a.value_soft) for B in batches},
+                          "adjoint_weights": {str(B): adjoint_timings(B, a.steps, a.warmup, True, a.value_soft) for B in batches}}))
         return
     if a.plant:
         print(json.dumps({"plant": {"1024": plant_timings(1024, a.steps, a.warmup, a.lib)}, "lib": a.lib or "product"}))
