@@ -44,6 +44,7 @@
 #include "qp_lds.hpp"
 #include "qp_mrows.hpp"
 #include "qp_reduce.hpp"
+#include "qp_div.hpp"
 #include "qp_catalogue.hpp"
 #include "wave_sync.hpp"
 
@@ -266,6 +267,9 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     // want_res = false (wave-uniform): the stationarity residual of the incoming iterate -- an output only (ihm2mpc_get_residuals), a third of
     // the QP set-up -- is skipped; the persistent RTI loop asks for it on its last step alone
     constexpr int NT = 64 * NW;
+    // FULL: how many of a lane's 2 NSLOT quotients advance side by side (qp_div.hpp) -- the reciprocals 1 / t, the steps' -dlam / lam, the
+    // corrector's coefficients
+    constexpr int DIVW_RECIP = 5, DIVW_STEP = 5, DIVW_COEFF = 5;
     // M_k of the compiled-in horizon is kept stage-pair-major (qp_mrows.hpp): the factor sweep's straight-line stage writes it so, the lean vector and
     // forward sweeps take one 16-byte load per two stages.  Every other form keeps the stage-major RIC_IDX rows.
     constexpr bool PAIRM = NF > 0;
@@ -441,8 +445,8 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     // constraint slots owned by this lane
     // FULL: s_kc packs what the phases need of a slot into its one register (five more per lane tipped k_steps' allocation into scratch):
     // bits 0..15 the byte offset 8 (k NCK + c) of its word in cf and gam, bits 16..29 the byte offset of its word in a stage-major vector
-    // v[NS][10] (8 (k * 10 + c) of a box row, 8 (k * 10) of a general row), bit 31 (the sign) a general row, bit 30 which of the two -- what
-    // row_dot works out of k NCK + c on every call
+    // v[NS][10] of a box row (8 (k * 10 + c)), in the tile of a general row (8 (2 k + c - 10): where general_rows below leaves the row's product),
+    // bit 31 (the sign) a general row, bit 30 which of the two -- what row_dot works out of k NCK + c on every call (qp_lds.hpp: qp_full_slot_pack)
     int s_kc[NSLOT];
     double s_dl[NSLOT], s_du[NSLOT];      // bounds relative to the iterate (+-inf = absent)
     double lam_l[NSLOT], lam_u[NSLOT], t_l[NSLOT], t_u[NSLOT];
@@ -485,7 +489,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         if (kc >= 0) {
             const int k = kc >> 4, c = kc & 15;
             s_kc[r] = k * NCK + c;
-            if (FULL) s_kc[r] = ((k * NCK + c) * 8) | ((k * 10 + ((c < 10) ? c : 0)) << 19) | ((c >= 10) ? (int)(0x80000000u | ((unsigned)(c - 10) << 30)) : 0);
+            if (FULL) s_kc[r] = qp_full_slot_pack(k, c, NCK);
             double cz;
             if (c < 8) cz = xb[k * 8 + c];
             else if (c < 10) cz = ub[k * 2 + c - 8];
@@ -541,16 +545,31 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         for (int j = 0; j < 10; j++) acc = fma(CDV(k, c - 10, j), v[k * 10 + j], acc);
         return acc;
     };
-    // the same of slot r of a full table: a box row is its word, a general row the same chain of ten products in the same order
+    // the same of slot r of a full table, without a branch: one word -- a box row's in v, a general row's in the tile, where general_rows(v) has
+    // left the row's product for this phase; a lane's reads do not wait for one another
     auto row_dot_full = [&](int r, const double *v) -> double {
         const int pk = here(s_kc[r]);
-        const double *vk = reinterpret_cast<const double *>(reinterpret_cast<const char *>(v) + ((pk >> 16) & 0x3fff));
-        if (pk >= 0) return vk[0];
-        const double *cd = CDl + (((unsigned)pk >> 30) & 1) * 10;
-        double acc = 0.0;
+        return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(pk < 0 ? tile : v) + ((pk >> 16) & 0x3fff));
+    };
+    // FULL: the general rows [C D] v_k of all stages k < N, once per phase: element e = 2 k + row -> tile[e], the chain of ten products that
+    // row_dot forms per slot, in its order.  A lane has up to two elements, NT apart (so of the same row): their operands are loaded ahead
+    // of both chains, which then run side by side.  The factor sweep parks stores in the tile; every word a slot reads is rewritten here
+    // before the phase reads it (qp_lds.hpp: qp_reach_general_rows).
+    static_assert(FULL == 0 || qp_general_rows_inside(qp_lds(NF > 0 ? NF : 2, CLS), NF > 0 ? NF : 2), "the general rows of a phase leave the transpose tile");
+    auto general_rows = [&](const double *v) {
+        for (int e0 = tid; e0 < 2 * N; e0 += 2 * NT) {
+            const bool two = e0 + NT < 2 * N;
+            const double *cd = CDl + (e0 & 1) * 10, *v0 = v + (e0 >> 1) * 10, *v1 = v + ((two ? e0 + NT : e0) >> 1) * 10;
+            double c[10], p[10], q[10];
 #pragma unroll
-        for (int j = 0; j < 10; j++) acc = fma(cd[j], vk[j], acc);
-        return acc;
+            for (int j = 0; j < 10; j++) { c[j] = cd[j]; p[j] = v0[j]; q[j] = v1[j]; }
+            double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+            for (int j = 0; j < 10; j++) { acc0 = fma(c[j], p[j], acc0); acc1 = fma(c[j], q[j], acc1); }
+            tile[e0] = acc0;
+            if (two) tile[e0 + NT] = acc1;
+        }
+        BSYNC();
     };
 
 /*@S:0*/
@@ -560,6 +579,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     // FULL: the one zeroing of cf and gam -- from here on a word is rewritten by its slot in every pass that reads it, or never written again
     if (FULL) for (int e = tid; e < NS * NCK; e += NT) { cf[e] = 0.0; gam[e] = 0.0; }
     BSYNC();
+    if constexpr (FULL != 0) general_rows(z);
 #pragma unroll
     for (int r = 0; r < NSLOT; r++) {
         if (NO_SLOT(r)) continue;
@@ -616,6 +636,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
         // and whether the lane met a NaN is a flag per norm
         double lane_d = 0.0, lane_m = 0.0;
         bool bad_d = false, bad_m = false, bad_gs = false;
+        if constexpr (FULL != 0) general_rows(z);
 #pragma unroll
         for (int r = 0; r < NSLOT; r++) {
             rd_l[r] = rd_u[r] = 0.0;
@@ -762,6 +783,23 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 BSYNC();
             }
             const double mu_t = fmax(sigma * mu, mu_floor);
+            if constexpr (FULL != 0) {
+                if (pass == 1) {        // the corrector's quotients of the loop below, both sides of every slot side by side (qp_div.hpp)
+                    double cn[2 * NSLOT], cd[2 * NSLOT], cq[2 * NSLOT];
+#pragma unroll
+                    for (int r = 0; r < NSLOT; r++) { cn[2 * r] = pa_l[r] - mu_t; cd[2 * r] = t_l[r]; cn[2 * r + 1] = pa_u[r] - mu_t; cd[2 * r + 1] = t_u[r]; }
+                    div_sets<DIVW_COEFF>(cn, cd, cq);
+#pragma unroll
+                    for (int r = 0; r < NSLOT; r++) {
+                        double c = 0.0;
+                        c += cq[2 * r];
+                        c -= cq[2 * r + 1];
+                        SLOT_AT(cf, r) = c;
+                    }
+                    BSYNC();
+                    return;
+                }
+            }
 #pragma unroll
             for (int r = 0; r < NSLOT; r++) {
                 if (NO_SLOT(r)) continue;
@@ -832,6 +870,16 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             if (lane < 8) dz[lane] = 0.0;
         }
         BSYNC();
+        // FULL: the reciprocals 1 / t of both sides of every slot, once per iteration (t moves with the step, behind the pass loop), side by side
+        double it_l[NSLOT], it_u[NSLOT];
+        if constexpr (FULL != 0) {
+            double one[2 * NSLOT], tt[2 * NSLOT], rc[2 * NSLOT];
+#pragma unroll
+            for (int r = 0; r < NSLOT; r++) { one[2 * r] = one[2 * r + 1] = 1.0; tt[2 * r] = t_l[r]; tt[2 * r + 1] = t_u[r]; }
+            div_sets<DIVW_RECIP>(one, tt, rc);
+#pragma unroll
+            for (int r = 0; r < NSLOT; r++) { it_l[r] = rc[2 * r]; it_u[r] = rc[2 * r + 1]; }
+        }
         for (int pass = 0; pass < 2; pass++) {
             const double mu_t = fmax(sigma * mu, mu_floor);
             if (pass == 1) slot_coeffs(1);
@@ -1016,6 +1064,37 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 /*@S:11*/
             // ---- slack / multiplier steps, step length ----
             double amax = 1.0, amax_d = 1.0, mu_aff = 0.0, rmax = 1.0, rmax_d = 1.0;
+            if constexpr (FULL != 0) general_rows(dz);
+            if constexpr (FULL != 0) {
+                // the statements of the loop below for a table of two-sided hard rows, phase by phase instead of slot by slot: the row products
+                // (one read each, issued together), the steps with the reciprocals 1 / t taken once per iteration above the pass loop, the
+                // 2 NSLOT quotients -dlam / lam side by side (qp_div.hpp), and the two maxima in the loop's order
+                double drz[NSLOT], qn[2 * NSLOT], qd[2 * NSLOT], qq[2 * NSLOT];
+#pragma unroll
+                for (int r = 0; r < NSLOT; r++) drz[r] = ROW_DOT(r, dz);
+#pragma unroll
+                for (int r = 0; r < NSLOT; r++) {
+                    {
+                        const double rm = (pass == 0) ? lam_l[r] * t_l[r] : lam_l[r] * t_l[r] + pa_l[r] - mu_t;
+                        dt_l[r] = drz[r] + rd_l[r];
+                        dlam_l[r] = -(rm + lam_l[r] * dt_l[r]) * it_l[r];
+                    }
+                    {
+                        const double rm = (pass == 0) ? lam_u[r] * t_u[r] : lam_u[r] * t_u[r] + pa_u[r] - mu_t;
+                        dt_u[r] = -drz[r] + rd_u[r];
+                        dlam_u[r] = -(rm + lam_u[r] * dt_u[r]) * it_u[r];
+                    }
+                    qn[2 * r] = -dlam_l[r]; qd[2 * r] = lam_l[r]; qn[2 * r + 1] = -dlam_u[r]; qd[2 * r + 1] = lam_u[r];
+                }
+                div_sets<DIVW_STEP>(qn, qd, qq);
+#pragma unroll
+                for (int r = 0; r < NSLOT; r++) {
+                    rmax = fmax(rmax, -dt_l[r] * it_l[r]);
+                    rmax_d = fmax(rmax_d, qq[2 * r]);
+                    rmax = fmax(rmax, -dt_u[r] * it_u[r]);
+                    rmax_d = fmax(rmax_d, qq[2 * r + 1]);
+                }
+            } else
 #pragma unroll
             for (int r = 0; r < NSLOT; r++) {
                 dlam_l[r] = dlam_u[r] = dt_l[r] = dt_u[r] = 0.0;
@@ -1073,6 +1152,12 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             }
 /*@S:15*/
             // hard sides collect max(-dt/t), max(-dlam/lam) (>= 1 matters only); soft sides the step bounds themselves
+            if constexpr (FULL != 0) {      // (the pair of reciprocals side by side)
+                const double one[2] = {1.0, 1.0}, rm2[2] = {rmax, rmax_d};
+                double rc[2];
+                div_batch<2>(one, rm2, rc);
+                amax = fmin(amax, rc[0]); amax_d = fmin(amax_d, rc[1]);
+            } else
             if (NSOFT == 0) { amax = fmin(amax, 1.0 / rmax); amax_d = fmin(amax_d, 1.0 / rmax_d); }
             if constexpr (FULL != 0) wave_min2(lane, amax, amax_d);      // (in [0, 1], never NaN: rmax = fmax(1, .) dropped them)
             else { amax = blk_min(amax); amax_d = blk_min(amax_d); }

@@ -180,6 +180,25 @@ QP_LDS_FN bool qp_full_zeroes_kept(const QpLds &l, int N)
     const QpReach s = qp_reach_plain_stores(l), p = qp_reach_plain_store_pv(l, N);
     return s.lo >= l.cf.end() && qp_inside(s, l.cf.end(), l.total) && qp_inside(p, 0, l.gam) && l.cf == l.gam.end();
 }
+// The full slot form evaluates the general rows [C D] v_k once per phase (kernels_qp.hip: general_rows): element e = 2 k + row of the
+// stages k < N goes to tile[e], and a general-row slot reads its word back from there.  The tile is shared with the straight-line factor
+// stage, which parks its idle lanes' stores in it (qp_reach_plain_parking), so a word of it holds nothing across a factor sweep: the pass
+// rewrites ALL the words a slot can read -- [tile, tile + 2 N) -- behind the sweep and before the first read of each phase, and no slot
+// reads a word outside them (qp_full_slot_pack below: the offsets 8 (2 k + row), k < N).  Parked words at 2 N and above are read by nobody.
+QP_LDS_FN QpReach qp_reach_general_rows(const QpLds &l, int N) { return {l.tile, l.tile + 2 * N}; }
+QP_LDS_FN bool qp_general_rows_inside(const QpLds &l, int N) { return qp_inside(qp_reach_general_rows(l, N), l.tile, l.tile.end()); }
+static_assert(qp_general_rows_inside(qp_lds(40, qp_lds_class(0, true)), 40) && qp_general_rows_inside(qp_lds(2, qp_lds_class(0, true)), 2),
+              "the general rows of a phase leave the transpose tile");
+// What the full slot form keeps of the slot (k, c) in its one register: bits 0..15 the byte offset 8 (k nck + c) of its word in cf and
+// gam; bits 16..29 the byte offset of the word a phase reads for R_c . v -- of a box row (c < 10) its word 8 (k 10 + c) in the stage-major
+// vector v[NS][10], of a general row its word 8 (2 k + c - 10) in the tile; bit 31 (the sign) a general row, bit 30 which of the two.
+QP_LDS_FN int qp_full_slot_pack(int k, int c, int nck)
+{
+    return ((k * nck + c) * 8) | ((c < 10 ? k * 10 + c : 2 * k + (c - 10)) << 19) | ((c >= 10) ? (int)(0x80000000u | ((unsigned)(c - 10) << 30)) : 0);
+}
+QP_LDS_FN bool qp_full_slot_general(int pk) { return pk < 0; }
+QP_LDS_FN int qp_full_slot_read(int pk) { return (pk >> 16) & 0x3fff; }      // the byte offset of the bits 16..29
+QP_LDS_FN int qp_full_slot_word(int pk) { return pk & 0xffff; }             // the byte offset of the bits 0..15
 // the four-wave kernel's block reductions: one word per wave, in the tile
 QP_LDS_FN QpReach qp_reach_block_reduce(const QpLds &l, int nw) { return {l.tile, l.tile + nw}; }
 
