@@ -126,6 +126,8 @@ SYMBOLS = {
     "ihm2mpc_eval_cost_gradient": (C.c_int, [_H] + [c_double_p] * 8),
     "ihm2mpc_eval_adjoint_sensitivities_s": (C.c_int, [_H, C.c_int32] + [c_double_p] * 9),
     "ihm2mpc_eval_cost_gradient_soft": (C.c_int, [_H] + [c_double_p] * 8),
+    "ihm2mpc_eval_adjoint_sensitivities_p": (C.c_int, [_H, C.c_int32] + [c_double_p] * 14),
+    "ihm2mpc_eval_cost_gradient_penalties": (C.c_int, [_H] + [c_double_p] * 12),
 }
 
 _lib = None

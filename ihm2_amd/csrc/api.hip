@@ -1228,10 +1228,62 @@ static int adjoint_buffers(ihm2mpc_handle *h, size_t S, bool weights)
     return 0;
 }
 
-// ihm2mpc_eval_adjoint_sensitivities, ihm2mpc_eval_adjoint_sensitivities_w (weights: grad_W / grad_W_e are computed and may be asked for) and
-// ihm2mpc_eval_adjoint_sensitivities_s (seed_s / seed_sa: seeds on the soft slacks, folded onto the stage seeds by k_slack_fold first)
+static bool any_soft_side(const ihm2mpc_handle *h);
+
+// The host outputs of the penalty entries (ihm2mpc_eval_adjoint_sensitivities_p, ihm2mpc_eval_cost_gradient_penalties), any may be NULL,
+// and their call-local device memory "penalty_grad_work" for S seeds: zeta (B,S,NS,10), then grad_z, grad_Z (B,S,NS,28), grad_za,
+// grad_Za (B,S,NS,2)
+struct PenaltyOut { double *z, *Z, *za, *Za, *zeta; };
+struct PenaltyWork {
+    WorkBuf<double> buf;
+    double *zeta, *z, *Z, *za, *Za;
+    int alloc(ihm2mpc_handle *h, size_t S)
+    {
+        const size_t n = (size_t)h->B * S * h->NS;
+        buf.poison(poisoned(h, "penalty_grad_work"));
+        if (buf.alloc(n * (NZ + 2 * NLAM + 4)) != hipSuccess) return fail("out of device memory");
+        zeta = buf; z = zeta + n * NZ; Z = z + n * NLAM; za = Z + n * NLAM; Za = za + n * 2;
+        return 0;
+    }
+};
+
+// the copies of the penalty outputs onto h->stream, behind the kernels (soft: k_penalty_grad ran and wrote the four gradients)
+static int penalty_download(ihm2mpc_handle *h, size_t S, const PenaltyWork &w, const PenaltyOut &o, bool soft)
+{
+    const size_t n = (size_t)h->B * S * h->NS;
+    if (o.zeta) HIP_TRY(hipMemcpyAsync(o.zeta, w.zeta, n * NZ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (!soft) return 0;
+    if (o.z) HIP_TRY(hipMemcpyAsync(o.z, w.z, n * NLAM * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (o.Z) HIP_TRY(hipMemcpyAsync(o.Z, w.Z, n * NLAM * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (o.za) HIP_TRY(hipMemcpyAsync(o.za, w.za, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (o.Za) HIP_TRY(hipMemcpyAsync(o.Za, w.Za, n * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+
+// a handle without a soft side: no kernel ran, the four gradients are zeros, NaN for instances whose status is neither 0 nor 2 (blocking)
+static int penalty_zeros(ihm2mpc_handle *h, size_t S, const PenaltyOut &o)
+{
+    if (!o.z && !o.Z && !o.za && !o.Za) return 0;
+    std::vector<int32_t> st(h->B);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->status, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t n = S * h->NS;
+    for (int b = 0; b < h->B; b++) {
+        const double v = (st[b] == 0 || st[b] == 2) ? 0.0 : NAN;
+        if (o.z) std::fill_n(o.z + b * n * NLAM, n * NLAM, v);
+        if (o.Z) std::fill_n(o.Z + b * n * NLAM, n * NLAM, v);
+        if (o.za) std::fill_n(o.za + b * n * 2, n * 2, v);
+        if (o.Za) std::fill_n(o.Za + b * n * 2, n * 2, v);
+    }
+    return 0;
+}
+
+// ihm2mpc_eval_adjoint_sensitivities, ihm2mpc_eval_adjoint_sensitivities_w (weights: grad_W / grad_W_e are computed and may be asked for),
+// ihm2mpc_eval_adjoint_sensitivities_s (seed_s / seed_sa: seeds on the soft slacks, folded onto the stage seeds by k_slack_fold first) and
+// ihm2mpc_eval_adjoint_sensitivities_p (pen: k_adj<true, true> keeps zeta and, on a table with a soft side, k_penalty_grad runs behind it)
 static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, const double *seed_s, const double *seed_sa,
-                        double *grad_x0, double *grad_yref, double *grad_yref_e, bool weights, double *grad_W, double *grad_W_e)
+                        double *grad_x0, double *grad_yref, double *grad_yref_e, bool weights, double *grad_W, double *grad_W_e,
+                        const PenaltyOut *pen = nullptr)
 {
     CHECK_H(h);
     if (adjoint_refused_in_sqp(h)) return -1;
@@ -1246,6 +1298,11 @@ static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x
     if (adjoint_buffers(h, S, weights)) return -1;
     if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (seed_u) HIP_TRY(hipMemcpyAsync(h->adj_su, seed_u, B * S * N * NU * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PenaltyWork pw;
+    if (pen && pw.alloc(h, S)) return -1;
+    double *zeta = pen ? pw.zeta : nullptr;
+    const bool soft = pen && any_soft_side(h);
+    const double *pen_s = nullptr, *pen_sa = nullptr;   // the slack seeds in device memory, as the fold took them
     WorkBuf<double> slack_seed_work;    // "slack_seed_work": seed_s (B,S,NS,28), then seed_sa (B,S,NS,2); the part of a NULL seed is not read
     if (slack) {
         slack_seed_work.poison(poisoned(h, "slack_seed_work"));
@@ -1256,18 +1313,22 @@ static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x
         // the fold adds to the stage seeds: a NULL one is zero first
         if (!seed_x) HIP_TRY(hipMemsetAsync(h->adj_sx, 0, B * S * NS * NX * sizeof(double), h->stream));
         if (!seed_u) HIP_TRY(hipMemsetAsync(h->adj_su, 0, B * S * N * NU * sizeof(double), h->stream));
-        ihm2_launch_slack_fold(h, 0, n_seeds, seed_s ? ds : nullptr, seed_sa ? dsa : nullptr, h->adj_sx, h->adj_su);
-        ihm2_launch_adj(h, n_seeds, h->adj_sx, h->adj_su, 0, weights ? 1 : 0);
+        pen_s = seed_s ? ds : nullptr; pen_sa = seed_sa ? dsa : nullptr;
+        ihm2_launch_slack_fold(h, 0, n_seeds, pen_s, pen_sa, h->adj_sx, h->adj_su);
+        ihm2_launch_adj(h, n_seeds, h->adj_sx, h->adj_su, 0, weights ? 1 : 0, zeta);
     } else {
-        ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0, weights ? 1 : 0);
+        ihm2_launch_adj(h, n_seeds, seed_x ? h->adj_sx.get() : nullptr, seed_u ? h->adj_su.get() : nullptr, unit_u0 ? 1 : 0, weights ? 1 : 0, zeta);
     }
+    if (soft) ihm2_launch_penalty_grad(h, 0, n_seeds, pen_s, pen_sa, pw.zeta, pw.z, pw.Z, pw.za, pw.Za);
     HIP_TRY(hipGetLastError());
     if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, h->adj_gy, B * S * N * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, h->adj_gye, B * S * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_W) HIP_TRY(hipMemcpyAsync(grad_W, h->adj_gW, B * S * NY * NY * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, h->adj_gWe, B * S * NX * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));      // the seeds may be reused and the gradients read as soon as we return; slack_seed_work is released behind it
+    if (pen && penalty_download(h, S, pw, *pen, soft)) return -1;
+    HIP_TRY(hipStreamSynchronize(h->stream));      // the seeds may be reused and the gradients read as soon as we return; the call's work buffers are released behind it
+    if (pen && !soft) return penalty_zeros(h, S, *pen);
     return 0;
 }
 
@@ -1288,6 +1349,14 @@ int ihm2mpc_eval_adjoint_sensitivities_s(ihm2mpc_handle *h, int32_t n_seeds, con
                                          double *grad_W_e)
 {
     return eval_adjoint(h, n_seeds, seed_x, seed_u, seed_s, seed_sa, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
+}
+
+int ihm2mpc_eval_adjoint_sensitivities_p(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, const double *seed_s,
+                                         const double *seed_sa, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                                         double *grad_W_e, double *grad_z, double *grad_Z, double *grad_za, double *grad_Za, double *zeta)
+{
+    const PenaltyOut pen = {grad_z, grad_Z, grad_za, grad_Za, zeta};
+    return eval_adjoint(h, n_seeds, seed_x, seed_u, seed_s, seed_sa, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e, &pen);
 }
 
 // ---- the objective and its total gradient (kernels_cost.hip) ----
@@ -1322,9 +1391,10 @@ int ihm2mpc_eval_cost(ihm2mpc_handle *h, double *cost, double *stage_cost, doubl
 }
 
 // ihm2mpc_eval_cost_gradient and ihm2mpc_eval_cost_gradient_soft (soft: every table is taken, and on one with a soft side k_slack_fold<true>
-// carries dJ_slack/ds onto the seeds between the cost kernel and the adjoint)
+// carries dJ_slack/ds onto the seeds between the cost kernel and the adjoint) and ihm2mpc_eval_cost_gradient_penalties (pen: k_adj<true, true>
+// keeps zeta and, on a table with a soft side, k_penalty_grad<true> runs behind it)
 static int eval_cost_gradient(ihm2mpc_handle *h, bool soft, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
-                              double *grad_W_e, double *seed_x, double *seed_u)
+                              double *grad_W_e, double *seed_x, double *seed_u, const PenaltyOut *pen = nullptr)
 {
     CHECK_H(h);
     if (adjoint_refused_in_sqp(h)) return -1;
@@ -1342,8 +1412,11 @@ static int eval_cost_gradient(ihm2mpc_handle *h, bool soft, double *cost, double
     double *dc = dwork, *dgy = dc + B, *dgye = dgy + B * N * NY, *dgW = dgye + B * NX, *dgWe = dgW + B * NY * NY;
     // the seeds dJ/dz straight into the adjoint entries' seed buffers, k_adj<true> on them, the explicit partials added: no host round trip
     ihm2_launch_cost(h, 1, dc, nullptr, nullptr, h->adj_sx, h->adj_su, dgy, dgye, dgW, dgWe);
+    PenaltyWork pw;
+    if (pen && pw.alloc(h, 1)) return -1;
     if (fold) ihm2_launch_slack_fold(h, 1, 1, nullptr, nullptr, h->adj_sx, h->adj_su);
-    ihm2_launch_adj(h, 1, h->adj_sx, h->adj_su, 0, 1);
+    ihm2_launch_adj(h, 1, h->adj_sx, h->adj_su, 0, 1, pen ? pw.zeta : nullptr);
+    if (pen && fold) ihm2_launch_penalty_grad(h, 1, 1, nullptr, nullptr, pw.zeta, pw.z, pw.Z, pw.za, pw.Za);
     ihm2_launch_cost_epilogue(h, dgy, dgye, dgW, dgWe);
     HIP_TRY(hipGetLastError());
     if (cost) HIP_TRY(hipMemcpyAsync(cost, dc, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1354,7 +1427,9 @@ static int eval_cost_gradient(ihm2mpc_handle *h, bool soft, double *cost, double
     if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, dgWe, B * NX * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (seed_x) HIP_TRY(hipMemcpyAsync(seed_x, h->adj_sx, B * NS * NX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (seed_u) HIP_TRY(hipMemcpyAsync(seed_u, h->adj_su, B * N * NU * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (pen && penalty_download(h, 1, pw, *pen, fold)) return -1;
     HIP_TRY(hipStreamSynchronize(h->stream));
+    if (pen && !fold) return penalty_zeros(h, 1, *pen);
     return 0;
 }
 
@@ -1368,6 +1443,14 @@ int ihm2mpc_eval_cost_gradient_soft(ihm2mpc_handle *h, double *cost, double *gra
                                     double *grad_W_e, double *seed_x, double *seed_u)
 {
     return eval_cost_gradient(h, true, cost, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e, seed_x, seed_u);
+}
+
+int ihm2mpc_eval_cost_gradient_penalties(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W,
+                                         double *grad_W_e, double *grad_z, double *grad_Z, double *grad_za, double *grad_Za, double *seed_x,
+                                         double *seed_u)
+{
+    const PenaltyOut pen = {grad_z, grad_Z, grad_za, grad_Za, nullptr};
+    return eval_cost_gradient(h, true, cost, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e, seed_x, seed_u, &pen);
 }
 
 int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)

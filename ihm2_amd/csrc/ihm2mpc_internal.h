@@ -276,8 +276,9 @@ void ihm2_launch_sens(ihm2mpc_handle *h);
 size_t ihm2_sens_lds_bytes(const ihm2mpc_handle *h);
 // kernels_adj.hip: the gradients of n_seeds scalar functions of that solution in x0, yref, yref_e into h->adj_gx0, adj_gy, adj_gye;
 // seeds in device memory (nullptr = zero), unit_u0: the two unit seeds on u_0 instead; weights: also the gradients in W, W_e into
-// h->adj_gW, adj_gWe (the other three are the same bits either way)
-void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights);
+// h->adj_gW, adj_gWe (the other three are the same bits either way); zeta: with weights, also the adjoint solution into this device array
+// (B,n_seeds,NS,10), nullptr = not kept (the five gradients are the same bits either way)
+void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights, double *zeta);
 // kernels_cost.hip: the objective at the handle's (x, u) into cost (B), stage_cost (B,NS), slack_cost (B), each may be nullptr; grad: also
 // its seeds dJ/dz into seed_x (B,NS,8), seed_u (B,N,2) and its explicit partials in yref, yref_e, W, W_e into ex_* ((B,N,12), (B,8),
 // (B,12,12), (B,8,8); NaN for instances whose status is neither 0 nor 2).  The epilogue adds h->adj_gy, adj_gye, adj_gW, adj_gWe of one
@@ -288,6 +289,11 @@ void ihm2_launch_cost_epilogue(ihm2mpc_handle *h, double *ex_yref, double *ex_yr
 // kernels_slackseed.hip: seeds on the soft slacks folded onto seed_x (B,n_seeds,NS,8), seed_u (B,n_seeds,N,2) in place, before ihm2_launch_adj.
 // cost: the slack terms' own dJ/ds (one seed, seed_s / seed_sa not read); else seed_s (B,n_seeds,NS,28), seed_sa (B,n_seeds,NS,2), nullptr = zero
 void ihm2_launch_slack_fold(ihm2mpc_handle *h, int cost, int n_seeds, const double *seed_s, const double *seed_sa, double *seed_x, double *seed_u);
+// kernels_penaltygrad.hip: the gradients in the slack penalties from the adjoint solution zeta (B,n_seeds,NS,10) that ihm2_launch_adj left
+// behind the fold, into grad_z, grad_Z (B,n_seeds,NS,28) and grad_za, grad_Za (B,n_seeds,NS,2), all device memory.  cost: the slack seeds
+// are the cost's own z + Z s and the explicit partials of J are added (one seed); else seed_s, seed_sa as the fold took them
+void ihm2_launch_penalty_grad(ihm2mpc_handle *h, int cost, int n_seeds, const double *seed_s, const double *seed_sa, const double *zeta,
+                              double *grad_z, double *grad_Z, double *grad_za, double *grad_Za);
 
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'

@@ -44,6 +44,8 @@ struct AdjArgs {
     const double *yref, *yref_e;        // (B,N,12), (B,8) as the solve read them
     double cs;                          // cost_scale_stage
     double *grad_W, *grad_W_e;          // (B,n_seeds,12,12), (B,n_seeds,8,8)
+    // k_adj<true, true> only
+    double *zeta;                       // (B,n_seeds,N+1,10) the adjoint solution zeta_k = (zeta_x,k, zeta_u,k), zeros on the input part of row N
 };
 
 // LDS of one instance (doubles) behind the factorisation's arrays: see the carve-up in k_adj
@@ -59,8 +61,9 @@ __host__ __device__ constexpr size_t adjw_lds_doubles(size_t N)
 static_assert(adj_lds_doubles(40) == 2965 && adj_lds_doubles(1) == 742, "k_adj<false>: launch LDS at N = 40 and N = 1");
 static_assert(adjw_lds_doubles(40) == 2981 && adjw_lds_doubles(1) == 8 * 144, "k_adj<true>: likewise; N = 1 sits on the floor of 8 x 144");
 
-// WG: also the gradients in the cost weights (grad_W, grad_W_e); the three other outputs are computed by the same instructions either way
-template <bool WG>
+// WG: also the gradients in the cost weights (grad_W, grad_W_e); the three other outputs are computed by the same instructions either way.
+// ZETA: the forward sweep also stores zeta itself (kernels_penaltygrad.hip reads it); every gradient keeps its instructions
+template <bool WG, bool ZETA = false>
 __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
 {
     extern __shared__ double sm[];
@@ -101,6 +104,10 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
                 double *gW = aa.grad_W + (bs * S + sd) * 144, *gWe = aa.grad_W_e + (bs * S + sd) * 64;
                 for (int e = row; e < 144; e += 8) gW[e] = NAN;
                 for (int e = row; e < 64; e += 8) gWe[e] = NAN;
+            }
+            if constexpr (ZETA) {
+                double *zt = aa.zeta + (bs * S + sd) * NS * 10;
+                for (int e = row; e < NS * 10; e += 8) zt[e] = NAN;
             }
         }
         return;
@@ -161,6 +168,8 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
     double wr[12], wh[6];
     const int hr = row >> 1, hc0 = (row & 1) * 6;
     const double *yrb = WG ? aa.yref + bs * N * 12 : nullptr;
+    double *zt = nullptr;
+    if constexpr (ZETA) zt = aa.zeta + (bs * S + sd) * NS * 10;
     if (WG) {
 #pragma unroll
         for (int j = 0; j < 12; j++) wr[j] = 0.0;
@@ -196,6 +205,12 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
         g0 = fma(G[8 * 12 + row], u0, g0);
         g0 = fma(G[9 * 12 + row], u1, g0);
         if (live) gyr[k * 12 + row] = g0;          // columns row and (row < 4) 8 + row of Gy_k' zeta_k
+        if constexpr (ZETA) {
+            if (live) {
+                zt[k * 10 + row] = zk[row];
+                if (row < 2) zt[k * 10 + 8 + row] = row ? u1 : u0;
+            }
+        }
         if (row < 4) {
             g1 = fma(G[8 * 12 + 8 + row], u0, g1);
             g1 = fma(G[9 * 12 + 8 + row], u1, g1);
@@ -219,6 +234,12 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
 #pragma unroll
         for (int l = 0; l < 8; l++) ge = fma(GyT[l * 12 + row], zk[l], ge);
         if (live) gye[row] = ge;
+        if constexpr (ZETA) {
+            if (live) {
+                zt[N * 10 + row] = zk[row];
+                if (row < 2) zt[N * 10 + 8 + row] = 0.0;
+            }
+        }
         if (WG) {
             // the terminal outer product: both products rounded before they are added, so that entry (i, j) and entry (j, i) get the same bits
             double *gWe = aa.grad_W_e + (bs * S + sd) * 64;
@@ -251,8 +272,9 @@ __global__ __launch_bounds__(64) void k_adj(AdjArgs aa)
 }  // namespace
 
 // The handle's adjoint evaluation on h->stream: seeds from h->adj_sx / h->adj_su (nullptr = zero; unit_u0: the two unit seeds on u_0),
-// gradients into h->adj_gx0, h->adj_gy, h->adj_gye and (weights) h->adj_gW, h->adj_gWe.
-void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights)
+// gradients into h->adj_gx0, h->adj_gy, h->adj_gye and (weights) h->adj_gW, h->adj_gWe.  zeta (device, (B,n_seeds,N+1,10)) or nullptr: with
+// weights, k_adj<true, true> also stores the adjoint solution there.
+void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const double *seed_u, int unit_u0, int weights, double *zeta)
 {
     AdjArgs a;
     ihm2_sens_args(h, &a.s);
@@ -263,8 +285,14 @@ void ihm2_launch_adj(ihm2mpc_handle *h, int n_seeds, const double *seed_x, const
     a.grad_x0 = h->adj_gx0; a.grad_yref = h->adj_gy; a.grad_yref_e = h->adj_gye;
     a.yref = h->yref; a.yref_e = h->yref_e; a.cs = h->cfg.cost_scale_stage;
     a.grad_W = h->adj_gW; a.grad_W_e = h->adj_gWe;
+    a.zeta = zeta;
     if (weights) {
         const size_t lds = sizeof(double) * adjw_lds_doubles((size_t)h->N);
+        if (zeta) {
+            (void)hipFuncSetAttribute((const void *)k_adj<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((k_adj<true, true>), dim3(h->B), dim3(64), lds, h->stream, a);
+            return;
+        }
         (void)hipFuncSetAttribute((const void *)k_adj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(k_adj<true>, dim3(h->B), dim3(64), lds, h->stream, a);
         return;

@@ -581,6 +581,16 @@ class BatchedOcpSolver:
         without a slack is ignored.  Any seed may be ``None`` = zero; all four ``None``: the two unit seeds on ``u_0``.  Returns the
         dict of ``eval_adjoint_weight_sensitivities``; without slack seeds the same bits (``ihm2mpc_eval_adjoint_sensitivities_s``)."""
         B, N = self.B, self.N
+        S, squeeze, ptrs = self._slack_seed_args(seed_x, seed_u, seed_s, seed_sa)
+        out = dict(x0=np.empty((B, S, NX)), yref=np.empty((B, S, N, NY)), yref_e=np.empty((B, S, NX)), W=np.empty((B, S, NY, NY)),
+                   W_e=np.empty((B, S, NX, NX)))
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_s(self._h, S, *[None if p is None else _ptr(p) for p in ptrs],
+                                                                 *[_ptr(v) for v in out.values()]))
+        return {k: v[:, 0] for k, v in out.items()} if squeeze else out
+
+    def _slack_seed_args(self, seed_x, seed_u, seed_s, seed_sa):
+        """``(S, squeeze, the four seed arrays or None)`` of the entries that take seeds on the slacks."""
+        B, N = self.B, self.N
         shapes = dict(seed_x=(N + 1, NX), seed_u=(N, NU), seed_s=(N + 1, 28), seed_sa=(N + 1, 2))
         seeds = dict(seed_x=seed_x, seed_u=seed_u, seed_s=seed_s, seed_sa=seed_sa)
         given = next((v for v in seeds.values() if v is not None), None)
@@ -593,11 +603,42 @@ class BatchedOcpSolver:
         for name, v in seeds.items():
             shape = (B, S) + shapes[name]
             ptrs.append(None if v is None else _f64(np.asarray(v, dtype=np.float64).reshape(shape), shape, name))
+        return S, squeeze, ptrs
+
+    # ---- gradients in the slack penalties of the soft sides ----
+    def eval_adjoint_penalty_sensitivities(self, seed_x=None, seed_u=None, seed_s=None, seed_sa=None):
+        """``eval_adjoint_slack_sensitivities`` with the gradients in the slack penalties: its dict (the same bits) plus ``soft_z``,
+        ``soft_Z`` ``(B,S,N+1,28)`` in the layout of ``set_soft`` / ``get_slacks``, ``alat_soft_z``, ``alat_soft_Z`` ``(B,S,N+1,2)`` for
+        the two sides of the lateral-acceleration row, and ``zeta`` ``(B,S,N+1,10)``, the adjoint solution ``(zeta_x,k, zeta_u,k)``.
+        ``soft_z = -zeta_s``, ``soft_Z = -s zeta_s`` with ``zeta_s`` the slack component of the adjoint; 0 on a side without a slack or
+        with a zero multiplier, so the sum over the batch is the gradient in the shared table.  Bounds are not differentiated
+        (``ihm2mpc_eval_adjoint_sensitivities_p``)."""
+        B, N = self.B, self.N
+        S, squeeze, ptrs = self._slack_seed_args(seed_x, seed_u, seed_s, seed_sa)
         out = dict(x0=np.empty((B, S, NX)), yref=np.empty((B, S, N, NY)), yref_e=np.empty((B, S, NX)), W=np.empty((B, S, NY, NY)),
-                   W_e=np.empty((B, S, NX, NX)))
-        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_s(self._h, S, *[None if p is None else _ptr(p) for p in ptrs],
+                   W_e=np.empty((B, S, NX, NX)), soft_z=np.empty((B, S, N + 1, NLAM)), soft_Z=np.empty((B, S, N + 1, NLAM)),
+                   alat_soft_z=np.empty((B, S, N + 1, 2)), alat_soft_Z=np.empty((B, S, N + 1, 2)), zeta=np.empty((B, S, N + 1, NX + NU)))
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_p(self._h, S, *[None if p is None else _ptr(p) for p in ptrs],
                                                                  *[_ptr(v) for v in out.values()]))
         return {k: v[:, 0] for k, v in out.items()} if squeeze else out
+
+    def eval_cost_gradient_penalties(self):
+        """:meth:`eval_cost_gradient_soft` with the total derivative of the cost in the slack penalties: the same dict (the same bits)
+        plus ``soft_z``, ``soft_Z`` ``(B,N+1,28)`` and ``alat_soft_z``, ``alat_soft_Z`` ``(B,N+1,2)``: ``dJ/dz = s - zeta_s``,
+        ``dJ/dZ = s^2 / 2 - s zeta_s`` (``ihm2mpc_eval_cost_gradient_penalties``)."""
+        B, N = self.B, self.N
+        out = dict(cost=np.empty(B), x0=np.empty((B, NX)), yref=np.empty((B, N, NY)), yref_e=np.empty((B, NX)), W=np.empty((B, NY, NY)),
+                   W_e=np.empty((B, NX, NX)), soft_z=np.empty((B, N + 1, NLAM)), soft_Z=np.empty((B, N + 1, NLAM)),
+                   alat_soft_z=np.empty((B, N + 1, 2)), alat_soft_Z=np.empty((B, N + 1, 2)), seed_x=np.empty((B, N + 1, NX)),
+                   seed_u=np.empty((B, N, NU)))
+        _lib.check(self.lib.ihm2mpc_eval_cost_gradient_penalties(self._h, *[_ptr(v) for v in out.values()]))
+        return out
+
+    def du0_dsoft(self):
+        """``dict(soft_z, soft_Z (B,2,N+1,28), alat_soft_z, alat_soft_Z (B,2,N+1,2))``: the derivative of the first control of the last
+        solve in the slack penalties (the two unit seeds on ``u_0``)."""
+        g = self.eval_adjoint_penalty_sensitivities()
+        return {k: g[k] for k in ("soft_z", "soft_Z", "alat_soft_z", "alat_soft_Z")}
 
     def du0_ds_target(self):
         """``(B,2)``: the reaction of the first control of the last solve to ``prepare_step``'s ``s_target`` -- the reference ramp puts
@@ -871,6 +912,14 @@ class AcadosOcpSolver:
         sx, su = self._adjoint_seeds(seed_x, seed_u, "eval_adjoint_weight_sensitivity")
         g = self.batch.eval_adjoint_weight_sensitivities(sx, su)
         return g["W"][self.i].copy(), g["W_e"][self.i].copy()
+
+    def eval_adjoint_penalty_sensitivity(self, seed_x, seed_u):
+        """The gradient of ``sum_k seed_x[k]' x_k + seed_u[k]' u_k`` of this instance's last solution in the slack penalties: seeds as for
+        ``eval_adjoint_solution_sensitivity``, returns ``dict(soft_z, soft_Z (n_seeds, N+1, 28), alat_soft_z, alat_soft_Z
+        (n_seeds, N+1, 2))`` (``BatchedOcpSolver.eval_adjoint_penalty_sensitivities``).  acados has no counterpart."""
+        sx, su = self._adjoint_seeds(seed_x, seed_u, "eval_adjoint_penalty_sensitivity")
+        g = self.batch.eval_adjoint_penalty_sensitivities(sx, su)
+        return {k: g[k][self.i].copy() for k in ("soft_z", "soft_Z", "alat_soft_z", "alat_soft_Z")}
 
     def get_cost(self) -> float:
         """acados' ``get_cost``: the objective at this instance's current iterate, stage terms scaled by ``cost_scale_stage``

@@ -38,6 +38,7 @@
  *   ihm2mpc_eval_cost_gradient <- solver.eval_and_get_optimal_value_gradient("initial_state") (acados), of the RTI step's cost, and the
  *                                 gradients of that cost in yref, yref_e, W, W_e
  *   ihm2mpc_eval_adjoint_sensitivities_s, ihm2mpc_eval_cost_gradient_soft <- the same two on tables with soft sides: seeds on the slacks
+ *   ihm2mpc_eval_adjoint_sensitivities_p, ihm2mpc_eval_cost_gradient_penalties <- those two, and the gradients in the slack penalties
  *   ihm2mpc_set_soft          <- ocp.constraints.idxsbx/idxsg/idxsh, cost.zl..Zu         old/generate_acaods_interface.py:380-449
  *   ihm2mpc_set_path_constraints <- model.con_h_expr (track rows), constraints.lh/uh     old/generate_acaods_interface.py:191-212,411-449
  *   ihm2mpc_set_track_geometry, ihm2mpc_project <- Track(csv), Track::project + Frenet states
@@ -393,11 +394,32 @@ int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, con
  * without a slack -- a hard side, or one with no finite bound -- is ignored, as is one on a side whose multiplier is zero.  Any of the
  * four seeds may be NULL (= zero); all four NULL with n_seeds == 2: the two unit seeds on u_0.  With seed_s and seed_sa NULL no fold
  * runs and the outputs are the bits of ihm2mpc_eval_adjoint_sensitivities_w.  Outputs, preconditions, refusals and NaN rows are that
- * entry's; instances whose status is neither 0 nor 2 are not folded.  Gradients in the soft penalties and in the bounds are not computed.
- * Blocking. */
+ * entry's; instances whose status is neither 0 nor 2 are not folded.  Gradients in the soft penalties are those of
+ * ihm2mpc_eval_adjoint_sensitivities_p; gradients in the bounds are not computed.  Blocking. */
 int ihm2mpc_eval_adjoint_sensitivities_s(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
                                          const double *seed_s, const double *seed_sa,
                                          double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e);
+/* The same call with the gradients in the slack penalties z_i, Z_i of ihm2mpc_set_soft (grad_z, grad_Z, in the layout of
+ * ihm2mpc_get_slacks) and of the two sides of the lateral-acceleration row (grad_za, grad_Za: lower, upper).  The slack's row above
+ * linearises its stationarity z_i + Z_i s_i - lam_i - nu_i = 0, which a change of the penalties moves by dz_i + s_i dZ_i.  With zeta_k the
+ * adjoint solution of stage k on the folded seeds, c_i the seed on the slack (zero where none is given) and s_i the slack value after the
+ * solve,
+ *     zeta_s,i = (c_i t_i - lam_i sgn_i r_i zeta_k) / (t_i rho_i + lam_i),      dL/dz_i = -zeta_s,i,      dL/dZ_i = -s_i zeta_s,i
+ * (= (c_i - w_i sgn_i r_i zeta_k) / (w_i + rho_i) with w_i = lam_i / t_i, which is never formed; sgn_i = +1 on a lower and -1 on an
+ * upper side).  A side whose multiplier is not positive (lam_i = 0) is dropped, as the fold drops it: both gradients are 0 -- there
+ * rho_i >= nu_i / tau, so what is dropped is at most |c_i| tau / z_i.  A side without a slack -- hard, or with no finite bound -- has
+ * both gradients 0, not NaN, so that the gradients can be summed over the batch for the shared table.  zeta (B,n_seeds,N+1,10), may be
+ * NULL: the adjoint solution itself, (zeta_x,k, zeta_u,k) per stage, zeros on the input part of row N.  The first five gradients are
+ * the bits of ihm2mpc_eval_adjoint_sensitivities_s for the same seeds; on a handle without a soft side the four new gradients are
+ * zeros.  Every output may be NULL; instances whose status is neither 0 nor 2 get NaN in all of them.  Arguments, preconditions and
+ * refusals are that entry's.  The memory of the new outputs lives for the call only.  Bounds stay undifferentiated: a gradient in a
+ * bound would carry lam_i / t_i itself.  Blocking. */
+int ihm2mpc_eval_adjoint_sensitivities_p(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u,
+                                         const double *seed_s, const double *seed_sa,
+                                         double *grad_x0, double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e,
+                                         double *grad_z, double *grad_Z,      /* (B,n_seeds,N+1,28) each */
+                                         double *grad_za, double *grad_Za,    /* (B,n_seeds,N+1,2) each */
+                                         double *zeta);                       /* (B,n_seeds,N+1,10), may be NULL */
 
 /* ---- the objective and its total gradient (kernels_cost.hip) ----
  * The objective at the handle's current (x, u) -- after a solve the returned solution z+ -- as acados documents get_cost, stage terms
@@ -441,6 +463,15 @@ int ihm2mpc_eval_cost_gradient(ihm2mpc_handle *h, double *cost, double *grad_x0,
  * ihm2mpc_eval_cost_gradient.  Same arguments, shapes, preconditions, refusals (but the soft-side one) and NaN rows.  Blocking. */
 int ihm2mpc_eval_cost_gradient_soft(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e,
                                     double *grad_W, double *grad_W_e, double *seed_x, double *seed_u);
+/* ihm2mpc_eval_cost_gradient_soft with the total derivative of the cost in the slack penalties: the gradients of
+ * ihm2mpc_eval_adjoint_sensitivities_p for the cost's seeds (c_i = z_i + Z_i s_i) plus the explicit partials of J_slack,
+ *     dJ/dz_i = s_i - zeta_s,i,      dJ/dZ_i = s_i^2 / 2 - s_i zeta_s,i
+ * into grad_z, grad_Z (B,N+1,28) and grad_za, grad_Za (B,N+1,2), any may be NULL; 0 on a side without a slack or with lam_i = 0, NaN for
+ * instances whose status is neither 0 nor 2, zeros on a handle without a soft side.  Every other output is the bits of
+ * ihm2mpc_eval_cost_gradient_soft.  Bounds stay undifferentiated.  Blocking. */
+int ihm2mpc_eval_cost_gradient_penalties(ihm2mpc_handle *h, double *cost, double *grad_x0, double *grad_yref, double *grad_yref_e,
+                                         double *grad_W, double *grad_W_e, double *grad_z, double *grad_Z, double *grad_za,
+                                         double *grad_Za, double *seed_x, double *seed_u);
 
 /* ---- device-pointer variants (zero-copy closed loop, RCCL gather of results) ----
  * dptr is device memory on the handle's device, SAME (instance-major) layout as the host variant */

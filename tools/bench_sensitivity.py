@@ -27,7 +27,13 @@
       100 / 100 on both sides (bench.py's track_rows="soft") -- where k_slack_fold<true> (kernels_slackseed.hip) runs between k_cost<1>
       and k_adj<true>, and in the same process the eight-seed rows of (e) on that handle's table; a kernel profiler run on this mode
       sets the fold against k_adj<true>.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --plant [--lib PATH]] > result.json"""
+  (i) --penalties: the gradients in the slack penalties (kernels_penaltygrad.hip) on the soft table of (h), B = 1024 and 8192
+      (--batches), n_seeds = 1 and 8 with seeds on the stages and on the slacks: ihm2mpc_eval_adjoint_sensitivities_w (k_adj<true>),
+      ihm2mpc_eval_adjoint_sensitivities_s (k_slack_fold, k_adj<true>) and ihm2mpc_eval_adjoint_sensitivities_p (k_slack_fold,
+      k_adj<true, true>, k_penalty_grad) in the same process -- HIP events around each call with every output NULL (uploads, the
+      call-local allocations, the kernels) and the wall time of the whole blocking call with every output -- and the extra time of _p
+      over _s.  A kernel profiler run on this mode gives k_penalty_grad and k_adj<true, true> beside k_adj<true>.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --penalties [--batches 1024,8192] | --plant [--lib PATH]] > result.json"""
 import argparse
 import ctypes
 import json
@@ -244,6 +250,63 @@ def value_timings(B, steps, warmup, soft=False):
     return out
 
 
+def penalty_timings(B, steps, warmup):
+    """The three adjoint entries on soft_track_problem after one RTI step, the same seeds for all: see (i) above."""
+    from ihm2_amd import _lib
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    ocp, track, widths = soft_track_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref, track_widths=widths)
+    s.set_x0_sensitivities(1)
+    s.set_x0(bench.sample_x0(track, B, 20240607))
+    s.init_guess()
+    s.prepare_step(40.0)
+    st = s.solve()
+    stream = ctypes.c_void_p()
+    _lib.check(s.lib.ihm2mpc_get_stream(s._h, ctypes.byref(stream)))
+    ev = [ctypes.c_void_p(), ctypes.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(ctypes.byref(e)) == 0
+    rng = np.random.default_rng(1)
+    N = s.N
+    ptr = lambda a: a.ctypes.data_as(_lib.c_double_p)      # noqa: E731
+    out = {"status_0_or_2": float(np.isin(st, (0, 2)).mean()), "slack_cost_in_use": float((s.get_slack_cost() > 1e-6).mean())}
+    for S in (1, 8):
+        sx, su = rng.standard_normal((B, S, N + 1, 8)), rng.standard_normal((B, S, N, 2))
+        ss, sa = rng.standard_normal((B, S, N + 1, 28)), rng.standard_normal((B, S, N + 1, 2))
+        g = [np.empty((B, S, 8)), np.empty((B, S, N, 12)), np.empty((B, S, 8)), np.empty((B, S, 12, 12)), np.empty((B, S, 8, 8))]
+        gp = [np.empty((B, S, N + 1, 28)), np.empty((B, S, N + 1, 28)), np.empty((B, S, N + 1, 2)), np.empty((B, S, N + 1, 2)),
+              np.empty((B, S, N + 1, 10))]
+        entries = (("w", s.lib.ihm2mpc_eval_adjoint_sensitivities_w, [sx, su], g),
+                   ("s", s.lib.ihm2mpc_eval_adjoint_sensitivities_s, [sx, su, ss, sa], g),
+                   ("p", s.lib.ihm2mpc_eval_adjoint_sensitivities_p, [sx, su, ss, sa], g + gp))
+        r = {}
+        for name, fn, seeds, bufs in entries:
+            wall, dev = [], []
+            for i in range(warmup + steps):
+                t0 = time.perf_counter()
+                _lib.check(fn(s._h, S, *[ptr(a) for a in seeds], *[ptr(a) for a in bufs]))
+                wall.append((time.perf_counter() - t0) * 1e3)
+            for i in range(warmup + steps):
+                assert hip.hipEventRecord(ev[0], stream) == 0
+                _lib.check(fn(s._h, S, *[ptr(a) for a in seeds], *[None] * len(bufs)))
+                assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+                ms = ctypes.c_float()
+                assert hip.hipEventElapsedTime(ctypes.byref(ms), ev[0], ev[1]) == 0
+                dev.append(ms.value)
+            r[name] = dict(call_wall_ms=float(np.median(wall[warmup:])), upload_alloc_and_kernel_event_ms=float(np.median(dev[warmup:])),
+                           event_ms_spread=float(np.ptp(dev[warmup:]) / np.median(dev[warmup:])))
+        r["p_over_s_event_ms"] = r["p"]["upload_alloc_and_kernel_event_ms"] - r["s"]["upload_alloc_and_kernel_event_ms"]
+        r["p_over_s_wall_ms"] = r["p"]["call_wall_ms"] - r["s"]["call_wall_ms"]
+        r["live_penalty_rows"] = float(np.any(gp[0] != 0.0, axis=(1, 2, 3)).mean())
+        out[f"n_seeds_{S}"] = r
+    for e in ev:
+        hip.hipEventDestroy(e)
+    s.free()
+    return out
+
+
 def plant_timings(B, steps, warmup, lib_path=None):
     from ihm2_amd import _lib
 
@@ -333,8 +396,12 @@ def main():
     ap.add_argument("--lib", default=None, help="--plant: path of another build of libihm2mpc.so (one without the new entries times ihm2mpc_sim_step alone)")
     ap.add_argument("--value", action="store_true")
     ap.add_argument("--value-soft", action="store_true")
-    ap.add_argument("--batches", default="1024,8192", help="--value, --value-soft: the batch sizes (one at a time under a kernel profiler)")
+    ap.add_argument("--penalties", action="store_true")
+    ap.add_argument("--batches", default="1024,8192", help="--value, --value-soft, --penalties: the batch sizes (one at a time under a kernel profiler)")
     a = ap.parse_args()
+    if a.penalties:
+        print(json.dumps({"penalties": {str(B): penalty_timings(B, a.steps, a.warmup) for B in (int(v) for v in a.batches.split(","))}}))
+        return
     if a.value or a.value_soft:
         batches = [int(v) for v in a.batches.split(",")]
         print(json.dumps({"value_soft" if a.value_soft else "value": {str(B): value_timings(B, a.steps, a.warmup, a.value_soft) for B in batches},
