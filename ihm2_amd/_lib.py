@@ -80,6 +80,7 @@ SYMBOLS = {
                                          c_double_p]),
     "ihm2mpc_set_sqp_options": (C.c_int, [_H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, c_double_p]),
     "ihm2mpc_get_sqp_stats": (C.c_int, [_H, c_int32_p, c_double_p]),
+    "ihm2mpc_get_sqp_merit": (C.c_int, [_H, c_double_p]),
     "ihm2mpc_linearize": (C.c_int, [_H]),
     "ihm2mpc_get_linearization": (C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
     "ihm2mpc_get_x": (C.c_int, [_H, c_double_p]),

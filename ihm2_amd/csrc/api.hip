@@ -66,7 +66,7 @@ struct Poisonable { const char *name; WorkBuf<double> ihm2mpc_handle::*buf; };
 #define PB(m) {#m, &ihm2mpc_handle::m}
 const Poisonable POISONABLE[] = {
     PB(lin), PB(q_g), PB(q_rg), PB(q_P), PB(q_M), PB(scratch), PB(res), PB(qp_res), PB(dyn10), PB(ls_phi),
-    PB(ls_x), PB(ls_u), PB(ls_pi), PB(ls_lam), PB(ls_slk), PB(ls_wpi), PB(ls_wlam), PB(ls_alpha),
+    PB(ls_x), PB(ls_u), PB(ls_pi), PB(ls_lam), PB(ls_slk), PB(ls_wpi), PB(ls_wlam), PB(ls_alpha), PB(ls_merit),
     PB(hist_u0), PB(hist_x0), PB(hist_k),
     PB(sens_xbar), PB(sens_ubar), PB(sens_u0), PB(sens_x), PB(sens_u),
     PB(adj_sx), PB(adj_su), PB(adj_gx0), PB(adj_gy), PB(adj_gye), PB(adj_gW), PB(adj_gWe),
@@ -993,7 +993,7 @@ static int sqp_buffers(ihm2mpc_handle *h)
     if (h->ls_x) return 0;
     const size_t B = h->B, N = h->N, NS = h->NS;
     return alloc_all(h->ls_x, B * NS * 8, h->ls_u, B * N * 2, h->ls_pi, B * NS * 8, h->ls_lam, B * NS * NLAM, h->ls_slk, B * NS * NLAM,
-                     h->ls_wpi, B * NS * 8, h->ls_wlam, B * NS * NLAM, h->ls_alpha, B, h->ls_args, 64, h->ls_done, B, h->ls_status, B,
+                     h->ls_wpi, B * NS * 8, h->ls_wlam, B * NS * NLAM, h->ls_alpha, B, h->ls_merit, B * 4, h->ls_args, 64, h->ls_done, B, h->ls_status, B,
                      h->ls_iter, B, h->ls_qp_acc, B, h->ls_pending, B);
 }
 
@@ -1102,6 +1102,16 @@ int ihm2mpc_get_sqp_stats(ihm2mpc_handle *h, int32_t *sqp_iter, double *alpha)
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (sqp_iter) HIP_TRY(hipMemcpy(sqp_iter, h->ls_iter, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (alpha) HIP_TRY(hipMemcpy(alpha, h->ls_alpha, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int ihm2mpc_get_sqp_merit(ihm2mpc_handle *h, double *m)
+{
+    CHECK_H(h);
+    if (!m) return fail("null output");
+    if (!h->ls_x) return fail("no SQP-mode solve has run on this handle");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(m, h->ls_merit, (size_t)h->B * 4 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

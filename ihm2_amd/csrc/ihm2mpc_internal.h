@@ -194,6 +194,7 @@ struct ihm2mpc_handle {
     StateBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of rows.sz / rows.sZ
     // allocated together by the first SQP solve (api.hip: sqp_buffers): the iterate the QP was built at, merit weights, per-solve bookkeeping
     WorkBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
+    WorkBuf<double> ls_merit;               // (B,4) merit values of the last line search (ihm2mpc_get_sqp_merit; sqp_body.hpp: LsArgs.merit)
     WorkBuf<int32_t> ls_done, ls_status, ls_iter, ls_qp_acc;
     WorkBuf<int32_t> ls_pending;            // (B) instances whose line search goes past the first rollouts (two-launch ladder)
     // The three argument blocks (ls_args, step_args, sens_args) are workspace that is never poisoned: they hold pointers, counts and loop

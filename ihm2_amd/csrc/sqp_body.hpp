@@ -29,6 +29,10 @@ struct LsArgs {
     const double *res;
     int32_t *status, *qp_iter, *done, *sqp_status, *sqp_iter, *qp_acc;
     double *alpha, *u0;
+    // (B,4) read-back of the last line search of the solve: m(0), m at the last trial step (the accepted one; the last rung tried when
+    // none passed and the step fell to alpha_min, where the merit is not evaluated), D (0 on plain decrease), the infeasibility part of
+    // m(0); zeros for an instance that ran none.  nullptr: not kept
+    double *merit;
     const double *phi;               // IRK: Phi at the trial points, (n_alpha, B, N, 8), from k_rollout_irk; nullptr: RK4 rollouts in this kernel
     int n_alpha;
     // the ladder in two launches (IRK): phase 1 tries the first j_limit step lengths and marks the instances that need more in
@@ -106,6 +110,8 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
     if (resume && !a.pending[b]) return;
     if (a.phase == 1 && lane == 0) a.pending[b] = 0;
     if (!resume) {
+    if (it == 0 && lane == 0 && a.merit)
+        for (int i = 0; i < 4; i++) a.merit[(size_t)b * 4 + i] = 0.0;
     if (a.done[b]) { restore(true); finish(a.sqp_status[b]); return; }
     const int qst = a.status[b];
     if (lane == 0) a.qp_acc[b] += a.qp_iter[b];
@@ -279,7 +285,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
             if (a.st_sZ[e] >= 0.0) acc = fma(a.st_sz[e] + a.st_sZ[e] * slpb[e], slb[e] - slpb[e], acc);
         D = fmin(wave_sum(acc) - i0, 0.0);
     }
-    double al = 1.0;
+    double al = 1.0, m_last = m0;
     for (int jtrial = 0;; jtrial++) {              // at most log(alpha_min) / log(alpha_red) + 1 trials: al shrinks every pass
         if (a.phase == 1 && jtrial >= a.j_limit) {      // rollouts beyond this one are not there yet: phase 2 takes this instance
             if (lane == 0) a.pending[b] = 1;
@@ -299,6 +305,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
         double c1, i1;
         merit(al, jtrial, false, c1, i1);
         const double m1 = c1 + i1;
+        m_last = m1;
         if (a.use_suff ? (m1 - m0 <= a.eps * al * D) : (m1 < m0)) break;
         al *= a.alpha_red;
         // (the second condition never decides: ihm2mpc_set_sqp_options refuses ladders longer than the rollout buffer; it keeps a
@@ -318,6 +325,10 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
     __syncthreads();
     if (lane < 2) a.u0[(size_t)b * 2 + lane] = ub[lane];
     if (lane == 0) a.alpha[b] = al;
+    if (lane == 0 && a.merit) {
+        double *mb = a.merit + (size_t)b * 4;
+        mb[0] = m0; mb[1] = m_last; mb[2] = D; mb[3] = i0;
+    }
     finish(last ? 2 : 0);
 }
 
@@ -343,7 +354,7 @@ static inline LsArgs make_ls_args(ihm2mpc_handle *h)
     a.wpi = h->ls_wpi; a.wlam = h->ls_wlam;
     a.res = h->res; a.status = h->status; a.qp_iter = h->qp_iter;
     a.done = h->ls_done; a.sqp_status = h->ls_status; a.sqp_iter = h->ls_iter; a.qp_acc = h->ls_qp_acc;
-    a.alpha = h->ls_alpha; a.u0 = h->u0;
+    a.alpha = h->ls_alpha; a.u0 = h->u0; a.merit = h->ls_merit;
     a.phi = ihm2_is_irk(h->cfg.integrator_type) ? h->ls_phi.get() : nullptr; a.n_alpha = (int)(h->ls_phi.size() / ((size_t)h->B * h->N * 8));
     a.phase = 0; a.j_limit = 0; a.pending = h->ls_pending; a.irk_tab = h->irk_tab;
     return a;

@@ -320,6 +320,13 @@ class BatchedOcpSolver:
         _lib.check(self.lib.ihm2mpc_get_sqp_stats(self._h, it.ctypes.data_as(_lib.c_int32_p), _ptr(alpha)))
         return {"sqp_iter": it, "alpha": alpha}
 
+    def get_sqp_merit(self):
+        """(B,4) merit values of the last line search of the last SQP-mode solve: m(0), m at the last trial step (the accepted step length,
+        or the last one tried when the step fell to ``alpha_min``), D, the infeasibility part of m(0); zeros where no line search ran."""
+        m = np.empty((self.B, 4))
+        _lib.check(self.lib.ihm2mpc_get_sqp_merit(self._h, _ptr(m)))
+        return m
+
     def synchronize(self):
         _lib.check(self.lib.ihm2mpc_synchronize(self._h))
 

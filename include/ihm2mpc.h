@@ -21,7 +21,8 @@
  *   ihm2mpc_solve             <- solver.solve()                                 python/main.py:325; mpc_control_node.cpp:189
  *   ihm2mpc_set_sqp_options   <- ocp.solver_options.globalization / alpha_min / ... / nlp_solver_tol_*   python/main.py:230-237
  *   ihm2mpc_get_sqp_stats     <- solver.get_stats("sqp_iter") / ("alpha") (acados)
- *   ihm2mpc_get_x/_u/_u0      <- solver.get(i,"x"/"u")                          python/main.py:331-334; mpc_control_node.cpp:202-206
+ *   ihm2mpc_get_sqp_merit     <- (no acados call: the line search's merit values m(0), m(alpha), D, read back for its tests)
+ *   ihm2mpc_get_x/_u/_u0      <- solver.get(i,"x"/"u")                        python/main.py:331-334; mpc_control_node.cpp:202-206
  *   ihm2mpc_get_status        <- return value of solve()                        python/main.py:325-328; dpc/main.py:287-293
  *   ihm2mpc_get_residuals     <- solver.get_stats("residuals") (acados)
  *   ihm2mpc_sim_step          <- AcadosSimSolver.simulate(x,u)                  python/main.py:476-502; python/sim.py:9-25
@@ -272,6 +273,11 @@ int ihm2mpc_set_sqp_options(ihm2mpc_handle *h, int32_t globalization, double alp
                             const double *tol);
 /* QP solves made (B) and the last step length (B) of the last SQP-mode solve; either pointer may be NULL */
 int ihm2mpc_get_sqp_stats(ihm2mpc_handle *h, int32_t *sqp_iter, double *alpha);
+/* m (B,4): the merit values of the last line search of the last SQP-mode solve -- [0] m(0), [1] m at the last trial step (the accepted
+ * alpha; when no trial step passed and the step fell to alpha_min, the last one tried: the merit is not evaluated at alpha_min), [2] D
+ * (0 without use_sufficient_descent), [3] the infeasibility part of m(0), sum w |..| + sum w max(0, ..).  Zeros for an instance that
+ * ran no line search in that solve (converged at once, QP failure, IHM2MPC_FIXED_STEP). */
+int ihm2mpc_get_sqp_merit(ihm2mpc_handle *h, double *m);
 /* phases of solve(), exposed for parity tests and profiling */
 int ihm2mpc_linearize(ihm2mpc_handle *h);
 int ihm2mpc_get_linearization(ihm2mpc_handle *h, double *A, double *Bm, double *b); /* (B,N,8,8),(B,N,8,2),(B,N,8) */

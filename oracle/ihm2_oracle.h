@@ -157,7 +157,9 @@ void orc_rti_step(const orc_problem *P, int B, double *x, double *u, const doubl
 /* --- globalised SQP (python/main.py:230-237: "SQP", max_iter 2, "MERIT_BACKTRACKING"): up to max_iter iterations of
  * [KKT test at the iterate -> QP -> backtracking line search on the l1 merit function -> step alpha on primal and dual];
  * see ihm2_oracle_rti.c.  globalization 0 = FIXED_STEP (alpha = 1).  sl (B,N+1,28): slack values, in/out (start at 0);
- * status: 0 converged, 2 max_iter, 4 QP failure, 1 NaN; sqp_iter (B): QP solves made; alpha (B): last step length */
+ * status: 0 converged, 2 max_iter, 4 QP failure, 1 NaN; sqp_iter (B): QP solves made; alpha (B): last step length;
+ * merit (B,4) or NULL: m(0), m at the last trial step, D, the infeasibility part of m(0) of the instance's last line search,
+ * zeros if it ran none */
 typedef struct {
     int max_iter;
     int globalization;
@@ -168,7 +170,7 @@ typedef struct {
 } orc_sqp_opts;
 void orc_sqp_solve(const orc_problem *P, const orc_sqp_opts *O, int B, double *x, double *u, const double *x0,
                    const double *yref, const double *yref_e, const int *track_id, double *pi, double *lam, double *sl,
-                   int *status, double *res, int *qp_iter, int *sqp_iter, double *alpha, int nthreads);
+                   int *status, double *res, int *qp_iter, int *sqp_iter, double *alpha, int nthreads, double *merit);
 
 /* linearisation only: A (B,N,8,8), Bm (B,N,8,2), b (B,N,8) where b = Phi(x_k,u_k) - x_{k+1} */
 void orc_linearize(const orc_problem *P, int B, const double *x, const double *u,

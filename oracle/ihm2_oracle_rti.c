@@ -384,7 +384,7 @@ static double merit_eval(const orc_problem *P, const double *x, const double *u,
 
 static void sqp_one(const orc_problem *P, const orc_sqp_opts *O, double *x, double *u, const double *x0, const double *yref,
                     const double *yref_e, int tid, double *pi, double *lam, double *sl, int *status, double *res, int *qp_iter,
-                    int *sqp_iter, double *alpha_out)
+                    int *sqp_iter, double *alpha_out, double *merit)
 {
     const int N = P->N, NS = N + 1, nx = NS * NX, nu = N * NU, nl = NS * 2 * NC;
     double *xp = malloc(sizeof(double) * nx), *up = malloc(sizeof(double) * nu), *pip = malloc(sizeof(double) * nx);
@@ -396,6 +396,7 @@ static void sqp_one(const orc_problem *P, const orc_sqp_opts *O, double *x, doub
     double pi0[NX];
     int st = 2, iters_total = 0, it;
     double alpha = 1.0;
+    if (merit) for (int i = 0; i < 4; i++) merit[i] = 0.0;
     for (it = 0; it < O->max_iter; it++) {
         memcpy(xp, x, sizeof(double) * nx); memcpy(up, u, sizeof(double) * nu);
         memcpy(pip, pi, sizeof(double) * nx); memcpy(lamp, lam, sizeof(double) * nl); memcpy(slp, sl, sizeof(double) * nl);
@@ -422,16 +423,16 @@ static void sqp_one(const orc_problem *P, const orc_sqp_opts *O, double *x, doub
         const double m0 = merit_eval(P, xp, up, slp, x0, yref, yref_e, tid, wpi, wlam, dl, du, b0);   /* defects: from the linearisation */
         /* directional derivative of the merit along the step: grad cost . d - (weighted infeasibility at alpha = 0),
          * the linearised constraints hold at the full step */
-        double D = 0.0;
-        if (O->use_sufficient_descent) {
-            double eqi = m0;
-            for (int k = 0; k <= N; k++)
-                for (int j = 0; j < ((k < N) ? NZ : NX); j++) D += g[k * NZ + j] * dz[k * NZ + j];
-            /* infeasibility part of m0 = m0 - cost(0): recompute the cost with zero weights */
+        double D = 0.0, eqi = m0;
+        {   /* infeasibility part of m0 = m0 - cost(0): recompute the cost with zero weights */
             double *zw = calloc(nx > nl ? nx : nl, sizeof(double));
             const double c0 = merit_eval(P, xp, up, slp, x0, yref, yref_e, tid, zw, zw, dl, du, b0);
             free(zw);
             eqi -= c0;
+        }
+        if (O->use_sufficient_descent) {
+            for (int k = 0; k <= N; k++)
+                for (int j = 0; j < ((k < N) ? NZ : NX); j++) D += g[k * NZ + j] * dz[k * NZ + j];
             if (P->soft_Z)
                 for (int i = 0; i < nl; i++)
                     if (P->soft_Z[i] >= 0.0) D += (P->soft_z[i] + P->soft_Z[i] * slp[i]) * (sln[i] - slp[i]);
@@ -439,15 +440,19 @@ static void sqp_one(const orc_problem *P, const orc_sqp_opts *O, double *x, doub
             if (D > 0.0) D = 0.0;
         }
         alpha = 1.0;
+        double m_last = m0;
         for (;;) {
             for (int i = 0; i < nx; i++) xt[i] = xp[i] + alpha * (x[i] - xp[i]);
             for (int i = 0; i < nu; i++) ut[i] = up[i] + alpha * (u[i] - up[i]);
             for (int i = 0; i < nl; i++) slt[i] = slp[i] + alpha * (sln[i] - slp[i]);
             const double m1 = merit_eval(P, xt, ut, slt, x0, yref, yref_e, tid, wpi, wlam, dl, du, 0);
+            m_last = m1;
             if (O->use_sufficient_descent ? (m1 - m0 <= O->eps_sufficient_descent * alpha * D) : (m1 < m0)) break;
             alpha *= O->alpha_reduction;
             if (alpha < O->alpha_min) { alpha = O->alpha_min; break; }
         }
+        /* m(0), m at the last trial step (the merit is not evaluated at alpha_min), D, the infeasibility part of m(0) */
+        if (merit) { merit[0] = m0; merit[1] = m_last; merit[2] = D; merit[3] = eqi; }
         for (int i = 0; i < nx; i++) x[i] = xp[i] + alpha * (x[i] - xp[i]);
         for (int i = 0; i < nu; i++) u[i] = up[i] + alpha * (u[i] - up[i]);
         for (int i = 0; i < nl; i++) sl[i] = slp[i] + alpha * (sln[i] - slp[i]);
@@ -463,7 +468,7 @@ static void sqp_one(const orc_problem *P, const orc_sqp_opts *O, double *x, doub
 
 void orc_sqp_solve(const orc_problem *P, const orc_sqp_opts *O, int B, double *x, double *u, const double *x0,
                    const double *yref, const double *yref_e, const int *track_id, double *pi, double *lam, double *sl,
-                   int *status, double *res, int *qp_iter, int *sqp_iter, double *alpha, int nthreads)
+                   int *status, double *res, int *qp_iter, int *sqp_iter, double *alpha, int nthreads, double *merit)
 {
     const int N = P->N;
 #ifdef _OPENMP
@@ -474,7 +479,7 @@ void orc_sqp_solve(const orc_problem *P, const orc_sqp_opts *O, int B, double *x
         sqp_one(P, O, x + (size_t)i * (N + 1) * NX, u + (size_t)i * N * NU, x0 + (size_t)i * NX, yref + (size_t)i * N * NY,
                 yref_e + (size_t)i * NX, track_id ? track_id[i] : 0, pi + (size_t)i * (N + 1) * NX,
                 lam + (size_t)i * (N + 1) * 2 * NC, sl + (size_t)i * (N + 1) * 2 * NC, status + i, res + (size_t)i * 4,
-                qp_iter + i, sqp_iter + i, alpha + i);
+                qp_iter + i, sqp_iter + i, alpha + i, merit ? merit + (size_t)i * 4 : NULL);
 }
 
 void orc_linearize(const orc_problem *P, int B, const double *x, const double *u,

@@ -303,7 +303,8 @@ class OracleProblem:
     def sqp_solve(self, x, u, x0, yref, yref_e, track_id=None, pi=None, lam=None, sl=None, max_iter=2, globalization="MERIT_BACKTRACKING",
                   tol=1e-6, alpha_min=0.05, alpha_reduction=0.7, eps_sufficient_descent=1e-4, use_sufficient_descent=False,
                   full_step_dual=False, nthreads=0):
-        """Globalised SQP (``orc_sqp_solve``); ``x``, ``u`` (and ``pi``, ``lam``, ``sl`` when given) are updated IN PLACE."""
+        """Globalised SQP (``orc_sqp_solve``); ``x``, ``u`` (and ``pi``, ``lam``, ``sl`` when given) are updated IN PLACE.
+        ``out["merit"]`` (B,4): m(0), m at the last trial step, D, the infeasibility part of m(0) of each instance's last line search."""
         N = self.N
         assert x.dtype == np.float64 and x.flags.c_contiguous and u.dtype == np.float64 and u.flags.c_contiguous
         B = x.shape[0]
@@ -319,12 +320,12 @@ class OracleProblem:
         for i, t in enumerate(np.broadcast_to(np.asarray(tol, dtype=np.float64), (4,))): o.tol[i] = float(t)
         o.alpha_min, o.alpha_reduction, o.eps_sufficient_descent = float(alpha_min), float(alpha_reduction), float(eps_sufficient_descent)
         status = np.zeros(B, dtype=np.int32); res = np.zeros((B, 4)); qp_iter = np.zeros(B, dtype=np.int32)
-        sqp_iter = np.zeros(B, dtype=np.int32); alpha = np.zeros(B)
+        sqp_iter = np.zeros(B, dtype=np.int32); alpha = np.zeros(B); merit = np.zeros((B, 4))
         lib().orc_sqp_solve(C.byref(self.p), C.byref(o), C.c_int(B), x.ctypes.data_as(_dp), u.ctypes.data_as(_dp), x0p, yp, yep, tp,
                             pi.ctypes.data_as(_dp), lam.ctypes.data_as(_dp), sl.ctypes.data_as(_dp), status.ctypes.data_as(_ip),
                             res.ctypes.data_as(_dp), qp_iter.ctypes.data_as(_ip), sqp_iter.ctypes.data_as(_ip),
-                            alpha.ctypes.data_as(_dp), C.c_int(nthreads))
-        return dict(status=status, res=res, qp_iter=qp_iter, sqp_iter=sqp_iter, alpha=alpha, pi=pi, lam=lam, sl=sl)
+                            alpha.ctypes.data_as(_dp), C.c_int(nthreads), merit.ctypes.data_as(_dp))
+        return dict(status=status, res=res, qp_iter=qp_iter, sqp_iter=sqp_iter, alpha=alpha, pi=pi, lam=lam, sl=sl, merit=merit)
 
     def linearize(self, x, u, track_id=None, nthreads=0):
         N = self.N; B = x.shape[0]

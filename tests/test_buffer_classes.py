@@ -12,7 +12,7 @@ CSRC = os.path.join(ROOT, "ihm2_amd", "csrc")
 # workspace that is never poisoned, with the reason written next to its declaration: the argument blocks hold pointers and counts
 ZERO_FILLED = {"ls_args", "step_args", "sens_args"}
 
-WORKSPACE = set("""lin q_g q_rg q_P q_M scratch res qp_res dyn10 ls_phi ls_x ls_u ls_pi ls_lam ls_slk ls_wpi ls_wlam ls_alpha
+WORKSPACE = set("""lin q_g q_rg q_P q_M scratch res qp_res dyn10 ls_phi ls_x ls_u ls_pi ls_lam ls_slk ls_wpi ls_wlam ls_alpha ls_merit
                    hist_u0 hist_x0 hist_k sens_xbar sens_ubar sens_u0 sens_x sens_u adj_sx adj_su adj_gx0 adj_gy adj_gye adj_gW adj_gWe
                    step_args ls_args sens_args ls_done ls_status ls_iter ls_qp_acc ls_pending hist_st hist_it""".split())
 # (u0 is state: the plant of the next step reads the last solve's control, 0 before the first solve)

@@ -20,7 +20,7 @@ def _declared_symbols():
 def test_header_declares_the_boundary():
     syms = _declared_symbols()
     for must in ("ihm2mpc_create", "ihm2mpc_free", "ihm2mpc_solve", "ihm2mpc_set_x0", "ihm2mpc_get_u0",
-                 "ihm2mpc_get_status", "ihm2mpc_set_tracks", "ihm2mpc_set_weights", "ihm2mpc_prepare_step"):
+                 "ihm2mpc_get_status", "ihm2mpc_set_tracks", "ihm2mpc_set_weights", "ihm2mpc_prepare_step", "ihm2mpc_get_sqp_merit"):
         assert must in syms
 
 

@@ -2,7 +2,7 @@
 oracle's statement of the same algorithm (oracle/ihm2_oracle_rti.c, orc_sqp_solve)."""
 import numpy as np
 import pytest
-from conftest import make_ocp, sample_x0
+from sqp_cases import setup as _setup
 
 pytestmark = pytest.mark.gpu
 
@@ -11,46 +11,6 @@ N = 40
 
 def _rel(a, b, floor=1.0):
     return np.max(np.abs(a - b) / (floor + np.abs(b)))
-
-
-def _setup(track, model, variant, B, seed, **opts):
-    from ihm2_amd.solver import BatchedOcpSolver
-    from oracle import oracle as orc
-
-    o = dict(nlp_solver_type="SQP", globalization="MERIT_BACKTRACKING", nlp_tol=1e-3, nlp_solver_tol_eq=1e-8, nlp_solver_tol_ineq=1e-8)
-    o.update(opts)
-    ocp = make_ocp(model=model, n_max=0.6 if variant == "soft" else 2.0, **o)
-    c = ocp.constraints
-    widths = None
-    if variant == "soft":       # soft track bound on n (both sides) and soft steering-rate row
-        c.idxsbx = np.array([0]); c.idxsg = np.array([1])
-        ocp.cost.zl = np.array([50.0, 5.0]); ocp.cost.zu = np.array([50.0, 5.0])
-        ocp.cost.Zl = np.array([200.0, 20.0]); ocp.cost.Zu = np.array([200.0, 20.0])
-    if variant == "track":      # soft nonlinear track rows (old/generate_acaods_interface.py:380-449)
-        ocp.model.con_h_expr = "track"
-        c.lh = c.lh_e = np.array([-1e3, -1e3]); c.uh = c.uh_e = np.array([0.0, 0.0])
-        c.idxsh, c.idxsh_e = np.arange(2), np.arange(2)
-        ocp.cost.zl = ocp.cost.zu = ocp.cost.Zl = ocp.cost.Zu = np.full(2, 100.0)
-        ocp.cost.zl_e = ocp.cost.zu_e = ocp.cost.Zl_e = ocp.cost.Zu_e = np.full(2, 100.0)
-        widths = np.array([[1.2, 1.1]])
-    data = ocp.flatten()
-    solver = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref, track_widths=widths)
-    if data.soft_Z is not None:
-        solver.set_soft(data.soft_z, data.soft_Z)
-    P = orc.OracleProblem(data.as_dict(track.s_ref, track.kappa_ref, track_widths=widths))
-    x0 = sample_x0(track, B, seed=seed)
-    if model != "fkin6":
-        x0[:, 3] = np.linspace(6.0, 14.0, B)
-    solver.set_x0(x0); solver.init_guess()
-    u = solver.get_u()
-    u[:, :, 1] = np.clip(u[:, :, 1] + 0.1 * np.sin(np.arange(N))[None], -0.5, 0.5)     # a poor steering guess: full steps overshoot
-    solver.set_u(u)
-    yref = np.zeros((B, N, 12)); yref[:, :, 0] = x0[:, 0:1] + 40.0 * np.arange(N)[None] / N
-    yref_e = np.zeros((B, 8)); yref_e[:, 0] = x0[:, 0] + 40.0
-    if variant == "track":
-        yref[:, :, 1] = np.where(np.arange(B) % 2 == 0, 1.5, -1.5)[:, None]; yref_e[:, 1] = yref[:, 0, 1]
-    solver.set_yref(yref); solver.set_yref_e(yref_e); solver.set_multipliers(None, None)
-    return solver, P, data, x0, yref, yref_e
 
 
 @pytest.mark.parametrize("model,variant,suff", [("fkin6", "hard", False), ("fkin6", "hard", True), ("fkin6", "soft", False),

@@ -62,6 +62,9 @@ def test_backtracking_picks_steps_from_the_ladder_and_never_raises_the_merit(tra
         moved = out["sqp_iter"] == 1
         assert np.all(np.min(np.abs(out["alpha"][moved, None] - ladder[None]), axis=1) < 1e-12)
         n_short += int((out["alpha"][moved] < 1.0).sum())
+        # the merit never rises: m(alpha) < m(0) wherever a trial step was accepted (at the floor alpha_min the merit is not evaluated)
+        took = moved & (out["alpha"] > 0.05)
+        assert took.any() and np.all(out["merit"][took, 1] < out["merit"][took, 0])
         # the accepted point is the convex combination of the start and the full step of a plain RTI iteration
         xf, uf = xp.copy(), up.copy()
         P.rti_step(xf, uf, x0, yref, yref_e, pi=None if it == 0 else pi_prev, lam=None if it == 0 else lam_prev)
