@@ -15,9 +15,10 @@
 // |c_i| tau / z_i).  A side without a slack -- hard, or no finite bound -- has the gradients 0 as well.  COST: c_i = z_i + Z_i s_i and the
 // explicit partials of J are added on every slack, dJ/dz_i = s_i - zeta_s,i, dJ/dZ_i = s_i^2 / 2 - s_i zeta_s,i (one seed).
 //
-// Mapping: one wavefront per instance.  Phase 1 runs over the slot table as phase 1 of k_slack_fold does (s = lane, lane + 64, ..; the
-// row gradients at xbar, rcoef and the row evaluation restated from that file) and keeps t_i, lam_i, rho_i, s_i of every soft side in LDS
-// tables (NS, 30) -- 14 lower sides, 14 upper sides, the two sides of the lateral-acceleration row -- with lam_i = 0 for "no slack here".
+// Mapping: one wavefront per instance.  Phase 1 is the fragment sens_rows_body.hpp, the text k_sens, k_adj and k_slack_fold take their rows
+// from: the row gradients at xbar, rcoef and the walk over the slot table (s = lane, lane + 64, ..), with hooks that skip the hard slots and
+// keep t_i, lam_i, rho_i (sens_body.hpp: side_slack_terms) and s_i of every soft side in LDS tables (NS, SENS_SIDES) (sens_body.hpp:
+// sens_side), with lam_i = 0 for "no slack here".
 // Phase 2, per seed: zeta of the seed is staged in LDS, and the lane owns the sides e = lane, lane + 64, .. of the table: r_i zeta_k in
 // ascending j (over the entries of the row that rcoef does not have zero), zeta_s,i, one plain store per output entry -- no atomics, the same bits whatever the batch.  Instances whose status is
 // neither 0 nor 2 get NaN.  fp64.
@@ -27,8 +28,6 @@
 #include "sens_body.hpp"
 
 namespace {
-
-#define PG_SIDES 30     // per stage: lower sides of the rows 0..13, their upper sides, the lower and the upper side of the a_lat row
 
 struct PenaltyGradArgs {
     SensArgs s;                         // k_sens' block (sens_u0, sens_x, sens_u, hist unused)
@@ -40,7 +39,7 @@ struct PenaltyGradArgs {
 };
 
 // LDS of one instance (doubles): hc (NS*2) | ha (NS*4) | t, lam, rho, s (NS*30 each) | zeta of one seed (NS*10) | COST: c (NS*30)
-__host__ __device__ constexpr size_t penalty_grad_lds_doubles(size_t N, bool cost) { return (N + 1) * (6 + 10 + PG_SIDES * (cost ? 5 : 4)); }
+__host__ __device__ constexpr size_t penalty_grad_lds_doubles(size_t N, bool cost) { return (N + 1) * (6 + 10 + SENS_SIDES * (cost ? 5 : 4)); }
 static_assert(penalty_grad_lds_doubles(40, false) * sizeof(double) == 44608 && penalty_grad_lds_doubles(40, true) * sizeof(double) == 54448,
               "k_penalty_grad: launch LDS at N = 40");
 
@@ -66,99 +65,42 @@ __global__ __launch_bounds__(64) void k_penalty_grad(PenaltyGradArgs pa)
     double *hc = sm;                    // NS*2   d h_R / d psi, d h_L / d psi of the track rows at xbar
     double *ha = hc + NS * 2;           // NS*4   d a_lat / d (v_x, v_y, T, delta) at xbar
     double *tt = ha + NS * 4;           // NS*30  t_i of the soft sides
-    double *lmt = tt + NS * PG_SIDES;   // NS*30  lam_i, 0 = no slack here (or a dropped side)
-    double *rho = lmt + NS * PG_SIDES;  // NS*30  rho_i
-    double *slt = rho + NS * PG_SIDES;  // NS*30  s_i
-    double *zl = slt + NS * PG_SIDES;   // NS*10  zeta of the seed at hand
+    double *lmt = tt + NS * SENS_SIDES; // NS*30  lam_i, 0 = no slack here (or a dropped side)
+    double *rho = lmt + NS * SENS_SIDES;    // NS*30  rho_i
+    double *slt = rho + NS * SENS_SIDES;    // NS*30  s_i
+    double *zl = slt + NS * SENS_SIDES; // NS*10  zeta of the seed at hand
     double *cof = zl + NS * 10;         // NS*30  COST: c_i
 
-    const double *xb = a.xbar + bs * NS * 8, *ubb = a.ubar + bs * N * 2;
-    const double *xo = a.x + bs * NS * 8, *uo = a.u + bs * N * 2;
-    const double *lamb = a.lam + bs * NS * 28, *slkb = a.slk + bs * NS * 28;
-    const double *lamab = a.lam_a + bs * NS * 2, *slkab = a.slk_a + bs * NS * 2;
-    const double *slb = a.slot_lb + bs * a.sl_bs, *sub = a.slot_ub + bs * a.sl_bs;
-
-    // ---- row gradients of the nonlinear rows at xbar (kernels_slackseed.hip), the marker table zeroed ----
-    double w_R = 0.0, w_L = 0.0;
-    if (a.path) {
-        const int trk = a.track_id[b];
-        w_R = a.widths[trk * 2 + 0]; w_L = a.widths[trk * 2 + 1];
-    }
-    for (int k = lane; k < NS; k += 64) {
-        const double psi = xb[k * 8 + 2], sgn = (psi > 0.0) - (psi < 0.0);
-        const double dfoot = -0.5 * a.car_L * cos(fabs(psi)) * sgn, dlat = -0.5 * a.car_W * sin(psi);
-        hc[k * 2 + 0] = (a.path && k >= 1) ? dfoot + dlat : 0.0;
-        hc[k * 2 + 1] = (a.path && k >= 1) ? -dfoot + dlat : 0.0;
-        double g4[4] = {0.0, 0.0, 0.0, 0.0};
-        if (a.alat && k >= 1 && k < N) ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
-#pragma unroll
-        for (int q = 0; q < 4; q++) ha[k * 4 + q] = g4[q];
-    }
-    for (int e = lane; e < NS * PG_SIDES; e += 64) {
-        lmt[e] = 0.0;
-        if (COST) slt[e] = 0.0;         // the explicit partials are taken on every side: 0 where there is no slack
-    }
-    WSYNC();
-
-    // coefficient of row c of stage k on the variable j of z_k = (dx_k, du_k)
-    auto rcoef = [&](int k, int c, int j) -> double {
-        if (c < 10) return (j == c) ? 1.0 : 0.0;
-        if (c < 12) return a.CD[((size_t)k * 2 + (c - 10)) * 10 + j];
-        if (c < 14) return (j == 1) ? ((c == 12) ? 1.0 : -1.0) : (j == 2) ? hc[k * 2 + (c - 12)] : 0.0;
-        return (j == 3) ? ha[k * 4] : (j == 4) ? ha[k * 4 + 1] : (j == 6) ? ha[k * 4 + 2] : (j == 7) ? ha[k * 4 + 3] : 0.0;
-    };
-    // t, lam, rho, s of one soft side into entry e of the tables: t, nu and rho as side_slack_share forms them (sens_body.hpp)
+    // t, lam, rho, s of one soft side into entry e of the tables
     auto keep_side = [&](int e, double lm, double gap, double sl, double zw, double Zw) {
         slt[e] = sl;
         if (!(lm > 0.0)) return;        // a dropped side: the marker stays 0
-        const double nu = fmax(zw + Zw * sl - lm, 0.0);
-        tt[e] = fmax(gap, a.tau);
+        side_slack_terms(lm, gap, sl, zw, Zw, a.tau, tt[e], rho[e]);
         lmt[e] = lm;
-        rho[e] = Zw + nu / fmax(sl, a.tau);
         if (COST) cof[e] = fma(Zw, sl, zw);
     };
 
-    // ======== phase 1: the terms of every soft side, each entry of the slot table on the lane that owns it in the QP ========
-    for (int s = lane; s < a.nslots; s += 64) {
-        const int kc = a.slot_kc[s];
-        if (kc < 0) continue;
-        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s];
-        if (!(Zw >= 0.0)) continue;         // a hard slot: no slack
-        const int k = kc >> 4, c = kc & 15;
-        // row value at xbar (as the QP forms it) and the row times the step
-        double cz, rdz = 0.0;
-        if (c < 8) cz = xb[k * 8 + c];
-        else if (c < 10) cz = ubb[k * 2 + c - 8];
-        else if (c == 14) {
-            double g4[4];
-            cz = ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
-        } else if (c >= 12) {
-            const double n = xb[k * 8 + 1], psi = xb[k * 8 + 2];
-            const double foot = -0.5 * a.car_L * sin(fabs(psi)), lat = 0.5 * a.car_W * cos(psi);
-            cz = (c == 12) ? n + foot + lat - w_R : -n - foot + lat - w_L;
-        } else {
-            cz = 0.0;
-            for (int j = 0; j < 8; j++) cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + j], xb[k * 8 + j], cz);
-            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 8], ubb[k * 2 + 0], cz);
-            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 9], ubb[k * 2 + 1], cz);
-        }
-        for (int j = 0; j < 10; j++) {
-            const double dzj = (j < 8) ? xo[k * 8 + j] - xb[k * 8 + j] : (k < N) ? uo[k * 2 + j - 8] - ubb[k * 2 + j - 8] : 0.0;
-            rdz = fma(rcoef(k, c, j), dzj, rdz);
-        }
-        const double lb = slb[s], ub = sub[s];
-        if (sfin(lb)) {
-            const double lm = (c == 14) ? lamab[k * 2] : lamb[k * 28 + c];
-            const double sl = (c == 14) ? slkab[k * 2] : slkb[k * 28 + c];
-            keep_side(k * PG_SIDES + ((c == 14) ? 28 : c), lm, rdz - (lb - cz) + sl, sl, zw, Zw);
-        }
-        if (sfin(ub)) {
-            const double lm = (c == 14) ? lamab[k * 2 + 1] : lamb[k * 28 + 14 + c];
-            const double sl = (c == 14) ? slkab[k * 2 + 1] : slkb[k * 28 + 14 + c];
-            keep_side(k * PG_SIDES + ((c == 14) ? 29 : 14 + c), lm, (ub - cz) - rdz + sl, sl, zw, Zw);
-        }
+    // ======== phase 1: the rows at xbar (sens_rows_body.hpp); the terms of every soft side, the marker table zeroed ========
+#define SENS_ROWS_CLEAR                                    \
+    for (int e = lane; e < NS * SENS_SIDES; e += 64) {     \
+        lmt[e] = 0.0;                                      \
+        if (COST) slt[e] = 0.0;         /* the explicit partials are taken on every side: 0 where there is no slack */ \
     }
-    WSYNC();
+#define SENS_ROWS_SLOT_OPEN(s)                             \
+        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s]; \
+        if (!(Zw >= 0.0)) continue;         // a hard slot: no slack
+#define SENS_ROWS_SLOT_BEGIN(s)
+#define SENS_ROWS_SIDE(k, c, up, LM, GAP, SL)              \
+            const double lm = LM;                          \
+            const double sl = SL;                          \
+            keep_side(k * SENS_SIDES + sens_side(c, up), lm, GAP + sl, sl, zw, Zw);
+#define SENS_ROWS_SLOT_END(k, c)
+#include "sens_rows_body.hpp"
+#undef SENS_ROWS_CLEAR
+#undef SENS_ROWS_SLOT_OPEN
+#undef SENS_ROWS_SLOT_BEGIN
+#undef SENS_ROWS_SIDE
+#undef SENS_ROWS_SLOT_END
 
     // ======== phase 2: per seed, zeta_s of the sides this lane owns and the two gradients, one store per output entry ========
     for (int q = 0; q < S; q++) {
@@ -168,11 +110,11 @@ __global__ __launch_bounds__(64) void k_penalty_grad(PenaltyGradArgs pa)
         if (q > 0) WSYNC();             // every lane is done with the last seed's zeta
         for (int e = lane; e < NS * 10; e += 64) zl[e] = zq[e];
         WSYNC();
-        for (int e = lane; e < NS * PG_SIDES; e += 64) {
-            const int k = e / PG_SIDES, o = e - k * PG_SIDES;
-            const bool al = o >= 28;                        // a side of the a_lat row
-            const int c = al ? 14 : (o < 14) ? o : o - 14;
-            const double sgn = (al ? o == 28 : o < 14) ? 1.0 : -1.0;
+        for (int e = lane; e < NS * SENS_SIDES; e += 64) {
+            const int k = e / SENS_SIDES, o = e - k * SENS_SIDES;
+            const bool al = o >= 28;                        // a side of the a_lat row: its outputs are grad_za / grad_Za [o - 28]
+            const int c = sens_side_row(o);
+            const double sgn = sens_side_upper(o) ? -1.0 : 1.0;
             const double lm = lmt[e];
             double dz = 0.0, dZ = 0.0;
             if (lm != 0.0) {            // a side without a slack is not read

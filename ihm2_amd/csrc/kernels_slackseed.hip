@@ -9,11 +9,10 @@
 // -- gamma_i = sigma_i / rho_i is the share of a row move that the slack takes (1 for rho_i = 0, 0 for lam_i = 0).  Everything behind
 // the fold is k_adj, unchanged.  For the cost (COST) c_i = dJ_slack / ds_i = z_i + Z_i s_i, from the penalties and slacks themselves.
 //
-// Mapping: one wavefront per instance.  Phase 1 runs over the slot table exactly as the row-weight phase of sens_factor_body.hpp does
-// (s = lane, lane + 64, ..: a split row's halves are on one lane) and writes gamma_i of every soft side into one LDS table (NS, 30):
-// 14 lower sides, 14 upper sides, the two sides of the lateral-acceleration row.  The row gradients at xbar (hc, ha), rcoef and the row
-// evaluation of a slot mirror that fragment statement by statement; the fragment itself is not included, since it carries the Riccati
-// sweep.  Phase 2, per seed: the lane owns the entries (k, j) of seed_z with k * 10 + j = lane, lane + 64, .. and subtracts
+// Mapping: one wavefront per instance.  Phase 1 is the fragment sens_rows_body.hpp, the text k_sens and k_adj take their rows from: the row
+// gradients at xbar (hc, ha), rcoef and the walk over the slot table (s = lane, lane + 64, ..: a split row's halves are on one lane), with
+// hooks that skip the hard slots and write gamma_i of every soft side into one LDS table (NS, SENS_SIDES) (sens_body.hpp: sens_side).
+// Phase 2, per seed: the lane owns the entries (k, j) of seed_z with k * 10 + j = lane, lane + 64, .. and subtracts
 // sum_c rcoef(k, c, j) (c_lower gamma_lower - c_upper gamma_upper) in ascending c -- one read-modify-write per entry, no atomics, the
 // same bits whatever the batch.  Instances whose status is neither 0 nor 2 are skipped (k_adj writes NaN gradients for them).  fp64.
 #include <cmath>
@@ -23,8 +22,6 @@
 
 namespace {
 
-#define FOLD_SIDES 30   // per stage: lower sides of the rows 0..13, their upper sides, the lower and the upper side of the a_lat row
-
 struct FoldArgs {
     SensArgs s;                         // k_sens' block (sens_u0, sens_x, sens_u, hist unused)
     int n_seeds;                        // 1..8 (COST: 1)
@@ -33,7 +30,7 @@ struct FoldArgs {
 };
 
 // LDS of one instance (doubles): hc (NS*2) | ha (NS*4) | gamma (NS*30) | COST: c (NS*30)
-__host__ __device__ constexpr size_t fold_lds_doubles(size_t N, bool cost) { return (N + 1) * (6 + FOLD_SIDES * (cost ? 2 : 1)); }
+__host__ __device__ constexpr size_t fold_lds_doubles(size_t N, bool cost) { return (N + 1) * (6 + SENS_SIDES * (cost ? 2 : 1)); }
 static_assert(fold_lds_doubles(40, false) * sizeof(double) == 11808 && fold_lds_doubles(40, true) * sizeof(double) == 21648,
               "k_slack_fold: launch LDS at N = 40");
 
@@ -52,87 +49,29 @@ __global__ __launch_bounds__(64) void k_slack_fold(FoldArgs fa)
     double *hc = sm;                    // NS*2   d h_R / d psi, d h_L / d psi of the track rows at xbar
     double *ha = hc + NS * 2;           // NS*4   d a_lat / d (v_x, v_y, T, delta) at xbar
     double *gam = ha + NS * 4;          // NS*30  gamma_i of the soft sides, 0 elsewhere
-    double *cof = gam + NS * FOLD_SIDES;    // NS*30  COST: c_i of the same sides
+    double *cof = gam + NS * SENS_SIDES;    // NS*30  COST: c_i of the same sides
 
     const size_t bs = (size_t)b;
-    const double *xb = a.xbar + bs * NS * 8, *ubb = a.ubar + bs * N * 2;
-    const double *xo = a.x + bs * NS * 8, *uo = a.u + bs * N * 2;
-    const double *lamb = a.lam + bs * NS * 28, *slkb = a.slk + bs * NS * 28;
-    const double *lamab = a.lam_a + bs * NS * 2, *slkab = a.slk_a + bs * NS * 2;
-    const double *slb = a.slot_lb + bs * a.sl_bs, *sub = a.slot_ub + bs * a.sl_bs;
 
-    // ---- row gradients of the nonlinear rows at xbar (sens_factor_body.hpp), the table zeroed ----
-    double w_R = 0.0, w_L = 0.0;
-    if (a.path) {
-        const int trk = a.track_id[b];
-        w_R = a.widths[trk * 2 + 0]; w_L = a.widths[trk * 2 + 1];
-    }
-    for (int k = lane; k < NS; k += 64) {
-        const double psi = xb[k * 8 + 2], sgn = (psi > 0.0) - (psi < 0.0);
-        const double dfoot = -0.5 * a.car_L * cos(fabs(psi)) * sgn, dlat = -0.5 * a.car_W * sin(psi);
-        hc[k * 2 + 0] = (a.path && k >= 1) ? dfoot + dlat : 0.0;
-        hc[k * 2 + 1] = (a.path && k >= 1) ? -dfoot + dlat : 0.0;
-        double g4[4] = {0.0, 0.0, 0.0, 0.0};
-        if (a.alat && k >= 1 && k < N) ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
-#pragma unroll
-        for (int q = 0; q < 4; q++) ha[k * 4 + q] = g4[q];
-    }
-    for (int e = lane; e < NS * FOLD_SIDES; e += 64) gam[e] = 0.0;
-    WSYNC();
-
-    // coefficient of row c of stage k on the variable j of z_k = (dx_k, du_k)
-    auto rcoef = [&](int k, int c, int j) -> double {
-        if (c < 10) return (j == c) ? 1.0 : 0.0;
-        if (c < 12) return a.CD[((size_t)k * 2 + (c - 10)) * 10 + j];
-        if (c < 14) return (j == 1) ? ((c == 12) ? 1.0 : -1.0) : (j == 2) ? hc[k * 2 + (c - 12)] : 0.0;
-        return (j == 3) ? ha[k * 4] : (j == 4) ? ha[k * 4 + 1] : (j == 6) ? ha[k * 4 + 2] : (j == 7) ? ha[k * 4 + 3] : 0.0;
-    };
-
-    // ======== phase 1: gamma of every soft side, each entry of the slot table on the lane that owns it in the QP ========
-    for (int s = lane; s < a.nslots; s += 64) {
-        const int kc = a.slot_kc[s];
-        if (kc < 0) continue;
-        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s];
+    // ======== phase 1: the rows at xbar (sens_rows_body.hpp); gamma of every soft side, 0 elsewhere ========
+#define SENS_ROWS_CLEAR for (int e = lane; e < NS * SENS_SIDES; e += 64) gam[e] = 0.0;
+#define SENS_ROWS_SLOT_OPEN(s)                             \
+        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s]; \
         if (!(Zw >= 0.0)) continue;         // a hard slot: no slack
-        const int k = kc >> 4, c = kc & 15;
-        // row value at xbar (as the QP forms it) and the row times the step
-        double cz, rdz = 0.0;
-        if (c < 8) cz = xb[k * 8 + c];
-        else if (c < 10) cz = ubb[k * 2 + c - 8];
-        else if (c == 14) {
-            double g4[4];
-            cz = ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
-        } else if (c >= 12) {
-            const double n = xb[k * 8 + 1], psi = xb[k * 8 + 2];
-            const double foot = -0.5 * a.car_L * sin(fabs(psi)), lat = 0.5 * a.car_W * cos(psi);
-            cz = (c == 12) ? n + foot + lat - w_R : -n - foot + lat - w_L;
-        } else {
-            cz = 0.0;
-            for (int j = 0; j < 8; j++) cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + j], xb[k * 8 + j], cz);
-            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 8], ubb[k * 2 + 0], cz);
-            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 9], ubb[k * 2 + 1], cz);
-        }
-        for (int j = 0; j < 10; j++) {
-            const double dzj = (j < 8) ? xo[k * 8 + j] - xb[k * 8 + j] : (k < N) ? uo[k * 2 + j - 8] - ubb[k * 2 + j - 8] : 0.0;
-            rdz = fma(rcoef(k, c, j), dzj, rdz);
-        }
-        const double lb = slb[s], ub = sub[s];
-        if (sfin(lb)) {
-            const double lm = (c == 14) ? lamab[k * 2] : lamb[k * 28 + c];
-            const double sl = (c == 14) ? slkab[k * 2] : slkb[k * 28 + c];
-            const int e = k * FOLD_SIDES + ((c == 14) ? 28 : c);
-            gam[e] = side_slack_share(lm, rdz - (lb - cz) + sl, sl, zw, Zw, a.tau);
+#define SENS_ROWS_SLOT_BEGIN(s)
+#define SENS_ROWS_SIDE(k, c, up, LM, GAP, SL)              \
+            const double lm = LM;                          \
+            const double sl = SL;                          \
+            const int e = k * SENS_SIDES + sens_side(c, up); \
+            gam[e] = side_slack_share(lm, GAP + sl, sl, zw, Zw, a.tau); \
             if (COST) cof[e] = fma(Zw, sl, zw);
-        }
-        if (sfin(ub)) {
-            const double lm = (c == 14) ? lamab[k * 2 + 1] : lamb[k * 28 + 14 + c];
-            const double sl = (c == 14) ? slkab[k * 2 + 1] : slkb[k * 28 + 14 + c];
-            const int e = k * FOLD_SIDES + ((c == 14) ? 29 : 14 + c);
-            gam[e] = side_slack_share(lm, (ub - cz) - rdz + sl, sl, zw, Zw, a.tau);
-            if (COST) cof[e] = fma(Zw, sl, zw);
-        }
-    }
-    WSYNC();
+#define SENS_ROWS_SLOT_END(k, c)
+#include "sens_rows_body.hpp"
+#undef SENS_ROWS_CLEAR
+#undef SENS_ROWS_SLOT_OPEN
+#undef SENS_ROWS_SLOT_BEGIN
+#undef SENS_ROWS_SIDE
+#undef SENS_ROWS_SLOT_END
 
     // ======== phase 2: the fold, one read-modify-write per entry of seed_z and per seed ========
     for (int q = 0; q < S; q++) {
@@ -141,7 +80,7 @@ __global__ __launch_bounds__(64) void k_slack_fold(FoldArgs fa)
         const double *sa = (!COST && fa.seed_sa) ? fa.seed_sa + (bs * S + q) * NS * 2 : nullptr;
         // sum over the two sides of row c of sgn c gamma, lower before upper; a side without a slack (gamma = 0) is not read
         auto share = [&](int k, int c) -> double {
-            const int lo = k * FOLD_SIDES + ((c == 14) ? 28 : c), up = k * FOLD_SIDES + ((c == 14) ? 29 : 14 + c);
+            const int lo = k * SENS_SIDES + sens_side(c, false), up = k * SENS_SIDES + sens_side(c, true);
             const double gl = gam[lo], gu = gam[up];
             double t = 0.0;
             if (gl != 0.0) {

@@ -18,7 +18,7 @@ namespace {
 static_assert(SENS_NR == ihm2::SENS_ROWS, "sens_factor_lds_doubles counts other rows than the carve-up");
 using ihm2::sens_factor_lds_doubles;
 
-#define SSYNC() WSYNC()      // (the name the 16 hand-offs of sens_body, sens_factor_body.hpp and kernels_adj.hip were written with)
+#define SSYNC() WSYNC()      // (the name the 14 hand-offs of sens_body, sens_factor_body.hpp and kernels_adj.hip were written with)
 
 __device__ __forceinline__ bool sfin(double v) { return fabs(v) < SENS_INF; }
 
@@ -33,16 +33,32 @@ __device__ __forceinline__ double side_sigma(double lm, double gap, double sl, d
     return lm * rho / (t * rho + lm);          // 1 / (t / lm + 1 / rho), finite for rho = 0
 }
 
+// t and rho of one soft side (arguments as side_sigma's, Zw >= 0, lm > 0), as side_sigma forms them
+__device__ __forceinline__ void side_slack_terms(double lm, double gap, double sl, double zw, double Zw, double tau, double &t, double &rho)
+{
+    t = fmax(gap, tau);
+    const double nu = fmax(zw + Zw * sl - lm, 0.0);
+    rho = Zw + nu / fmax(sl, tau);
+}
+
 // gamma of one soft side (arguments as side_sigma's, Zw >= 0): the share sigma / rho of a move of the row that its slack takes, which is what
-// carries a seed on the slack onto the stage variables (kernels_slackseed.hip) -- t, nu and rho as side_sigma forms them
+// carries a seed on the slack onto the stage variables (kernels_slackseed.hip)
 __device__ __forceinline__ double side_slack_share(double lm, double gap, double sl, double zw, double Zw, double tau)
 {
     if (!(lm > 0.0)) return 0.0;
-    const double t = fmax(gap, tau);
-    const double nu = fmax(zw + Zw * sl - lm, 0.0);
-    const double rho = Zw + nu / fmax(sl, tau);
+    double t, rho;
+    side_slack_terms(lm, gap, sl, zw, Zw, tau, t, rho);
     return lm / (t * rho + lm);                // finite for rho = 0, where it is 1
 }
+
+// The sides of one stage as the tables of k_slack_fold and k_penalty_grad hold them (kernels_slackseed.hip, kernels_penaltygrad.hip):
+// the layout of lam / slk -- the lower sides of the rows 0..13, then their upper sides -- and behind it the lower and the upper side of
+// the lateral-acceleration row (lam_a / slk_a).
+#define SENS_SIDES 30
+__device__ __forceinline__ int sens_side(int c, bool upper) { return upper ? ((c == 14) ? 29 : 14 + c) : ((c == 14) ? 28 : c); }
+// ... and back: the row of side o, and whether o is its upper side
+__device__ __forceinline__ int sens_side_row(int o) { return (o >= 28) ? 14 : (o < 14) ? o : o - 14; }
+__device__ __forceinline__ bool sens_side_upper(int o) { return (o >= 28) ? o == 29 : o >= 14; }
 
 // The body of k_sens for instance b on the calling wavefront (lane = threadIdx.x), sm the block's dynamic LDS (written before it is
 // read).  step: the control step of the persistent loop (k_sens: 0) -- the row of a.hist it writes, and the forward sweep of mode 2 runs

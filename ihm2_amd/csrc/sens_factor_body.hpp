@@ -1,93 +1,37 @@
-// sens_factor_body.hpp -- the factorisation both sensitivities differentiate (formulas: top of kernels_sens.hip): the row gradients of the
-// track rows and the a_lat row at xbar, rcoef, the row weights over the slot table (side_sigma), htilde, the backward Riccati sweep on Ht.
+// sens_factor_body.hpp -- the factorisation both sensitivities differentiate (formulas: top of kernels_sens.hip): the row weights over the
+// slot table (side_sigma) on the constraint rows at xbar, htilde, the backward Riccati sweep on Ht.  The rows themselves -- their gradients
+// at xbar, rcoef, the walk over the slot table -- are the fragment sens_rows_body.hpp, included here with the hooks that form the weights.
 // A code fragment, not a header (no include guard, no namespace, no function of its own): sens_body (sens_body.hpp) and k_adj
 // (kernels_adj.hip) #include it behind their LDS carve-up and early return, so that the compiler reads the same statements in both --
 // as functions the pieces changed the register allocation of both kernels (NOTES.md R5.6).
 //   Expects in scope: a (const SensArgs &), b, bs, lane, N, NS and the LDS pointers w, hc, ha, Kl, P, Al, Bl, Ht, PA, PB, Q.
 //   Leaves in scope: linb, ra, rbv (both kernels' later sweeps), xo, uo (k_adj's weight gradients) and every other local, the lambdas
-//   included: include it once per function body.
+//   and what sens_rows_body.hpp leaves included: include it once per function body.
 //   SENS_FACTOR_KEEP_QUU_INV(k, m, j, i0, i1): the includer's statement on the lanes < 16 of stage k, (i0, i1) = row m of Quu_k^-1.
 #ifndef SENS_FACTOR_KEEP_QUU_INV
 #error "define SENS_FACTOR_KEEP_QUU_INV (sens_body: empty, k_adj: the store of Quu_k^-1) before including sens_factor_body.hpp"
 #endif
-    const double *xb = a.xbar + bs * NS * 8, *ubb = a.ubar + bs * N * 2;
-    const double *xo = a.x + bs * NS * 8, *uo = a.u + bs * N * 2;
-    const double *lamb = a.lam + bs * NS * 28, *slkb = a.slk + bs * NS * 28;
-    const double *lamab = a.lam_a + bs * NS * 2, *slkab = a.slk_a + bs * NS * 2;
     const double *linb = a.lin + bs * N * LIN_REC;
     const double *Hs0 = a.Hs + bs * a.hs_bs, *HsT = Hs0 + a.hs_te;
-    const double *slb = a.slot_lb + bs * a.sl_bs, *sub = a.slot_ub + bs * a.sl_bs;
 
-    // ---- row gradients of the nonlinear rows at xbar, zero weights ----
-    double w_R = 0.0, w_L = 0.0;
-    if (a.path) {
-        const int trk = a.track_id[b];
-        w_R = a.widths[trk * 2 + 0]; w_L = a.widths[trk * 2 + 1];
-    }
-    for (int k = lane; k < NS; k += 64) {
-        // the track rows as the QP forms them (kernels_qp.hip: qp_wave_body), stages 1..N
-        const double psi = xb[k * 8 + 2], sgn = (psi > 0.0) - (psi < 0.0);
-        const double dfoot = -0.5 * a.car_L * cos(fabs(psi)) * sgn, dlat = -0.5 * a.car_W * sin(psi);
-        hc[k * 2 + 0] = (a.path && k >= 1) ? dfoot + dlat : 0.0;
-        hc[k * 2 + 1] = (a.path && k >= 1) ? -dfoot + dlat : 0.0;
-        double g4[4] = {0.0, 0.0, 0.0, 0.0};
-        if (a.alat && k >= 1 && k < N) ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
-#pragma unroll
-        for (int q = 0; q < 4; q++) ha[k * 4 + q] = g4[q];
-    }
-    for (int e = lane; e < NS * SENS_NR; e += 64) w[e] = 0.0;
-    SSYNC();
-
-    // coefficient of row c of stage k on the variable j of z_k = (dx_k, du_k)
-    auto rcoef = [&](int k, int c, int j) -> double {
-        if (c < 10) return (j == c) ? 1.0 : 0.0;
-        if (c < 12) return a.CD[((size_t)k * 2 + (c - 10)) * 10 + j];
-        if (c < 14) return (j == 1) ? ((c == 12) ? 1.0 : -1.0) : (j == 2) ? hc[k * 2 + (c - 12)] : 0.0;
-        return (j == 3) ? ha[k * 4] : (j == 4) ? ha[k * 4 + 1] : (j == 6) ? ha[k * 4 + 2] : (j == 7) ? ha[k * 4 + 3] : 0.0;
-    };
-
-    // ---- row weights: every entry of the slot table on the lane that owns it in the QP (a split row's halves share a lane: no race) ----
-    for (int s = lane; s < a.nslots; s += 64) {
-        const int kc = a.slot_kc[s];
-        if (kc < 0) continue;
-        const int k = kc >> 4, c = kc & 15;
-        // row value at xbar (as the QP forms it) and the row times the step
-        double cz, rdz = 0.0;
-        if (c < 8) cz = xb[k * 8 + c];
-        else if (c < 10) cz = ubb[k * 2 + c - 8];
-        else if (c == 14) {
-            double g4[4];
-            cz = ihm2::alat_eval(xb[k * 8 + 3], xb[k * 8 + 4], xb[k * 8 + 6], xb[k * 8 + 7], g4);
-        } else if (c >= 12) {
-            const double n = xb[k * 8 + 1], psi = xb[k * 8 + 2];
-            const double foot = -0.5 * a.car_L * sin(fabs(psi)), lat = 0.5 * a.car_W * cos(psi);
-            cz = (c == 12) ? n + foot + lat - w_R : -n - foot + lat - w_L;
-        } else {
-            cz = 0.0;
-            for (int j = 0; j < 8; j++) cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + j], xb[k * 8 + j], cz);
-            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 8], ubb[k * 2 + 0], cz);
-            cz = fma(a.CD[((size_t)k * 2 + (c - 10)) * 10 + 9], ubb[k * 2 + 1], cz);
-        }
-        for (int j = 0; j < 10; j++) {
-            const double dzj = (j < 8) ? xo[k * 8 + j] - xb[k * 8 + j] : (k < N) ? uo[k * 2 + j - 8] - ubb[k * 2 + j - 8] : 0.0;
-            rdz = fma(rcoef(k, c, j), dzj, rdz);
-        }
-        const double lb = slb[s], ub = sub[s], zw = a.slot_zw[s], Zw = a.slot_Zw[s];
-        const bool soft = Zw >= 0.0;
+    // ---- row weights w = sigma_lower + sigma_upper of every row: a hard side (Zw < 0) has no slack, and its slk is not read ----
+#define SENS_ROWS_CLEAR for (int e = lane; e < NS * SENS_NR; e += 64) w[e] = 0.0;
+#define SENS_ROWS_SLOT_OPEN(s)
+#define SENS_ROWS_SLOT_BEGIN(s)                            \
+        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s]; \
+        const bool soft = Zw >= 0.0;                       \
         double sig = 0.0;
-        if (sfin(lb)) {
-            const double lm = (c == 14) ? lamab[k * 2] : lamb[k * 28 + c];
-            const double sl = soft ? ((c == 14) ? slkab[k * 2] : slkb[k * 28 + c]) : 0.0;
-            sig += side_sigma(lm, rdz - (lb - cz) + sl, sl, zw, Zw, a.tau);
-        }
-        if (sfin(ub)) {
-            const double lm = (c == 14) ? lamab[k * 2 + 1] : lamb[k * 28 + 14 + c];
-            const double sl = soft ? ((c == 14) ? slkab[k * 2 + 1] : slkb[k * 28 + 14 + c]) : 0.0;
-            sig += side_sigma(lm, (ub - cz) - rdz + sl, sl, zw, Zw, a.tau);
-        }
-        w[k * SENS_NR + c] += sig;
-    }
-    SSYNC();
+#define SENS_ROWS_SIDE(k, c, up, LM, GAP, SL)              \
+            const double lm = LM;                          \
+            const double sl = soft ? (SL) : 0.0;           \
+            sig += side_sigma(lm, GAP + sl, sl, zw, Zw, a.tau);
+#define SENS_ROWS_SLOT_END(k, c) w[k * SENS_NR + c] += sig;
+#include "sens_rows_body.hpp"
+#undef SENS_ROWS_CLEAR
+#undef SENS_ROWS_SLOT_OPEN
+#undef SENS_ROWS_SLOT_BEGIN
+#undef SENS_ROWS_SIDE
+#undef SENS_ROWS_SLOT_END
 
     // entry (i, j) of Ht_k = H_k + sum_c w_c r_c r_c'
     auto htilde = [&](int k, int i, int j) -> double {

@@ -76,6 +76,29 @@ def test_sensitivity_factorisation_is_written_once():
     assert calls == defs
 
 
+def test_constraint_rows_at_xbar_are_written_once():
+    """k_sens, k_adj, k_slack_fold and k_penalty_grad differentiate the same constraint rows: rcoef is defined in one file of csrc, the
+    fragment all four include; the row evaluation (the track rows' `dfoot`) stands there and in kernels_qp.hip, which forms the QP's own
+    rows, and nowhere else; side_slack_share is defined in one file."""
+    csrc = os.path.join(ROOT, "ihm2_amd", "csrc")
+    rcoef, rows, share = [], [], []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp", ".h", ".cpp")):
+            continue
+        code = re.sub(r"//.*", "", open(os.path.join(csrc, f), errors="ignore").read())
+        if "auto rcoef = " in code:
+            rcoef.append(f)
+        if re.search(r"\bdfoot\b", code):
+            rows.append(f)
+        if re.search(r"\bdouble side_slack_share\(", code):
+            share.append(f)
+    assert len(rcoef) == 1, f"rcoef is defined in {rcoef}"
+    assert rows == sorted(["kernels_qp.hip"] + rcoef), f"the row evaluation is written in {rows}"
+    assert len(share) == 1, f"side_slack_share is defined in {share}"
+    for f in ("sens_factor_body.hpp", "kernels_slackseed.hip", "kernels_penaltygrad.hip"):      # ... and every user includes that file
+        assert f'#include "{rcoef[0]}"' in open(os.path.join(csrc, f)).read(), f
+
+
 def test_lean_trig_functions_of_the_models_match_libm(tmp_path):
     """The models' sincos / tanh (csrc/model.hpp: fast_sincos, tanh_e) restated in C with the same constants and operation order:
     within 2.5e-16 absolute of libm over +-64 rad / +-200 (tools/probes/check_fast_trig.c)."""
