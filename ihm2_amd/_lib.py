@@ -56,6 +56,8 @@ SYMBOLS = {
     "ihm2mpc_set_bounds": (C.c_int, [_H] + [c_double_p] * 8),
     "ihm2mpc_set_instance_weights": (C.c_int, [_H, c_double_p, c_double_p]),
     "ihm2mpc_set_instance_bounds": (C.c_int, [_H] + [c_double_p] * 6),
+    "ihm2mpc_set_instance_soft": (C.c_int, [_H, c_double_p, c_double_p]),
+    "ihm2mpc_set_instance_alat_soft": (C.c_int, [_H, c_double_p, c_double_p]),
     "ihm2mpc_set_soft": (C.c_int, [_H, c_double_p, c_double_p]),
     "ihm2mpc_set_path_constraints": (C.c_int, [_H, C.c_int32, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
     "ihm2mpc_set_alat_constraint": (C.c_int, [_H, C.c_int32, C.c_double, C.c_double, c_double_p, c_double_p]),

@@ -125,6 +125,51 @@ def instance_tuning(B: int, weights: dict, limits: dict, nknots: int, Nf: int, *
     return inst_w, inst_b
 
 
+def _first(v):
+    return v if np.ndim(v) == 0 else float(np.asarray(v).reshape(-1)[0])
+
+
+def _first_pair(pair):
+    return None if pair is None else tuple(_first(v) for v in pair)
+
+
+def instance_penalties(B: int, limits: dict, nknots: int, Nf: int, soft_state_bounds: tuple | None = None,
+                       track_rows_penalty: tuple | None = (100.0, 100.0), **ocp_kw):
+    """Per-instance slack penalties from ``(B,)`` arrays inside ``soft_state_bounds = (z, Z)`` and ``track_rows_penalty = (z, Z)`` of
+    :class:`IHM2Controller` (scalars broadcast; the a_lat row follows the track rows' penalty).  Returns ``(soft, alat)``:
+    ``soft = (soft_z, soft_Z)``, ``(B,N+1,28)`` each, and ``alat = (z, Z)``, ``(B,2)`` each, for
+    ``BatchedOcpSolver.set_instance_soft`` / ``set_instance_alat_soft`` -- for instance b exactly the tables that
+    ``controller_ocp(...).flatten()`` builds from b's scalars (one OCP per distinct set) -- or ``(None, None)`` when every penalty is
+    a scalar; ``alat`` is ``None`` as well where the OCP has no soft a_lat row.  ``limits`` are scalars: the penalties' tables do not
+    depend on their values."""
+    pens = {}
+    for name, pair in (("soft_state_bounds", soft_state_bounds), ("track_rows_penalty", track_rows_penalty)):
+        if pair is None:
+            continue
+        for part, v in zip("zZ", pair):
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.shape != (B,)):
+                raise ValueError(f"{name} {part} must be a scalar or have shape ({B},), got {v.shape}")
+            pens[name, part] = v
+    if all(v.ndim == 0 for v in pens.values()):
+        return None, None
+    pens = {k: np.broadcast_to(v, (B,)) for k, v in pens.items()}
+    cache, soft_z, soft_Z, alat_z, alat_Z = {}, [], [], [], []
+    for b in range(B):
+        key = tuple(float(v[b]) for v in pens.values())
+        if key not in cache:
+            pair = lambda name: None if (name, "z") not in pens else (float(pens[name, "z"][b]), float(pens[name, "Z"][b]))   # noqa: E731
+            cache[key] = controller_ocp(nknots, Nf, limits, soft_state_bounds=pair("soft_state_bounds"),
+                                        track_rows_penalty=pair("track_rows_penalty"), **ocp_kw)[1].flatten()
+        d = cache[key]
+        if d.soft_Z is None:        # the penalties given belong to rows this OCP does not have
+            return None, None
+        soft_z.append(np.asarray(d.soft_z, dtype=np.float64)); soft_Z.append(np.asarray(d.soft_Z, dtype=np.float64))
+        if d.alat_soft_Z is not None:
+            alat_z.append(np.asarray(d.alat_soft_z, dtype=np.float64)); alat_Z.append(np.asarray(d.alat_soft_Z, dtype=np.float64))
+    return (np.stack(soft_z), np.stack(soft_Z)), ((np.stack(alat_z), np.stack(alat_Z)) if alat_z else None)
+
+
 class Controller(ABC):
     """``new_python/controller.py:134-159``."""
 
@@ -229,10 +274,14 @@ class IHM2Controller(Controller):
         weights = dict(zip(WEIGHT_NAMES, (q_s, q_n, q_psi, q_v_x, q_v_y, q_r, q_T, q_delta, q_s_f, q_n_f, q_psi_f, q_v_x_f, q_v_y_f,
                                           q_r_f, q_T_f, q_delta_f, q_T_dot, q_delta_dot)))
         limits = dict(zip(LIMIT_NAMES, (n_max, v_x_max, T_max, delta_max, T_dot_max, delta_dot_max)))
-        ocp_kw = dict(a_lat_max=a_lat_max, terminal_bounds=terminal_bounds, soft_state_bounds=soft_state_bounds,
-                      track_rows=track_widths is not None, track_rows_penalty=track_rows_penalty, lateral_acceleration_row=lateral_acceleration_row)
+        # the penalties inside soft_state_bounds = (z, Z) and track_rows_penalty = (z, Z) as well (set_instance_soft / _alat_soft)
+        ocp_kw = dict(a_lat_max=a_lat_max, terminal_bounds=terminal_bounds, soft_state_bounds=_first_pair(soft_state_bounds),
+                      track_rows=track_widths is not None, track_rows_penalty=_first_pair(track_rows_penalty),
+                      lateral_acceleration_row=lateral_acceleration_row)
         inst_w, inst_b = instance_tuning(self.B, weights, limits, s_ref.shape[1], Nf, **ocp_kw)
-        first = lambda v: v if np.ndim(v) == 0 else float(np.asarray(v).reshape(-1)[0])      # noqa: E731
+        first = _first
+        inst_soft, inst_alat = instance_penalties(self.B, {k: first(v) for k, v in limits.items()}, s_ref.shape[1], Nf,
+                                                  **{**ocp_kw, "soft_state_bounds": soft_state_bounds, "track_rows_penalty": track_rows_penalty})
         model, ocp = controller_ocp(s_ref.shape[1], Nf, {k: first(v) for k, v in limits.items()}, **ocp_kw)
         opts = AcadosOcpOptions()                      # python/main.py:227-238, with ERK x M for IRK
         opts.tf = Nf * dt
@@ -253,6 +302,10 @@ class IHM2Controller(Controller):
             self.solver.set_instance_weights(*inst_w)
         if inst_b is not None:
             self.solver.set_instance_bounds(**inst_b)
+        if inst_soft is not None:
+            self.solver.set_instance_soft(*inst_soft)
+        if inst_alat is not None:
+            self.solver.set_instance_alat_soft(*inst_alat)
         # cold start of the prediction arrays (python/main.py:242-246)
         x_pred = np.zeros((self.B, Nf + 1, NX))
         x_pred[:, :, 0] = -6.0 + np.arange(Nf + 1) * dt

@@ -133,25 +133,97 @@ int check_instance_pattern(const ihm2mpc_handle *h, const double *il, const doub
                 row_name(m.c), m.lower ? "lower" : "-", m.upper ? "upper" : "-", m.shared_lower ? "lower" : "-", m.shared_upper ? "upper" : "-");
 }
 
-int scatter_instance_bounds(ihm2mpc_handle *h)
+int scatter_instance_tables(ihm2mpc_handle *h);
+int scatter_instance_bounds(ihm2mpc_handle *h) { return scatter_instance_tables(h); }
+
+// Per-instance slack penalties (ihm2mpc_set_instance_soft / _alat_soft): the same for the values z, Z of the soft sides.
+const char *side_name(int side)
 {
-    const int B = h->B;
-    h->inst_b_ok = false;
-    h->slots_full = false;
-    if (check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
-    const size_t n = h->slots.entries();
-    if ((size_t)B * n > h->i_slot_lb.size()) {
-        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
-        h->i_slot_lb.reset(); h->i_slot_ub.reset();
-        if (alloc_all(h->i_slot_lb, (size_t)B * n, h->i_slot_ub, (size_t)B * n)) return -1;
+    static const char *names[NLAM + 2] = {
+        "lbx[0]", "lbx[1]", "lbx[2]", "lbx[3]", "lbx[4]", "lbx[5]", "lbx[6]", "lbx[7]", "lbu[0]", "lbu[1]", "lg[0]", "lg[1]", "lh[0]", "lh[1]",
+        "ubx[0]", "ubx[1]", "ubx[2]", "ubx[3]", "ubx[4]", "ubx[5]", "ubx[6]", "ubx[7]", "ubu[0]", "ubu[1]", "ug[0]", "ug[1]", "uh[0]", "uh[1]",
+        "a_lat lower", "a_lat upper"};
+    return (side >= 0 && side < NLAM + 2) ? names[side] : "?";
+}
+
+// iz, iZ (B,NS,NLAM), az, aZ (B,2); either pair may be nullptr (those rows are batch-shared)
+int check_penalty_pattern(const ihm2mpc_handle *h, const double *iz, const double *iZ, const double *az, const double *aZ)
+{
+    const ihm2::PenaltyMismatch m = ihm2::find_penalty_mismatch(h->rows, h->B, iz, iZ, az, aZ);
+    using P = ihm2::PenaltyMismatch;
+    switch (m.kind) {
+    case P::NONE: return 0;
+    case P::NOT_A_NUMBER: return fail("instance %d, stage %d, side %d (%s): slack penalty is NaN", m.b, m.k, m.side, side_name(m.side));
+    case P::FLAG:
+        return fail("instance %d, stage %d, side %d (%s): the side is %s (soft_Z %s 0) where the batch-shared table holds it %s", m.b, m.k, m.side,
+                    side_name(m.side), m.soft ? "soft" : "hard", m.soft ? ">=" : "<", m.shared_soft ? "soft" : "hard");
+    case P::NEGATIVE:
+        return fail("instance %d, stage %d, side %d (%s): soft_z < 0 (the slack penalty must be non-decreasing)", m.b, m.k, m.side, side_name(m.side));
+    default:
+        return fail("instance %d, stage %d, side %d (%s): the soft side has neither a linear nor a quadratic penalty", m.b, m.k, m.side, side_name(m.side));
     }
-    std::vector<double> slb, sub, stl, stu;
-    ihm2::scatter_slot_bounds(h->slots, B, h->NS, h->ih_lb.data(), h->ih_ub.data(), slb, sub);
-    ihm2::scatter_stage_bounds(h->rows, B, h->ih_lb.data(), h->ih_ub.data(), stl, stu);
-    if (n && (upload_shared(h, slb.data(), h->i_slot_lb, slb.size()) || upload_shared(h, sub.data(), h->i_slot_ub, sub.size()))) return -1;
-    if (upload_shared(h, stl.data(), h->i_st_lb, stl.size()) || upload_shared(h, stu.data(), h->i_st_ub, stu.size())) return -1;
-    h->inst_b_ok = true;
-    h->slots_full = ihm2::slot_table_full(h->slots, ihm2::full_form_nslot()) && ihm2::slot_bounds_full(h->slots, B, slb, sub);
+}
+
+// The per-instance tables of either mode (bounds, slack penalties) onto the device, in the layout the kernels read: per instance the slot
+// table's bounds and behind them its penalties -- (B, 2, entries): lb | zw and ub | Zw -- and the (stage, row) bounds with the (stage, side)
+// penalties behind them -- (B, NS*NC + NS*NLAM): lb | z and ub | Z -- so that one base per instance serves both.  A mode that is off
+// contributes the batch-shared values.  Bounds whose finite sides differ from the shared table's are a refusal (-1, as before); penalties that
+// the pattern does not take any more (a later shared setter changed it) are no error of that setter: inst_p_ok stays false and ready()
+// reports it before the next solve.
+int scatter_instance_tables(ihm2mpc_handle *h)
+{
+    const int B = h->B, NS = h->NS;
+    h->inst_b_ok = false; h->inst_p_ok = false;
+    h->slots_full = false;
+    if (h->inst_b && check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
+    const double *iz = h->ih_sz.empty() ? nullptr : h->ih_sz.data(), *iZ = h->ih_sZ.empty() ? nullptr : h->ih_sZ.data();
+    const double *az = h->ih_az.empty() ? nullptr : h->ih_az.data(), *aZ = h->ih_aZ.empty() ? nullptr : h->ih_aZ.data();
+    const bool p_fit = h->inst_p && !ihm2::find_penalty_mismatch(h->rows, B, iz, iZ, az, aZ).found();
+    if (!p_fit) iz = iZ = az = aZ = nullptr;       // (the shared values: launches are refused until the penalties are set again or dropped)
+    const ihm2::SlotTable &t = h->slots;
+    const ihm2::ConstraintRows &r = h->rows;
+    const size_t n = t.entries(), nb = (size_t)NS * NC, np = (size_t)NS * NLAM;
+    std::vector<double> slb, sub, stl, stu, szw, sZw, stz, stZ, alz, alZ;
+    if (h->inst_b) {
+        ihm2::scatter_slot_bounds(t, B, NS, h->ih_lb.data(), h->ih_ub.data(), slb, sub);
+        ihm2::scatter_stage_bounds(r, B, h->ih_lb.data(), h->ih_ub.data(), stl, stu);
+    } else {
+        for (int b = 0; b < B; b++) {
+            slb.insert(slb.end(), t.lb.begin(), t.lb.end()); sub.insert(sub.end(), t.ub.begin(), t.ub.end());
+            stl.insert(stl.end(), r.lb.begin(), r.lb.end()); stu.insert(stu.end(), r.ub.begin(), r.ub.end());
+        }
+    }
+    ihm2::scatter_slot_penalties(t, r, B, NS, iz, iZ, az, aZ, szw, sZw);
+    ihm2::scatter_stage_penalties(r, B, iz, iZ, az, aZ, stz, stZ, alz, alZ);
+    std::vector<double> dl((size_t)B * 2 * n), du((size_t)B * 2 * n), tl((size_t)B * (nb + np)), tu((size_t)B * (nb + np));
+    for (size_t b = 0; b < (size_t)B; b++) {
+        std::copy(slb.begin() + b * n, slb.begin() + (b + 1) * n, dl.begin() + b * 2 * n);
+        std::copy(szw.begin() + b * n, szw.begin() + (b + 1) * n, dl.begin() + b * 2 * n + n);
+        std::copy(sub.begin() + b * n, sub.begin() + (b + 1) * n, du.begin() + b * 2 * n);
+        std::copy(sZw.begin() + b * n, sZw.begin() + (b + 1) * n, du.begin() + b * 2 * n + n);
+        std::copy(stl.begin() + b * nb, stl.begin() + (b + 1) * nb, tl.begin() + b * (nb + np));
+        std::copy(stz.begin() + b * np, stz.begin() + (b + 1) * np, tl.begin() + b * (nb + np) + nb);
+        std::copy(stu.begin() + b * nb, stu.begin() + (b + 1) * nb, tu.begin() + b * (nb + np));
+        std::copy(stZ.begin() + b * np, stZ.begin() + (b + 1) * np, tu.begin() + b * (nb + np) + nb);
+    }
+    if (dl.size() > h->i_slot_lb.size() || !h->i_st_lb) {
+        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
+        if (dl.size() > h->i_slot_lb.size()) {
+            h->i_slot_lb.reset(); h->i_slot_ub.reset();
+            if (alloc_all(h->i_slot_lb, dl.size(), h->i_slot_ub, du.size())) return -1;
+        }
+        if (!h->i_st_lb && alloc_all(h->i_st_lb, tl.size(), h->i_st_ub, tu.size())) return -1;
+    }
+    if (n && (upload_shared(h, dl.data(), h->i_slot_lb, dl.size()) || upload_shared(h, du.data(), h->i_slot_ub, du.size()))) return -1;
+    if (upload_shared(h, tl.data(), h->i_st_lb, tl.size()) || upload_shared(h, tu.data(), h->i_st_ub, tu.size())) return -1;
+    if (h->inst_p) {        // the cost kernel's copies: (B,NS,NLAM) and the a_lat row's (B,2)
+        if (!h->ip.st_sz && alloc_all(h->ip.st_sz, stz.size(), h->ip.st_sZ, stZ.size(), h->ip.alat_sz, alz.size(), h->ip.alat_sZ, alZ.size())) return -1;
+        if (upload_shared(h, stz.data(), h->ip.st_sz, stz.size()) || upload_shared(h, stZ.data(), h->ip.st_sZ, stZ.size()) ||
+            upload_shared(h, alz.data(), h->ip.alat_sz, alz.size()) || upload_shared(h, alZ.data(), h->ip.alat_sZ, alZ.size()))
+            return -1;
+    }
+    h->inst_b_ok = h->inst_b; h->inst_p_ok = p_fit;
+    h->slots_full = ihm2::slot_table_full(t, ihm2::full_form_nslot()) && ihm2::slot_bounds_full(t, B, slb, sub);
     return 0;
 }
 
@@ -192,11 +264,11 @@ QpArgs qp_args(ihm2mpc_handle *h)
     a.Hs = h->Hs; a.Gy = h->Gy; a.CD = h->CD; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.slot_kc = h->slot_kc;
     a.hs_bs = 0; a.hs_te = h->N * 100; a.gy_bs = 0; a.gy_te = h->N * 120; a.sl_bs = 0;
     if (h->inst_w) { a.Hs = h->iHs; a.Gy = h->iGy; a.hs_bs = 200; a.hs_te = 100; a.gy_bs = 240; a.gy_te = 120; }
-    if (h->inst_b) { a.sl_bs = h->slots.per_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }
+    if (h->inst_b || h->inst_p) { a.sl_bs = 2 * h->slots.per_lane * 64; a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; }    // bounds | penalties per instance
     a.x = h->x; a.u = h->u; a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e;
     a.pi = h->pi; a.lam = h->lam; a.res = h->res; a.qp_res = h->qp_res; a.u0 = h->u0; a.status = h->status; a.qp_iter = h->qp_iter;
     a.lin = h->lin; a.g = h->q_g; a.rg = h->q_rg; a.P = h->q_P; a.M = h->q_M + (size_t)QM_PAD * 64;
-    a.slot_zw = h->slot_zw; a.slot_Zw = h->slot_Zw; a.slk = h->slk;
+    a.slot_zw = h->slot_zw; a.slot_Zw = h->slot_Zw; a.slk = h->slk;      // (the kernels read zw, Zw behind slot_lb, slot_ub)
     a.track_id = h->track_id; a.widths = h->widths; a.car_L = h->car_L; a.car_W = h->car_W;
     a.lam_a = h->lam_a; a.slk_a = h->slk_a;
     a.symmetrize = (h->cfg.model == IHM2MPC_MODEL_FDYN6) ? 1 : 0;
@@ -321,6 +393,7 @@ int ready(ihm2mpc_handle *h)
     if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called");
     if (h->inst_w && !h->uniform_CD) return fail("per-instance weights need stage-independent general rows C, D (the QP keeps one copy of them)");
     if (h->inst_b && !h->inst_b_ok) return fail("the per-instance bounds do not fit the batch-shared constraint pattern any more: set them again, or pass NULL");
+    if (h->inst_p && !h->inst_p_ok) return fail("the per-instance penalties do not fit the batch-shared constraint pattern any more: set them again, or pass NULL");
     if (!h->slots_fit) {        // the limits of the catalogue's instantiations for these rows
         std::string hard = "none", soft;
         for (const auto &[S, NSL] : ihm2::slot_limits(path_class(h)))
@@ -372,7 +445,7 @@ ihm2::QpSituation ihm2_situation(const ihm2mpc_handle *h)
     s.slots_full = h->slots_full;
     s.path = path_class(h);
     s.uni = h->uniform_H && h->uniform_CD;
-    s.inst_b = h->inst_b; s.block_qp = h->block_qp;
+    s.inst_b = h->inst_b || h->inst_p; s.block_qp = h->block_qp;     // (either per-instance table: k_qp_block reads the shared one)
     s.qp_form = qp_form_limit();
     s.irk_tab = !!h->irk_tab; s.ls_x = !!h->ls_x; s.ls_phi = !!h->ls_phi;
     s.sens_lds = (int)(ihm2_sens_lds_bytes(h) / sizeof(double));
@@ -500,10 +573,10 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
     }
     if (alloc_all(h->s_ref, nt, h->kappa_ref, nt, h->track_id, B, h->Hs, NS * 100, h->Gy, NS * 120, h->lbx, NS * 8, h->ubx, NS * 8,
                   h->lbu, N * 2, h->ubu, N * 2, h->CD, N * 20, h->lg, N * 2, h->ug, N * 2, h->slot_kc_blk, 1024, h->slot_lb_blk, 1024,
-                  h->slot_ub_blk, 1024, h->slot_kc, MAX_SLOTS, h->slot_lb, MAX_SLOTS, h->slot_ub, MAX_SLOTS, h->slot_zw, MAX_SLOTS,
+                  h->slot_ub_blk, 1024, h->slot_kc, MAX_SLOTS, h->slot_lb, 2 * MAX_SLOTS, h->slot_ub, 2 * MAX_SLOTS, h->slot_zw, MAX_SLOTS,
                   h->slot_Zw, MAX_SLOTS, h->slk, B * NS * NLAM, h->widths, (size_t)cfg->ntracks * 2, h->lam_a, B * NS * 2, h->slk_a, B * NS * 2,
                   h->X_ref, nt, h->Y_ref, nt, h->phi_ref, nt, h->xc, B * 8, h->s_guess, B, h->step_args, 48, h->Wd, N * 144 + 64,
-                  h->st_lb, NS * NC, h->st_ub, NS * NC, h->st_sz, NS * NLAM, h->st_sZ, NS * NLAM, h->x, B * NS * 8, h->u, B * N * 2, h->x0, B * 8,
+                  h->st_lb, NS * (NC + NLAM), h->st_ub, NS * (NC + NLAM), h->st_sz, NS * NLAM, h->st_sZ, NS * NLAM, h->x, B * NS * 8, h->u, B * N * 2, h->x0, B * 8,
                   h->yref, B * N * 12, h->yref_e, B * 8, h->pi, B * NS * 8, h->lam, B * NS * NLAM, h->res, B * 4, h->qp_res, B * 4, h->status, B,
                   h->qp_iter, B, h->active, B, h->u0, B * 2,
                   h->lin, (B * N + B) * LIN_REC,      // + one spare record per instance (the kinematic plant's, never read)
@@ -718,16 +791,18 @@ static int rebuild_slots(ihm2mpc_handle *h)
     }
     // the SQP mode's copies of the rows
     if (upload_shared(h, r.lb.data(), h->st_lb, r.lb.size()) || upload_shared(h, r.ub.data(), h->st_ub, r.ub.size()) ||
-        upload_shared(h, r.sz.data(), h->st_sz, r.sz.size()) || upload_shared(h, r.sZ.data(), h->st_sZ, r.sZ.size()))
-        return -1;
+        upload_shared(h, r.sz.data(), h->st_sz, r.sz.size()) || upload_shared(h, r.sZ.data(), h->st_sZ, r.sZ.size()) ||
+        upload_shared(h, r.sz.data(), h->st_lb + r.lb.size(), r.sz.size()) || upload_shared(h, r.sZ.data(), h->st_ub + r.ub.size(), r.sZ.size()))
+        return -1;      // (the penalties once more behind the bounds: what the line search reads)
     if (const size_t n = s.entries()) {
         HIP_TRY(hipMemcpyAsync(h->slot_kc, s.kc.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         if (upload_shared(h, s.lb.data(), h->slot_lb, n) || upload_shared(h, s.ub.data(), h->slot_ub, n) ||
-            upload_shared(h, s.zw.data(), h->slot_zw, n) || upload_shared(h, s.Zw.data(), h->slot_Zw, n))
-            return -1;
+            upload_shared(h, s.zw.data(), h->slot_zw, n) || upload_shared(h, s.Zw.data(), h->slot_Zw, n) ||
+            upload_shared(h, s.zw.data(), h->slot_lb + n, n) || upload_shared(h, s.Zw.data(), h->slot_ub + n, n))
+            return -1;      // (zw, Zw once more behind the bounds: what the kernels read)
     }
-    if (h->inst_b) return scatter_instance_bounds(h);      // the per-instance values into the new table (or a refusal: ready() then reports it)
+    if (h->inst_b || h->inst_p) return scatter_instance_tables(h);     // the per-instance values into the new table (or a refusal: ready() then reports it)
     h->slots_full = ihm2::slot_table_full(s, ihm2::full_form_nslot());
     return 0;
 }
@@ -768,10 +843,12 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
     CHECK_H(h);
     const bool none = !lbx && !ubx && !lbu && !ubu && !lg && !ug;
     if (none) {
-        h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset();
+        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the arrays
+        if (!h->inst_p) { h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset(); }     // (the penalties' mode keeps them)
         h->i_lbu.reset(); h->i_ubu.reset(); h->i_lg.reset(); h->i_ug.reset();
         h->ih_lb = std::vector<double>(); h->ih_ub = std::vector<double>();
         h->inst_b = false; h->inst_b_ok = false;
+        if (h->inst_p) return scatter_instance_tables(h);       // the per-instance penalties stay, beside the shared bounds
         h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, ihm2::full_form_nslot());        // the batch-shared bounds again
         return 0;
     }
@@ -793,8 +870,7 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
     // the pattern check before anything of the handle changes
     if (check_instance_pattern(h, il.data(), iu.data())) return -1;
     const size_t nb = (size_t)B;
-    if (!h->i_st_lb && alloc_all(h->i_st_lb, nb * NS * NC, h->i_st_ub, nb * NS * NC, h->i_lbu, nb * N * 2, h->i_ubu, nb * N * 2,
-                                 h->i_lg, nb * N * 2, h->i_ug, nb * N * 2))
+    if (!h->i_lbu && alloc_all(h->i_lbu, nb * N * 2, h->i_ubu, nb * N * 2, h->i_lg, nb * N * 2, h->i_ug, nb * N * 2))
         return -1;
     h->ih_lb = std::move(il); h->ih_ub = std::move(iu);
     if (upload_shared(h, lbu, h->i_lbu, (size_t)B * N * 2) || upload_shared(h, ubu, h->i_ubu, (size_t)B * N * 2) ||
@@ -819,6 +895,65 @@ int ihm2mpc_set_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft
     HIP_TRY(hipMemsetAsync(h->slk, 0, (size_t)h->B * h->NS * NLAM * sizeof(double), h->stream));
     if (h->bounds_set && rebuild_slots(h)) return -1;
     return 0;
+}
+
+// The slack penalties per instance: the values of the soft sides, the pattern (which sides are soft) from the batch-shared setters.
+// Both entries keep their values on the host and share one mode for the kernels; the mode goes when both are off.
+static int instance_penalties_changed(ihm2mpc_handle *h)
+{
+    h->inst_p = !h->ih_sz.empty() || !h->ih_az.empty();
+    if (!h->inst_p) {
+        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the arrays
+        h->ip.reset();
+        h->inst_p_ok = false;
+        if (h->inst_b) return scatter_instance_tables(h);       // the per-instance bounds stay, beside the shared penalties
+        h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset();
+        h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, ihm2::full_form_nslot());
+        return 0;
+    }
+    return scatter_instance_tables(h);
+}
+
+// the new values of one entry into the handle (empty vectors: shared again); on a failure the previous ones are put back, on the host and,
+// as far as that still succeeds, on the device
+static int take_instance_penalties(ihm2mpc_handle *h, std::vector<double> &z, std::vector<double> &Z, std::vector<double> nz, std::vector<double> nZ)
+{
+    z.swap(nz); Z.swap(nZ);
+    if (instance_penalties_changed(h) == 0) return 0;
+    const std::string why = ihm2mpc_last_error();
+    z.swap(nz); Z.swap(nZ);
+    (void)instance_penalties_changed(h);
+    return fail("%s", why.c_str());
+}
+
+int ihm2mpc_set_instance_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft_Z)
+{
+    CHECK_H(h);
+    if (!soft_z && !soft_Z) {
+        return take_instance_penalties(h, h->ih_sz, h->ih_sZ, {}, {});
+    }
+    if (!soft_z || !soft_Z) return fail("soft_z and soft_Z must both be given, or both be NULL (batch-shared penalties again)");
+    bool any = false;
+    for (double Z : h->rows.sZ) any = any || Z >= 0.0;
+    if (!any) return fail("ihm2mpc_set_soft has not been called with a soft side (the batch-shared table gives the pattern)");
+    // the pattern check before anything of the handle changes (a failure behind it puts the previous values back)
+    if (check_penalty_pattern(h, soft_z, soft_Z, nullptr, nullptr)) return -1;
+    const size_t n = (size_t)h->B * h->NS * NLAM;
+    return take_instance_penalties(h, h->ih_sz, h->ih_sZ, std::vector<double>(soft_z, soft_z + n), std::vector<double>(soft_Z, soft_Z + n));
+}
+
+int ihm2mpc_set_instance_alat_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft_Z)
+{
+    CHECK_H(h);
+    if (!soft_z && !soft_Z) {
+        return take_instance_penalties(h, h->ih_az, h->ih_aZ, {}, {});
+    }
+    if (!soft_z || !soft_Z) return fail("soft_z and soft_Z must both be given, or both be NULL (batch-shared penalties again)");
+    if (!h->rows.alat_on || !(h->rows.alat_sZ[0] >= 0.0 || h->rows.alat_sZ[1] >= 0.0))
+        return fail("ihm2mpc_set_alat_constraint has not been called with a soft side (the batch-shared a_lat row gives the pattern)");
+    if (check_penalty_pattern(h, nullptr, nullptr, soft_z, soft_Z)) return -1;
+    const size_t n = (size_t)h->B * 2;
+    return take_instance_penalties(h, h->ih_az, h->ih_aZ, std::vector<double>(soft_z, soft_z + n), std::vector<double>(soft_Z, soft_Z + n));
 }
 
 int ihm2mpc_set_path_constraints(ihm2mpc_handle *h, int32_t enable, double car_length, double car_width, const double *widths,

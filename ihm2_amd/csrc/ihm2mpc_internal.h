@@ -100,6 +100,14 @@ public:
     }
 };
 
+// The per-instance slack penalties on the device (ihm2mpc_set_instance_soft / _alat_soft), allocated while the mode is on: state, every
+// member a StateBuf.  The handle holds the block by value (ihm2mpc_handle::ip).
+struct ihm2_inst_penalties {
+    StateBuf<double> st_sz, st_sZ;         // (B,NS,NLAM) per (stage, side): the cost
+    StateBuf<double> alat_sz, alat_sZ;     // (B,2) the a_lat row's: the cost
+    void reset() { st_sz.reset(); st_sZ.reset(); alat_sz.reset(); alat_sZ.reset(); }
+};
+
 // Created by value-initialisation (std::make_unique<ihm2mpc_handle>() in ihm2mpc_create): there is no user-provided constructor, so every
 // scalar member starts at zero and every buffer empty.  The destructor (api.hip) waits for both streams and releases what is not a buffer.
 struct ihm2mpc_handle {
@@ -132,8 +140,9 @@ struct ihm2mpc_handle {
     bool slots_full;               // the table (with the per-instance bounds, if any) takes the full slot form (qp_tables.hpp: slot_table_full)
     bool slots_fit;                // false: the rows set so far fit no instantiation (reported by the next solve: a later setter may still change them)
     StateBuf<int32_t> slot_kc;             // (slots.per_lane*64) stage * 16 + row, -1 = padding
-    StateBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided)
-    StateBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot
+    StateBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided); behind them, at the offset
+                                           // slots.per_lane*64, the slots' slack penalties: zw behind lb, Zw behind ub -- what the kernels read
+    StateBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot (the batch-shared table on its own)
     StateBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
     StateBuf<double> slot_lb_blk, slot_ub_blk;
     std::string poison;            // IHM2MPC_POISON_WORKSPACE as read at creation: "" / "0" off, "1" every workspace of doubles, else a list of names
@@ -190,7 +199,7 @@ struct ihm2mpc_handle {
     int sqp_globalization, sqp_use_suff, sqp_full_step_dual;   // globalization: 0 FIXED_STEP, 1 MERIT_BACKTRACKING
     double sqp_alpha_min, sqp_alpha_red, sqp_eps, sqp_tol[4];
     StateBuf<double> Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
-    StateBuf<double> st_lb, st_ub;           // (NS,NC) device copies of rows.lb / rows.ub
+    StateBuf<double> st_lb, st_ub;           // (NS,NC) device copies of rows.lb / rows.ub, and behind them (NS,NLAM) rows.sz / rows.sZ: z behind lb, Z behind ub
     StateBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of rows.sz / rows.sZ
     // allocated together by the first SQP solve (api.hip: sqp_buffers): the iterate the QP was built at, merit weights, per-solve bookkeeping
     WorkBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
@@ -213,9 +222,16 @@ struct ihm2mpc_handle {
     bool shared_uniform_H;         // uniform_H of the batch-shared weights (restored when the per-instance weights go)
     StateBuf<double> iHs, iGy, iWd;          // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
     std::vector<double> ih_lb, ih_ub;      // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
-    StateBuf<double> i_slot_lb, i_slot_ub;   // (B,slots.per_lane*64) the slot table's bounds per instance, grown on demand
-    StateBuf<double> i_st_lb, i_st_ub;       // (B,NS,NC) the SQP mode's bounds per instance
+    StateBuf<double> i_slot_lb, i_slot_ub;   // (B,2,slots.per_lane*64) the slot table's bounds, then penalties, per instance (either mode), grown on demand
+    StateBuf<double> i_st_lb, i_st_ub;       // (B, NS*NC + NS*NLAM) the SQP mode's bounds, then penalties, per instance (either mode)
     StateBuf<double> i_lbu, i_ubu, i_lg, i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
+    // Slack penalties (ihm2mpc_set_instance_soft / _alat_soft): the VALUES z, Z per instance; which sides are soft stays batch-shared.
+    // One mode for the kernels (inst_p: either entry is on); the rows an entry has not set hold the shared values in the buffers below.
+    bool inst_p;
+    bool inst_p_ok;                // false: a later setter changed the shared pattern and the stored values no longer fit it
+    std::vector<double> ih_sz, ih_sZ;      // host (B,NS,NLAM) penalties of the rows 0..13, empty: shared
+    std::vector<double> ih_az, ih_aZ;      // host (B,2) penalties of the a_lat row, empty: shared
+    ihm2_inst_penalties ip;                // their device copies (state; tests/test_instance_penalties_abi.py reads the struct's classes)
 
     // ---- history of ihm2mpc_run_steps, grown on demand ----
     WorkBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)

@@ -31,9 +31,13 @@ struct CostArgs {
     int w_bs, w_ks, w_te, w_same;
     const double *st_lb, *st_ub;        // (NS,14) bounds per (stage, row), -+inf = absent; st_bs doubles per instance (0: batch-shared)
     int st_bs;
-    const double *st_sz, *st_sZ;        // (NS,28) slack penalties per side, sZ < 0 = hard
-    // the lateral-acceleration row (stages 1 .. N-1): its finite sides and their penalties, lower / upper
+    const double *st_sz, *st_sZ;        // (NS,28) slack penalties per side, sZ < 0 = hard; sp_bs doubles per instance (0: batch-shared)
+    int sp_bs;
+    // the lateral-acceleration row (stages 1 .. N-1): its finite sides, lower / upper, and their penalties -- device memory, al_bs
+    // doubles per instance (per-instance penalties: (B,2), al_bs = 2), or nullptr: the batch-shared pair below
     int alat_on, alat_fin[2];
+    const double *alat_pz, *alat_pZ;
+    int al_bs;
     double alat_sz[2], alat_sZ[2];
     const double *x, *u, *yref, *yref_e, *slk, *slk_a;
     const int32_t *status;
@@ -76,6 +80,12 @@ __global__ __launch_bounds__(64) void k_cost(CostArgs a)
     const double *xb = a.x + bs * NS * 8, *ub = a.u + bs * N * 2, *yrb = a.yref + bs * N * 12, *yeb = a.yref_e + bs * 8;
     const double *slb = a.slk + bs * NS * 28, *slab = a.slk_a + bs * NS * 2;
     const double *lbb = a.st_lb + bs * a.st_bs, *ubb = a.st_ub + bs * a.st_bs;
+    const double *szb = a.st_sz + bs * a.sp_bs, *sZb = a.st_sZ + bs * a.sp_bs;
+    double al_z[2], al_Z[2];            // wave-uniform
+    for (int m = 0; m < 2; m++) {
+        al_z[m] = a.alat_pz ? a.alat_pz[bs * a.al_bs + m] : a.alat_sz[m];
+        al_Z[m] = a.alat_pZ ? a.alat_pZ[bs * a.al_bs + m] : a.alat_sZ[m];
+    }
 
     if (a.w_same)
         for (int e = lane; e < 144; e += 64) Wl[e] = Wb[e];
@@ -136,20 +146,20 @@ __global__ __launch_bounds__(64) void k_cost(CostArgs a)
         // the soft sides of the stage: a finite side with Z >= 0 carries a slack (sqp_body.hpp: merit)
         double sl = 0.0;
         for (int c = 0; c < 14; c++) {
-            if (lbb[k * 14 + c] > -INFINITY && a.st_sZ[k * 28 + c] >= 0.0) {
+            if (lbb[k * 14 + c] > -INFINITY && sZb[k * 28 + c] >= 0.0) {
                 const double sv = slb[k * 28 + c];
-                sl += fma(0.5 * a.st_sZ[k * 28 + c] * sv, sv, a.st_sz[k * 28 + c] * sv);
+                sl += fma(0.5 * sZb[k * 28 + c] * sv, sv, szb[k * 28 + c] * sv);
             }
-            if (ubb[k * 14 + c] < INFINITY && a.st_sZ[k * 28 + 14 + c] >= 0.0) {
+            if (ubb[k * 14 + c] < INFINITY && sZb[k * 28 + 14 + c] >= 0.0) {
                 const double sv = slb[k * 28 + 14 + c];
-                sl += fma(0.5 * a.st_sZ[k * 28 + 14 + c] * sv, sv, a.st_sz[k * 28 + 14 + c] * sv);
+                sl += fma(0.5 * sZb[k * 28 + 14 + c] * sv, sv, szb[k * 28 + 14 + c] * sv);
             }
         }
         if (a.alat_on && k >= 1 && k < N)
             for (int m = 0; m < 2; m++)
-                if (a.alat_fin[m] && a.alat_sZ[m] >= 0.0) {
+                if (a.alat_fin[m] && al_Z[m] >= 0.0) {
                     const double sv = slab[k * 2 + m];
-                    sl += fma(0.5 * a.alat_sZ[m] * sv, sv, a.alat_sz[m] * sv);
+                    sl += fma(0.5 * al_Z[m] * sv, sv, al_z[m] * sv);
                 }
         const double v = track + sl;
         if (a.stage_cost) a.stage_cost[bs * NS + k] = v;
@@ -204,8 +214,13 @@ void ihm2_launch_cost(ihm2mpc_handle *h, int grad, double *cost, double *stage_c
     a.W = h->Wd; a.w_bs = 0; a.w_ks = 144; a.w_te = h->N * 144; a.w_same = h->shared_uniform_H ? 1 : 0;
     if (h->inst_w) { a.W = h->iWd; a.w_bs = 208; a.w_ks = 0; a.w_te = 144; a.w_same = 1; }
     a.st_lb = h->st_lb; a.st_ub = h->st_ub; a.st_bs = 0;
-    if (h->inst_b) { a.st_lb = h->i_st_lb; a.st_ub = h->i_st_ub; a.st_bs = h->NS * NC; }
-    a.st_sz = h->st_sz; a.st_sZ = h->st_sZ;
+    if (h->inst_b || h->inst_p) { a.st_lb = h->i_st_lb; a.st_ub = h->i_st_ub; a.st_bs = h->NS * (NC + NLAM); }
+    a.st_sz = h->st_sz; a.st_sZ = h->st_sZ; a.sp_bs = 0;
+    a.alat_pz = nullptr; a.alat_pZ = nullptr; a.al_bs = 0;
+    if (h->inst_p) {
+        a.st_sz = h->ip.st_sz; a.st_sZ = h->ip.st_sZ; a.sp_bs = h->NS * NLAM;
+        a.alat_pz = h->ip.alat_sz; a.alat_pZ = h->ip.alat_sZ; a.al_bs = 2;
+    }
     a.alat_on = h->rows.alat_on;
     a.alat_fin[0] = std::isfinite(h->rows.alat_lb); a.alat_fin[1] = std::isfinite(h->rows.alat_ub);
     for (int m = 0; m < 2; m++) { a.alat_sz[m] = h->rows.alat_sz[m]; a.alat_sZ[m] = h->rows.alat_sZ[m]; }

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(64) void k_penalty_grad(PenaltyGradArgs pa)
         if (COST) slt[e] = 0.0;         /* the explicit partials are taken on every side: 0 where there is no slack */ \
     }
 #define SENS_ROWS_SLOT_OPEN(s)                             \
-        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s]; \
+        const double zw = SENS_ROWS_ZW(s), Zw = SENS_ROWS_ZZ(s); \
         if (!(Zw >= 0.0)) continue;         // a hard slot: no slack
 #define SENS_ROWS_SLOT_BEGIN(s)
 #define SENS_ROWS_SIDE(k, c, up, LM, GAP, SL)              \

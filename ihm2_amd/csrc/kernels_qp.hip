@@ -509,7 +509,8 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             }
             const double lb = slot_lbb[s], ubd = slot_ubb[s];
             bool soft = false;
-            if (r < NSOFT) { so_zw[r < NSOFT ? r : 0] = a.slot_zw[s]; so_Zw[r < NSOFT ? r : 0] = a.slot_Zw[s]; soft = a.slot_Zw[s] >= 0.0; }
+            // (the slots' slack penalties zw, Zw lie behind the bounds, in the same arrays: batch-shared or the instance's with them, through the one base)
+            if (r < NSOFT) { const size_t po = (size_t)b * a.sl_bs + a.nslots_can; const double *zp = a.slot_lb + po, *Zp = a.slot_ub + po; so_zw[r < NSOFT ? r : 0] = zp[s]; so_Zw[r < NSOFT ? r : 0] = Zp[s]; soft = Zp[s] >= 0.0; }
             // soft sides may be violated: they do not count as infeasibility of the iterate
             // (the incoming multipliers are fetched where they are used: as values of their own they were two loads per slot in every QP and moved the
             // all-hard kernels' register allocation -- slot bounds from the accumulator file to scratch, -1.6 % on the headline)

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64) void k_slack_fold(FoldArgs fa)
     // ======== phase 1: the rows at xbar (sens_rows_body.hpp); gamma of every soft side, 0 elsewhere ========
 #define SENS_ROWS_CLEAR for (int e = lane; e < NS * SENS_SIDES; e += 64) gam[e] = 0.0;
 #define SENS_ROWS_SLOT_OPEN(s)                             \
-        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s]; \
+        const double zw = SENS_ROWS_ZW(s), Zw = SENS_ROWS_ZZ(s); \
         if (!(Zw >= 0.0)) continue;         // a hard slot: no slack
 #define SENS_ROWS_SLOT_BEGIN(s)
 #define SENS_ROWS_SIDE(k, c, up, LM, GAP, SL)              \

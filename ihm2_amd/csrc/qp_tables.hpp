@@ -323,6 +323,97 @@ inline void scatter_stage_bounds(const ConstraintRows &rows, int B, const double
             }
 }
 
+// ---- per-instance slack penalties in the pattern of the batch-shared table ----
+// iz, iZ (B,NS,NLAM): the penalties of the rows 0..13 per instance, the layout of ConstraintRows::sz / sZ; az, aZ (B,2): those of the
+// a_lat row, lower / upper side.  Either pair may be nullptr: those rows keep the batch-shared penalties.
+
+// the first (instance, stage, side) whose penalties the shared pattern does not take; side = 0..27 as in sz / sZ (NC lower, then NC
+// upper sides), 28 / 29 = lower / upper side of the a_lat row (stage 0: the row's penalties do not depend on the stage)
+struct PenaltyMismatch {
+    enum Kind { NONE = 0, FLAG, NEGATIVE, NOT_A_NUMBER, NO_PENALTY } kind;
+    int b, k, side;
+    bool soft, shared_soft;
+    bool found() const { return kind != NONE; }
+};
+namespace slot_detail {
+// one side's (z, Z) against the shared Z of that side
+inline PenaltyMismatch::Kind penalty_side(double z, double Z, double shared_Z)
+{
+    if (z != z || Z != Z) return PenaltyMismatch::NOT_A_NUMBER;
+    if ((Z >= 0.0) != (shared_Z >= 0.0)) return PenaltyMismatch::FLAG;
+    if (Z >= 0.0 && !(z >= 0.0)) return PenaltyMismatch::NEGATIVE;
+    if (Z >= 0.0 && !(Z + z > 0.0)) return PenaltyMismatch::NO_PENALTY;
+    return PenaltyMismatch::NONE;
+}
+}  // namespace slot_detail
+// A side is soft (Z >= 0) for an instance exactly where the shared rows hold it soft (FLAG); z >= 0 on a soft side (NEGATIVE); no NaN
+// anywhere (NOT_A_NUMBER); and, as ihm2mpc_set_soft refuses it for the shared table, no soft side with z = Z = 0, which has neither a
+// linear nor a quadratic penalty (NO_PENALTY).  What an instance gives on a hard side is otherwise not read.
+inline PenaltyMismatch find_penalty_mismatch(const ConstraintRows &rows, int B, const double *iz, const double *iZ, const double *az, const double *aZ)
+{
+    const int NS = rows.NS;
+    for (int b = 0; b < B; b++) {
+        if (iz && iZ)
+            for (int k = 0; k < NS; k++)
+                for (int i = 0; i < NLAM; i++) {
+                    const size_t e = ((size_t)b * NS + k) * NLAM + i;
+                    const PenaltyMismatch::Kind kind = slot_detail::penalty_side(iz[e], iZ[e], rows.sZ[k * NLAM + i]);
+                    if (kind) return {kind, b, k, i, iZ[e] >= 0.0, rows.sZ[k * NLAM + i] >= 0.0};
+                }
+        if (az && aZ)
+            for (int m = 0; m < 2; m++) {
+                const PenaltyMismatch::Kind kind = slot_detail::penalty_side(az[b * 2 + m], aZ[b * 2 + m], rows.alat_sZ[m]);
+                if (kind) return {kind, b, 0, NLAM + m, aZ[b * 2 + m] >= 0.0, rows.alat_sZ[m] >= 0.0};
+            }
+    }
+    return {PenaltyMismatch::NONE, 0, 0, 0, false, false};
+}
+
+// The slot table's penalties per instance, (B, entries): the values of instance b on the soft slots -- a soft slot is one-sided, the
+// side its finite bound -- and the shared table's on the hard slots and the padding.  Instance b's block is then the zw, Zw of
+// lay_out_slots on rows that hold b's penalties: the layout depends on which sides are soft, not on the values.
+inline void scatter_slot_penalties(const SlotTable &t, const ConstraintRows &rows, int B, int NS, const double *iz, const double *iZ,
+                                   const double *az, const double *aZ, std::vector<double> &szw, std::vector<double> &sZw)
+{
+    (void)rows;     // (the table holds everything of the rows that is needed: kc, the finite side of a soft slot, the shared zw / Zw)
+    const size_t n = t.entries();
+    szw.resize((size_t)B * n); sZw.resize((size_t)B * n);
+    for (int b = 0; b < B; b++)
+        for (size_t e = 0; e < n; e++) {
+            const int kc = t.kc[e], k = kc >> 4, c = kc & 15;
+            double z = t.zw[e], Z = t.Zw[e];
+            if (kc >= 0 && Z >= 0.0) {
+                const int up = std::isfinite(t.ub[e]) ? 1 : 0;
+                if (c == NC) {
+                    if (az && aZ) { z = az[b * 2 + up]; Z = aZ[b * 2 + up]; }
+                } else if (iz && iZ) {
+                    const size_t i = ((size_t)b * NS + k) * NLAM + up * NC + c;
+                    z = iz[i]; Z = iZ[i];
+                }
+            }
+            szw[(size_t)b * n + e] = z; sZw[(size_t)b * n + e] = Z;
+        }
+}
+
+// the (B,NS,NLAM) copies for the kernels that read the penalties by (stage, side) -- the line search's merit and the cost -- and the
+// (B,2) pairs of the a_lat row: the instance's values, the shared rows' where a pair is nullptr
+inline void scatter_stage_penalties(const ConstraintRows &rows, int B, const double *iz, const double *iZ, const double *az, const double *aZ,
+                                    std::vector<double> &stz, std::vector<double> &stZ, std::vector<double> &alz, std::vector<double> &alZ)
+{
+    const size_t per = (size_t)rows.NS * NLAM;
+    stz.resize((size_t)B * per); stZ.resize((size_t)B * per); alz.resize((size_t)B * 2); alZ.resize((size_t)B * 2);
+    for (int b = 0; b < B; b++) {
+        for (size_t i = 0; i < per; i++) {
+            stz[(size_t)b * per + i] = (iz && iZ) ? iz[(size_t)b * per + i] : rows.sz[i];
+            stZ[(size_t)b * per + i] = (iz && iZ) ? iZ[(size_t)b * per + i] : rows.sZ[i];
+        }
+        for (int m = 0; m < 2; m++) {
+            alz[b * 2 + m] = (az && aZ) ? az[b * 2 + m] : rows.alat_sz[m];
+            alZ[b * 2 + m] = (az && aZ) ? aZ[b * 2 + m] : rows.alat_sZ[m];
+        }
+    }
+}
+
 // ---- weights ----
 
 // y = Vx x + Vu u of python/mpc.py:49-58 as one 12x10 selector

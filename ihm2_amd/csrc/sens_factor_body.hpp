@@ -18,7 +18,7 @@
 #define SENS_ROWS_CLEAR for (int e = lane; e < NS * SENS_NR; e += 64) w[e] = 0.0;
 #define SENS_ROWS_SLOT_OPEN(s)
 #define SENS_ROWS_SLOT_BEGIN(s)                            \
-        const double zw = a.slot_zw[s], Zw = a.slot_Zw[s]; \
+        const double zw = SENS_ROWS_ZW(s), Zw = SENS_ROWS_ZZ(s); \
         const bool soft = Zw >= 0.0;                       \
         double sig = 0.0;
 #define SENS_ROWS_SIDE(k, c, up, LM, GAP, SL)              \

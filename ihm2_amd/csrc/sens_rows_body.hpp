@@ -24,6 +24,10 @@
     const double *lamb = a.lam + bs * NS * 28, *slkb = a.slk + bs * NS * 28;
     const double *lamab = a.lam_a + bs * NS * 2, *slkab = a.slk_a + bs * NS * 2;
     const double *slb = a.slot_lb + bs * a.sl_bs, *sub = a.slot_ub + bs * a.sl_bs;
+    // the slots' slack penalties zw, Zw, behind the bounds, for the hooks: the base is formed where it is read, wave-uniform, and not kept beside
+    // slb / sub (the persistent loop's twin holds no register for it through the walk)
+#define SENS_ROWS_ZW(s) ((a.slot_lb + (bs * a.sl_bs + a.nslots))[s])
+#define SENS_ROWS_ZZ(s) ((a.slot_ub + (bs * a.sl_bs + a.nslots))[s])
 
     // ---- row gradients of the nonlinear rows at xbar, the includer's tables zeroed ----
     double w_R = 0.0, w_L = 0.0;
@@ -91,3 +95,5 @@
         SENS_ROWS_SLOT_END(k, c)
     }
     WSYNC();
+#undef SENS_ROWS_ZW
+#undef SENS_ROWS_ZZ

@@ -16,8 +16,10 @@ struct LsArgs {
     const double *s_ref, *kappa_ref;
     const int32_t *track_id;
     const double *W;                 // (N,12,12) then W_e (8,8)
-    const double *st_lb, *st_ub;     // (NS,14) bounds per (stage, row), -+inf = absent
-    const double *st_sz, *st_sZ;     // (NS,28) slack penalties per side, sZ < 0 = hard
+    // (NS,14) bounds per (stage, row), -+inf = absent, and behind them, in the same arrays, the (NS,28) slack penalties per side: z behind
+    // st_lb, Z behind st_ub (Z < 0 = hard) -- st_bs = NS * 42 doubles per instance, so that one base per instance serves both
+    const double *st_lb, *st_ub;
+    const double *st_sz, *st_sZ;     // the batch-shared (NS,28) penalties on their own (not read by the line search)
     const double *CD, *Hs, *widths;
     // per-instance tuning: doubles per instance of W (B,144+64), Hs (B,2,100), st_lb / st_ub (0: batch-shared); W's stage stride (144 shared, 0:
     // one stage weight per instance) and the offset of W_e (N * 144 shared, 144 per instance)
@@ -91,6 +93,7 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
     // the instance's tuning (kernels_qp.hip: QpArgs::wi); batch-shared: the tables themselves
     const double *Wb = a.W + (size_t)b * a.w_bs, *Hsb = a.Hs + (size_t)b * a.hs_bs;
     const double *st_lbb = a.st_lb + (size_t)b * a.st_bs, *st_ubb = a.st_ub + (size_t)b * a.st_bs;
+    // (the slack penalties per (stage, side) lie behind the bounds, in the same arrays: z behind the lower, Z behind the upper bounds)
 
     auto restore = [&](bool primal_dual) {
         if (primal_dual) {
@@ -239,27 +242,28 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
                 cv[12] = xk[1] + foot + lat - w_R;
                 cv[13] = -xk[1] - foot + lat - w_L;
             }
+            const int spk = NS * 14 + k * 28;       // the stage's penalties behind the bounds
 #pragma unroll
             for (int c = 0; c < 14; c++) {
                 const double lb = st_lbb[k * 14 + c], ubd = st_ubb[k * 14 + c];
                 if (lb > -INFINITY) {
                     double viol = lb - cv[c];
-                    const double Z = a.st_sZ[k * 28 + c];
+                    const double Z = st_ubb[spk + c];
                     if (Z >= 0.0) {
                         const int e1 = k * 28 + c;
                         const double sv = slpb[e1] + al * (slb[e1] - slpb[e1]);
-                        cost += a.st_sz[e1] * sv + 0.5 * Z * sv * sv;
+                        cost += st_lbb[spk + c] * sv + 0.5 * Z * sv * sv;
                         viol -= sv;
                     }
                     inf += wlamb[k * 28 + c] * fmax(0.0, viol);
                 }
                 if (ubd < INFINITY) {
                     double viol = cv[c] - ubd;
-                    const double Z = a.st_sZ[k * 28 + 14 + c];
+                    const double Z = st_ubb[spk + 14 + c];
                     if (Z >= 0.0) {
                         const int e1 = k * 28 + 14 + c;
                         const double sv = slpb[e1] + al * (slb[e1] - slpb[e1]);
-                        cost += a.st_sz[e1] * sv + 0.5 * Z * sv * sv;
+                        cost += st_lbb[spk + 14 + c] * sv + 0.5 * Z * sv * sv;
                         viol -= sv;
                     }
                     inf += wlamb[k * 28 + 14 + c] * fmax(0.0, viol);
@@ -281,8 +285,9 @@ __device__ __forceinline__ void line_search_body(const LsArgs &a, const int b, c
             if (j < 8) acc = fma(gb[e], xb[k * 8 + j] - xpb[k * 8 + j], acc);
             else if (k < N) acc = fma(gb[e], ub[k * 2 + j - 8] - upb[k * 2 + j - 8], acc);
         }
+        const int sp0 = NS * 14;
         for (int e = lane; e < NS * 28; e += 64)
-            if (a.st_sZ[e] >= 0.0) acc = fma(a.st_sz[e] + a.st_sZ[e] * slpb[e], slb[e] - slpb[e], acc);
+            if (st_ubb[sp0 + e] >= 0.0) acc = fma(st_lbb[sp0 + e] + st_ubb[sp0 + e] * slpb[e], slb[e] - slpb[e], acc);
         D = fmin(wave_sum(acc) - i0, 0.0);
     }
     double al = 1.0, m_last = m0;
@@ -347,7 +352,7 @@ static inline LsArgs make_ls_args(ihm2mpc_handle *h)
     a.CD = h->CD; a.Hs = h->Hs; a.widths = h->widths;
     a.w_bs = 0; a.w_ks = 144; a.w_te = h->N * 144; a.hs_bs = 0; a.st_bs = 0;
     if (h->inst_w) { a.W = h->iWd; a.Hs = h->iHs; a.w_bs = 208; a.w_ks = 0; a.w_te = 144; a.hs_bs = 200; }
-    if (h->inst_b) { a.st_bs = h->NS * NC; a.st_lb = h->i_st_lb; a.st_ub = h->i_st_ub; }
+    if (h->inst_b || h->inst_p) { a.st_bs = h->NS * (NC + NLAM); a.st_lb = h->i_st_lb; a.st_ub = h->i_st_ub; }
     a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e; a.g = h->q_g; a.lin = h->lin;
     a.x = h->x; a.u = h->u; a.pi = h->pi; a.lam = h->lam; a.slk = h->slk;
     a.xp = h->ls_x; a.up = h->ls_u; a.pip = h->ls_pi; a.lamp = h->ls_lam; a.slkp = h->ls_slk;

@@ -219,6 +219,28 @@ class BatchedOcpSolver:
         arrs = [_f64(a, sh, n) for a, sh, n in zip(arrs, shapes, ("lbx", "ubx", "lbu", "ubu", "lg", "ug"))]
         _lib.check(self.lib.ihm2mpc_set_instance_bounds(self._h, *[_ptr(a) for a in arrs]))
 
+    def set_instance_soft(self, soft_z=None, soft_Z=None):
+        """Slack penalties per instance, ``(B,N+1,28)`` each in the layout of :meth:`set_soft`.  A side must be soft (``soft_Z >= 0``)
+        exactly where the shared table (:meth:`set_soft`, called first) holds it soft; the values are the instance's own.  Instance b
+        then gives what a batch whose shared penalties are ``(soft_z[b], soft_Z[b])`` gives, bit for bit -- the QP, the SQP mode's
+        merit, the cost and every gradient.  The bounds of the a_lat row, the track rows' ``lh`` / ``uh``, the widths and C, D stay
+        shared.  ``None, None``: the shared penalties again."""
+        self._set_instance_penalties(self.lib.ihm2mpc_set_instance_soft, soft_z, soft_Z, (self.B, self.N + 1, NLAM))
+
+    def set_instance_alat_soft(self, soft_z=None, soft_Z=None):
+        """Slack penalties of the lateral-acceleration row per instance, ``(B,2)`` each = lower / upper side; the row's shared
+        penalties (``ihm2mpc_set_alat_constraint`` with soft sides) give the pattern.  ``None, None``: shared again."""
+        self._set_instance_penalties(self.lib.ihm2mpc_set_instance_alat_soft, soft_z, soft_Z, (self.B, 2))
+
+    def _set_instance_penalties(self, entry, soft_z, soft_Z, shape):
+        if soft_z is None and soft_Z is None:
+            _lib.check(entry(self._h, None, None))
+            return
+        if soft_z is None or soft_Z is None:
+            raise ValueError("soft_z and soft_Z must both be given, or both be None")
+        z = _f64(soft_z, shape, "soft_z"); Z = _f64(soft_Z, shape, "soft_Z")
+        _lib.check(entry(self._h, _ptr(z), _ptr(Z)))
+
     # ---- per-instance data, batched ----
     def set_x0(self, x0):
         _lib.check(self.lib.ihm2mpc_set_x0(self._h, _ptr(_f64(x0, (self.B, NX), "x0"))))
@@ -618,8 +640,9 @@ class BatchedOcpSolver:
         ``soft_Z`` ``(B,S,N+1,28)`` in the layout of ``set_soft`` / ``get_slacks``, ``alat_soft_z``, ``alat_soft_Z`` ``(B,S,N+1,2)`` for
         the two sides of the lateral-acceleration row, and ``zeta`` ``(B,S,N+1,10)``, the adjoint solution ``(zeta_x,k, zeta_u,k)``.
         ``soft_z = -zeta_s``, ``soft_Z = -s zeta_s`` with ``zeta_s`` the slack component of the adjoint; 0 on a side without a slack or
-        with a zero multiplier, so the sum over the batch is the gradient in the shared table.  Bounds are not differentiated
-        (``ihm2mpc_eval_adjoint_sensitivities_p``)."""
+        with a zero multiplier, so the sum over the batch is the gradient in the shared table.  With per-instance penalties
+        (:meth:`set_instance_soft`, :meth:`set_instance_alat_soft`) the rows are each instance's own: row ``b`` is the gradient in
+        instance ``b``'s penalties, at its values.  Bounds are not differentiated (``ihm2mpc_eval_adjoint_sensitivities_p``)."""
         B, N = self.B, self.N
         S, squeeze, ptrs = self._slack_seed_args(seed_x, seed_u, seed_s, seed_sa)
         out = dict(x0=np.empty((B, S, NX)), yref=np.empty((B, S, N, NY)), yref_e=np.empty((B, S, NX)), W=np.empty((B, S, NY, NY)),
@@ -632,7 +655,8 @@ class BatchedOcpSolver:
     def eval_cost_gradient_penalties(self):
         """:meth:`eval_cost_gradient_soft` with the total derivative of the cost in the slack penalties: the same dict (the same bits)
         plus ``soft_z``, ``soft_Z`` ``(B,N+1,28)`` and ``alat_soft_z``, ``alat_soft_Z`` ``(B,N+1,2)``: ``dJ/dz = s - zeta_s``,
-        ``dJ/dZ = s^2 / 2 - s zeta_s`` (``ihm2mpc_eval_cost_gradient_penalties``)."""
+        ``dJ/dZ = s^2 / 2 - s zeta_s``; with per-instance penalties (:meth:`set_instance_soft`) the cost and the gradient rows are
+        each instance's own (``ihm2mpc_eval_cost_gradient_penalties``)."""
         B, N = self.B, self.N
         out = dict(cost=np.empty(B), x0=np.empty((B, NX)), yref=np.empty((B, N, NY)), yref_e=np.empty((B, NX)), W=np.empty((B, NY, NY)),
                    W_e=np.empty((B, NX, NX)), soft_z=np.empty((B, N + 1, NLAM)), soft_Z=np.empty((B, N + 1, NLAM)),
@@ -643,7 +667,8 @@ class BatchedOcpSolver:
 
     def du0_dsoft(self):
         """``dict(soft_z, soft_Z (B,2,N+1,28), alat_soft_z, alat_soft_Z (B,2,N+1,2))``: the derivative of the first control of the last
-        solve in the slack penalties (the two unit seeds on ``u_0``)."""
+        solve in the slack penalties (the two unit seeds on ``u_0``).  With per-instance penalties (:meth:`set_instance_soft`) row
+        ``b`` is the derivative in instance ``b``'s own penalties: one launch differentiates a whole penalty sweep."""
         g = self.eval_adjoint_penalty_sensitivities()
         return {k: g[k] for k in ("soft_z", "soft_Z", "alat_soft_z", "alat_soft_Z")}
 

@@ -199,6 +199,19 @@ int ihm2mpc_set_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, 
 int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const double *W_e);
 int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, const double *lbu,
                                 const double *ubu, const double *lg, const double *ug);
+/* Slack penalties per instance: the VALUES z, Z of the soft sides; which sides are soft is the batch-shared pattern of
+ * ihm2mpc_set_soft (ihm2mpc_set_alat_constraint for the a_lat row), which must have been called first.  A side must be soft
+ * (Z >= 0) for an instance exactly where the shared table holds it soft, with z >= 0 and, as ihm2mpc_set_soft asks, z + Z > 0 there (z = Z = 0 is no penalty) and no NaN anywhere; what
+ * an instance gives on a hard side is otherwise not read.  Everything that reads a penalty follows the instance: the QP (per step
+ * and in the persistent loop), the SQP mode's merit, ihm2mpc_eval_cost and the gradients of ihm2mpc_eval_adjoint_sensitivities_s /
+ * _p and ihm2mpc_eval_cost_gradient_soft / _penalties, whose rows are then each instance's own.  The bounds of the a_lat row, lh / uh
+ * of the track rows, the track widths and C, D stay shared.  A later ihm2mpc_set_soft / _set_bounds / _set_path_constraints /
+ * _set_alat_constraint re-applies the stored values (or the next solve refuses, if the pattern no longer matches).  Errors name the
+ * instance, stage and side (0..13 lower, 14..27 upper sides, as the columns of soft_z).
+ * (B,N+1,28) each, layout of ihm2mpc_set_soft per instance; NULL, NULL = batch-shared penalties again */
+int ihm2mpc_set_instance_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft_Z);
+/* (B,2) each: lower / upper side of the a_lat row; NULL, NULL = shared again */
+int ihm2mpc_set_instance_alat_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft_Z);
 /* SOFT constraint sides (AcadosOcpConstraints idxsbx / idxsbx_e / idxsg with AcadosOcpCost zl, zu, Zl, Zu --
  * declared by the reference's OCP class, python/mpc.py:58-90 uses hard sides only): soft_z, soft_Z (N+1,28) per
  * one-sided constraint, 14 lower sides [x(8) u(2) g(2) h(2)] then 14 upper sides.  A side with soft_Z >= 0 carries a
