@@ -94,6 +94,11 @@ def fit_spline(path: np.ndarray, curv_weight: float = 1.0) -> tuple[np.ndarray, 
     n = path.shape[0]
     nxt = np.roll(np.arange(n), -1)
     chord = np.linalg.norm(path[nxt] - path, axis=1)          # ds_i: point i -> point i+1 (closing)
+    if not np.all(np.isfinite(path)):
+        raise ValueError("path has non-finite coordinates")
+    if not np.all(chord > 0.0):           # 1 / ds^2 and the chord ratios would not be finite, and neither would the solution
+        i = int(np.argmin(chord > 0.0))
+        raise ValueError(f"points {i} and {(i + 1) % n} of the closed path coincide: a chord of length 0 (the last point must not repeat the first)")
     rho = chord / chord[nxt]
     nv = 4 * n
     # continuity constraints E c = 0, 3 rows per junction

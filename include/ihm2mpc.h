@@ -178,7 +178,13 @@ int ihm2mpc_build_tracks(ihm2mpc_handle *h, int32_t max_seg, const int32_t *nseg
  * min 1/2 p'Pp + q'p s.t. Ap = 0; here: its KKT system, one workgroup per track, sparse Gaussian elimination with partial pivoting).
  * xy (ntracks, max_pts, 2): centre-line points of every track, the first npts[t] rows used (closed path: the last point is NOT the first
  * again); curv_weight: weight of the curvature term (offline_motion_plan uses 2.0, :358); out coeffs_X, coeffs_Y (ntracks, max_pts, 4), host:
- * feed them to ihm2mpc_build_tracks; the rows past a track's npts[t] are returned as 0.  3 <= npts[t] <= max_pts <= 182. */
+ * feed them to ihm2mpc_build_tracks; the rows past a track's npts[t] are returned as 0.  3 <= npts[t] <= max_pts <= 182.
+ * A track's result depends on its own points, npts[t] and curv_weight only: not on its place in the batch, its neighbours or max_pts.
+ * Centre lines that cannot be fitted: two CONSECUTIVE equal points (the closing chord from the last point to the first counts: a chord of
+ * length 0 has no chord ratio) and any non-finite coordinate.  The elimination then runs out of usable pivots -- a NaN never wins the pivot
+ * search -- and the call returns non-zero with "the spline fit of track %d is singular" for the first such track
+ * (tests/test_gpu_track_shapes.py holds one line of each kind).  After a failure coeffs_X, coeffs_Y are undefined and the handle is as usable
+ * as before.  A point repeated elsewhere along the line (a crossing) is an ordinary input. */
 int ihm2mpc_fit_tracks(ihm2mpc_handle *h, int32_t max_pts, const int32_t *npts, const double *xy, double curv_weight, double *coeffs_X,
                        double *coeffs_Y);
 /* read the tables back, (ntracks, nknots) each; any pointer may be NULL */
