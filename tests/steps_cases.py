@@ -78,6 +78,7 @@ class Case:
     reason: str = ""        # FALLBACK entries: the steps_fallback the launch record must report
     form: tuple = ("general", "general")        # the launch record's (steps_form, steps_slots): which object of the name find_form takes
     B: int = B
+    tracks: int = 1         # 2: the handle holds the two tables of tests/multi_track_cases.py, instance b on track b mod 2 (TWO_TRACK)
 
     def ocp_opts(self) -> dict:
         o = dict(model=self.model, **INTEG[self.irk][1])
@@ -104,6 +105,10 @@ def start(track, case):
 
     N = LAYOUTS[case.layout].N
     lead = s_target(LAYOUTS[case.layout])
+    if case.tracks > 1:         # per track from that track's own table (``track`` is not used)
+        import multi_track_cases as MT
+
+        return MT.start_arrays(LAYOUTS[case.layout], case.B, case.seed, lead)
     x0 = drive.clipped_start(track, case.B, case.seed)
     yref = np.zeros((case.B, N, 12)); yref[:, :, 0] = x0[:, 0:1] + lead * np.arange(N)[None] / N
     yref_e = np.zeros((case.B, 8)); yref_e[:, 0] = x0[:, 0] + lead
@@ -117,12 +122,21 @@ def sqp_kwargs(data) -> dict:
                 full_step_dual=bool(data.full_step_dual))
 
 
-def oracle_problem(track, data, lay):
+def track_ids(case):
+    """The per-instance track ids of a case, None on one track."""
+    import multi_track_cases as MT
+
+    return MT.track_ids(case.B) if case.tracks > 1 else None
+
+
+def oracle_problem(track, data, lay, tables=None, widths=None):
     """The OracleProblem of a handle's data.  The C oracle has no ERK_LAG integrator: for such a handle it is used for everything but the
-    dynamics (its own records are replaced, see oracle_rti_step), as tests/test_gpu_lag_integrator.py does."""
+    dynamics (its own records are replaced, see oracle_rti_step), as tests/test_gpu_lag_integrator.py does.  ``tables`` = (s_ref,
+    kappa_ref) of several tracks and ``widths`` (ntracks, 2) replace the track's table and the layout's widths."""
     from oracle import oracle as orc
 
-    desc = dict(data.as_dict(track.s_ref, track.kappa_ref, track_widths=L.track_widths(lay)))
+    s_ref, kappa_ref = (track.s_ref, track.kappa_ref) if tables is None else tables
+    desc = dict(data.as_dict(s_ref, kappa_ref, track_widths=L.track_widths(lay) if widths is None else widths))
     if data.integrator == 3:        # ocp.INTEG_ERK_LAG
         desc["integrator"], desc["M"] = orc.INTEG_RK4, 25
     return orc.OracleProblem(desc)
@@ -135,14 +149,16 @@ def rti_status_of_qp(r) -> int:
     return 1 if r["status"] == 3 or not np.all(np.isfinite(r["dz"])) else 4 if r["status"] in (2, 4) else 0
 
 
-def oracle_rti_step(P, data, track, x, u, x0, yref, yref_e):
+def oracle_rti_step(P, data, track, x, u, x0, yref, yref_e, track_id=None):
     """OracleProblem.rti_step (x, u updated in place; status, qp_iter, pi, lam).  ERK_LAG: OracleProblem.build_qp at the iterate with
     A, B, b replaced by those of tests/lag_ref.py, orc.qp_solve, the step applied by orc_rti_step's rule
-    (tests/test_gpu_lag_integrator.py::test_rti_step_matches_the_oracle_qp_on_lag_ref_records)."""
+    (tests/test_gpu_lag_integrator.py::test_rti_step_matches_the_oracle_qp_on_lag_ref_records).  ``track_id``: per-instance track ids
+    of a problem with several tables (not with ERK_LAG: lag_ref takes one table)."""
     import numpy as np
 
     if data.integrator != 3:
-        return P.rti_step(x, u, x0, yref, yref_e)
+        return P.rti_step(x, u, x0, yref, yref_e, track_id=track_id)
+    assert track_id is None
     import lag_ref
     from oracle import oracle as orc
 
@@ -250,6 +266,21 @@ FALLBACK = {
     # select_steps: qp_sweeps_inside -- the SQP loops keep the sweeps' earlier form, whose prefetch starts in front of the LDS at N = 2, 3
     # (B = 50: 150 intervals -- at 128 and fewer the per-step plant is the state-only rollout, which rounds differently from the loop's)
     "sqp_N3": Case("per_step", "ref_N3", sqp=True, seed=701, reason=_NO, B=50),
+}
+
+# Two-track variants of the cases with track rows (PATH = 1: hard, soft, one with the SENS guest, one with collocation, whose
+# linearisation and plant take the track id by other ways; PATH = 2 has no k_steps and goes per step): the handle holds the two tables of
+# tests/multi_track_cases.py with that module's widths, instance b on track b mod 2, B = 8 (320 intervals: no latency batch).  A sibling
+# table -- CASES, FALLBACK, expected_records() and the record bookkeeping of tests/test_gpu_steps_catalogue.py do not see it;
+# tests/test_gpu_multi_track.py runs it and tests/test_oracle_multi_track.py checks the oracle's first step on both tracks.
+# id -> (case, the launch record run_steps must leave)
+_TWO = dict(tracks=2, B=8)
+TWO_TRACK = {
+    "hard": (dataclasses.replace(BY_NAME["k_steps<8,0,1,1,0,0,0>"], **_TWO), "k_steps<8,0,1,1,0,0,0>"),
+    "soft": (dataclasses.replace(BY_NAME["k_steps<10,4,1,1,0,0,0>"], **_TWO), "k_steps<10,4,1,1,0,0,0>"),
+    "soft_sens": (dataclasses.replace(BY_NAME["k_steps<8,3,1,1,0,0,0,1>"], **_TWO), "k_steps<8,3,1,1,0,0,0,1>"),
+    "soft_irk": (dataclasses.replace(BY_NAME["k_steps<10,4,1,1,0,1,0>"], **_TWO), "k_steps<10,4,1,1,0,1,0>"),
+    "alat_row": (dataclasses.replace(FALLBACK["alat_row"], **_TWO), "per_step:" + _NO),
 }
 
 # Catalogue entries no handle configuration can select: name -> the line of select_steps / find_form / rebuild_slots that rules it out

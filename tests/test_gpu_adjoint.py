@@ -40,7 +40,7 @@ def _identity_error(g_x0, sx, su, seed_x, seed_u, ok):
     return float((np.abs(g_x0[ok] - want).max((1, 2)) / scale).max())
 
 
-def _reference_errors(s, P, data, x0, yref, yref_e, xbar, ubar, g, seed_x, seed_u, nc, z, Z, path, idx, seeds=(0,)):
+def _reference_errors(s, P, data, x0, yref, yref_e, xbar, ubar, g, seed_x, seed_u, nc, z, Z, path, idx, seeds=(0,), track_id=None):
     """k_adj's gradients g of the instances idx against the dense reference at the GPU's own iterate and linearisation: the worst
     deviations of (grad_yref and grad_yref_e, grad_x0), each relative to the instance's largest entry of its kind."""
     A, Bm, b = s.get_linearization()
@@ -49,11 +49,12 @@ def _reference_errors(s, P, data, x0, yref, yref_e, xbar, ubar, g, seed_x, seed_
     N = s.N
     worst_y = worst_x = 0.0
     for i in idx:
-        ref = P.build_qp(xbar[i], ubar[i], x0[i], yref[i], yref_e[i]) if path else None
+        t = 0 if track_id is None else int(track_id[i])         # the instance's track where the handle holds several
+        ref = P.build_qp(xbar[i], ubar[i], x0[i], yref[i], yref_e[i], track_id=t) if path else None
         qp = L.assemble_qp(data, xbar[i], ubar[i], x0[i], yref[i], yref_e[i], A[i], Bm[i], b[i], nonlinear=ref)
         dz = np.zeros((N + 1, 10)); dz[:, :8] = o["x"][i] - xbar[i]; dz[:N, 8:] = o["u"][i] - ubar[i]
         # Gy from the oracle's own gradient (g is affine in the reference: adj_ref.gy_tables)
-        Gy, Gye = R.gy_tables(lambda yr, yre: P.build_qp(xbar[i], ubar[i], x0[i], yr, yre)["g"], yref[i], yref_e[i])
+        Gy, Gye = R.gy_tables(lambda yr, yre: P.build_qp(xbar[i], ubar[i], x0[i], yr, yre, track_id=t)["g"], yref[i], yref_e[i])
         for j in seeds:
             sd = np.zeros((N + 1, 10)); sd[:, :8] = seed_x[i, j]; sd[:N, 8:] = seed_u[i, j]
             zeta, nu0 = R.adjoint(qp, dz, lam[i], slk[i], z, Z, sd)

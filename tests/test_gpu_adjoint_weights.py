@@ -142,7 +142,7 @@ def _solve_refined(M, rhs, steps=3):
     return x.astype(np.float64)
 
 
-def _reference_errors(s, P, data, x0, yref, yref_e, xbar, ubar, g, seed_x, seed_u, nc, z, Z, path, idx):
+def _reference_errors(s, P, data, x0, yref, yref_e, xbar, ubar, g, seed_x, seed_u, nc, z, Z, path, idx, track_id=None):
     """The kernel's grad_W / grad_W_e of the instances idx, all seeds, against adj_ref + adjw_ref at the GPU's own iterate and
     linearisation: the worst deviation relative to the largest entry of the magnitude (per instance and seed), and the worst deviation
     of an entry relative to its own magnitude.  (adjw_ref's grad_W is the sum of its per-stage terms: on the stage_W layouts this is the
@@ -155,7 +155,7 @@ def _reference_errors(s, P, data, x0, yref, yref_e, xbar, ubar, g, seed_x, seed_
     worst = worst_entry = 0.0
     zp = _zplus(o["x"], o["u"])
     for i in idx:
-        ref = P.build_qp(xbar[i], ubar[i], x0[i], yref[i], yref_e[i]) if path else None
+        ref = P.build_qp(xbar[i], ubar[i], x0[i], yref[i], yref_e[i], track_id=0 if track_id is None else int(track_id[i])) if path else None
         qp = L.assemble_qp(data, xbar[i], ubar[i], x0[i], yref[i], yref_e[i], A[i], Bm[i], b[i], nonlinear=ref)
         dz = np.zeros((N + 1, 10)); dz[:, :8] = o["x"][i] - xbar[i]; dz[:N, 8:] = o["u"][i] - ubar[i]
         M = R.kkt_matrix(qp, dz, lam[i], slk[i], z, Z)           # adj_ref.adjoint's system, factored once for the eight seeds

@@ -54,15 +54,27 @@ class _Solved:
     """One solve of a layout from the start of tests/test_gpu_qp_layouts.py, and the host's view of every instance's QP at the GPU's own
     iterate: qp(i) -> (assemble_qp dict, dz, lam, sl) with the lateral-acceleration row's sides widened in where the layout has it."""
 
-    def __init__(self, track, lay, B, seed, build=None, solves=1):
+    def __init__(self, track, lay, B, seed, build=None, solves=1, tracks=None, sens_mode=1):
+        """``tracks``: a case of tests/multi_track_cases.py -- the handle then holds that case's tables, per-instance track ids and
+        widths (track, B and seed are the case's own), and the host's view takes every instance's own track."""
         from oracle import oracle as orc
 
         self.lay, self.B, self.N = lay, B, lay.N
-        self.s = s = _solver(track, lay, B, build)
+        if tracks is None:
+            self.track_id, self.widths = np.zeros(B, dtype=np.int32), (L.track_widths(lay) if lay.path else None)
+            self.s = s = _solver(track, lay, B, build)
+            self.P = orc.OracleProblem(s.data.as_dict(track.s_ref, track.kappa_ref, track_widths=L.track_widths(lay)))
+            self.x0, self.yref, self.yref_e = _start(s, track, B, seed)
+        else:
+            import multi_track_cases as MT
+
+            assert (lay, B) == (tracks.lay, tracks.B)
+            self.track_id, self.widths = tracks.track_id, tracks.widths
+            self.s = s = MT.solver(tracks, build or BUILD)
+            self.P = MT.oracle_problem(s.data, lay)
+            self.x0, self.yref, self.yref_e = MT.start(s, tracks)
         self.data = s.data
-        self.P = orc.OracleProblem(s.data.as_dict(track.s_ref, track.kappa_ref, track_widths=L.track_widths(lay)))
-        self.x0, self.yref, self.yref_e = _start(s, track, B, seed)
-        s.set_x0_sensitivities(1)
+        s.set_x0_sensitivities(sens_mode)
         for _ in range(solves):
             self.xbar, self.ubar = s.get_x(), s.get_u()
             self.st = s.solve()
@@ -76,7 +88,7 @@ class _Solved:
         N, o = self.N, self.o
         A, Bm, b = self.lin
         args = (self.xbar[i], self.ubar[i], self.x0[i], self.yref[i], self.yref_e[i])
-        ref = self.P.build_qp(*args) if self.lay.path else None
+        ref = self.P.build_qp(*args, track_id=int(self.track_id[i])) if self.lay.path else None
         qp = L.assemble_qp(self.data, *args, A[i], Bm[i], b[i], nonlinear=ref)
         dz = np.zeros((N + 1, 10)); dz[:, :8] = o["x"][i] - self.xbar[i]; dz[:N, 8:] = o["u"][i] - self.ubar[i]
         return qp, dz, self.lam[i], self.slk[i]
@@ -94,15 +106,16 @@ class _Solved:
         if lay.path:
             raw[:, 12:14], raw[:, nc + 12:nc + 14] = np.asarray(d.lh)[:2], np.asarray(d.uh)[:2]
             common = np.abs(xb[:, 1]) + 0.5 * d.car_L * np.abs(np.sin(xb[:, 2])) + 0.5 * d.car_W * np.abs(np.cos(xb[:, 2]))
-            vm[:, 12:14] = common[:, None] + L.track_widths(lay)[0][None]
+            vm[:, 12:14] = common[:, None] + self.widths[self.track_id[i]][None]
         if lay.alat:
             raw[:, 14], raw[:, nc + 14] = d.alat_lb, d.alat_ub
-            du14 = self.P.build_qp(xb, ub, self.x0[i], self.yref[i], self.yref_e[i])["du"][:, 14]
+            du14 = self.P.build_qp(xb, ub, self.x0[i], self.yref[i], self.yref_e[i], track_id=int(self.track_id[i]))["du"][:, 14]
             vm[:, 14] = np.abs(np.where(np.isfinite(du14), d.alat_ub - du14, 0.0))
         return np.abs(raw) + np.concatenate([vm, vm], 1)
 
     def gy(self, i):
-        return R.gy_tables(lambda yr, yre: self.P.build_qp(self.xbar[i], self.ubar[i], self.x0[i], yr, yre)["g"], self.yref[i], self.yref_e[i])
+        t = int(self.track_id[i])
+        return R.gy_tables(lambda yr, yre: self.P.build_qp(self.xbar[i], self.ubar[i], self.x0[i], yr, yre, track_id=t)["g"], self.yref[i], self.yref_e[i])
 
 
 def _refined(M, rhs):

@@ -32,9 +32,13 @@ def _solver(track, case, build="default", **more):
     from ihm2_amd.solver import BatchedOcpSolver
 
     lay = S.LAYOUTS[case.layout]
+    tables, tracks = (track.s_ref, track.kappa_ref), dict(track_widths=L.track_widths(lay))
+    if case.tracks > 1:         # a case of steps_cases.TWO_TRACK: both tables, per-instance ids and widths per track
+        import multi_track_cases as MT
+
+        tables, tracks = MT.tables(), dict(track_id=S.track_ids(case), track_widths=MT.widths(lay))
     with _build(build):
-        s = BatchedOcpSolver(L.make_ocp(lay, **{**case.ocp_opts(), **more}), case.B, track.s_ref, track.kappa_ref,
-                             track_widths=L.track_widths(lay))
+        s = BatchedOcpSolver(L.make_ocp(lay, **{**case.ocp_opts(), **more}), case.B, *tables, **tracks)
     arr = L.apply(s.data, lay)
     if arr["W"] is not None:
         s._push_weights()
@@ -144,6 +148,10 @@ def _rel(a, b):
 
 
 def _oracle(track, s, case):
+    if case.tracks > 1:
+        import multi_track_cases as MT
+
+        return S.oracle_problem(track, s.data, S.LAYOUTS[case.layout], tables=MT.tables(), widths=MT.widths(S.LAYOUTS[case.layout]))
     return S.oracle_problem(track, s.data, S.LAYOUTS[case.layout])
 
 
@@ -159,7 +167,8 @@ def _assert_rti_matches_oracle(track, case):
     x, u = s.get_x(), s.get_u()
     x_lin, u_lin = x.copy(), u.copy()
     st = s.solve()
-    out = S.oracle_rti_step(P, data, track, x, u, x0, yref, yref_e)
+    tid = S.track_ids(case)         # None on one track
+    out = S.oracle_rti_step(P, data, track, x, u, x0, yref, yref_e, track_id=tid)
     pi, lam = out["pi"], out["lam"]
     itg = s.get_qp_iter()
     xg, ug = s.get_x(), s.get_u()
@@ -181,7 +190,7 @@ def _assert_rti_matches_oracle(track, case):
     if data.soft_Z is not None:
         z, Z = L.soft_arrays(data)
         for i in np.flatnonzero(ok):
-            ref = P.build_qp(x_lin[i], u_lin[i], x0[i], yref[i], yref_e[i])
+            ref = P.build_qp(x_lin[i], u_lin[i], x0[i], yref[i], yref_e[i], track_id=0 if tid is None else int(tid[i]))
             sol = orc.qp_solve(**ref, iter_max=data.ipm_iter_max, tol=data.ipm_tol, mu0=data.ipm_mu0, tau0=data.ipm_tau0, soft_z=z, soft_Z=Z)
             if sol["iters"] == itg[i]:
                 assert np.max(np.abs(slg[i] - sol["sl"]) / (1 + np.abs(sol["sl"]))) < 1e-7
