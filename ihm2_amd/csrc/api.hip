@@ -123,8 +123,8 @@ const char *row_name(int c)
     return (c >= 0 && c < NC) ? names[c] : "?";
 }
 
-// Per-instance bounds -> the slot table of the batch-shared pattern (qp_tables.hpp: scatter_slot_bounds), and the SQP mode's (NS,NC)
-// bounds alike.  Refuses when the stored values' finite sides differ from the shared table's (a later shared setter may have changed them).
+// Per-instance bounds take the batch-shared pattern: refuses when the values' finite sides differ from the shared table's (a later shared
+// setter may have changed them).
 int check_instance_pattern(const ihm2mpc_handle *h, const double *il, const double *iu)
 {
     const ihm2::PatternMismatch m = ihm2::find_pattern_mismatch(h->rows, h->B, il, iu);
@@ -132,9 +132,6 @@ int check_instance_pattern(const ihm2mpc_handle *h, const double *il, const doub
     return fail("instance %d, stage %d, row %d (%s): the finite sides (%s, %s) differ from the batch-shared table's (%s, %s)", m.b, m.k, m.c,
                 row_name(m.c), m.lower ? "lower" : "-", m.upper ? "upper" : "-", m.shared_lower ? "lower" : "-", m.shared_upper ? "upper" : "-");
 }
-
-int scatter_instance_tables(ihm2mpc_handle *h);
-int scatter_instance_bounds(ihm2mpc_handle *h) { return scatter_instance_tables(h); }
 
 // Per-instance slack penalties (ihm2mpc_set_instance_soft / _alat_soft): the same for the values z, Z of the soft sides.
 const char *side_name(int side)
@@ -164,66 +161,54 @@ int check_penalty_pattern(const ihm2mpc_handle *h, const double *iz, const doubl
     }
 }
 
-// The per-instance tables of either mode (bounds, slack penalties) onto the device, in the layout the kernels read: per instance the slot
-// table's bounds and behind them its penalties -- (B, 2, entries): lb | zw and ub | Zw -- and the (stage, row) bounds with the (stage, side)
-// penalties behind them -- (B, NS*NC + NS*NLAM): lb | z and ub | Z -- so that one base per instance serves both.  A mode that is off
-// contributes the batch-shared values.  Bounds whose finite sides differ from the shared table's are a refusal (-1, as before); penalties that
-// the pattern does not take any more (a later shared setter changed it) are no error of that setter: inst_p_ok stays false and ready()
-// reports it before the next solve.
-int scatter_instance_tables(ihm2mpc_handle *h)
+// The constraint tables onto the device, and the flags that say what the device holds: the one place for both.  qp_tables.hpp:
+// table_images builds every image in the layout the kernels read -- the slot table's lb | zw and ub | Zw, the (stage, row) bounds with the
+// (stage, side) penalties behind them, lb | z and ub | Z -- so that one base serves the bounds and the penalties.  The batch-shared images
+// always; the per-instance images (B of each, one base per instance) while either per-instance mode (bounds, slack penalties) is on -- a
+// mode that is off contributes the batch-shared values -- and released when both are off.  Bounds whose finite sides differ from the shared
+// table's are a refusal (-1); penalties that the pattern does not take any more (a later shared setter changed it) are no error of that
+// setter: inst_p_ok stays false and ready() reports it before the next solve.
+int tables_to_device(ihm2mpc_handle *h)
 {
-    const int B = h->B, NS = h->NS;
-    h->inst_b_ok = false; h->inst_p_ok = false;
-    h->slots_full = false;
-    if (h->inst_b && check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
-    const double *iz = h->ih_sz.empty() ? nullptr : h->ih_sz.data(), *iZ = h->ih_sZ.empty() ? nullptr : h->ih_sZ.data();
-    const double *az = h->ih_az.empty() ? nullptr : h->ih_az.data(), *aZ = h->ih_aZ.empty() ? nullptr : h->ih_aZ.data();
-    const bool p_fit = h->inst_p && !ihm2::find_penalty_mismatch(h->rows, B, iz, iZ, az, aZ).found();
-    if (!p_fit) iz = iZ = az = aZ = nullptr;       // (the shared values: launches are refused until the penalties are set again or dropped)
+    const int B = h->B;
+    const bool inst = h->inst_b || h->inst_p;
     const ihm2::SlotTable &t = h->slots;
-    const ihm2::ConstraintRows &r = h->rows;
-    const size_t n = t.entries(), nb = (size_t)NS * NC, np = (size_t)NS * NLAM;
-    std::vector<double> slb, sub, stl, stu, szw, sZw, stz, stZ, alz, alZ;
-    if (h->inst_b) {
-        ihm2::scatter_slot_bounds(t, B, NS, h->ih_lb.data(), h->ih_ub.data(), slb, sub);
-        ihm2::scatter_stage_bounds(r, B, h->ih_lb.data(), h->ih_ub.data(), stl, stu);
-    } else {
-        for (int b = 0; b < B; b++) {
-            slb.insert(slb.end(), t.lb.begin(), t.lb.end()); sub.insert(sub.end(), t.ub.begin(), t.ub.end());
-            stl.insert(stl.end(), r.lb.begin(), r.lb.end()); stu.insert(stu.end(), r.ub.begin(), r.ub.end());
+    h->inst_b_ok = false; h->inst_p_ok = false;
+    h->slots_full = false;      // until a table and every bound that goes with it are on the device
+    ihm2::TableImages m = ihm2::table_images(t, h->rows, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (m.entries && (upload_shared(h, m.slot_lo.data(), h->slot_lb, m.slot_lo.size()) || upload_shared(h, m.slot_up.data(), h->slot_ub, m.slot_up.size())))
+        return -1;
+    if (upload_shared(h, m.stage_lo.data(), h->st_lb, m.stage_lo.size()) || upload_shared(h, m.stage_up.data(), h->st_ub, m.stage_up.size())) return -1;
+    if ((!inst && h->i_st_lb) || (!h->inst_p && h->ip.alat_sz)) HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the arrays
+    if (!h->inst_p) h->ip.reset();
+    if (!inst) { h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset(); }
+    if (inst) {
+        if (h->inst_b && check_instance_pattern(h, h->ih_lb.data(), h->ih_ub.data())) return -1;
+        const double *il = h->inst_b ? h->ih_lb.data() : nullptr, *iu = h->inst_b ? h->ih_ub.data() : nullptr;
+        const double *iz = h->ih_sz.empty() ? nullptr : h->ih_sz.data(), *iZ = h->ih_sZ.empty() ? nullptr : h->ih_sZ.data();
+        const double *az = h->ih_az.empty() ? nullptr : h->ih_az.data(), *aZ = h->ih_aZ.empty() ? nullptr : h->ih_aZ.data();
+        const bool p_fit = h->inst_p && !ihm2::find_penalty_mismatch(h->rows, B, iz, iZ, az, aZ).found();
+        if (!p_fit) iz = iZ = az = aZ = nullptr;       // (the shared values: launches are refused until the penalties are set again or dropped)
+        m = ihm2::table_images(t, h->rows, B, il, iu, iz, iZ, az, aZ);
+        if (m.slot_lo.size() > h->i_slot_lb.size() || !h->i_st_lb) {
+            HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
+            if (m.slot_lo.size() > h->i_slot_lb.size()) {
+                h->i_slot_lb.reset(); h->i_slot_ub.reset();
+                if (alloc_all(h->i_slot_lb, m.slot_lo.size(), h->i_slot_ub, m.slot_up.size())) return -1;
+            }
+            if (!h->i_st_lb && alloc_all(h->i_st_lb, m.stage_lo.size(), h->i_st_ub, m.stage_up.size())) return -1;
         }
-    }
-    ihm2::scatter_slot_penalties(t, r, B, NS, iz, iZ, az, aZ, szw, sZw);
-    ihm2::scatter_stage_penalties(r, B, iz, iZ, az, aZ, stz, stZ, alz, alZ);
-    std::vector<double> dl((size_t)B * 2 * n), du((size_t)B * 2 * n), tl((size_t)B * (nb + np)), tu((size_t)B * (nb + np));
-    for (size_t b = 0; b < (size_t)B; b++) {
-        std::copy(slb.begin() + b * n, slb.begin() + (b + 1) * n, dl.begin() + b * 2 * n);
-        std::copy(szw.begin() + b * n, szw.begin() + (b + 1) * n, dl.begin() + b * 2 * n + n);
-        std::copy(sub.begin() + b * n, sub.begin() + (b + 1) * n, du.begin() + b * 2 * n);
-        std::copy(sZw.begin() + b * n, sZw.begin() + (b + 1) * n, du.begin() + b * 2 * n + n);
-        std::copy(stl.begin() + b * nb, stl.begin() + (b + 1) * nb, tl.begin() + b * (nb + np));
-        std::copy(stz.begin() + b * np, stz.begin() + (b + 1) * np, tl.begin() + b * (nb + np) + nb);
-        std::copy(stu.begin() + b * nb, stu.begin() + (b + 1) * nb, tu.begin() + b * (nb + np));
-        std::copy(stZ.begin() + b * np, stZ.begin() + (b + 1) * np, tu.begin() + b * (nb + np) + nb);
-    }
-    if (dl.size() > h->i_slot_lb.size() || !h->i_st_lb) {
-        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
-        if (dl.size() > h->i_slot_lb.size()) {
-            h->i_slot_lb.reset(); h->i_slot_ub.reset();
-            if (alloc_all(h->i_slot_lb, dl.size(), h->i_slot_ub, du.size())) return -1;
-        }
-        if (!h->i_st_lb && alloc_all(h->i_st_lb, tl.size(), h->i_st_ub, tu.size())) return -1;
-    }
-    if (n && (upload_shared(h, dl.data(), h->i_slot_lb, dl.size()) || upload_shared(h, du.data(), h->i_slot_ub, du.size()))) return -1;
-    if (upload_shared(h, tl.data(), h->i_st_lb, tl.size()) || upload_shared(h, tu.data(), h->i_st_ub, tu.size())) return -1;
-    if (h->inst_p) {        // the cost kernel's copies: (B,NS,NLAM) and the a_lat row's (B,2)
-        if (!h->ip.st_sz && alloc_all(h->ip.st_sz, stz.size(), h->ip.st_sZ, stZ.size(), h->ip.alat_sz, alz.size(), h->ip.alat_sZ, alZ.size())) return -1;
-        if (upload_shared(h, stz.data(), h->ip.st_sz, stz.size()) || upload_shared(h, stZ.data(), h->ip.st_sZ, stZ.size()) ||
-            upload_shared(h, alz.data(), h->ip.alat_sz, alz.size()) || upload_shared(h, alZ.data(), h->ip.alat_sZ, alZ.size()))
+        if (m.entries && (upload_shared(h, m.slot_lo.data(), h->i_slot_lb, m.slot_lo.size()) || upload_shared(h, m.slot_up.data(), h->i_slot_ub, m.slot_up.size())))
             return -1;
+        if (upload_shared(h, m.stage_lo.data(), h->i_st_lb, m.stage_lo.size()) || upload_shared(h, m.stage_up.data(), h->i_st_ub, m.stage_up.size())) return -1;
+        if (h->inst_p) {        // the a_lat row's (B,2) pairs, which the cost reads beside the tables
+            if (!h->ip.alat_sz && alloc_all(h->ip.alat_sz, m.alat_z.size(), h->ip.alat_sZ, m.alat_Z.size())) return -1;
+            if (upload_shared(h, m.alat_z.data(), h->ip.alat_sz, m.alat_z.size()) || upload_shared(h, m.alat_Z.data(), h->ip.alat_sZ, m.alat_Z.size())) return -1;
+        }
+        h->inst_b_ok = h->inst_b; h->inst_p_ok = p_fit;
     }
-    h->inst_b_ok = h->inst_b; h->inst_p_ok = p_fit;
-    h->slots_full = ihm2::slot_table_full(t, ihm2::full_form_nslot()) && ihm2::slot_bounds_full(t, B, slb, sub);
+    // the full slot form: the table, with the bounds of every instance that the device now holds
+    h->slots_full = h->slots_fit && ihm2::slot_table_full(t, ihm2::full_form_nslot()) && ihm2::slot_bounds_full(t, inst ? B : 1, m.slot_lo, m.slot_up);
     return 0;
 }
 
@@ -268,7 +253,7 @@ QpArgs qp_args(ihm2mpc_handle *h)
     a.x = h->x; a.u = h->u; a.x0 = h->x0; a.yref = h->yref; a.yref_e = h->yref_e;
     a.pi = h->pi; a.lam = h->lam; a.res = h->res; a.qp_res = h->qp_res; a.u0 = h->u0; a.status = h->status; a.qp_iter = h->qp_iter;
     a.lin = h->lin; a.g = h->q_g; a.rg = h->q_rg; a.P = h->q_P; a.M = h->q_M + (size_t)QM_PAD * 64;
-    a.slot_zw = h->slot_zw; a.slot_Zw = h->slot_Zw; a.slk = h->slk;      // (the kernels read zw, Zw behind slot_lb, slot_ub)
+    a.unused_pad0 = nullptr; a.unused_pad1 = nullptr; a.slk = h->slk;
     a.track_id = h->track_id; a.widths = h->widths; a.car_L = h->car_L; a.car_W = h->car_W;
     a.lam_a = h->lam_a; a.slk_a = h->slk_a;
     a.symmetrize = (h->cfg.model == IHM2MPC_MODEL_FDYN6) ? 1 : 0;
@@ -573,10 +558,10 @@ int ihm2mpc_create(const ihm2mpc_config *cfg, ihm2mpc_handle **out)
     }
     if (alloc_all(h->s_ref, nt, h->kappa_ref, nt, h->track_id, B, h->Hs, NS * 100, h->Gy, NS * 120, h->lbx, NS * 8, h->ubx, NS * 8,
                   h->lbu, N * 2, h->ubu, N * 2, h->CD, N * 20, h->lg, N * 2, h->ug, N * 2, h->slot_kc_blk, 1024, h->slot_lb_blk, 1024,
-                  h->slot_ub_blk, 1024, h->slot_kc, MAX_SLOTS, h->slot_lb, 2 * MAX_SLOTS, h->slot_ub, 2 * MAX_SLOTS, h->slot_zw, MAX_SLOTS,
-                  h->slot_Zw, MAX_SLOTS, h->slk, B * NS * NLAM, h->widths, (size_t)cfg->ntracks * 2, h->lam_a, B * NS * 2, h->slk_a, B * NS * 2,
+                  h->slot_ub_blk, 1024, h->slot_kc, MAX_SLOTS, h->slot_lb, 2 * MAX_SLOTS, h->slot_ub, 2 * MAX_SLOTS,
+                  h->slk, B * NS * NLAM, h->widths, (size_t)cfg->ntracks * 2, h->lam_a, B * NS * 2, h->slk_a, B * NS * 2,
                   h->X_ref, nt, h->Y_ref, nt, h->phi_ref, nt, h->xc, B * 8, h->s_guess, B, h->step_args, 48, h->Wd, N * 144 + 64,
-                  h->st_lb, NS * (NC + NLAM), h->st_ub, NS * (NC + NLAM), h->st_sz, NS * NLAM, h->st_sZ, NS * NLAM, h->x, B * NS * 8, h->u, B * N * 2, h->x0, B * 8,
+                  h->st_lb, NS * (NC + NLAM), h->st_ub, NS * (NC + NLAM), h->x, B * NS * 8, h->u, B * N * 2, h->x0, B * 8,
                   h->yref, B * N * 12, h->yref_e, B * 8, h->pi, B * NS * 8, h->lam, B * NS * NLAM, h->res, B * 4, h->qp_res, B * 4, h->status, B,
                   h->qp_iter, B, h->active, B, h->u0, B * 2,
                   h->lin, (B * N + B) * LIN_REC,      // + one spare record per instance (the kinematic plant's, never read)
@@ -779,32 +764,20 @@ static int rebuild_slots(ihm2mpc_handle *h)
 {
     ihm2::SlotTable t = ihm2::lay_out_slots(h->rows, ihm2::slot_limits(path_class(h)));
     h->slots_fit = t.fit;
-    h->slots_full = false;      // until a table and every bound that goes with it are on the device (a table that does not fit: launches are refused)
+    h->slots_full = false;      // (a table that does not fit: launches are refused)
     if (!t.fit) return 0;
     h->slots = std::move(t);
     const ihm2::SlotTable &s = h->slots;
-    const ihm2::ConstraintRows &r = h->rows;
     if (s.per_blk) {
         HIP_TRY(hipMemcpyAsync(h->slot_kc_blk, s.kc_blk.data(), s.kc_blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         if (upload_shared(h, s.lb_blk.data(), h->slot_lb_blk, s.lb_blk.size()) || upload_shared(h, s.ub_blk.data(), h->slot_ub_blk, s.ub_blk.size())) return -1;
     }
-    // the SQP mode's copies of the rows
-    if (upload_shared(h, r.lb.data(), h->st_lb, r.lb.size()) || upload_shared(h, r.ub.data(), h->st_ub, r.ub.size()) ||
-        upload_shared(h, r.sz.data(), h->st_sz, r.sz.size()) || upload_shared(h, r.sZ.data(), h->st_sZ, r.sZ.size()) ||
-        upload_shared(h, r.sz.data(), h->st_lb + r.lb.size(), r.sz.size()) || upload_shared(h, r.sZ.data(), h->st_ub + r.ub.size(), r.sZ.size()))
-        return -1;      // (the penalties once more behind the bounds: what the line search reads)
     if (const size_t n = s.entries()) {
         HIP_TRY(hipMemcpyAsync(h->slot_kc, s.kc.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        if (upload_shared(h, s.lb.data(), h->slot_lb, n) || upload_shared(h, s.ub.data(), h->slot_ub, n) ||
-            upload_shared(h, s.zw.data(), h->slot_zw, n) || upload_shared(h, s.Zw.data(), h->slot_Zw, n) ||
-            upload_shared(h, s.zw.data(), h->slot_lb + n, n) || upload_shared(h, s.Zw.data(), h->slot_ub + n, n))
-            return -1;      // (zw, Zw once more behind the bounds: what the kernels read)
     }
-    if (h->inst_b || h->inst_p) return scatter_instance_tables(h);     // the per-instance values into the new table (or a refusal: ready() then reports it)
-    h->slots_full = ihm2::slot_table_full(s, ihm2::full_form_nslot());
-    return 0;
+    return tables_to_device(h);     // the bounds and penalties of the new table, per instance too (or a refusal: ready() then reports it)
 }
 
 int ihm2mpc_set_bounds(ihm2mpc_handle *h, const double *lbx, const double *ubx, const double *lbu, const double *ubu,
@@ -844,13 +817,10 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
     const bool none = !lbx && !ubx && !lbu && !ubu && !lg && !ug;
     if (none) {
         HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the arrays
-        if (!h->inst_p) { h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset(); }     // (the penalties' mode keeps them)
         h->i_lbu.reset(); h->i_ubu.reset(); h->i_lg.reset(); h->i_ug.reset();
         h->ih_lb = std::vector<double>(); h->ih_ub = std::vector<double>();
-        h->inst_b = false; h->inst_b_ok = false;
-        if (h->inst_p) return scatter_instance_tables(h);       // the per-instance penalties stay, beside the shared bounds
-        h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, ihm2::full_form_nslot());        // the batch-shared bounds again
-        return 0;
+        h->inst_b = false;
+        return tables_to_device(h);     // the batch-shared bounds again, beside the per-instance penalties if there are any
     }
     if (!lbx || !ubx || !lbu || !ubu || !lg || !ug) return fail("lbx, ubx, lbu, ubu, lg, ug must all be given, or all be NULL (batch-shared bounds again)");
     if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called (the batch-shared table gives the pattern)");
@@ -877,8 +847,7 @@ int ihm2mpc_set_instance_bounds(ihm2mpc_handle *h, const double *lbx, const doub
         upload_shared(h, lg, h->i_lg, (size_t)B * N * 2) || upload_shared(h, ug, h->i_ug, (size_t)B * N * 2))
         return -1;
     h->inst_b = true;
-    if (scatter_instance_bounds(h)) return -1;
-    return 0;
+    return tables_to_device(h);
 }
 
 int ihm2mpc_set_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft_Z)
@@ -902,16 +871,7 @@ int ihm2mpc_set_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft
 static int instance_penalties_changed(ihm2mpc_handle *h)
 {
     h->inst_p = !h->ih_sz.empty() || !h->ih_az.empty();
-    if (!h->inst_p) {
-        HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the arrays
-        h->ip.reset();
-        h->inst_p_ok = false;
-        if (h->inst_b) return scatter_instance_tables(h);       // the per-instance bounds stay, beside the shared penalties
-        h->i_slot_lb.reset(); h->i_slot_ub.reset(); h->i_st_lb.reset(); h->i_st_ub.reset();
-        h->slots_full = h->bounds_set && h->slots_fit && ihm2::slot_table_full(h->slots, ihm2::full_form_nslot());
-        return 0;
-    }
-    return scatter_instance_tables(h);
+    return tables_to_device(h);
 }
 
 // the new values of one entry into the handle (empty vectors: shared again); on a failure the previous ones are put back, on the host and,

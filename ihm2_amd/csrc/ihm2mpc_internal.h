@@ -100,12 +100,12 @@ public:
     }
 };
 
-// The per-instance slack penalties on the device (ihm2mpc_set_instance_soft / _alat_soft), allocated while the mode is on: state, every
-// member a StateBuf.  The handle holds the block by value (ihm2mpc_handle::ip).
+// What the per-instance slack penalties (ihm2mpc_set_instance_soft / _alat_soft) keep on the device beside the constraint tables
+// (i_slot_*, i_st_* of the handle, which hold the penalties of the rows 0..13 and of the slots), allocated while the mode is on: state,
+// every member a StateBuf.  The handle holds the block by value (ihm2mpc_handle::ip).
 struct ihm2_inst_penalties {
-    StateBuf<double> st_sz, st_sZ;         // (B,NS,NLAM) per (stage, side): the cost
     StateBuf<double> alat_sz, alat_sZ;     // (B,2) the a_lat row's: the cost
-    void reset() { st_sz.reset(); st_sZ.reset(); alat_sz.reset(); alat_sZ.reset(); }
+    void reset() { alat_sz.reset(); alat_sZ.reset(); }
 };
 
 // Created by value-initialisation (std::make_unique<ihm2mpc_handle>() in ihm2mpc_create): there is no user-provided constructor, so every
@@ -139,10 +139,16 @@ struct ihm2mpc_handle {
     ihm2::SlotTable slots;         // the last table that fitted, as the device holds it
     bool slots_full;               // the table (with the per-instance bounds, if any) takes the full slot form (qp_tables.hpp: slot_table_full)
     bool slots_fit;                // false: the rows set so far fit no instantiation (reported by the next solve: a later setter may still change them)
-    StateBuf<int32_t> slot_kc;             // (slots.per_lane*64) stage * 16 + row, -1 = padding
-    StateBuf<double> slot_lb, slot_ub;     // raw bounds, +-inf if that side is absent (soft slots are one-sided); behind them, at the offset
-                                           // slots.per_lane*64, the slots' slack penalties: zw behind lb, Zw behind ub -- what the kernels read
-    StateBuf<double> slot_zw, slot_Zw;     // slack cost zw s + 1/2 Zw s^2 of a soft slot; Zw < 0 = hard slot (the batch-shared table on its own)
+    // The constraint tables on the device, one copy of each (api.hip: tables_to_device uploads the images of qp_tables.hpp: table_images).
+    // Every table is a pair of arrays with two halves, the bounds and behind them the slack penalties, so that one base serves both:
+    //   the slot table    (2, entries)            lb | zw and ub | Zw, entries = slots.per_lane*64: raw bounds, +-inf if that side is absent
+    //                                             (soft slots are one-sided), then the slack cost zw s + 1/2 Zw s^2 of a soft slot, Zw < 0 =
+    //                                             hard slot -- the QP, the sensitivities and the adjoint kernels
+    //   the stage table   (NS*NC + NS*NLAM)       rows.lb | rows.sz and rows.ub | rows.sZ per (stage, row) and (stage, side) -- the SQP
+    //                                             mode's line search and the cost
+    // batch-shared here; per instance (B of each, i_slot_*, i_st_* below) while a per-instance mode is on.
+    StateBuf<int32_t> slot_kc;             // (entries) stage * 16 + row, -1 = padding
+    StateBuf<double> slot_lb, slot_ub;     // the slot table
     StateBuf<int32_t> slot_kc_blk;         // the same rows spread over 256 lanes (k_qp_block: four wavefronts per instance), all-hard tables only
     StateBuf<double> slot_lb_blk, slot_ub_blk;
     std::string poison;            // IHM2MPC_POISON_WORKSPACE as read at creation: "" / "0" off, "1" every workspace of doubles, else a list of names
@@ -199,8 +205,7 @@ struct ihm2mpc_handle {
     int sqp_globalization, sqp_use_suff, sqp_full_step_dual;   // globalization: 0 FIXED_STEP, 1 MERIT_BACKTRACKING
     double sqp_alpha_min, sqp_alpha_red, sqp_eps, sqp_tol[4];
     StateBuf<double> Wd;                     // (N,12,12) then W_e (8,8): the merit function evaluates the cost from the weights themselves
-    StateBuf<double> st_lb, st_ub;           // (NS,NC) device copies of rows.lb / rows.ub, and behind them (NS,NLAM) rows.sz / rows.sZ: z behind lb, Z behind ub
-    StateBuf<double> st_sz, st_sZ;           // (NS,NLAM) device copies of rows.sz / rows.sZ
+    StateBuf<double> st_lb, st_ub;           // the stage table (described at slot_lb above)
     // allocated together by the first SQP solve (api.hip: sqp_buffers): the iterate the QP was built at, merit weights, per-solve bookkeeping
     WorkBuf<double> ls_x, ls_u, ls_pi, ls_lam, ls_slk, ls_wpi, ls_wlam, ls_alpha;
     WorkBuf<double> ls_merit;               // (B,4) merit values of the last line search (ihm2mpc_get_sqp_merit; sqp_body.hpp: LsArgs.merit)
@@ -222,16 +227,16 @@ struct ihm2mpc_handle {
     bool shared_uniform_H;         // uniform_H of the batch-shared weights (restored when the per-instance weights go)
     StateBuf<double> iHs, iGy, iWd;          // (B,2,100) stage, terminal | (B,2,120) | (B,144+64): the layouts of Hs, Gy, Wd with one stage
     std::vector<double> ih_lb, ih_ub;      // host (B,NS,12) bounds of the rows 0..11, +-inf = absent
-    StateBuf<double> i_slot_lb, i_slot_ub;   // (B,2,slots.per_lane*64) the slot table's bounds, then penalties, per instance (either mode), grown on demand
-    StateBuf<double> i_st_lb, i_st_ub;       // (B, NS*NC + NS*NLAM) the SQP mode's bounds, then penalties, per instance (either mode)
+    StateBuf<double> i_slot_lb, i_slot_ub;   // (B,2,entries) the slot table per instance (either mode; the other's rows hold the shared values), grown on demand
+    StateBuf<double> i_st_lb, i_st_ub;       // (B, NS*NC + NS*NLAM) the stage table per instance (either mode)
     StateBuf<double> i_lbu, i_ubu, i_lg, i_ug;   // (B,N,2) as given: the Stanley guess clamps to them
     // Slack penalties (ihm2mpc_set_instance_soft / _alat_soft): the VALUES z, Z per instance; which sides are soft stays batch-shared.
-    // One mode for the kernels (inst_p: either entry is on); the rows an entry has not set hold the shared values in the buffers below.
+    // One mode for the kernels (inst_p: either entry is on); the rows an entry has not set hold the shared values in the tables above.
     bool inst_p;
     bool inst_p_ok;                // false: a later setter changed the shared pattern and the stored values no longer fit it
     std::vector<double> ih_sz, ih_sZ;      // host (B,NS,NLAM) penalties of the rows 0..13, empty: shared
     std::vector<double> ih_az, ih_aZ;      // host (B,2) penalties of the a_lat row, empty: shared
-    ihm2_inst_penalties ip;                // their device copies (state; tests/test_instance_penalties_abi.py reads the struct's classes)
+    ihm2_inst_penalties ip;                // the a_lat pairs' device copies (state; tests/test_instance_penalties_abi.py reads the struct's classes)
 
     // ---- history of ihm2mpc_run_steps, grown on demand ----
     WorkBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)
@@ -322,7 +327,10 @@ struct QpArgs {
     int nslots_can;     // entries of the 64-lane slot table: the order in which the slot sums (mu, mu_aff) are taken, whatever the number of waves per instance
     double tol, mu0, tau0;
     // shared
-    const double *Hs, *Gy, *CD, *slot_lb, *slot_ub, *slot_zw, *slot_Zw;
+    // slot_lb, slot_ub: lb | zw and ub | Zw, the penalties nslots_can doubles behind the bounds.  unused_pad0, unused_pad1: read by nothing and
+    // set to nullptr -- they keep the offsets of the members behind them, on which the compiler's grouping of the kernels' scalar loads depends
+    // (without them the soft k_qp_wave instantiations change their instruction counts, NOTES.md R27)
+    const double *Hs, *Gy, *CD, *slot_lb, *slot_ub, *unused_pad0, *unused_pad1;
     const int32_t *slot_kc;
     // per-instance tuning (api.hip: ihm2mpc_set_instance_weights / _bounds): doubles of Hs / Gy / slot_lb, slot_ub per instance (0: batch-shared)
     // and the offset of the terminal stage's Hs / Gy block (N * 100, N * 120 batch-shared; 100, 120 per instance: (B,2,100), (B,2,120))
@@ -352,7 +360,7 @@ struct SensArgs {
     int hs_bs, hs_te, hs_ks;
     const double *CD;
     const int32_t *slot_kc;
-    const double *slot_lb, *slot_ub, *slot_zw, *slot_Zw;
+    const double *slot_lb, *slot_ub, *unused_pad0, *unused_pad1;     // lb | zw and ub | Zw, and the padding, as QpArgs' (without it k_sens changes)
     int sl_bs;          // doubles of slot_lb / slot_ub per instance (0: batch-shared)
     const int32_t *track_id;
     const double *widths;

@@ -215,12 +215,9 @@ void ihm2_launch_cost(ihm2mpc_handle *h, int grad, double *cost, double *stage_c
     if (h->inst_w) { a.W = h->iWd; a.w_bs = 208; a.w_ks = 0; a.w_te = 144; a.w_same = 1; }
     a.st_lb = h->st_lb; a.st_ub = h->st_ub; a.st_bs = 0;
     if (h->inst_b || h->inst_p) { a.st_lb = h->i_st_lb; a.st_ub = h->i_st_ub; a.st_bs = h->NS * (NC + NLAM); }
-    a.st_sz = h->st_sz; a.st_sZ = h->st_sZ; a.sp_bs = 0;
+    a.st_sz = a.st_lb + h->NS * NC; a.st_sZ = a.st_ub + h->NS * NC; a.sp_bs = a.st_bs;      // the penalties: the second half of the same table
     a.alat_pz = nullptr; a.alat_pZ = nullptr; a.al_bs = 0;
-    if (h->inst_p) {
-        a.st_sz = h->ip.st_sz; a.st_sZ = h->ip.st_sZ; a.sp_bs = h->NS * NLAM;
-        a.alat_pz = h->ip.alat_sz; a.alat_pZ = h->ip.alat_sZ; a.al_bs = 2;
-    }
+    if (h->inst_p) { a.alat_pz = h->ip.alat_sz; a.alat_pZ = h->ip.alat_sZ; a.al_bs = 2; }
     a.alat_on = h->rows.alat_on;
     a.alat_fin[0] = std::isfinite(h->rows.alat_lb); a.alat_fin[1] = std::isfinite(h->rows.alat_ub);
     for (int m = 0; m < 2; m++) { a.alat_sz[m] = h->rows.alat_sz[m]; a.alat_sZ[m] = h->rows.alat_sZ[m]; }

@@ -47,7 +47,7 @@ void ihm2_sens_args(const ihm2mpc_handle *h, void *out)
     a.Hs = h->Hs; a.hs_bs = 0; a.hs_te = h->N * 100; a.hs_ks = 100;
     if (h->inst_w) { a.Hs = h->iHs; a.hs_bs = 200; a.hs_te = 100; a.hs_ks = 0; }
     a.CD = h->CD;
-    a.slot_kc = h->slot_kc; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.slot_zw = h->slot_zw; a.slot_Zw = h->slot_Zw; a.sl_bs = 0;
+    a.slot_kc = h->slot_kc; a.slot_lb = h->slot_lb; a.slot_ub = h->slot_ub; a.unused_pad0 = nullptr; a.unused_pad1 = nullptr; a.sl_bs = 0;
     if (h->inst_b || h->inst_p) { a.slot_lb = h->i_slot_lb; a.slot_ub = h->i_slot_ub; a.sl_bs = 2 * h->slots.per_lane * 64; }
     a.track_id = h->track_id; a.widths = h->widths; a.car_L = h->car_L; a.car_W = h->car_W;
     a.lin = h->lin; a.xbar = h->sens_xbar; a.ubar = h->sens_ubar; a.x = h->x; a.u = h->u;

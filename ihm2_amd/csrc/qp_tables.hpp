@@ -253,16 +253,18 @@ inline bool slot_table_full(const SlotTable &t, int nslot)
     }
     return true;
 }
-// ... and with per-instance bounds (scatter_slot_bounds: (B, entries) each): those of every instance.  A second line of defence: the
-// setter refuses per-instance values whose finite sides differ from the shared table's (find_pattern_mismatch) before anything is
-// scattered, so once slot_table_full holds no call of the library reaches this function with an infinite value -- only the CPU probe
-// (tools/probes/check_full_table.cpp) does.  It stays because the kernel asks nothing, and the pattern check may change.
-inline bool slot_bounds_full(const SlotTable &t, int B, const std::vector<double> &slb, const std::vector<double> &sub)
+// ... and with per-instance bounds: those of every instance, read from the bounds half of the slot images (table_images below: (B, 2,
+// entries) each).  A second line of defence: the setter refuses per-instance values whose finite sides differ from the shared table's
+// (find_pattern_mismatch) before an image is built, so once slot_table_full holds no call of the library reaches this function with an
+// infinite value -- only the CPU probe (tools/probes/check_full_table.cpp) does.  It stays because the kernel asks nothing, and the
+// pattern check may change.
+inline bool slot_bounds_full(const SlotTable &t, int B, const std::vector<double> &slot_lo, const std::vector<double> &slot_up)
 {
-    const size_t n = (size_t)B * t.entries();
-    if (slb.size() != n || sub.size() != n) return false;
-    for (size_t i = 0; i < n; i++)
-        if (!full_bound(slb[i]) || !full_bound(sub[i])) return false;
+    const size_t n = t.entries();
+    if (slot_lo.size() != (size_t)B * 2 * n || slot_up.size() != (size_t)B * 2 * n) return false;
+    for (size_t b = 0; b < (size_t)B; b++)
+        for (size_t e = 0; e < n; e++)
+            if (!full_bound(slot_lo[b * 2 * n + e]) || !full_bound(slot_up[b * 2 * n + e])) return false;
     return true;
 }
 
@@ -287,40 +289,6 @@ inline PatternMismatch find_pattern_mismatch(const ConstraintRows &rows, int B, 
                 if (lo != slo || up != sup) return {true, b, k, c, lo, up, slo, sup};
             }
     return {false, 0, 0, 0, false, false, false, false};
-}
-
-// The slot table's bounds per instance, (B, entries): the values of instance b where the shared entry has that side finite, in the rows
-// 0..11; the track rows, the a_lat row and the absent side of a split (soft) row's halves keep the shared value.
-inline void scatter_slot_bounds(const SlotTable &t, int B, int NS, const double *il, const double *iu, std::vector<double> &slb, std::vector<double> &sub)
-{
-    const size_t n = t.entries();
-    slb.resize((size_t)B * n); sub.resize((size_t)B * n);
-    for (int b = 0; b < B; b++) {
-        const double *l = il + (size_t)b * NS * 12, *u = iu + (size_t)b * NS * 12;
-        for (size_t e = 0; e < n; e++) {
-            const int kc = t.kc[e], k = kc >> 4, c = kc & 15;
-            double lo = t.lb[e], up = t.ub[e];
-            if (kc >= 0 && c < 12) {
-                if (std::isfinite(lo)) lo = l[k * 12 + c];
-                if (std::isfinite(up)) up = u[k * 12 + c];
-            }
-            slb[(size_t)b * n + e] = lo; sub[(size_t)b * n + e] = up;
-        }
-    }
-}
-
-// the SQP mode's (B,NS,NC) bounds alike: the rows 0..11 per instance, the track rows batch-shared
-inline void scatter_stage_bounds(const ConstraintRows &rows, int B, const double *il, const double *iu, std::vector<double> &stl, std::vector<double> &stu)
-{
-    const int NS = rows.NS;
-    stl.resize((size_t)B * NS * NC); stu.resize((size_t)B * NS * NC);
-    for (int b = 0; b < B; b++)
-        for (int k = 0; k < NS; k++)
-            for (int c = 0; c < NC; c++) {
-                const size_t i = ((size_t)b * NS + k) * 12 + c, o = ((size_t)b * NS + k) * NC + c;
-                stl[o] = (c < 12) ? il[i] : rows.lb[k * NC + c];
-                stu[o] = (c < 12) ? iu[i] : rows.ub[k * NC + c];
-            }
 }
 
 // ---- per-instance slack penalties in the pattern of the batch-shared table ----
@@ -369,49 +337,73 @@ inline PenaltyMismatch find_penalty_mismatch(const ConstraintRows &rows, int B, 
     return {PenaltyMismatch::NONE, 0, 0, 0, false, false};
 }
 
-// The slot table's penalties per instance, (B, entries): the values of instance b on the soft slots -- a soft slot is one-sided, the
-// side its finite bound -- and the shared table's on the hard slots and the padding.  Instance b's block is then the zw, Zw of
-// lay_out_slots on rows that hold b's penalties: the layout depends on which sides are soft, not on the values.
-inline void scatter_slot_penalties(const SlotTable &t, const ConstraintRows &rows, int B, int NS, const double *iz, const double *iZ,
-                                   const double *az, const double *aZ, std::vector<double> &szw, std::vector<double> &sZw)
+// ---- the device images ----
+// The constraint tables as the kernels read them, for B instances (B = 1 with every per-instance array nullptr: the batch-shared tables).
+// Each table is one pair of arrays with two halves per instance, so that one base per instance serves the bounds and the penalties:
+//   slot_lo, slot_up    (B, 2, entries)             lb | zw and ub | Zw of the slot table; the second half starts at `entries`
+//   stage_lo, stage_up  (B, NS*NC + NS*NLAM)        lb | z and ub | Z per (stage, row) and (stage, side): the SQP mode's line search and
+//                                                   the cost; the second half starts at NS*NC
+//   alat_z, alat_Z      (B, 2)                      the a_lat row's penalties, lower / upper side: the cost
+// il, iu (B,NS,12); iz, iZ (B,NS,NLAM); az, aZ (B,2) as above; each pair may be nullptr: those rows hold the batch-shared values.
+//   * bounds of a slot: the value of instance b where the shared entry has that side finite, in the rows 0..11; the track rows, the
+//     a_lat row and the absent side of a split (soft) row's halves keep the shared value;
+//   * penalties of a slot: the values of instance b on the soft slots -- a soft slot is one-sided, the side its finite bound -- and the
+//     shared table's on the hard slots and the padding.  Instance b's block is then the zw, Zw of lay_out_slots on rows that hold b's
+//     penalties: the layout depends on which sides are soft, not on the values;
+//   * (stage, row) bounds: the rows 0..11 per instance, the track rows batch-shared; (stage, side) penalties and the a_lat pairs: the
+//     instance's values as given.
+struct TableImages {
+    size_t entries = 0, stage_rows = 0;     // offsets of the second halves: SlotTable::entries(), NS*NC
+    std::vector<double> slot_lo, slot_up, stage_lo, stage_up, alat_z, alat_Z;
+};
+inline TableImages table_images(const SlotTable &t, const ConstraintRows &rows, int B, const double *il, const double *iu, const double *iz,
+                                const double *iZ, const double *az, const double *aZ)
 {
-    (void)rows;     // (the table holds everything of the rows that is needed: kc, the finite side of a soft slot, the shared zw / Zw)
-    const size_t n = t.entries();
-    szw.resize((size_t)B * n); sZw.resize((size_t)B * n);
-    for (int b = 0; b < B; b++)
+    const int NS = rows.NS;
+    const size_t n = t.entries(), nb = (size_t)NS * NC, np = (size_t)NS * NLAM;
+    const bool ib = il && iu, ip = iz && iZ, ia = az && aZ;
+    TableImages m;
+    m.entries = n; m.stage_rows = nb;
+    m.slot_lo.resize((size_t)B * 2 * n); m.slot_up.resize((size_t)B * 2 * n);
+    m.stage_lo.resize((size_t)B * (nb + np)); m.stage_up.resize((size_t)B * (nb + np));
+    m.alat_z.resize((size_t)B * 2); m.alat_Z.resize((size_t)B * 2);
+    for (int b = 0; b < B; b++) {
+        double *slo = m.slot_lo.data() + (size_t)b * 2 * n, *sup = m.slot_up.data() + (size_t)b * 2 * n;     // (a table without rows: n = 0)
         for (size_t e = 0; e < n; e++) {
             const int kc = t.kc[e], k = kc >> 4, c = kc & 15;
-            double z = t.zw[e], Z = t.Zw[e];
+            double lo = t.lb[e], up = t.ub[e], z = t.zw[e], Z = t.Zw[e];
+            if (ib && kc >= 0 && c < 12) {
+                if (std::isfinite(lo)) lo = il[((size_t)b * NS + k) * 12 + c];
+                if (std::isfinite(up)) up = iu[((size_t)b * NS + k) * 12 + c];
+            }
             if (kc >= 0 && Z >= 0.0) {
-                const int up = std::isfinite(t.ub[e]) ? 1 : 0;
+                const int side = std::isfinite(t.ub[e]) ? 1 : 0;
                 if (c == NC) {
-                    if (az && aZ) { z = az[b * 2 + up]; Z = aZ[b * 2 + up]; }
-                } else if (iz && iZ) {
-                    const size_t i = ((size_t)b * NS + k) * NLAM + up * NC + c;
+                    if (ia) { z = az[b * 2 + side]; Z = aZ[b * 2 + side]; }
+                } else if (ip) {
+                    const size_t i = ((size_t)b * NS + k) * NLAM + side * NC + c;
                     z = iz[i]; Z = iZ[i];
                 }
             }
-            szw[(size_t)b * n + e] = z; sZw[(size_t)b * n + e] = Z;
+            slo[e] = lo; sup[e] = up; slo[n + e] = z; sup[n + e] = Z;
         }
-}
-
-// the (B,NS,NLAM) copies for the kernels that read the penalties by (stage, side) -- the line search's merit and the cost -- and the
-// (B,2) pairs of the a_lat row: the instance's values, the shared rows' where a pair is nullptr
-inline void scatter_stage_penalties(const ConstraintRows &rows, int B, const double *iz, const double *iZ, const double *az, const double *aZ,
-                                    std::vector<double> &stz, std::vector<double> &stZ, std::vector<double> &alz, std::vector<double> &alZ)
-{
-    const size_t per = (size_t)rows.NS * NLAM;
-    stz.resize((size_t)B * per); stZ.resize((size_t)B * per); alz.resize((size_t)B * 2); alZ.resize((size_t)B * 2);
-    for (int b = 0; b < B; b++) {
-        for (size_t i = 0; i < per; i++) {
-            stz[(size_t)b * per + i] = (iz && iZ) ? iz[(size_t)b * per + i] : rows.sz[i];
-            stZ[(size_t)b * per + i] = (iz && iZ) ? iZ[(size_t)b * per + i] : rows.sZ[i];
+        double *tlo = m.stage_lo.data() + (size_t)b * (nb + np), *tup = m.stage_up.data() + (size_t)b * (nb + np);
+        for (int k = 0; k < NS; k++)
+            for (int c = 0; c < NC; c++) {
+                const size_t i = ((size_t)b * NS + k) * 12 + c;
+                tlo[k * NC + c] = (ib && c < 12) ? il[i] : rows.lb[k * NC + c];
+                tup[k * NC + c] = (ib && c < 12) ? iu[i] : rows.ub[k * NC + c];
+            }
+        for (size_t i = 0; i < np; i++) {
+            tlo[nb + i] = ip ? iz[(size_t)b * np + i] : rows.sz[i];
+            tup[nb + i] = ip ? iZ[(size_t)b * np + i] : rows.sZ[i];
         }
-        for (int m = 0; m < 2; m++) {
-            alz[b * 2 + m] = (az && aZ) ? az[b * 2 + m] : rows.alat_sz[m];
-            alZ[b * 2 + m] = (az && aZ) ? aZ[b * 2 + m] : rows.alat_sZ[m];
+        for (int s = 0; s < 2; s++) {
+            m.alat_z[b * 2 + s] = ia ? az[b * 2 + s] : rows.alat_sz[s];
+            m.alat_Z[b * 2 + s] = ia ? aZ[b * 2 + s] : rows.alat_sZ[s];
         }
     }
+    return m;
 }
 
 // ---- weights ----

@@ -19,7 +19,6 @@ struct LsArgs {
     // (NS,14) bounds per (stage, row), -+inf = absent, and behind them, in the same arrays, the (NS,28) slack penalties per side: z behind
     // st_lb, Z behind st_ub (Z < 0 = hard) -- st_bs = NS * 42 doubles per instance, so that one base per instance serves both
     const double *st_lb, *st_ub;
-    const double *st_sz, *st_sZ;     // the batch-shared (NS,28) penalties on their own (not read by the line search)
     const double *CD, *Hs, *widths;
     // per-instance tuning: doubles per instance of W (B,144+64), Hs (B,2,100), st_lb / st_ub (0: batch-shared); W's stage stride (144 shared, 0:
     // one stage weight per instance) and the offset of W_e (N * 144 shared, 144 per instance)
@@ -348,7 +347,7 @@ static inline LsArgs make_ls_args(ihm2mpc_handle *h)
     a.car_L = h->car_L; a.car_W = h->car_W;
     for (int i = 0; i < 4; i++) a.tol[i] = h->sqp_tol[i];
     a.s_ref = h->s_ref; a.kappa_ref = h->kappa_ref; a.track_id = h->track_id;
-    a.W = h->Wd; a.st_lb = h->st_lb; a.st_ub = h->st_ub; a.st_sz = h->st_sz; a.st_sZ = h->st_sZ;
+    a.W = h->Wd; a.st_lb = h->st_lb; a.st_ub = h->st_ub;
     a.CD = h->CD; a.Hs = h->Hs; a.widths = h->widths;
     a.w_bs = 0; a.w_ks = 144; a.w_te = h->N * 144; a.hs_bs = 0; a.st_bs = 0;
     if (h->inst_w) { a.W = h->iWd; a.Hs = h->iHs; a.w_bs = 208; a.w_ks = 0; a.w_te = 144; a.hs_bs = 200; }

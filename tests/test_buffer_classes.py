@@ -17,9 +17,9 @@ WORKSPACE = set("""lin q_g q_rg q_P q_M scratch res qp_res dyn10 ls_phi ls_x ls_
                    step_args ls_args sens_args ls_done ls_status ls_iter ls_qp_acc ls_pending hist_st hist_it""".split())
 # (u0 is state: the plant of the next step reads the last solve's control, 0 before the first solve)
 STATE = set("""x u x0 yref yref_e pi lam slk lam_a slk_a xc s_guess status qp_iter active track_id u0
-               s_ref kappa_ref Hs Gy lbx ubx lbu ubu CD lg ug widths X_ref Y_ref phi_ref Wd st_lb st_ub st_sz st_sZ irk_tab sim_irk_tab
+               s_ref kappa_ref Hs Gy lbx ubx lbu ubu CD lg ug widths X_ref Y_ref phi_ref Wd st_lb st_ub irk_tab sim_irk_tab
                iHs iGy iWd i_slot_lb i_slot_ub i_st_lb i_st_ub i_lbu i_ubu i_lg i_ug
-               slot_kc slot_lb slot_ub slot_zw slot_Zw slot_kc_blk slot_lb_blk slot_ub_blk""".split())
+               slot_kc slot_lb slot_ub slot_kc_blk slot_lb_blk slot_ub_blk""".split())
 
 
 def handle_body(text):

@@ -254,6 +254,75 @@ def test_null_restores_shared_and_rebuilds_keep_instance_penalties(track):
     s.free()
 
 
+def _instance_bounds(track, case, assign):
+    """Bound values per instance inside the shared pattern, as tests/test_gpu_instance_tuning.py builds them: the bound arrays of the
+    case's OCP under that file's limit tunings (tuning 0 is the shared table's own)."""
+    from ihm2_amd.controller import controller_ocp
+    from test_gpu_instance_tuning import TUNINGS
+
+    assert IP.CASES[case]["kind"] == "track"
+    flats = []
+    for t in TUNINGS:
+        lim = dict(n_max=t["n_max"], v_x_max=t["v_x_max"], T_max=t["T_max"], delta_max=t["delta_max"], T_dot_max=1e6, delta_dot_max=t["delta_dot_max"])
+        flats.append(controller_ocp(track.s_ref.shape[-1], IP.N, lim, a_lat_max=5.0, track_rows=True, track_rows_penalty=IP.PENALTIES[0])[1].flatten())
+    return {k: np.stack([getattr(flats[j], k) for j in assign]) for k in ("lbx", "ubx", "lbu", "ubu", "lg", "ug")}
+
+
+def _restart_and_run(s, x0):
+    """Three steps from a cold start of everything a solve starts from (a handle that has run before keeps its multipliers and slacks
+    through init_guess), then the cost and its slack part at the last solution."""
+    s.set_multipliers(None, None)
+    s.set_slacks(None)
+    s.set_alat_multipliers(None, None)
+    out = _run(s, x0, steps=3)
+    out.append(dict(cost=s.get_cost(), slack_cost=s.get_slack_cost()))
+    return out
+
+
+def test_both_instance_modes_on_one_handle_through_the_cross_transitions(track):
+    """Per-instance bounds and per-instance penalties share the device tables (csrc/api.hip: tables_to_device): one handle goes through
+    the transitions in which one mode comes or goes while the other stays, and in every state gives, bit for bit, what a fresh handle
+    built directly in that state gives -- the solves, the cost and its slack part.  In the bounds-only state the cost reads the
+    batch-shared penalties from the per-instance tables."""
+    case, B = "track_rows_soft", 3
+    ocps = _ocps(track, case)
+    flats = [o.flatten() for o in ocps]
+    assign = np.arange(B)                       # three distinct tunings, of the penalties and of the bounds
+    soft, _ = IP.instance_tables(flats, assign)
+    bounds = _instance_bounds(track, case, assign)
+    x0 = IP.x0_of(track, case, B, seed=5)
+    rows = np.arange(B)
+
+    # the target states on fresh handles (where both modes are on: in the other order than the handle under test sets them)
+    want = {}
+    for state in ("both", "penalties", "bounds"):
+        f = _solver(track, ocps[0], B, case)
+        if state != "bounds":
+            f.set_instance_soft(*soft)
+        if state != "penalties":
+            f.set_instance_bounds(**bounds)
+        want[state] = _restart_and_run(f, x0)
+        f.free()
+    # each mode reaches the kernels: the states differ from one another on the instances whose tuning is not the shared one
+    for a, b in (("both", "penalties"), ("both", "bounds")):
+        assert not np.array_equal(want[a][0]["u"][1:], want[b][0]["u"][1:]), (a, b)
+    assert want["bounds"][-1]["slack_cost"].max() > 1e-6            # slacks are in use, and paid for
+
+    s = _solver(track, ocps[0], B, case)
+    s.set_instance_bounds(**bounds)             # 1. bounds on, then penalties on
+    s.set_instance_soft(*soft)
+    _assert_rows_equal(_restart_and_run(s, x0), want["both"], rows)
+    s.set_instance_bounds()                     # 2. bounds dropped while penalties stay
+    _assert_rows_equal(_restart_and_run(s, x0), want["penalties"], rows)
+    s.set_instance_bounds(**bounds)             # 3. bounds on again, then penalties dropped while bounds stay
+    s.set_instance_soft(None, None)
+    _assert_rows_equal(_restart_and_run(s, x0), want["bounds"], rows)
+    s.set_instance_soft(*soft)                  # 4. both on, then a shared set_soft with the same pattern (other shared values)
+    s.set_soft(flats[2].soft_z, flats[2].soft_Z)
+    _assert_rows_equal(_restart_and_run(s, x0), want["both"], rows)
+    s.free()
+
+
 def test_refusals(track):
     from ihm2_amd._lib import Ihm2mpcError
 

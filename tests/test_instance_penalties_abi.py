@@ -41,7 +41,7 @@ def test_device_copies_are_state_buffers_of_the_handle():
     decl = re.findall(r"\b(DevBuf|StateBuf|WorkBuf)<(\w+)> ([\w, ]+);", code)
     assert decl and all(c == "StateBuf" and t == "double" for c, t, _ in decl)
     names = {n.strip() for _, _, ns in decl for n in ns.split(",")}
-    assert names == {"st_sz", "st_sZ", "alat_sz", "alat_sZ"}
+    assert names == {"alat_sz", "alat_sZ"}
     import test_buffer_classes as TB
 
     assert re.search(r"^\s*ihm2_inst_penalties ip;", TB.handle_body(text), re.M)

@@ -1,11 +1,12 @@
-"""The per-instance slack penalties of the host tables (csrc/qp_tables.hpp: find_penalty_mismatch, scatter_slot_penalties,
-scatter_stage_penalties, called by api.hip::ihm2mpc_set_instance_soft / _alat_soft) without a GPU.
+"""The per-instance slack penalties of the host tables (csrc/qp_tables.hpp: find_penalty_mismatch, table_images, called by api.hip for
+ihm2mpc_set_instance_soft / _alat_soft) without a GPU.
 
 For every soft layout of tests/layouts.py that the issue names, and one all-hard layout, at the compiled-in horizon N = 40 and at N = 7,
 the problem is written to a file as the solver pushes it and tools/probes/check_slot_penalties.cpp -- built with the address and
 undefined-behaviour sanitizers -- draws penalties for B = 5 instances inside the shared pattern and checks that instance b's scattered
 block is, entry for entry, the zw / Zw of lay_out_slots on rows holding b's penalties, that the (stage, side) copies are those rows'
-sz / sZ, that an all-hard table is scattered onto itself, and that the pattern check refuses a flipped soft flag, z < 0 and a NaN with
+sz / sZ, that an all-hard table is scattered onto itself, that each half of each device image sits at the offset the kernels use and
+the images for B = 1 with nothing per instance are the shared tables, and that the pattern check refuses a flipped soft flag, z < 0 and a NaN with
 the instance, stage and side."""
 import dataclasses
 

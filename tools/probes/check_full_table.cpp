@@ -1,5 +1,5 @@
-// The predicate that lets a handle take the QP kernels' full slot form (ihm2_amd/csrc/qp_tables.hpp: slot_table_full, slot_bounds_full)
-// evaluated on the CPU, through the functions api.hip calls: the reference's rows (state boxes on n, v_x, T, delta of the stages
+// The predicate that lets a handle take the QP kernels' full slot form (ihm2_amd/csrc/qp_tables.hpp: slot_table_full, slot_bounds_full
+// on the slot images of table_images) evaluated on the CPU, through the functions api.hip calls: the reference's rows (state boxes on n, v_x, T, delta of the stages
 // 1..N-1, on n, v_x, v_y, r of stage N, input boxes and the two rate rows on the stages 0..N-1) laid out for the all-hard
 // instantiations of the catalogue.  One line per case: name full(0/1) per_lane total; then "all checks passed" if the table of every
 // full case is what the kernel takes unasked.  No arguments.
@@ -95,12 +95,26 @@ int main()
                 if (broken && b == 1) ab.lbx[23 * 8 + 6] = -INFINITY;
                 box_rows(N, ab.lbx.data(), ab.ubx.data(), ab.lbu.data(), ab.ubu.data(), ab.lg.data(), ab.ug.data(), &il[(size_t)b * NS * 12], &iu[(size_t)b * NS * 12], 12);
             }
-            std::vector<double> slb, sub;
-            scatter_slot_bounds(t, B, NS, il.data(), iu.data(), slb, sub);
-            report(broken ? "instance_one_inf" : "instance_all_finite", slot_table_full(t, NSLOT_FULL) && slot_bounds_full(t, B, slb, sub), t);
+            const TableImages m = table_images(t, rows_of(a), B, il.data(), iu.data(), nullptr, nullptr, nullptr, nullptr);
+            report(broken ? "instance_one_inf" : "instance_all_finite", slot_table_full(t, NSLOT_FULL) && slot_bounds_full(t, B, m.slot_lo, m.slot_up), t);
+            // the predicate reads the bounds halves only, `entries` apart from the penalties: an all-hard table's Zw = -1 and zw = 0 are
+            // finite, so an infinity planted in a penalty half must not change the answer, and one planted in a bounds half must
+            TableImages p = m;
+            p.slot_lo[(size_t)2 * 2 * t.entries() + t.entries() + 3] = INFINITY;
+            CHECK(slot_bounds_full(t, B, p.slot_lo, p.slot_up) == !broken);
+            p = m;
+            p.slot_up[(size_t)2 * 2 * t.entries() + t.entries() - 1] = INFINITY;
+            CHECK(!slot_bounds_full(t, B, p.slot_lo, p.slot_up));
+        }
+        {       // B = 1, nothing per instance: the shared table itself
+            const TableImages m = table_images(t, rows_of(a), 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            CHECK(m.entries == t.entries() && m.slot_lo.size() == 2 * t.entries() && slot_bounds_full(t, 1, m.slot_lo, m.slot_up));
+            CHECK(std::equal(t.lb.begin(), t.lb.end(), m.slot_lo.begin()) && std::equal(t.zw.begin(), t.zw.end(), m.slot_lo.begin() + t.entries()));
+            CHECK(std::equal(t.ub.begin(), t.ub.end(), m.slot_up.begin()) && std::equal(t.Zw.begin(), t.Zw.end(), m.slot_up.begin() + t.entries()));
         }
         // arrays of another shape than the table's are no evidence
         CHECK(!slot_bounds_full(t, B, std::vector<double>(5), std::vector<double>(5)));
+        CHECK(!slot_bounds_full(t, B, std::vector<double>(B * t.entries(), 0.0), std::vector<double>(B * t.entries(), 0.0)));
     }
     {       // a soft table: the torque rate row's upper side soft on every stage
         ConstraintRows r = rows_of(reference_rows(40));

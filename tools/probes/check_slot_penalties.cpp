@@ -1,10 +1,12 @@
-// The per-instance slack penalties of the host tables (ihm2_amd/csrc/qp_tables.hpp: find_penalty_mismatch, scatter_slot_penalties,
-// scatter_stage_penalties) walked on the CPU.  Each argument is a problem file (tests/test_slot_penalties.py writes them; problem_file.hpp
+// The per-instance slack penalties of the host tables (ihm2_amd/csrc/qp_tables.hpp: find_penalty_mismatch, table_images) walked on the
+// CPU.  Each argument is a problem file (tests/test_slot_penalties.py writes them; problem_file.hpp
 // reads them).  Per problem, for B = 5 instances with penalties drawn inside the shared pattern (one of them with z = 0 on every side):
 //   * instance b's block of the scattered table equals, entry for entry, zw / Zw of lay_out_slots on rows that hold b's penalties -- and
 //     that table's kc, lb, ub are the shared table's (the layout depends on which sides are soft, not on the values);
 //   * the (stage, side) copies equal those rows' sz / sZ and the a_lat pairs their alat_sz / alat_sZ;
 //   * with one pair of arguments NULL those rows keep the shared penalties; an all-hard table is scattered onto itself;
+//   * each half of each image sits at the offset the kernels use (`entries` in the slot images, NS*NC in the stage images), the bounds
+//     halves hold the shared bounds, and with B = 1 and nothing per instance the images are the shared table and rows themselves;
 //   * the pattern check refuses a flipped soft flag (both ways), z < 0, z = Z = 0 and a NaN, with the instance, stage and side.
 // Per problem one line: name fit per_lane nsoft soft_slots.  Exit status 1 if any check failed.
 // Build: g++ -std=c++17 -I ihm2_amd/csrc tools/probes/check_slot_penalties.cpp   (also with -fsanitize=address,undefined)
@@ -65,27 +67,46 @@ static void check_scatter(const ConstraintRows &rows, const SlotTable &t, const 
 {
     const double *iz = stage ? d.iz.data() : nullptr, *iZ = stage ? d.iZ.data() : nullptr;
     const double *az = alat ? d.az.data() : nullptr, *aZ = alat ? d.aZ.data() : nullptr;
-    const size_t n = t.entries(), per = (size_t)rows.NS * NLAM;
-    std::vector<double> szw, sZw, stz, stZ, alz, alZ;
-    scatter_slot_penalties(t, rows, B, rows.NS, iz, iZ, az, aZ, szw, sZw);
-    scatter_stage_penalties(rows, B, iz, iZ, az, aZ, stz, stZ, alz, alZ);
-    CHECK(szw.size() == B * n && sZw.size() == B * n, "%zu", szw.size());
-    CHECK(stz.size() == B * per && stZ.size() == B * per && alz.size() == (size_t)B * 2 && alZ.size() == (size_t)B * 2, "%zu", stz.size());
+    const size_t n = t.entries(), per = (size_t)rows.NS * NLAM, nb = (size_t)rows.NS * NC;
+    const TableImages m = table_images(t, rows, B, nullptr, nullptr, iz, iZ, az, aZ);
+    CHECK(m.entries == n && m.stage_rows == nb, "%zu %zu", m.entries, m.stage_rows);
+    CHECK(m.slot_lo.size() == B * 2 * n && m.slot_up.size() == B * 2 * n, "%zu", m.slot_lo.size());
+    CHECK(m.stage_lo.size() == B * (nb + per) && m.stage_up.size() == B * (nb + per) && m.alat_z.size() == (size_t)B * 2 && m.alat_Z.size() == (size_t)B * 2, "%zu", m.stage_lo.size());
     if (fails) return;
     for (int b = 0; b < B; b++) {
+        // instance b's blocks, the halves where the kernels look for them: zw / Zw `entries` doubles behind lb / ub, z / Z NS*NC behind the rows' bounds
+        const double *slb = m.slot_lo.data() + b * 2 * n, *sub = m.slot_up.data() + b * 2 * n, *szw = slb + n, *sZw = sub + n;
+        const double *stl = m.stage_lo.data() + b * (nb + per), *stu = m.stage_up.data() + b * (nb + per), *stz = stl + nb, *stZ = stu + nb;
         const ConstraintRows rb = rows_with(rows, d, b, stage, alat);
         const SlotTable tb = lay_out_slots(rb, limits);
         CHECK(tb.fit && tb.per_lane == t.per_lane && tb.nsoft == t.nsoft && tb.total == t.total && tb.m_act == t.m_act, "instance %d", b);
         CHECK(tb.kc == t.kc && tb.lb.size() == n && same_bits(tb.lb.data(), t.lb.data(), n) && same_bits(tb.ub.data(), t.ub.data(), n), "instance %d: the layout moved", b);
         if (tb.entries() != n) continue;
         for (size_t e = 0; e < n; e++) {
-            CHECK(same_bits(&szw[b * n + e], &tb.zw[e], 1), "instance %d entry %zu: zw %g, laid out %g", b, e, szw[b * n + e], tb.zw[e]);
-            CHECK(same_bits(&sZw[b * n + e], &tb.Zw[e], 1), "instance %d entry %zu: Zw %g, laid out %g", b, e, sZw[b * n + e], tb.Zw[e]);
+            CHECK(same_bits(&szw[e], &tb.zw[e], 1), "instance %d entry %zu: zw %g, laid out %g", b, e, szw[e], tb.zw[e]);
+            CHECK(same_bits(&sZw[e], &tb.Zw[e], 1), "instance %d entry %zu: Zw %g, laid out %g", b, e, sZw[e], tb.Zw[e]);
             if (fails > 20) return;
         }
-        CHECK(same_bits(&stz[b * per], rb.sz.data(), per) && same_bits(&stZ[b * per], rb.sZ.data(), per), "instance %d: stage copies", b);
-        CHECK(same_bits(&alz[b * 2], rb.alat_sz, 2) && same_bits(&alZ[b * 2], rb.alat_sZ, 2), "instance %d: a_lat pairs", b);
+        CHECK(same_bits(stz, rb.sz.data(), per) && same_bits(stZ, rb.sZ.data(), per), "instance %d: stage copies", b);
+        CHECK(same_bits(m.alat_z.data() + b * 2, rb.alat_sz, 2) && same_bits(m.alat_Z.data() + b * 2, rb.alat_sZ, 2), "instance %d: a_lat pairs", b);
+        // no per-instance bounds: the bounds halves are the shared table's and the shared rows'
+        CHECK(same_bits(slb, t.lb.data(), n) && same_bits(sub, t.ub.data(), n), "instance %d: slot bounds", b);
+        CHECK(same_bits(stl, rows.lb.data(), nb) && same_bits(stu, rows.ub.data(), nb), "instance %d: stage bounds", b);
     }
+}
+
+// B = 1 and nothing per instance: the images are the batch-shared tables, each half where the kernels read it
+static void check_shared_identity(const ConstraintRows &rows, const SlotTable &t)
+{
+    const size_t n = t.entries(), per = (size_t)rows.NS * NLAM, nb = (size_t)rows.NS * NC;
+    const TableImages m = table_images(t, rows, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    CHECK(m.entries == n && m.stage_rows == nb && m.slot_lo.size() == 2 * n && m.slot_up.size() == 2 * n && m.stage_lo.size() == nb + per && m.stage_up.size() == nb + per, "sizes");
+    if (fails) return;
+    CHECK(same_bits(m.slot_lo.data(), t.lb.data(), n) && same_bits(m.slot_lo.data() + n, t.zw.data(), n), "slot_lo is not lb | zw");
+    CHECK(same_bits(m.slot_up.data(), t.ub.data(), n) && same_bits(m.slot_up.data() + n, t.Zw.data(), n), "slot_up is not ub | Zw");
+    CHECK(same_bits(m.stage_lo.data(), rows.lb.data(), nb) && same_bits(m.stage_lo.data() + nb, rows.sz.data(), per), "stage_lo is not lb | z");
+    CHECK(same_bits(m.stage_up.data(), rows.ub.data(), nb) && same_bits(m.stage_up.data() + nb, rows.sZ.data(), per), "stage_up is not ub | Z");
+    CHECK(same_bits(m.alat_z.data(), rows.alat_sz, 2) && same_bits(m.alat_Z.data(), rows.alat_sZ, 2), "a_lat pair");
 }
 
 static void expect(const ConstraintRows &rows, const Drawn &d, PenaltyMismatch::Kind kind, int b, int k, int side, const char *what)
@@ -157,11 +178,12 @@ int main(int argc, char **argv)
         check_scatter(rows, t, limits, d, true, false);
         check_scatter(rows, t, limits, d, false, true);
         check_scatter(rows, t, limits, d, false, false);
+        check_shared_identity(rows, t);
         if (soft_slots == 0) {      // an all-hard table: the scatter is a no-op, whatever the instances hold
-            std::vector<double> szw, sZw;
-            scatter_slot_penalties(t, rows, B, rows.NS, d.iz.data(), d.iZ.data(), d.az.data(), d.aZ.data(), szw, sZw);
+            const size_t n = t.entries();
+            const TableImages m = table_images(t, rows, B, nullptr, nullptr, d.iz.data(), d.iZ.data(), d.az.data(), d.aZ.data());
             for (int b = 0; b < B; b++)
-                CHECK(same_bits(szw.data() + b * t.entries(), t.zw.data(), t.entries()) && same_bits(sZw.data() + b * t.entries(), t.Zw.data(), t.entries()), "instance %d", b);
+                CHECK(same_bits(m.slot_lo.data() + b * 2 * n + n, t.zw.data(), n) && same_bits(m.slot_up.data() + b * 2 * n + n, t.Zw.data(), n), "instance %d", b);
         }
         check_refusals(rows, d);
     }

@@ -1,7 +1,7 @@
 // The tables the host builds for the interior-point QP (ihm2_amd/csrc/qp_tables.hpp, qp_catalogue.hpp) walked on the CPU.  Each argument
 // is a problem file (tests/test_slot_table.py writes them; problem_file.hpp reads them; C, D and the weights' flag are ignored here).
 // The rows go through the functions api.hip calls, in the order of its setters; the table is then checked against what the kernels
-// take from it unchecked (the list at the top of qp_tables.hpp), the per-instance scatter against values drawn inside the shared pattern,
+// take from it unchecked (the list at the top of qp_tables.hpp), the device images (table_images) against values drawn inside the shared pattern,
 // and the weight tables against the closed form of V'WV.  Per problem one line: name fit per_lane nsoft total m_act digest (FNV-1a over
 // the bytes of kc, lb, ub, zw, Zw and the 256-lane kc, lb, ub).  Exit status 1 if any check failed.
 // Build: g++ -std=c++17 -I ihm2_amd/csrc tools/probes/check_slot_table.cpp   (also with -fsanitize=address,undefined)
@@ -170,28 +170,42 @@ static void check_scatter(const Problem &p, const ConstraintRows &rows, const Sl
         box_rows(N, v[0].data(), v[1].data(), v[2].data(), v[3].data(), v[4].data(), v[5].data(), &il[(size_t)b * NS * 12], &iu[(size_t)b * NS * 12], 12);
     }
     CHECK(!find_pattern_mismatch(rows, B, il.data(), iu.data()).found, "values inside the pattern are refused");
-    std::vector<double> slb, sub, stl, stu;
-    scatter_slot_bounds(t, B, NS, il.data(), iu.data(), slb, sub);
-    scatter_stage_bounds(rows, B, il.data(), iu.data(), stl, stu);
-    const size_t n = t.entries();
-    CHECK(slb.size() == B * n && sub.size() == B * n && stl.size() == (size_t)B * NS * NC && stu.size() == stl.size(), "sizes");
-    if (slb.size() != B * n || sub.size() != B * n) return;
+    const TableImages m = table_images(t, rows, B, il.data(), iu.data(), nullptr, nullptr, nullptr, nullptr);
+    const size_t n = t.entries(), nb = (size_t)NS * NC, np = (size_t)NS * NLAM;
+    CHECK(m.entries == n && m.stage_rows == nb && m.slot_lo.size() == B * 2 * n && m.slot_up.size() == B * 2 * n && m.stage_lo.size() == B * (nb + np) &&
+          m.stage_up.size() == m.stage_lo.size(), "sizes");
+    if (m.slot_lo.size() != B * 2 * n || m.slot_up.size() != B * 2 * n || m.stage_lo.size() != B * (nb + np) || m.stage_up.size() != B * (nb + np)) return;
     int moved = 0, wanted = 0;
     for (int b = 0; b < B; b++) {
+        // instance b's halves, at the offsets the kernels use: the penalties `entries` behind the slot bounds, NS*NC behind the rows' bounds
+        const double *slb = m.slot_lo.data() + (size_t)b * 2 * n, *sub = m.slot_up.data() + (size_t)b * 2 * n;
+        const double *stl = m.stage_lo.data() + (size_t)b * (nb + np), *stu = m.stage_up.data() + (size_t)b * (nb + np);
+        // no per-instance penalties: the second halves are the shared table's zw / Zw and the shared rows' sz / sZ
+        CHECK(std::equal(t.zw.begin(), t.zw.end(), slb + n) && std::equal(t.Zw.begin(), t.Zw.end(), sub + n), "instance %d: slot penalties", b);
+        CHECK(std::equal(rows.sz.begin(), rows.sz.end(), stl + nb) && std::equal(rows.sZ.begin(), rows.sZ.end(), stu + nb), "instance %d: stage penalties", b);
         for (size_t e = 0; e < n; e++) {
             const int kc = t.kc[e], k = kc >> 4, c = kc & 15;
             const bool mine = kc >= 0 && c < 12;
             const size_t i = mine ? ((size_t)b * NS + k) * 12 + c : 0;
             const double lo = (mine && t.lb[e] > -INF) ? il[i] : t.lb[e], up = (mine && t.ub[e] < INF) ? iu[i] : t.ub[e];
-            CHECK(slb[b * n + e] == lo && sub[b * n + e] == up, "instance %d entry %zu (stage %d row %d)", b, e, k, c);
-            moved += (int)(slb[b * n + e] != t.lb[e]) + (int)(sub[b * n + e] != t.ub[e]);
+            CHECK(slb[e] == lo && sub[e] == up, "instance %d entry %zu (stage %d row %d)", b, e, k, c);
+            moved += (int)(slb[e] != t.lb[e]) + (int)(sub[e] != t.ub[e]);
         }
         for (int k = 0; k < NS; k++)
             for (int c = 0; c < NC; c++) {
-                const size_t o = ((size_t)b * NS + k) * NC + c, i = ((size_t)b * NS + k) * 12 + c;
-                CHECK(stl[o] == (c < 12 ? il[i] : rows.lb[k * NC + c]) && stu[o] == (c < 12 ? iu[i] : rows.ub[k * NC + c]), "instance %d stage %d row %d of the (NS,NC) bounds", b, k, c);
+                const size_t i = ((size_t)b * NS + k) * 12 + c;
+                CHECK(stl[k * NC + c] == (c < 12 ? il[i] : rows.lb[k * NC + c]) && stu[k * NC + c] == (c < 12 ? iu[i] : rows.ub[k * NC + c]), "instance %d stage %d row %d of the (NS,NC) bounds", b, k, c);
                 if (c < 12) wanted += (int)std::isfinite(il[i]) + (int)std::isfinite(iu[i]);
             }
+    }
+    {       // B = 1, nothing per instance: the images are the batch-shared table and rows
+        const TableImages s1 = table_images(t, rows, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        CHECK(s1.slot_lo.size() == 2 * n && s1.slot_up.size() == 2 * n && s1.stage_lo.size() == nb + np && s1.stage_up.size() == nb + np, "sizes of the shared images");
+        if (s1.slot_lo.size() != 2 * n || s1.slot_up.size() != 2 * n || s1.stage_lo.size() != nb + np || s1.stage_up.size() != nb + np) return;
+        CHECK(std::equal(t.lb.begin(), t.lb.end(), s1.slot_lo.begin()) && std::equal(t.zw.begin(), t.zw.end(), s1.slot_lo.begin() + n), "shared slot_lo is not lb | zw");
+        CHECK(std::equal(t.ub.begin(), t.ub.end(), s1.slot_up.begin()) && std::equal(t.Zw.begin(), t.Zw.end(), s1.slot_up.begin() + n), "shared slot_up is not ub | Zw");
+        CHECK(std::equal(rows.lb.begin(), rows.lb.end(), s1.stage_lo.begin()) && std::equal(rows.sz.begin(), rows.sz.end(), s1.stage_lo.begin() + nb), "shared stage_lo is not lb | z");
+        CHECK(std::equal(rows.ub.begin(), rows.ub.end(), s1.stage_up.begin()) && std::equal(rows.sZ.begin(), rows.sZ.end(), s1.stage_up.begin() + nb), "shared stage_up is not ub | Z");
     }
     CHECK(moved == wanted, "%d sides of the table took an instance's value, the instances have %d finite sides", moved, wanted);
     // one side outside the pattern
@@ -199,9 +213,9 @@ static void check_scatter(const Problem &p, const ConstraintRows &rows, const Sl
     const size_t i = ((size_t)b * NS + k) * 12 + c;
     const bool shared = std::isfinite(rows.lb[k * NC + c]);
     il[i] = shared ? -INF : 0.0;
-    const PatternMismatch m = find_pattern_mismatch(rows, B, il.data(), iu.data());
-    CHECK(m.found && m.b == b && m.k == k && m.c == c && m.lower == !shared && m.shared_lower == shared && m.upper == m.shared_upper,
-          "mismatch reported at instance %d stage %d row %d", m.b, m.k, m.c);
+    const PatternMismatch mm = find_pattern_mismatch(rows, B, il.data(), iu.data());
+    CHECK(mm.found && mm.b == b && mm.k == k && mm.c == c && mm.lower == !shared && mm.shared_lower == shared && mm.upper == mm.shared_upper,
+          "mismatch reported at instance %d stage %d row %d", mm.b, mm.k, mm.c);
 }
 
 // Hs = c V'WV and Gy = c V'W for y = V z = [x; u; x[6:8] - u]: column i of V has a 1 in row i, the columns 6, 7 another 1 in the rows 10, 11
