@@ -103,6 +103,11 @@ SYMBOLS = {
     "ihm2mpc_get_x_device": (C.c_int, [_H, C.c_void_p]),
     "ihm2mpc_get_u_device": (C.c_int, [_H, C.c_void_p]),
     "ihm2mpc_get_status_device": (C.c_int, [_H, C.c_void_p]),
+    "ihm2mpc_set_yref_device": (C.c_int, [_H, C.c_void_p]),
+    "ihm2mpc_set_yref_e_device": (C.c_int, [_H, C.c_void_p]),
+    "ihm2mpc_set_instance_weights_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
+    "ihm2mpc_get_instance_weight_tables": (C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
+    "ihm2mpc_eval_adjoint_sensitivities_w_device": (C.c_int, [_H, C.c_int32] + [C.c_void_p] * 7),
     "ihm2mpc_sim_step": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "ihm2mpc_sim_advance": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "ihm2mpc_sim_step_sens": (C.c_int, [_H, C.c_int32, C.c_int32] + [c_double_p] * 5 + [c_int32_p]),

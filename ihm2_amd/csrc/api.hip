@@ -757,6 +757,60 @@ int ihm2mpc_set_instance_weights(ihm2mpc_handle *h, const double *W, const doubl
     return 0;
 }
 
+// The same from W (B,12,12), W_e (B,8,8) in device memory: k_weight_tables (kernels_weights.hip) expands on h->stream what the loop above
+// expands on the host, bit for bit.  check: the kernel's validating form runs first and its codes are read back (blocking) -- nothing of
+// the handle is written before every instance is accepted.
+int ihm2mpc_set_instance_weights_device(ihm2mpc_handle *h, const void *W, const void *W_e, int32_t check)
+{
+    CHECK_H(h);
+    if (!W && !W_e) return ihm2mpc_set_instance_weights(h, nullptr, nullptr);
+    if (!W || !W_e) return fail("W and W_e must both be given, or both be NULL (batch-shared weights again)");
+    if (!h->weights_set) return fail("ihm2mpc_set_weights has not been called (the batch-shared weights come first)");
+    if (h->bounds_set && !h->uniform_CD) return fail("per-instance weights need stage-independent general rows C, D");
+    const int B = h->B;
+    const double *dW = (const double *)W, *dWe = (const double *)W_e;
+    if (check) {
+        WorkBuf<int32_t> dcode;     // (B) the kernel writes every entry
+        if (dcode.alloc(B) != hipSuccess) return fail("out of device memory");
+        ihm2_launch_weight_tables(h, dW, dWe, nullptr, nullptr, nullptr, dcode);
+        HIP_TRY(hipGetLastError());
+        std::vector<int32_t> code(B);
+        HIP_TRY(hipMemcpyAsync(code.data(), dcode, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int b = 0; b < B; b++) {
+            const int c = code[b];
+            if (c == ihm2_weight_code_ok) continue;
+            if (c == ihm2_weight_code_asym_terminal)
+                return fail("instance %d: the weight matrix of stage %d (terminal) is not symmetric", b, h->N);
+            if (c == ihm2_weight_code_asym_stage) return fail("instance %d: the weight matrix of the stages 0..%d is not symmetric", b, h->N - 1);
+            if (c >= ihm2_weight_code_nan_We) {
+                const int i = c - ihm2_weight_code_nan_We;
+                return fail("instance %d: W_e[%d][%d] is NaN", b, i / 8, i % 8);
+            }
+            const int i = c - ihm2_weight_code_nan_W;
+            return fail("instance %d: W[%d][%d] is NaN", b, i / 12, i % 12);
+        }
+    }
+    if (!h->iHs && alloc_all(h->iHs, (size_t)B * 200, h->iGy, (size_t)B * 240, h->iWd, (size_t)B * 208)) return -1;
+    ihm2_launch_weight_tables(h, dW, dWe, h->iHs, h->iGy, h->iWd, nullptr);
+    HIP_TRY(hipGetLastError());
+    h->inst_w = true;
+    h->uniform_H = true;
+    return 0;
+}
+
+int ihm2mpc_get_instance_weight_tables(ihm2mpc_handle *h, double *Hs, double *Gy, double *Wd)
+{
+    CHECK_H(h);
+    if (!h->inst_w) return fail("per-instance weights are off: ihm2mpc_set_instance_weights or ihm2mpc_set_instance_weights_device first");
+    const size_t B = h->B;
+    if (Hs) HIP_TRY(hipMemcpyAsync(Hs, h->iHs, B * 200 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (Gy) HIP_TRY(hipMemcpyAsync(Gy, h->iGy, B * 240 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (Wd) HIP_TRY(hipMemcpyAsync(Wd, h->iWd, B * 208 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // The constraint-slot table of the QP kernels from the handle's rows (qp_tables.hpp: lay_out_slots, for the instantiations the catalogue
 // has for these rows).  A table that fits none leaves the previous one in the handle: ready() reports it, since the setters come one by one
 // and a later one may make the rows fit.
@@ -1333,6 +1387,17 @@ static int adjoint_buffers(ihm2mpc_handle *h, size_t S, bool weights)
     return 0;
 }
 
+// the refusals every adjoint entry shares, host or device seeds (unit_u0: no seed was given)
+static int adjoint_refused(const ihm2mpc_handle *h, int32_t n_seeds, bool unit_u0)
+{
+    if (adjoint_refused_in_sqp(h)) return -1;
+    if (n_seeds < 1 || n_seeds > 8) return fail("adjoint sensitivities: n_seeds = %d, one call takes 1 to 8 seeds", n_seeds);
+    if (unit_u0 && n_seeds != 2)
+        return fail("adjoint sensitivities: seed_x and seed_u both NULL stands for the two unit seeds on u_0 and needs n_seeds = 2, not %d", n_seeds);
+    // the factorisation is that of the x0 sensitivities: their snapshot of (xbar, ubar) must belong to the last solve
+    return sens_readable(h);
+}
+
 static bool any_soft_side(const ihm2mpc_handle *h);
 
 // The host outputs of the penalty entries (ihm2mpc_eval_adjoint_sensitivities_p, ihm2mpc_eval_cost_gradient_penalties), any may be NULL,
@@ -1391,14 +1456,9 @@ static int eval_adjoint(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x
                         const PenaltyOut *pen = nullptr)
 {
     CHECK_H(h);
-    if (adjoint_refused_in_sqp(h)) return -1;
-    if (n_seeds < 1 || n_seeds > 8) return fail("adjoint sensitivities: n_seeds = %d, one call takes 1 to 8 seeds", n_seeds);
     const bool slack = seed_s || seed_sa;
     const bool unit_u0 = !seed_x && !seed_u && !slack;
-    if (unit_u0 && n_seeds != 2)
-        return fail("adjoint sensitivities: seed_x and seed_u both NULL stands for the two unit seeds on u_0 and needs n_seeds = 2, not %d", n_seeds);
-    // the factorisation is that of the x0 sensitivities: their snapshot of (xbar, ubar) must belong to the last solve
-    if (sens_readable(h)) return -1;
+    if (adjoint_refused(h, n_seeds, unit_u0)) return -1;
     const size_t B = h->B, N = h->N, NS = h->NS, S = n_seeds;
     if (adjoint_buffers(h, S, weights)) return -1;
     if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1447,6 +1507,26 @@ int ihm2mpc_eval_adjoint_sensitivities_w(ihm2mpc_handle *h, int32_t n_seeds, con
                                          double *grad_yref, double *grad_yref_e, double *grad_W, double *grad_W_e)
 {
     return eval_adjoint(h, n_seeds, seed_x, seed_u, nullptr, nullptr, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e);
+}
+
+// Seeds and gradients in device memory: k_adj<true> reads the caller's seeds, the gradients leave the handle's buffers by device-to-device
+// copies behind it on h->stream.  No host copy, no wait (the buffers' first allocation and their growth aside).
+int ihm2mpc_eval_adjoint_sensitivities_w_device(ihm2mpc_handle *h, int32_t n_seeds, const void *seed_x, const void *seed_u, void *grad_x0,
+                                                void *grad_yref, void *grad_yref_e, void *grad_W, void *grad_W_e)
+{
+    CHECK_H(h);
+    const bool unit_u0 = !seed_x && !seed_u;
+    if (adjoint_refused(h, n_seeds, unit_u0)) return -1;
+    const size_t B = h->B, N = h->N, S = n_seeds;
+    if (adjoint_buffers(h, S, true)) return -1;
+    ihm2_launch_adj(h, n_seeds, (const double *)seed_x, (const double *)seed_u, unit_u0 ? 1 : 0, 1, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * S * NX * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, h->adj_gy, B * S * N * NY * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, h->adj_gye, B * S * NX * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (grad_W) HIP_TRY(hipMemcpyAsync(grad_W, h->adj_gW, B * S * NY * NY * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, h->adj_gWe, B * S * NX * NX * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
 }
 
 int ihm2mpc_eval_adjoint_sensitivities_s(ihm2mpc_handle *h, int32_t n_seeds, const double *seed_x, const double *seed_u, const double *seed_s,
@@ -1578,6 +1658,8 @@ int ihm2mpc_get_sens_u0_device(ihm2mpc_handle *h, void *dptr)
     }
 #define DEVCOPY_ARG const void *
 DEVCOPY(set_x0_device, h->x0, dptr, (size_t)h->B * NX * sizeof(double))
+DEVCOPY(set_yref_device, h->yref, dptr, (size_t)h->B * h->N * NY * sizeof(double))
+DEVCOPY(set_yref_e_device, h->yref_e, dptr, (size_t)h->B * NX * sizeof(double))
 #undef DEVCOPY_ARG
 #define DEVCOPY_ARG void *
 DEVCOPY(get_u0_device, dptr, h->u0, (size_t)h->B * NU * sizeof(double))

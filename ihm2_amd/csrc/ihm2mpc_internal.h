@@ -316,6 +316,13 @@ void ihm2_launch_slack_fold(ihm2mpc_handle *h, int cost, int n_seeds, const doub
 // are the cost's own z + Z s and the explicit partials of J are added (one seed); else seed_s, seed_sa as the fold took them
 void ihm2_launch_penalty_grad(ihm2mpc_handle *h, int cost, int n_seeds, const double *seed_s, const double *seed_sa, const double *zeta,
                               double *grad_z, double *grad_Z, double *grad_za, double *grad_Za);
+// kernels_weights.hip: the per-instance weight tables from W (B,12,12), W_e (B,8,8) in device memory, on h->stream -- the device twin of
+// ihm2::stage_weight_tables / terminal_weight_tables (qp_tables.hpp), bit for bit.  code == nullptr: writes Hs (B,2,100), Gy (B,2,120),
+// Wd (B,208), every entry.  code (B) given: writes nothing but code[b], the validation of instance b (ihm2_weight_code_*; Hs, Gy, Wd unused)
+void ihm2_launch_weight_tables(ihm2mpc_handle *h, const double *W, const double *W_e, double *Hs, double *Gy, double *Wd, int32_t *code);
+// code[b]: 0 accepted; NAN_W + i: W[i/12][i%12] is NaN (the first such i); NAN_WE + i: W_e[i/8][i%8] is NaN; then the symmetry tests
+enum { ihm2_weight_code_ok = 0, ihm2_weight_code_nan_W = 1, ihm2_weight_code_nan_We = 1 + 144, ihm2_weight_code_asym_stage = 1 + 208,
+       ihm2_weight_code_asym_terminal = 2 + 208 };
 
 // --- the kernels of kernels_qp.hip: the per-step QP (k_qp_wave, k_qp_block) and the persistent loop (k_steps) ---
 // Their argument blocks, built by the launch code in api.hip.  (In the unnamed namespace, as the kernels that take them: the kernels'

@@ -17,6 +17,7 @@ Host code is NumPy + ctypes only; all arithmetic runs in ``libihm2mpc.so`` (HIP,
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -96,6 +97,12 @@ class BatchedOcpSolver:
     # ---- lifetime ----
     def free(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            # ihm2_amd/torch_layer.py: a tensor that was marked as used on the handle's stream makes its allocator record an event on that
+            # stream when the tensor is released -- the stream must outlive it, and the stream goes with the handle
+            alive = sum(r() is not None for r in getattr(self, "_stream_users", ()))
+            if alive:
+                raise RuntimeError(f"the memory of {alive} tensors that went through rti_solve is still alive: their allocator records an event on the "
+                                   "solver's stream when they are released, so release them (and the graph that holds them) before the solver")
             self.lib.ihm2mpc_synchronize(self._h)
             for ptr in getattr(self, "_pinned", []):
                 self.lib.ihm2mpc_host_free(ptr)
@@ -499,6 +506,45 @@ class BatchedOcpSolver:
     def get_status_device(self, dptr: int):
         _lib.check(self.lib.ihm2mpc_get_status_device(self._h, C.c_void_p(dptr)))
 
+    def get_stream(self) -> int:
+        """The handle's HIP stream as an integer (``ihm2mpc_get_stream``): what every ``*_device`` entry is ordered on."""
+        stream = C.c_void_p()
+        _lib.check(self.lib.ihm2mpc_get_stream(self._h, C.byref(stream)))
+        return int(stream.value or 0)
+
+    def set_yref_device(self, dptr: int):
+        """``yref`` ``(B,N,12)`` from device memory, stream-ordered (``ihm2mpc_set_yref_device``)."""
+        _lib.check(self.lib.ihm2mpc_set_yref_device(self._h, C.c_void_p(dptr)))
+
+    def set_yref_e_device(self, dptr: int):
+        """``yref_e`` ``(B,8)`` from device memory, stream-ordered (``ihm2mpc_set_yref_e_device``)."""
+        _lib.check(self.lib.ihm2mpc_set_yref_e_device(self._h, C.c_void_p(dptr)))
+
+    def set_instance_weights_device(self, W_dptr: int, W_e_dptr: int, check: bool = True):
+        """:meth:`set_instance_weights` with ``W (B,12,12)`` and ``W_e (B,8,8)`` in device memory: the tables are expanded by a kernel,
+        bit for bit what the host setter uploads.  ``check=True`` validates as the host setter does (NaN, symmetry) and blocks;
+        ``check=False`` reads nothing back and does not block -- the caller vouches for symmetric weights without NaN.  ``0, 0``: the
+        shared weights again (``ihm2mpc_set_instance_weights_device``)."""
+        _lib.check(self.lib.ihm2mpc_set_instance_weights_device(self._h, C.c_void_p(int(W_dptr)) if W_dptr else None,
+                                                                C.c_void_p(int(W_e_dptr)) if W_e_dptr else None, int(bool(check))))
+        self._inst_W = None
+
+    def get_instance_weight_tables(self):
+        """``dict(Hs=(B,2,10,10), Gy=(B,2,10,12), Wd=(B,208))``: the per-instance weight tables as the QP reads them, stage then
+        terminal (``ihm2mpc_get_instance_weight_tables``; refused while the per-instance weights are off)."""
+        out = dict(Hs=np.empty((self.B, 2, 10, 10)), Gy=np.empty((self.B, 2, 10, NY)), Wd=np.empty((self.B, NY * NY + NX * NX)))
+        _lib.check(self.lib.ihm2mpc_get_instance_weight_tables(self._h, *[_ptr(v) for v in out.values()]))
+        return out
+
+    def eval_adjoint_weight_sensitivities_device(self, n_seeds: int, seed_x: int = 0, seed_u: int = 0, grad_x0: int = 0, grad_yref: int = 0,
+                                                 grad_yref_e: int = 0, grad_W: int = 0, grad_W_e: int = 0):
+        """:meth:`eval_adjoint_weight_sensitivities` on device memory, stream-ordered and without a wait: addresses as integers, 0 for
+        NULL (a zero seed, an output that is not wanted; both seeds 0 with ``n_seeds = 2``: the unit seeds on ``u_0``).  Seeds
+        ``(B,n_seeds,N+1,8)`` / ``(B,n_seeds,N,2)``, gradients ``(B,n_seeds,...)``; everything must stay alive, the seeds unchanged,
+        until the handle's stream has passed (``ihm2mpc_eval_adjoint_sensitivities_w_device``)."""
+        ptr = [C.c_void_p(int(a)) if a else None for a in (seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e)]
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_w_device(self._h, int(n_seeds), *ptr))
+
     # ---- sensitivities of the solution with respect to x0 (acados: eval_param_sens(j, 0, "ex"); get(k, "sens_x" / "sens_u")) ----
     def set_x0_sensitivities(self, mode: int = 2):
         """0 off; 1 ``du_0/dx_0`` only (the feedback gain K0); 2 the whole horizon.  Every later RTI ``solve`` /
@@ -795,6 +841,28 @@ class BatchedOcpSolver:
         out = np.empty(n)
         _lib.check(self.lib.ihm2mpc_get_stage(self._h, i, stage, field.encode(), _ptr(out), n))
         return out
+
+
+# The serial number of a solver: every solving call and every setter advances it.  The adjoint entries differentiate the last solve and must
+# follow it directly (include/ihm2mpc.h), which the library does not detect; a caller that keeps the serial of its solve can
+# (ihm2_amd/torch_layer.py: backward refuses when it has moved).  Getters and the eval_* entries leave it alone.
+_ADVANCES_SERIAL = ("init_guess", "reinit_failed", "prepare_step", "solve_async", "compute_control", "run_steps", "linearize", "build_tracks",
+                    "fit_tracks", "sim_advance", "sim_advance_cart", "step", "_set_stage")
+
+
+def _advancing(fn):
+    @functools.wraps(fn)
+    def wrapped(self, *args, **kw):
+        self._serial += 1
+        return fn(self, *args, **kw)
+    return wrapped
+
+
+BatchedOcpSolver._serial = 0
+for _name, _fn in list(vars(BatchedOcpSolver).items()):
+    if callable(_fn) and (_name.startswith(("set_", "_push_")) or _name in _ADVANCES_SERIAL):
+        setattr(BatchedOcpSolver, _name, _advancing(_fn))
+del _name, _fn
 
 
 class AcadosOcpSolver:

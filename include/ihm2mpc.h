@@ -505,6 +505,35 @@ int ihm2mpc_get_u0_device(ihm2mpc_handle *h, void *dptr);
 int ihm2mpc_get_x_device(ihm2mpc_handle *h, void *dptr);
 int ihm2mpc_get_u_device(ihm2mpc_handle *h, void *dptr);
 int ihm2mpc_get_status_device(ihm2mpc_handle *h, void *dptr);
+/* ---- device-resident parameters in, gradients out (a learning loop around the RTI step: ihm2_amd/torch_layer.py) ----
+ * All five are stream-ordered on the handle's stream like ihm2mpc_get_u0_device and do not block unless stated.
+ *   ihm2mpc_set_yref_device / _set_yref_e_device <- ihm2mpc_set_yref / _set_yref_e: (B,N,12) / (B,8), device-to-device into the same buffers. */
+int ihm2mpc_set_yref_device(ihm2mpc_handle *h, const void *yref);
+int ihm2mpc_set_yref_e_device(ihm2mpc_handle *h, const void *yref_e);
+/*   ihm2mpc_set_instance_weights_device <- ihm2mpc_set_instance_weights with W (B,12,12), W_e (B,8,8) in device memory: the tables
+ * c_s V'WV, c_s V'W, the terminal blocks and the copy [W | W_e] are expanded by one kernel (k_weight_tables), bit for bit what the host
+ * setter uploads.  Same preconditions and refusal texts: ihm2mpc_set_weights first, stage-independent C, D, both pointers or both NULL
+ * (NULL, NULL = the batch-shared weights again).  check != 0: validated as the host setter validates -- no NaN entry, both expanded
+ * Hessians symmetric to |a - b| <= 1e-12 (1 + |a|) -- and refused with the host setter's message for the first offending instance; this
+ * reads one int32 per instance back and BLOCKS; on a refusal the handle's tables and mode are untouched.  check == 0: nothing is read
+ * back and the call does not block -- THE CALLER VOUCHES for symmetric weights without NaN: nothing validates them; a NaN weight then
+ * surfaces as QP status 1 of that instance (its documented meaning), an asymmetric one gives a QP that is not the one asked for.
+ * W and W_e are read in stream order: keep them alive and unchanged until the stream has passed.  Memory for the tables on first use. */
+int ihm2mpc_set_instance_weights_device(ihm2mpc_handle *h, const void *W, const void *W_e, int32_t check);
+/* The expanded per-instance tables as the QP reads them, to host arrays: Hs (B,2,10,10) stage then terminal, Gy (B,2,10,12), Wd (B,208)
+ * = [W | W_e]; any may be NULL.  Blocking.  Refused while the per-instance weights are off.  (For comparing the two setters entry for
+ * entry: a comparison through solves cannot tell -0.0 from 0.0.) */
+int ihm2mpc_get_instance_weight_tables(ihm2mpc_handle *h, double *Hs, double *Gy, double *Wd);
+/*   ihm2mpc_eval_adjoint_sensitivities_w_device <- ihm2mpc_eval_adjoint_sensitivities_w with seeds and gradients in device memory: same
+ * shapes, NULL rules (either seed NULL = zero; both NULL with n_seeds == 2 = the unit seeds on u_0; any output NULL = skipped), NaN rows,
+ * preconditions and refusal texts, same bits.  The kernel reads the seeds straight from the caller's memory and the gradients reach the
+ * caller's memory in stream order: no host copy, no wait.  THE CALLER KEEPS the seeds alive and unchanged, and the outputs alive, until
+ * the stream has passed the call (ihm2mpc_synchronize, or an event on ihm2mpc_get_stream).  Memory for the gradients on first use and
+ * when n_seeds grows.
+ * Not offered with device pointers: the slack-seed, penalty and cost-gradient entries (ihm2mpc_eval_adjoint_sensitivities_s / _p,
+ * ihm2mpc_eval_cost_gradient*), the persistent loop (ihm2mpc_run_steps*) and the SQP mode. */
+int ihm2mpc_eval_adjoint_sensitivities_w_device(ihm2mpc_handle *h, int32_t n_seeds, const void *seed_x, const void *seed_u,
+                                                void *grad_x0, void *grad_yref, void *grad_yref_e, void *grad_W, void *grad_W_e);
 
 /* ---- plant step (closed-loop MiL): x_next = RK4 x M_sim over dt of `model` under u ---- */
 int ihm2mpc_sim_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const double *x,

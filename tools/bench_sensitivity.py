@@ -33,7 +33,12 @@
       k_adj<true, true>, k_penalty_grad) in the same process -- HIP events around each call with every output NULL (uploads, the
       call-local allocations, the kernels) and the wall time of the whole blocking call with every output -- and the extra time of _p
       over _s.  A kernel profiler run on this mode gives k_penalty_grad and k_adj<true, true> beside k_adj<true>.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --penalties [--batches 1024,8192] | --plant [--lib PATH]] > result.json"""
+  (j) --adjoint-device: the entries with device pointers beside their host twins, B = 1024 and 8192, in one process and in interleaved
+      rounds (host call, device call, host call, ..): wall time of ihm2mpc_eval_adjoint_sensitivities_w (host seeds and gradients; it
+      blocks) and of ihm2mpc_eval_adjoint_sensitivities_w_device followed by ihm2mpc_synchronize, with one and with eight seeds and
+      all five outputs; and of ihm2mpc_set_instance_weights (host expansion and upload) against ihm2mpc_set_instance_weights_device
+      with check = 0 (followed by ihm2mpc_synchronize) and check = 1 (it blocks itself).  Median and minimum of --steps rounds.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --penalties [--batches 1024,8192] | --plant [--lib PATH] | --adjoint-device] > result.json"""
 import argparse
 import ctypes
 import json
@@ -194,6 +199,79 @@ def adjoint_timings(B, steps, warmup, weights=False, soft=False):
     for e in ev:
         hip.hipEventDestroy(e)
     s.free()
+    return out
+
+
+def adjoint_device_timings(B, steps, warmup):
+    """Row (j): the host entries and their device twins on one handle, in interleaved rounds."""
+    from ihm2_amd import _lib
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    ocp, track = bench.build_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref)
+    s.set_x0_sensitivities(1)
+    s.set_x0(bench.sample_x0(track, B, 20240607))
+    s.init_guess()
+    rng = np.random.default_rng(1)
+    N = s.N
+    held = []
+
+    def dev(nbytes, src=None):
+        p = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(nbytes)) == 0
+        held.append(p)
+        if src is not None:
+            assert hip.hipMemcpy(p, ctypes.c_void_p(src.ctypes.data), ctypes.c_size_t(src.nbytes), 4) == 0
+        return p
+
+    ptr = lambda a: a.ctypes.data_as(_lib.c_double_p)      # noqa: E731
+
+    def rounds(calls):
+        """calls: name -> function; every round runs each once, in order; (median, min) ms per name over the rounds after the warm-up"""
+        t = {k: [] for k in calls}
+        for i in range(warmup + steps):
+            for k, fn in calls.items():
+                t0 = time.perf_counter()
+                fn()
+                t[k].append((time.perf_counter() - t0) * 1e3)
+        return {k: dict(median_ms=float(np.median(v[warmup:])), min_ms=float(np.min(v[warmup:]))) for k, v in t.items()}
+
+    # the weight setters first (the adjoint rows then differentiate a solve with per-instance weights, as a learning loop's would)
+    W = np.tile(np.asarray(s.data.W[0], dtype=np.float64)[None], (B, 1, 1)) * (1.0 + 0.001 * np.arange(B))[:, None, None]
+    We = np.tile(np.asarray(s.data.W_e, dtype=np.float64)[None], (B, 1, 1))
+    dW, dWe = dev(W.nbytes, W), dev(We.nbytes, We)
+
+    def set_device(check):
+        _lib.check(s.lib.ihm2mpc_set_instance_weights_device(s._h, dW, dWe, check))
+        _lib.check(s.lib.ihm2mpc_synchronize(s._h))
+
+    out = {"set_instance_weights": rounds({"host": lambda: _lib.check(s.lib.ihm2mpc_set_instance_weights(s._h, ptr(W), ptr(We))),
+                                           "device_check0": lambda: set_device(0), "device_check1": lambda: set_device(1)})}
+    s.prepare_step(40.0)
+    st = s.solve()
+    out["status0"] = float((st == 0).mean())
+    for S in (1, 8):
+        sx, su = rng.standard_normal((B, S, N + 1, 8)), rng.standard_normal((B, S, N, 2))
+        g = [np.empty((B, S, 8)), np.empty((B, S, N, 12)), np.empty((B, S, 8)), np.empty((B, S, 12, 12)), np.empty((B, S, 8, 8))]
+        dsx, dsu = dev(sx.nbytes, sx), dev(su.nbytes, su)
+        dg = [dev(a.nbytes) for a in g]
+
+        def host():
+            _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities_w(s._h, S, ptr(sx), ptr(su), *[ptr(a) for a in g]))
+            _lib.check(s.lib.ihm2mpc_synchronize(s._h))
+
+        def device():
+            _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities_w_device(s._h, S, dsx, dsu, *dg))
+            _lib.check(s.lib.ihm2mpc_synchronize(s._h))
+
+        out[f"adjoint_w_n_seeds_{S}"] = rounds({"host": host, "device": device})
+        back = np.empty_like(g[3])
+        assert hip.hipMemcpy(ctypes.c_void_p(back.ctypes.data), dg[3], ctypes.c_size_t(back.nbytes), 4) == 0
+        out[f"adjoint_w_n_seeds_{S}"]["same_bits"] = bool(np.array_equal(back.view(np.uint64), g[3].view(np.uint64)))
+    s.free()
+    for p in held:
+        hip.hipFree(p)
     return out
 
 
@@ -397,8 +475,12 @@ def main():
     ap.add_argument("--value", action="store_true")
     ap.add_argument("--value-soft", action="store_true")
     ap.add_argument("--penalties", action="store_true")
+    ap.add_argument("--adjoint-device", action="store_true")
     ap.add_argument("--batches", default="1024,8192", help="--value, --value-soft, --penalties: the batch sizes (one at a time under a kernel profiler)")
     a = ap.parse_args()
+    if a.adjoint_device:
+        print(json.dumps({"adjoint_device": {str(B): adjoint_device_timings(B, a.steps, a.warmup) for B in (1024, 8192)}}))
+        return
     if a.penalties:
         print(json.dumps({"penalties": {str(B): penalty_timings(B, a.steps, a.warmup) for B in (int(v) for v in a.batches.split(","))}}))
         return
