@@ -108,6 +108,11 @@ SYMBOLS = {
     "ihm2mpc_set_instance_weights_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
     "ihm2mpc_get_instance_weight_tables": (C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
     "ihm2mpc_eval_adjoint_sensitivities_w_device": (C.c_int, [_H, C.c_int32] + [C.c_void_p] * 7),
+    "ihm2mpc_set_instance_soft_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
+    "ihm2mpc_set_instance_alat_soft_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
+    "ihm2mpc_get_instance_penalty_tables": (C.c_int, [_H] + [c_double_p] * 6),
+    "ihm2mpc_get_slacks_device": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "ihm2mpc_eval_adjoint_sensitivities_p_device": (C.c_int, [_H, C.c_int32] + [C.c_void_p] * 14),
     "ihm2mpc_sim_step": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "ihm2mpc_sim_advance": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "ihm2mpc_sim_step_sens": (C.c_int, [_H, C.c_int32, C.c_int32] + [c_double_p] * 5 + [c_int32_p]),

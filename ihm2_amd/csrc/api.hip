@@ -167,13 +167,29 @@ int check_penalty_pattern(const ihm2mpc_handle *h, const double *iz, const doubl
 // always; the per-instance images (B of each, one base per instance) while either per-instance mode (bounds, slack penalties) is on -- a
 // mode that is off contributes the batch-shared values -- and released when both are off.  Bounds whose finite sides differ from the shared
 // table's are a refusal (-1); penalties that the pattern does not take any more (a later shared setter changed it) are no error of that
-// setter: inst_p_ok stays false and ready() reports it before the next solve.
+// setter: inst_p_ok stays false and ready() reports it before the next solve.  Penalties that came from device memory
+// (ihm2mpc_set_instance_soft_device / _alat_soft_device) have no host copy: the stage images' penalty halves and ip are the copy, which the
+// uploads below leave in place and from which k_penalty_tables puts the slot images' penalty halves back -- into whatever layout the
+// slot table now has, since the kernel reads the pattern from it.  What such values were admitted under is which sides the shared rows
+// hold soft (the four rules of penalty_side read nothing else of the shared table): the handle keeps those flags as they were when the
+// pair was set, and a pair whose flags a shared setter has changed is marked as not fitting, since nothing here can check its values
+// against the new ones.
+std::vector<char> soft_flags(const double *sZ, size_t n)
+{
+    std::vector<char> f(n);
+    for (size_t i = 0; i < n; i++) f[i] = sZ[i] >= 0.0;
+    return f;
+}
+
 int tables_to_device(ihm2mpc_handle *h)
 {
     const int B = h->B;
     const bool inst = h->inst_b || h->inst_p;
     const ihm2::SlotTable &t = h->slots;
     h->inst_b_ok = false; h->inst_p_ok = false;
+    h->inst_images = false;     // until the per-instance images of h->slots are on the device, every one of them (every early return below leaves it false)
+    if (h->dev_sp == 1 && h->dev_sp_flags != soft_flags(h->rows.sZ.data(), h->rows.sZ.size())) h->dev_sp = 2;
+    if (h->dev_ap == 1 && h->dev_ap_flags != soft_flags(h->rows.alat_sZ, 2)) h->dev_ap = 2;
     h->slots_full = false;      // until a table and every bound that goes with it are on the device
     ihm2::TableImages m = ihm2::table_images(t, h->rows, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (m.entries && (upload_shared(h, m.slot_lo.data(), h->slot_lb, m.slot_lo.size()) || upload_shared(h, m.slot_up.data(), h->slot_ub, m.slot_up.size())))
@@ -189,6 +205,8 @@ int tables_to_device(ihm2mpc_handle *h)
         const double *az = h->ih_az.empty() ? nullptr : h->ih_az.data(), *aZ = h->ih_aZ.empty() ? nullptr : h->ih_aZ.data();
         const bool p_fit = h->inst_p && !ihm2::find_penalty_mismatch(h->rows, B, iz, iZ, az, aZ).found();
         if (!p_fit) iz = iZ = az = aZ = nullptr;       // (the shared values: launches are refused until the penalties are set again or dropped)
+        h->host_p_fit = p_fit;
+        const bool keep_sp = h->dev_sp == 1 && h->i_st_lb, keep_ap = h->dev_ap == 1 && h->ip.alat_sz;     // device-set pairs that still fit
         m = ihm2::table_images(t, h->rows, B, il, iu, iz, iZ, az, aZ);
         if (m.slot_lo.size() > h->i_slot_lb.size() || !h->i_st_lb) {
             HIP_TRY(hipStreamSynchronize(h->stream));       // a launch in flight may still read the old arrays
@@ -200,12 +218,24 @@ int tables_to_device(ihm2mpc_handle *h)
         }
         if (m.entries && (upload_shared(h, m.slot_lo.data(), h->i_slot_lb, m.slot_lo.size()) || upload_shared(h, m.slot_up.data(), h->i_slot_ub, m.slot_up.size())))
             return -1;
-        if (upload_shared(h, m.stage_lo.data(), h->i_st_lb, m.stage_lo.size()) || upload_shared(h, m.stage_up.data(), h->i_st_ub, m.stage_up.size())) return -1;
+        if (keep_sp) {          // the bounds halves only: the penalty halves are the one copy of the device-set values
+            const size_t row = (m.stage_rows + (size_t)h->NS * NLAM) * sizeof(double), half = m.stage_rows * sizeof(double);
+            HIP_TRY(hipMemcpy2DAsync(h->i_st_lb, row, m.stage_lo.data(), row, half, B, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpy2DAsync(h->i_st_ub, row, m.stage_up.data(), row, half, B, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        } else if (upload_shared(h, m.stage_lo.data(), h->i_st_lb, m.stage_lo.size()) || upload_shared(h, m.stage_up.data(), h->i_st_ub, m.stage_up.size()))
+            return -1;
         if (h->inst_p) {        // the a_lat row's (B,2) pairs, which the cost reads beside the tables
             if (!h->ip.alat_sz && alloc_all(h->ip.alat_sz, m.alat_z.size(), h->ip.alat_sZ, m.alat_Z.size())) return -1;
-            if (upload_shared(h, m.alat_z.data(), h->ip.alat_sz, m.alat_z.size()) || upload_shared(h, m.alat_Z.data(), h->ip.alat_sZ, m.alat_Z.size())) return -1;
+            if (!keep_ap && (upload_shared(h, m.alat_z.data(), h->ip.alat_sz, m.alat_z.size()) || upload_shared(h, m.alat_Z.data(), h->ip.alat_sZ, m.alat_Z.size())))
+                return -1;
         }
-        h->inst_b_ok = h->inst_b; h->inst_p_ok = p_fit;
+        // the slot images' penalty halves of the device-set pairs, from the device's copy
+        if (keep_sp && m.entries) ihm2_launch_penalty_tables(h, 0, h->i_st_lb + m.stage_rows, h->i_st_ub + m.stage_rows, m.stage_rows + (size_t)h->NS * NLAM, 0);
+        if (keep_ap && m.entries) ihm2_launch_penalty_tables(h, 1, h->ip.alat_sz, h->ip.alat_sZ, 2, 0);
+        if (keep_sp || keep_ap) HIP_TRY(hipGetLastError());
+        h->inst_b_ok = h->inst_b; h->inst_p_ok = p_fit && h->dev_sp != 2 && h->dev_ap != 2;
+        h->inst_images = true;
     }
     // the full slot form: the table, with the bounds of every instance that the device now holds
     h->slots_full = h->slots_fit && ihm2::slot_table_full(t, ihm2::full_form_nslot()) && ihm2::slot_bounds_full(t, inst ? B : 1, m.slot_lo, m.slot_up);
@@ -821,6 +851,7 @@ static int rebuild_slots(ihm2mpc_handle *h)
     h->slots_full = false;      // (a table that does not fit: launches are refused)
     if (!t.fit) return 0;
     h->slots = std::move(t);
+    h->inst_images = false;     // the per-instance images are the previous table's, in length too, until tables_to_device has succeeded
     const ihm2::SlotTable &s = h->slots;
     if (s.per_blk) {
         HIP_TRY(hipMemcpyAsync(h->slot_kc_blk, s.kc_blk.data(), s.kc_blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
@@ -924,18 +955,21 @@ int ihm2mpc_set_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft
 // Both entries keep their values on the host and share one mode for the kernels; the mode goes when both are off.
 static int instance_penalties_changed(ihm2mpc_handle *h)
 {
-    h->inst_p = !h->ih_sz.empty() || !h->ih_az.empty();
+    h->inst_p = !h->ih_sz.empty() || !h->ih_az.empty() || h->dev_sp || h->dev_ap;
     return tables_to_device(h);
 }
 
 // the new values of one entry into the handle (empty vectors: shared again); on a failure the previous ones are put back, on the host and,
 // as far as that still succeeds, on the device
-static int take_instance_penalties(ihm2mpc_handle *h, std::vector<double> &z, std::vector<double> &Z, std::vector<double> nz, std::vector<double> nZ)
+// (dev: the pair's device-set mark, which the host's values replace)
+static int take_instance_penalties(ihm2mpc_handle *h, std::vector<double> &z, std::vector<double> &Z, int &dev, std::vector<double> nz, std::vector<double> nZ)
 {
-    z.swap(nz); Z.swap(nZ);
+    const int was = dev;
+    z.swap(nz); Z.swap(nZ); dev = 0;
     if (instance_penalties_changed(h) == 0) return 0;
     const std::string why = ihm2mpc_last_error();
     z.swap(nz); Z.swap(nZ);
+    dev = was ? 2 : 0;      // (its values may be gone from the images: they count as not fitting)
     (void)instance_penalties_changed(h);
     return fail("%s", why.c_str());
 }
@@ -944,7 +978,7 @@ int ihm2mpc_set_instance_soft(ihm2mpc_handle *h, const double *soft_z, const dou
 {
     CHECK_H(h);
     if (!soft_z && !soft_Z) {
-        return take_instance_penalties(h, h->ih_sz, h->ih_sZ, {}, {});
+        return take_instance_penalties(h, h->ih_sz, h->ih_sZ, h->dev_sp, {}, {});
     }
     if (!soft_z || !soft_Z) return fail("soft_z and soft_Z must both be given, or both be NULL (batch-shared penalties again)");
     bool any = false;
@@ -953,21 +987,145 @@ int ihm2mpc_set_instance_soft(ihm2mpc_handle *h, const double *soft_z, const dou
     // the pattern check before anything of the handle changes (a failure behind it puts the previous values back)
     if (check_penalty_pattern(h, soft_z, soft_Z, nullptr, nullptr)) return -1;
     const size_t n = (size_t)h->B * h->NS * NLAM;
-    return take_instance_penalties(h, h->ih_sz, h->ih_sZ, std::vector<double>(soft_z, soft_z + n), std::vector<double>(soft_Z, soft_Z + n));
+    return take_instance_penalties(h, h->ih_sz, h->ih_sZ, h->dev_sp, std::vector<double>(soft_z, soft_z + n), std::vector<double>(soft_Z, soft_Z + n));
 }
 
 int ihm2mpc_set_instance_alat_soft(ihm2mpc_handle *h, const double *soft_z, const double *soft_Z)
 {
     CHECK_H(h);
     if (!soft_z && !soft_Z) {
-        return take_instance_penalties(h, h->ih_az, h->ih_aZ, {}, {});
+        return take_instance_penalties(h, h->ih_az, h->ih_aZ, h->dev_ap, {}, {});
     }
     if (!soft_z || !soft_Z) return fail("soft_z and soft_Z must both be given, or both be NULL (batch-shared penalties again)");
     if (!h->rows.alat_on || !(h->rows.alat_sZ[0] >= 0.0 || h->rows.alat_sZ[1] >= 0.0))
         return fail("ihm2mpc_set_alat_constraint has not been called with a soft side (the batch-shared a_lat row gives the pattern)");
     if (check_penalty_pattern(h, nullptr, nullptr, soft_z, soft_Z)) return -1;
     const size_t n = (size_t)h->B * 2;
-    return take_instance_penalties(h, h->ih_az, h->ih_aZ, std::vector<double>(soft_z, soft_z + n), std::vector<double>(soft_Z, soft_Z + n));
+    return take_instance_penalties(h, h->ih_az, h->ih_aZ, h->dev_ap, std::vector<double>(soft_z, soft_z + n), std::vector<double>(soft_Z, soft_Z + n));
+}
+
+// The same two setters from device memory.  k_penalty_check stands for check_penalty_pattern (its codes are read back and turned into
+// that function's messages before anything of the handle changes), k_penalty_tables for the penalty part of table_images.  The images
+// exist before the kernel runs: tables_to_device builds them with the shared penalties when the per-instance tables are not there yet
+// or do not hold what the handle believes (a pattern change, a refused host pair), which is the one blocking step of an unchecked call.
+static int penalty_refusal(const ihm2mpc_handle *h, int alat, int b, int code, const double *shared_Z)
+{
+    const int idx = (code - 1) / 4, kind = (code - 1) % 4 + 1;
+    const int k = alat ? 0 : idx / NLAM, side = alat ? NLAM + idx : idx % NLAM;
+    const bool shared_soft = shared_Z[idx] >= 0.0;
+    switch (kind) {
+    case ihm2_penalty_nan: return fail("instance %d, stage %d, side %d (%s): slack penalty is NaN", b, k, side, side_name(side));
+    case ihm2_penalty_flag:     // (the instance's flag is the opposite of the shared one: that is the offence)
+        return fail("instance %d, stage %d, side %d (%s): the side is %s (soft_Z %s 0) where the batch-shared table holds it %s", b, k, side,
+                    side_name(side), !shared_soft ? "soft" : "hard", !shared_soft ? ">=" : "<", shared_soft ? "soft" : "hard");
+    case ihm2_penalty_negative:
+        return fail("instance %d, stage %d, side %d (%s): soft_z < 0 (the slack penalty must be non-decreasing)", b, k, side, side_name(side));
+    default:
+        return fail("instance %d, stage %d, side %d (%s): the soft side has neither a linear nor a quadratic penalty", b, k, side, side_name(side));
+    }
+}
+
+static int set_instance_penalties_device(ihm2mpc_handle *h, int alat, const double *z, const double *Z, int32_t check)
+{
+    if (!h->bounds_set) return fail("ihm2mpc_set_bounds has not been called (the batch-shared table gives the pattern)");
+    const int B = h->B;
+    if (check) {
+        WorkBuf<int32_t> dcode;     // (B) the kernel writes every entry
+        if (dcode.alloc(B) != hipSuccess) return fail("out of device memory");
+        ihm2_launch_penalty_check(h, alat, z, Z, dcode);
+        HIP_TRY(hipGetLastError());
+        std::vector<int32_t> code(B);
+        HIP_TRY(hipMemcpyAsync(code.data(), dcode, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int b = 0; b < B; b++)
+            if (code[b]) return penalty_refusal(h, alat, b, code[b], alat ? h->rows.alat_sZ : h->rows.sZ.data());
+    }
+    std::vector<double> &hz = alat ? h->ih_az : h->ih_sz, &hZ = alat ? h->ih_aZ : h->ih_sZ;
+    int &dev = alat ? h->dev_ap : h->dev_sp;
+    // the device's values replace the pair's previous ones, which are kept until the images are there: on a failure they are put back,
+    // on the host and, as far as that still succeeds, on the device, as take_instance_penalties does (a device-set pair's values may
+    // be gone from the images by then: it counts as not fitting)
+    std::vector<double> oz, oZ;
+    const int was = dev;
+    const bool was_on = h->inst_p;
+    hz.swap(oz); hZ.swap(oZ);
+    dev = 0;
+    // the images are there, with the host-held penalties in place (the other pair's device-set values are wherever they are valid)
+    // (inst_images: they are those of h->slots -- a shared setter that was refused half-way leaves the previous table's, of another length)
+    const bool images = h->inst_images && h->inst_p && h->i_st_lb && h->ip.alat_sz && h->host_p_fit;
+    if (!images) {
+        h->inst_p = true;
+        if (tables_to_device(h)) {
+            const std::string why = ihm2mpc_last_error();
+            hz.swap(oz); hZ.swap(oZ);
+            dev = was ? 2 : 0;
+            h->inst_p = was_on;
+            (void)tables_to_device(h);
+            return fail("%s", why.c_str());
+        }
+    }
+    ihm2_launch_penalty_tables(h, alat, z, Z, alat ? 2 : (size_t)h->NS * NLAM, 1);
+    HIP_TRY(hipGetLastError());
+    dev = 1;
+    if (alat) h->dev_ap_flags = soft_flags(h->rows.alat_sZ, 2);
+    else h->dev_sp_flags = soft_flags(h->rows.sZ.data(), h->rows.sZ.size());
+    h->inst_p_ok = h->host_p_fit && h->dev_sp != 2 && h->dev_ap != 2;
+    return 0;
+}
+
+int ihm2mpc_set_instance_soft_device(ihm2mpc_handle *h, const void *soft_z, const void *soft_Z, int32_t check)
+{
+    CHECK_H(h);
+    if (!soft_z && !soft_Z) return ihm2mpc_set_instance_soft(h, nullptr, nullptr);
+    if (!soft_z || !soft_Z) return fail("soft_z and soft_Z must both be given, or both be NULL (batch-shared penalties again)");
+    bool any = false;
+    for (double Z : h->rows.sZ) any = any || Z >= 0.0;
+    if (!any) return fail("ihm2mpc_set_soft has not been called with a soft side (the batch-shared table gives the pattern)");
+    return set_instance_penalties_device(h, 0, (const double *)soft_z, (const double *)soft_Z, check);
+}
+
+int ihm2mpc_set_instance_alat_soft_device(ihm2mpc_handle *h, const void *soft_z, const void *soft_Z, int32_t check)
+{
+    CHECK_H(h);
+    if (!soft_z && !soft_Z) return ihm2mpc_set_instance_alat_soft(h, nullptr, nullptr);
+    if (!soft_z || !soft_Z) return fail("soft_z and soft_Z must both be given, or both be NULL (batch-shared penalties again)");
+    if (!h->rows.alat_on || !(h->rows.alat_sZ[0] >= 0.0 || h->rows.alat_sZ[1] >= 0.0))
+        return fail("ihm2mpc_set_alat_constraint has not been called with a soft side (the batch-shared a_lat row gives the pattern)");
+    return set_instance_penalties_device(h, 1, (const double *)soft_z, (const double *)soft_Z, check);
+}
+
+// the penalty halves of the per-instance images, to host arrays: slot_z, slot_Z (B,MAX_SLOTS) -- the table's entries in table order, then
+// padding (0, -1) --, stage_z, stage_Z (B,NS,28), alat_z, alat_Z (B,2) (the shared pair while no per-instance penalty is on)
+int ihm2mpc_get_instance_penalty_tables(ihm2mpc_handle *h, double *slot_z, double *slot_Z, double *stage_z, double *stage_Z, double *alat_z,
+                                        double *alat_Z)
+{
+    CHECK_H(h);
+    if (h->i_st_lb && !h->inst_images)
+        return fail("the per-instance constraint tables are not those of the current constraint rows: a setter behind them was refused "
+                    "(its message said why); settle that first");
+    if (!h->i_st_lb)
+        return fail("the per-instance constraint tables do not exist: ihm2mpc_set_instance_soft, ihm2mpc_set_instance_alat_soft, their _device "
+                    "forms or ihm2mpc_set_instance_bounds first");
+    const size_t B = h->B, n = h->slots.entries(), nb = (size_t)h->NS * NC, np = (size_t)h->NS * NLAM, D = sizeof(double);
+    for (size_t b = 0; b < B; b++)
+        for (size_t e = n; e < MAX_SLOTS; e++) {
+            if (slot_z) slot_z[b * MAX_SLOTS + e] = ihm2::slot_detail::PADDING.zw;
+            if (slot_Z) slot_Z[b * MAX_SLOTS + e] = ihm2::slot_detail::PADDING.Zw;
+        }
+    if (slot_z && n) HIP_TRY(hipMemcpy2DAsync(slot_z, MAX_SLOTS * D, h->i_slot_lb + n, 2 * n * D, n * D, B, hipMemcpyDeviceToHost, h->stream));
+    if (slot_Z && n) HIP_TRY(hipMemcpy2DAsync(slot_Z, MAX_SLOTS * D, h->i_slot_ub + n, 2 * n * D, n * D, B, hipMemcpyDeviceToHost, h->stream));
+    if (stage_z) HIP_TRY(hipMemcpy2DAsync(stage_z, np * D, h->i_st_lb + nb, (nb + np) * D, np * D, B, hipMemcpyDeviceToHost, h->stream));
+    if (stage_Z) HIP_TRY(hipMemcpy2DAsync(stage_Z, np * D, h->i_st_ub + nb, (nb + np) * D, np * D, B, hipMemcpyDeviceToHost, h->stream));
+    if (h->ip.alat_sz) {
+        if (alat_z) HIP_TRY(hipMemcpyAsync(alat_z, h->ip.alat_sz, B * 2 * D, hipMemcpyDeviceToHost, h->stream));
+        if (alat_Z) HIP_TRY(hipMemcpyAsync(alat_Z, h->ip.alat_sZ, B * 2 * D, hipMemcpyDeviceToHost, h->stream));
+    } else
+        for (size_t i = 0; i < B * 2; i++) {
+            if (alat_z) alat_z[i] = h->rows.alat_sz[i & 1];
+            if (alat_Z) alat_Z[i] = h->rows.alat_sZ[i & 1];
+        }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 int ihm2mpc_set_path_constraints(ihm2mpc_handle *h, int32_t enable, double car_length, double car_width, const double *widths,
@@ -1542,6 +1700,65 @@ int ihm2mpc_eval_adjoint_sensitivities_p(ihm2mpc_handle *h, int32_t n_seeds, con
 {
     const PenaltyOut pen = {grad_z, grad_Z, grad_za, grad_Za, zeta};
     return eval_adjoint(h, n_seeds, seed_x, seed_u, seed_s, seed_sa, grad_x0, grad_yref, grad_yref_e, true, grad_W, grad_W_e, &pen);
+}
+
+// Seeds and gradients in device memory: the launches of eval_adjoint(pen) on the caller's pointers.  The fold works in place, so with a
+// slack seed the stage seeds are first copied (device to device) into the handle's seed buffers, as the host entry uploads them there;
+// k_slack_fold and k_penalty_grad read seed_s, seed_sa, and without a slack seed k_adj reads seed_x, seed_u, straight from the caller's
+// memory.  k_adj and k_penalty_grad write zeta and the four penalty gradients straight into the caller's memory, which they fill entry
+// for entry; an output that is not asked for lands in the handle's workspace (h->pd).  No host copy, no wait (the buffers' growth aside).
+int ihm2mpc_eval_adjoint_sensitivities_p_device(ihm2mpc_handle *h, int32_t n_seeds, const void *seed_x, const void *seed_u, const void *seed_s,
+                                                const void *seed_sa, void *grad_x0, void *grad_yref, void *grad_yref_e, void *grad_W,
+                                                void *grad_W_e, void *grad_z, void *grad_Z, void *grad_za, void *grad_Za, void *zeta)
+{
+    CHECK_H(h);
+    const bool slack = seed_s || seed_sa;
+    const bool unit_u0 = !seed_x && !seed_u && !slack;
+    if (adjoint_refused(h, n_seeds, unit_u0)) return -1;
+    const size_t B = h->B, N = h->N, NS = h->NS, S = n_seeds, D = sizeof(double);
+    if (adjoint_buffers(h, S, true)) return -1;
+    const size_t n = B * S * NS;
+    // (growth releases the old block, into which launches of an earlier call may still be queued: wait for them first)
+    if (h->pd.buf.size() < n * (NZ + 2 * NLAM + 4)) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->pd.buf.poison(poisoned(h, "penalty_grad_work"));
+        if (h->pd.buf.alloc(n * (NZ + 2 * NLAM + 4)) != hipSuccess) return fail("out of device memory");
+    }
+    double *w = h->pd.buf;
+    double *dzeta = zeta ? (double *)zeta : w, *gz = grad_z ? (double *)grad_z : w + n * NZ, *gZ = grad_Z ? (double *)grad_Z : w + n * (NZ + NLAM);
+    double *gza = grad_za ? (double *)grad_za : w + n * (NZ + 2 * NLAM), *gZa = grad_Za ? (double *)grad_Za : w + n * (NZ + 2 * NLAM + 2);
+    const double *ds = (const double *)seed_s, *dsa = (const double *)seed_sa;
+    if (slack) {
+        if (seed_x) HIP_TRY(hipMemcpyAsync(h->adj_sx, seed_x, B * S * NS * NX * D, hipMemcpyDeviceToDevice, h->stream));
+        else HIP_TRY(hipMemsetAsync(h->adj_sx, 0, B * S * NS * NX * D, h->stream));
+        if (seed_u) HIP_TRY(hipMemcpyAsync(h->adj_su, seed_u, B * S * N * NU * D, hipMemcpyDeviceToDevice, h->stream));
+        else HIP_TRY(hipMemsetAsync(h->adj_su, 0, B * S * N * NU * D, h->stream));
+        ihm2_launch_slack_fold(h, 0, n_seeds, ds, dsa, h->adj_sx, h->adj_su);
+        ihm2_launch_adj(h, n_seeds, h->adj_sx, h->adj_su, 0, 1, dzeta);
+    } else {
+        ihm2_launch_adj(h, n_seeds, (const double *)seed_x, (const double *)seed_u, unit_u0 ? 1 : 0, 1, dzeta);
+    }
+    if (any_soft_side(h)) ihm2_launch_penalty_grad(h, 0, n_seeds, ds, dsa, dzeta, gz, gZ, gza, gZa);
+    else if (grad_z || grad_Z || grad_za || grad_Za)
+        ihm2_launch_penalty_fill(h, n_seeds, (double *)grad_z, (double *)grad_Z, (double *)grad_za, (double *)grad_Za);
+    HIP_TRY(hipGetLastError());
+    if (grad_x0) HIP_TRY(hipMemcpyAsync(grad_x0, h->adj_gx0, B * S * NX * D, hipMemcpyDeviceToDevice, h->stream));
+    if (grad_yref) HIP_TRY(hipMemcpyAsync(grad_yref, h->adj_gy, B * S * N * NY * D, hipMemcpyDeviceToDevice, h->stream));
+    if (grad_yref_e) HIP_TRY(hipMemcpyAsync(grad_yref_e, h->adj_gye, B * S * NX * D, hipMemcpyDeviceToDevice, h->stream));
+    if (grad_W) HIP_TRY(hipMemcpyAsync(grad_W, h->adj_gW, B * S * NY * NY * D, hipMemcpyDeviceToDevice, h->stream));
+    if (grad_W_e) HIP_TRY(hipMemcpyAsync(grad_W_e, h->adj_gWe, B * S * NX * NX * D, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+// the slack values after the last QP, device to device: slk (B,N+1,28) as ihm2mpc_get_slacks, slk_alat (B,N+1,2) as the slk of
+// ihm2mpc_get_alat_multipliers; either may be NULL
+int ihm2mpc_get_slacks_device(ihm2mpc_handle *h, void *slk, void *slk_alat)
+{
+    CHECK_H(h);
+    if (!slk && !slk_alat) return fail("null argument");
+    if (slk) HIP_TRY(hipMemcpyAsync(slk, h->slk, (size_t)h->B * h->NS * NLAM * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (slk_alat) HIP_TRY(hipMemcpyAsync(slk_alat, h->slk_a, (size_t)h->B * h->NS * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
 }
 
 // ---- the objective and its total gradient (kernels_cost.hip) ----

@@ -108,6 +108,13 @@ struct ihm2_inst_penalties {
     void reset() { alat_sz.reset(); alat_sZ.reset(); }
 };
 
+// The device memory of ihm2mpc_eval_adjoint_sensitivities_p_device, which must not wait for its kernels and therefore cannot release work
+// buffers when it returns as the host entry does: the outputs the caller does not ask for (the layout of api.hip: PenaltyWork, named
+// "penalty_grad_work" for IHM2MPC_POISON_WORKSPACE) land here, grown on demand.  The handle holds the block by value (ihm2mpc_handle::pd).
+struct ihm2_penalty_device_work {
+    WorkBuf<double> buf;                    // zeta (B,S,NS,10) | grad_z, grad_Z (B,S,NS,28) | grad_za, grad_Za (B,S,NS,2)
+};
+
 // Created by value-initialisation (std::make_unique<ihm2mpc_handle>() in ihm2mpc_create): there is no user-provided constructor, so every
 // scalar member starts at zero and every buffer empty.  The destructor (api.hip) waits for both streams and releases what is not a buffer.
 struct ihm2mpc_handle {
@@ -237,6 +244,17 @@ struct ihm2mpc_handle {
     std::vector<double> ih_sz, ih_sZ;      // host (B,NS,NLAM) penalties of the rows 0..13, empty: shared
     std::vector<double> ih_az, ih_aZ;      // host (B,2) penalties of the a_lat row, empty: shared
     ihm2_inst_penalties ip;                // the a_lat pairs' device copies (state; tests/test_instance_penalties_abi.py reads the struct's classes)
+    // The same values from device memory (ihm2mpc_set_instance_soft_device / _alat_soft_device): the handle has no host copy of them.  The
+    // device's own copy is what the cost reads anyway -- the penalty halves of i_st_* for the rows 0..13, ip for the a_lat pairs -- and
+    // tables_to_device rebuilds the slot images from it (k_penalty_tables).  Per pair: 0 not set from device memory, 1 set, 2 set and a
+    // shared setter changed afterwards which sides are soft: nothing can check the values against the new flags without a read-back, so
+    // they count as not fitting.  dev_*_flags: which sides the shared rows held soft (sZ >= 0) when the pair was set
+    int dev_sp, dev_ap;
+    std::vector<char> dev_sp_flags, dev_ap_flags;
+    bool inst_images;              // the per-instance images on the device are those of `slots` and of the values the handle holds: set at
+                                   // the successful end of tables_to_device only, cleared when it starts and when `slots` is replaced
+    bool host_p_fit;               // the penalties the host holds fit the shared pattern (tables_to_device; true where it holds none)
+    ihm2_penalty_device_work pd;           // workspace of ihm2mpc_eval_adjoint_sensitivities_p_device
 
     // ---- history of ihm2mpc_run_steps, grown on demand ----
     WorkBuf<double> hist_u0, hist_x0;       // (steps,B,2), (steps,B,8)
@@ -316,6 +334,18 @@ void ihm2_launch_slack_fold(ihm2mpc_handle *h, int cost, int n_seeds, const doub
 // are the cost's own z + Z s and the explicit partials of J are added (one seed); else seed_s, seed_sa as the fold took them
 void ihm2_launch_penalty_grad(ihm2mpc_handle *h, int cost, int n_seeds, const double *seed_s, const double *seed_sa, const double *zeta,
                               double *grad_z, double *grad_Z, double *grad_za, double *grad_Za);
+// kernels_penalties.hip: the penalty halves of the per-instance images from z, Z in device memory on h->stream, the device twin of the
+// penalty part of ihm2::table_images (qp_tables.hpp), bit for bit.  alat = 0: z, Z (B,NS,28), `src_stride` doubles from instance to
+// instance -> zw | Zw of every slot of i_slot_lb / i_slot_ub but the a_lat row's and, with stage_out, z | Z of i_st_lb / i_st_ub; alat = 1:
+// z, Z (B,2) -> the a_lat row's slots and, with stage_out, ip.alat_sz / alat_sZ.  The images and the shared slot table must be on the device
+void ihm2_launch_penalty_tables(ihm2mpc_handle *h, int alat, const double *z, const double *Z, size_t src_stride, int stage_out);
+// ihm2::find_penalty_mismatch of one pair on the device: code[b] = 0, or ihm2_penalty_code of instance b's first offence in its scan order
+void ihm2_launch_penalty_check(ihm2mpc_handle *h, int alat, const double *z, const double *Z, int32_t *code);
+// the kinds are ihm2::PenaltyMismatch::Kind's values; idx = stage * NLAM + side (the a_lat pair: 0 lower, 1 upper)
+enum { ihm2_penalty_flag = 1, ihm2_penalty_negative = 2, ihm2_penalty_nan = 3, ihm2_penalty_none = 4 };
+static inline __host__ __device__ int ihm2_penalty_code(int idx, int kind) { return 1 + idx * 4 + (kind - 1); }
+// zeros into the four penalty gradients (device memory, any may be nullptr) of n_seeds seeds, NaN where the status is neither 0 nor 2
+void ihm2_launch_penalty_fill(ihm2mpc_handle *h, int n_seeds, double *grad_z, double *grad_Z, double *grad_za, double *grad_Za);
 // kernels_weights.hip: the per-instance weight tables from W (B,12,12), W_e (B,8,8) in device memory, on h->stream -- the device twin of
 // ihm2::stage_weight_tables / terminal_weight_tables (qp_tables.hpp), bit for bit.  code == nullptr: writes Hs (B,2,100), Gy (B,2,120),
 // Wd (B,208), every entry.  code (B) given: writes nothing but code[b], the validation of instance b (ihm2_weight_code_*; Hs, Gy, Wd unused)

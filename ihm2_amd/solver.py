@@ -545,6 +545,50 @@ class BatchedOcpSolver:
         ptr = [C.c_void_p(int(a)) if a else None for a in (seed_x, seed_u, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e)]
         _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_w_device(self._h, int(n_seeds), *ptr))
 
+    def set_instance_soft_device(self, soft_z_dptr: int, soft_Z_dptr: int, check: bool = True):
+        """:meth:`set_instance_soft` with ``soft_z``, ``soft_Z`` ``(B,N+1,28)`` in device memory: a kernel writes the penalty halves of
+        the per-instance constraint tables, bit for bit what the host setter uploads.  ``check=True`` validates as the host setter does
+        (its message for the first offending instance, stage and side) and blocks; ``check=False`` reads nothing back -- the caller
+        vouches.  The solver keeps no host copy: a later ``set_soft`` (for the a_lat pair: ``set_alat_constraint``) that changes which
+        sides are soft makes the next solve refuse until the penalties are set again; shared setters that leave those flags alone keep
+        the values.  ``0, 0``: the shared penalties again (``ihm2mpc_set_instance_soft_device``)."""
+        _lib.check(self.lib.ihm2mpc_set_instance_soft_device(self._h, C.c_void_p(int(soft_z_dptr)) if soft_z_dptr else None,
+                                                             C.c_void_p(int(soft_Z_dptr)) if soft_Z_dptr else None, int(bool(check))))
+
+    def set_instance_alat_soft_device(self, soft_z_dptr: int, soft_Z_dptr: int, check: bool = True):
+        """:meth:`set_instance_alat_soft` with the ``(B,2)`` pairs in device memory; otherwise as :meth:`set_instance_soft_device`
+        (``ihm2mpc_set_instance_alat_soft_device``)."""
+        _lib.check(self.lib.ihm2mpc_set_instance_alat_soft_device(self._h, C.c_void_p(int(soft_z_dptr)) if soft_z_dptr else None,
+                                                                  C.c_void_p(int(soft_Z_dptr)) if soft_Z_dptr else None, int(bool(check))))
+
+    def get_instance_penalty_tables(self):
+        """``dict(slot_z, slot_Z (B,640), stage_z, stage_Z (B,N+1,28), alat_z, alat_Z (B,2))``: the penalty halves of the per-instance
+        constraint tables as the kernels read them -- the slot table's entries in table order, padded with ``(0, -1)`` to 640
+        (``ihm2mpc_get_instance_penalty_tables``; refused while no per-instance bounds or penalties are on)."""
+        B, N = self.B, self.N
+        out = dict(slot_z=np.empty((B, 640)), slot_Z=np.empty((B, 640)), stage_z=np.empty((B, N + 1, NLAM)), stage_Z=np.empty((B, N + 1, NLAM)),
+                   alat_z=np.empty((B, 2)), alat_Z=np.empty((B, 2)))
+        _lib.check(self.lib.ihm2mpc_get_instance_penalty_tables(self._h, *[_ptr(v) for v in out.values()]))
+        return out
+
+    def get_slacks_device(self, slk_dptr: int = 0, slk_alat_dptr: int = 0):
+        """:meth:`get_slacks` ``(B,N+1,28)`` and the slacks of :meth:`get_alat_multipliers` ``(B,N+1,2)`` into device memory,
+        stream-ordered; 0 = not wanted (``ihm2mpc_get_slacks_device``)."""
+        _lib.check(self.lib.ihm2mpc_get_slacks_device(self._h, C.c_void_p(int(slk_dptr)) if slk_dptr else None,
+                                                      C.c_void_p(int(slk_alat_dptr)) if slk_alat_dptr else None))
+
+    def eval_adjoint_penalty_sensitivities_device(self, n_seeds: int, seed_x: int = 0, seed_u: int = 0, seed_s: int = 0, seed_sa: int = 0,
+                                                  grad_x0: int = 0, grad_yref: int = 0, grad_yref_e: int = 0, grad_W: int = 0, grad_W_e: int = 0,
+                                                  grad_z: int = 0, grad_Z: int = 0, grad_za: int = 0, grad_Za: int = 0, zeta: int = 0):
+        """:meth:`eval_adjoint_penalty_sensitivities` on device memory, stream-ordered and without a wait: addresses as integers, 0 for
+        NULL (a zero seed, an output that is not wanted; all four seeds 0 with ``n_seeds = 2``: the unit seeds on ``u_0``).  Seeds
+        ``(B,n_seeds,N+1,8)``, ``(B,n_seeds,N,2)``, ``(B,n_seeds,N+1,28)``, ``(B,n_seeds,N+1,2)``; the penalty gradients
+        ``(B,n_seeds,N+1,28)`` and ``(B,n_seeds,N+1,2)``, ``zeta (B,n_seeds,N+1,10)``; everything must stay alive, the seeds unchanged,
+        until the handle's stream has passed (``ihm2mpc_eval_adjoint_sensitivities_p_device``)."""
+        ptr = [C.c_void_p(int(a)) if a else None for a in (seed_x, seed_u, seed_s, seed_sa, grad_x0, grad_yref, grad_yref_e, grad_W, grad_W_e,
+                                                           grad_z, grad_Z, grad_za, grad_Za, zeta)]
+        _lib.check(self.lib.ihm2mpc_eval_adjoint_sensitivities_p_device(self._h, int(n_seeds), *ptr))
+
     # ---- sensitivities of the solution with respect to x0 (acados: eval_param_sens(j, 0, "ex"); get(k, "sens_x" / "sens_u")) ----
     def set_x0_sensitivities(self, mode: int = 2):
         """0 off; 1 ``du_0/dx_0`` only (the feedback gain K0); 2 the whole horizon.  Every later RTI ``solve`` /

@@ -530,10 +530,58 @@ int ihm2mpc_get_instance_weight_tables(ihm2mpc_handle *h, double *Hs, double *Gy
  * caller's memory in stream order: no host copy, no wait.  THE CALLER KEEPS the seeds alive and unchanged, and the outputs alive, until
  * the stream has passed the call (ihm2mpc_synchronize, or an event on ihm2mpc_get_stream).  Memory for the gradients on first use and
  * when n_seeds grows.
- * Not offered with device pointers: the slack-seed, penalty and cost-gradient entries (ihm2mpc_eval_adjoint_sensitivities_s / _p,
- * ihm2mpc_eval_cost_gradient*), the persistent loop (ihm2mpc_run_steps*) and the SQP mode. */
+ * Not offered with device pointers: the cost-gradient entries (ihm2mpc_eval_cost_gradient*), the persistent loop (ihm2mpc_run_steps*)
+ * and the SQP mode. */
 int ihm2mpc_eval_adjoint_sensitivities_w_device(ihm2mpc_handle *h, int32_t n_seeds, const void *seed_x, const void *seed_u,
                                                 void *grad_x0, void *grad_yref, void *grad_yref_e, void *grad_W, void *grad_W_e);
+/* ---- the penalty side of the same loop: slack penalties in, slack values out, penalty gradients back ----
+ *   ihm2mpc_set_instance_soft_device / _set_instance_alat_soft_device <- ihm2mpc_set_instance_soft / _set_instance_alat_soft with soft_z,
+ * soft_Z (B,N+1,28) / (B,2) in device memory.  One kernel (k_penalty_tables) writes the penalty halves of the per-instance constraint
+ * tables -- the slots' zw | Zw, the (stage, side) z | Z, the a_lat pairs -- bit for bit what the host setter uploads: the instance's
+ * values on the soft slots, the side the slot's finite bound names, the a_lat row's slots from the a_lat pair, the shared values on hard
+ * slots and padding.  The bounds halves keep what they hold (the shared bounds, or those of ihm2mpc_set_instance_bounds).  Same
+ * preconditions and refusal texts as the host setters (a soft side in the shared table first; both pointers or both NULL; NULL, NULL =
+ * batch-shared penalties again, the host setter's own path), and ihm2mpc_set_bounds must have been called.  check != 0: the four rules
+ * of the host setter run on the device in its scan order -- no NaN; soft exactly where the shared table is soft; soft_z >= 0 and
+ * soft_z + soft_Z > 0 on a soft side -- and the call is refused with the host setter's message for the first offending (instance, stage,
+ * side); this reads one int32 per instance back and BLOCKS; on a refusal the handle's tables and mode are untouched.  check == 0:
+ * nothing is read back and the call does not block once the per-instance tables exist (the first call builds them, which blocks) --
+ * THE CALLER VOUCHES for penalties that follow the four rules: nothing validates them.  soft_z, soft_Z are read in stream order:
+ * THE CALLER KEEPS them alive and unchanged until the stream has passed.  The values replace the pair's host-set ones; the other pair
+ * stays what it was.  The handle keeps NO HOST COPY of device-set values.  They were admitted under the sides the shared table held
+ * soft at that moment (the four rules read nothing else of it), so a later ihm2mpc_set_soft (the rows 0..13) or
+ * ihm2mpc_set_alat_constraint (the a_lat pair) that changes WHICH SIDES ARE SOFT cannot check them against the new flags and
+ * marks them as no longer fitting -- the next solve is refused ("the per-instance penalties do not fit the batch-shared constraint
+ * pattern any more") until every such pair is set again or dropped with NULL, NULL.  Shared setters that leave those flags as they
+ * are -- other shared penalty values, ihm2mpc_set_bounds, ihm2mpc_set_path_constraints, finite sides that come or go -- keep the
+ * device-set values, as they keep host-set ones: the slot tables are rebuilt from the device's own copy.
+ * ihm2mpc_set_instance_bounds and the host setter of the other pair leave device-set values in place as well.  Only a refusal by a
+ * precondition or by the check leaves the handle untouched: if building the per-instance tables fails behind them (out of device
+ * memory; per-instance bounds that no longer fit the shared table) the pair's previous values are put back as the host setter puts
+ * them back, and a previous device-set pair then counts as not fitting. */
+int ihm2mpc_set_instance_soft_device(ihm2mpc_handle *h, const void *soft_z, const void *soft_Z, int32_t check);
+int ihm2mpc_set_instance_alat_soft_device(ihm2mpc_handle *h, const void *soft_z, const void *soft_Z, int32_t check);
+/* The penalty halves of the per-instance tables as the kernels read them, to host arrays: slot_z, slot_Z (B,640) -- zw, Zw of the slot
+ * table's entries in table order, then padding (0, -1) up to the structural limit of 640 slots --, stage_z, stage_Z (B,N+1,28), alat_z,
+ * alat_Z (B,2); any may be NULL.  Blocking.  Refused while the per-instance tables do not exist (no per-instance bounds or penalties
+ * are on).  (For comparing the two setters entry for entry, as ihm2mpc_get_instance_weight_tables does for the weights.) */
+int ihm2mpc_get_instance_penalty_tables(ihm2mpc_handle *h, double *slot_z, double *slot_Z, double *stage_z, double *stage_Z,
+                                        double *alat_z, double *alat_Z);
+/*   ihm2mpc_get_slacks_device <- ihm2mpc_get_slacks and the slk of ihm2mpc_get_alat_multipliers: slk (B,N+1,28), slk_alat (B,N+1,2),
+ * device to device in stream order; either may be NULL.  THE CALLER KEEPS the outputs alive until the stream has passed. */
+int ihm2mpc_get_slacks_device(ihm2mpc_handle *h, void *slk, void *slk_alat);
+/*   ihm2mpc_eval_adjoint_sensitivities_p_device <- ihm2mpc_eval_adjoint_sensitivities_p with the four seeds and the ten outputs in device
+ * memory: same shapes, NULL rules (any seed NULL = zero; all four NULL with n_seeds == 2 = the unit seeds on u_0; any output NULL =
+ * skipped), NaN rows, preconditions and refusal texts, same bits.  The kernels read the seeds from the caller's memory (with a slack
+ * seed the stage seeds are first copied into the handle's seed buffers, where the fold works in place) and the results reach the
+ * caller's memory in stream order: no host copy, no wait.  THE CALLER KEEPS the seeds alive and unchanged, and the outputs alive, until
+ * the stream has passed the call.  With seed_s, seed_sa and the five new outputs NULL the first five are the bits of
+ * ihm2mpc_eval_adjoint_sensitivities_w_device.  Workspace for outputs that are not asked for belongs to the handle, on first use and when
+ * n_seeds grows. */
+int ihm2mpc_eval_adjoint_sensitivities_p_device(ihm2mpc_handle *h, int32_t n_seeds, const void *seed_x, const void *seed_u,
+                                                const void *seed_s, const void *seed_sa,
+                                                void *grad_x0, void *grad_yref, void *grad_yref_e, void *grad_W, void *grad_W_e,
+                                                void *grad_z, void *grad_Z, void *grad_za, void *grad_Za, void *zeta);
 
 /* ---- plant step (closed-loop MiL): x_next = RK4 x M_sim over dt of `model` under u ---- */
 int ihm2mpc_sim_step(ihm2mpc_handle *h, int32_t model, int32_t M_sim, const double *x,

@@ -38,7 +38,13 @@
       blocks) and of ihm2mpc_eval_adjoint_sensitivities_w_device followed by ihm2mpc_synchronize, with one and with eight seeds and
       all five outputs; and of ihm2mpc_set_instance_weights (host expansion and upload) against ihm2mpc_set_instance_weights_device
       with check = 0 (followed by ihm2mpc_synchronize) and check = 1 (it blocks itself).  Median and minimum of --steps rounds.
-usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --penalties [--batches 1024,8192] | --plant [--lib PATH] | --adjoint-device] > result.json"""
+  (k) --penalties-device: the same for the penalty side, on the soft table of (h), B = 1024 and 8192, interleaved rounds:
+      ihm2mpc_set_instance_soft (host images and upload) against ihm2mpc_set_instance_soft_device with check = 0 (followed by
+      ihm2mpc_synchronize) and check = 1 -- the device setter once behind the host setter (it then releases the handle's host copy)
+      and in rounds of its own; ihm2mpc_eval_adjoint_sensitivities_p (host seeds and outputs; it blocks) against
+      ihm2mpc_eval_adjoint_sensitivities_p_device followed by ihm2mpc_synchronize, one seed on the stages and on the slacks and all
+      ten outputs.
+usage: tools/bench_sensitivity.py [--steps 50] [--warmup 5] [--loop-steps 20,500] [--only-loops | --adjoint | --adjoint-weights | --value [--batches 1024,8192] | --value-soft [--batches 1024,8192] | --penalties [--batches 1024,8192] | --plant [--lib PATH] | --adjoint-device | --penalties-device] > result.json"""
 import argparse
 import ctypes
 import json
@@ -275,6 +281,94 @@ def adjoint_device_timings(B, steps, warmup):
     return out
 
 
+def penalties_device_timings(B, steps, warmup):
+    """Row (k): the host entries of the penalty side and their device twins on one handle, in interleaved rounds."""
+    from ihm2_amd import _lib
+    from ihm2_amd.solver import BatchedOcpSolver
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    ocp, track, widths = soft_track_problem(B)
+    s = BatchedOcpSolver(ocp, B, track.s_ref, track.kappa_ref, track_widths=widths)
+    s.set_x0_sensitivities(1)
+    s.set_x0(bench.sample_x0(track, B, 20240607))
+    s.init_guess()
+    rng = np.random.default_rng(1)
+    N = s.N
+    held = []
+
+    def dev(nbytes, src=None):
+        p = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(nbytes)) == 0
+        held.append(p)
+        if src is not None:
+            assert hip.hipMemcpy(p, ctypes.c_void_p(src.ctypes.data), ctypes.c_size_t(src.nbytes), 4) == 0
+        return p
+
+    ptr = lambda a: a.ctypes.data_as(_lib.c_double_p)      # noqa: E731
+
+    def rounds(calls):
+        t = {k: [] for k in calls}
+        for i in range(warmup + steps):
+            for k, fn in calls.items():
+                t0 = time.perf_counter()
+                fn()
+                t[k].append((time.perf_counter() - t0) * 1e3)
+        return {k: dict(median_ms=float(np.median(v[warmup:])), min_ms=float(np.min(v[warmup:]))) for k, v in t.items()}
+
+    # per-instance penalties: the shared table's on its soft sides times a factor, the shared values elsewhere
+    z0, Z0 = np.asarray(s.data.soft_z, dtype=np.float64), np.asarray(s.data.soft_Z, dtype=np.float64)
+    f = (1.0 + 0.0005 * np.arange(B))[:, None, None]
+    z, Z = np.ascontiguousarray(np.where(Z0 >= 0.0, z0 * f, z0)), np.ascontiguousarray(np.where(Z0 >= 0.0, Z0 * f, Z0))
+    dz, dZ = dev(z.nbytes, z), dev(Z.nbytes, Z)
+
+    def set_device(check):
+        _lib.check(s.lib.ihm2mpc_set_instance_soft_device(s._h, dz, dZ, check))
+        _lib.check(s.lib.ihm2mpc_synchronize(s._h))
+
+    # the device setter behind the host setter drops the handle's host copy of the pair (two arrays of B (N+1) 28 doubles that were the
+    # source of uploads a moment ago: releasing them is what that call's time consists of); a loop that stays on the device setter never
+    # does that, so the steady rows are timed in rounds of their own
+    out = {"set_instance_soft": rounds({"host": lambda: _lib.check(s.lib.ihm2mpc_set_instance_soft(s._h, ptr(z), ptr(Z))),
+                                        "device_check0_after_host": lambda: set_device(0)})}
+    out["set_instance_soft"].update(rounds({"device_check0": lambda: set_device(0), "device_check1": lambda: set_device(1)}))
+    tables = s.get_instance_penalty_tables()            # the device setter's (it ran last)
+    _lib.check(s.lib.ihm2mpc_set_instance_soft(s._h, ptr(z), ptr(Z)))
+    host_tables = s.get_instance_penalty_tables()
+    out["set_instance_soft"]["same_bits"] = bool(all(np.array_equal(tables[k].view(np.uint64), host_tables[k].view(np.uint64)) for k in tables))
+    set_device(0)
+    s.prepare_step(40.0)
+    st = s.solve()
+    out["status0"] = float((st == 0).mean())
+    S = 1
+    seeds = [rng.standard_normal((B, S, N + 1, 8)), rng.standard_normal((B, S, N, 2)), rng.standard_normal((B, S, N + 1, 28)),
+             rng.standard_normal((B, S, N + 1, 2))]
+    g = [np.empty((B, S, 8)), np.empty((B, S, N, 12)), np.empty((B, S, 8)), np.empty((B, S, 12, 12)), np.empty((B, S, 8, 8)),
+         np.empty((B, S, N + 1, 28)), np.empty((B, S, N + 1, 28)), np.empty((B, S, N + 1, 2)), np.empty((B, S, N + 1, 2)), np.empty((B, S, N + 1, 10))]
+    dseeds = [dev(a.nbytes, a) for a in seeds]
+    dg = [dev(a.nbytes) for a in g]
+
+    def host():
+        _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities_p(s._h, S, *[ptr(a) for a in seeds], *[ptr(a) for a in g]))
+        _lib.check(s.lib.ihm2mpc_synchronize(s._h))
+
+    def device():
+        _lib.check(s.lib.ihm2mpc_eval_adjoint_sensitivities_p_device(s._h, S, *dseeds, *dg))
+        _lib.check(s.lib.ihm2mpc_synchronize(s._h))
+
+    out["adjoint_p_n_seeds_1"] = rounds({"host": host, "device": device})
+    same = True
+    for a, p in zip(g, dg):
+        back = np.empty_like(a)
+        assert hip.hipMemcpy(ctypes.c_void_p(back.ctypes.data), p, ctypes.c_size_t(back.nbytes), 4) == 0
+        same = same and bool(np.array_equal(back.view(np.uint64), a.view(np.uint64)))
+    out["adjoint_p_n_seeds_1"]["same_bits"] = same
+    out["adjoint_p_n_seeds_1"]["live_penalty_gradient"] = bool(np.nan_to_num(g[5]).any())
+    s.free()
+    for p in held:
+        hip.hipFree(p)
+    return out
+
+
 def value_timings(B, steps, warmup, soft=False):
     """ihm2mpc_eval_cost and ihm2mpc_eval_cost_gradient after one RTI step: wall time of the whole blocking call with every output, and
     HIP events on the handle's stream around the call with every output NULL (no download: the call-local allocation on the host, then
@@ -476,8 +570,12 @@ def main():
     ap.add_argument("--value-soft", action="store_true")
     ap.add_argument("--penalties", action="store_true")
     ap.add_argument("--adjoint-device", action="store_true")
+    ap.add_argument("--penalties-device", action="store_true")
     ap.add_argument("--batches", default="1024,8192", help="--value, --value-soft, --penalties: the batch sizes (one at a time under a kernel profiler)")
     a = ap.parse_args()
+    if a.penalties_device:
+        print(json.dumps({"penalties_device": {str(B): penalties_device_timings(B, a.steps, a.warmup) for B in (1024, 8192)}}))
+        return
     if a.adjoint_device:
         print(json.dumps({"adjoint_device": {str(B): adjoint_device_timings(B, a.steps, a.warmup) for B in (1024, 8192)}}))
         return
