@@ -112,6 +112,13 @@ class BatchedOcpSolver:
 
     def __del__(self):
         try:
+            # A handle whose stream ihm2_amd/torch_layer.py has used is never freed from here: it is left to the process's end.  free()'s guard
+            # counts weak references, and when the solver and the tensors die in one garbage collection (a cycle: the frames of a
+            # traceback that hold both, say) the collector clears the weak references before it calls this, while the tensors' memory
+            # is still held -- the guard would see nothing alive, the stream would go, and the allocator would record its event on a
+            # destroyed stream when the tensors follow (the segmentation fault of NOTES.md R28, by another way: R30).
+            if getattr(self, "_stream_users", None):
+                return
             self.free()
         except Exception:
             pass

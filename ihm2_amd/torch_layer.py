@@ -148,7 +148,9 @@ def rti_solve(solver, x0, yref, yref_e, W=None, W_e=None, zero_failed: bool = Fa
 
     Lifetime: every tensor that goes in or comes out is marked as used on the solver's stream (``record_stream``), and PyTorch's
     allocator records an event on that stream when it releases such a tensor.  The solver must therefore outlive them:
-    ``solver.free()`` raises ``RuntimeError`` while one is alive."""
+    ``solver.free()`` raises ``RuntimeError`` while one is alive.  A solver that is garbage-collected without ``free()`` after it went
+    through the layer keeps its handle to the process's end: in a collection the weak references the guard counts are cleared before
+    the solver's finaliser runs, so it cannot tell whether the tensors have gone."""
     device = torch.device("cuda", solver.device)
     check_rti_inputs(solver.B, solver.N, device, x0, yref, yref_e, W, W_e)
     if not solver._sens_mode:

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import bitcmp
 import cost_cases as C
 import layouts as L
 import penalty_grad_cases as PC
@@ -564,14 +565,14 @@ def _layer_bits(c):
     s.set_x0(c.x0); s.set_yref(c.yref); s.set_yref_e(c.yref_e)
     st = s.solve()
     host = s.eval_adjoint_penalty_sensitivities(cx, cu, cs, csa)
-    np.testing.assert_array_equal(out["status"], st)
-    np.testing.assert_array_equal(out["x"], s.get_x()); np.testing.assert_array_equal(out["u"], s.get_u())
-    np.testing.assert_array_equal(out["slk"], s.get_slacks()); np.testing.assert_array_equal(out["slk_a"], s.get_alat_multipliers()[1])
+    # (tests/bitcmp.py: a failure names the array, counts the differing entries and shows the first of them with both values)
+    bitcmp.assert_all_same_bits("rti_solve_soft against the host setters and solve", out,
+                                dict(status=st, x=s.get_x(), u=s.get_u(), slk=s.get_slacks(), slk_a=s.get_alat_multipliers()[1]), nan_equal=True)
     ok = (st == 0) | (st == 2)
     assert not ok[0] and ok.mean() > 0.7 and out["slk"].max() > 1e-6, st
     for k in ADJ + ("soft_z", "soft_Z"):
-        np.testing.assert_array_equal(layer[k], host[k], err_msg=k)
-        assert np.array_equal(layer[k][ok].view(np.uint64), host[k][ok].view(np.uint64)), k
+        bitcmp.assert_same_bits(f"gradient in {k}", layer[k], host[k], nan_equal=True)
+        bitcmp.assert_same_bits(f"gradient in {k}, solved instances", layer[k], host[k], rows=ok)
     assert np.abs(layer["soft_z"][ok]).max() > 0.0 and np.abs(layer["soft_Z"][ok]).max() > 0.0
     # the a_lat pair is one pair for all stages: the layer sums the host entry's per-stage rows (N - 1 terms: the order of the sum is
     # the only difference, a few ulp of the sum of the absolute terms)
@@ -588,8 +589,8 @@ def _layer_bits(c):
         o = fn(s, *a)
         g = torch.autograd.grad((_t(cx) * o[0]).sum() + (_t(cu) * o[1]).sum(), a)
         res.append([o[0].detach().cpu().numpy(), o[1].detach().cpu().numpy(), o[-1].cpu().numpy()] + [v.cpu().numpy() for v in g])
-    for a, b in zip(*res):
-        np.testing.assert_array_equal(a, b)
+    for name, a, b in zip(("x", "u", "status") + tuple("gradient in " + k for k in ADJ), *res):
+        bitcmp.assert_same_bits(f"rti_solve against rti_solve_soft without penalties: {name}", a, b, nan_equal=True)
 
 
 # ---- 7. the layer against central differences of itself ----
@@ -721,23 +722,65 @@ def test_plant_step_between_a_solve_and_its_backward_and_a_closed_loop_chain(tra
         g = torch.autograd.grad(u.sum() + sl.sum(), (tx0, tZ))
         assert all(torch.isfinite(a).all() for a in g)
         # x0 -> rti -> plant -> rti -> loss: the second solve is the solver's last use when backward reaches it, the first solve's
-        # backward would come after it -- so each step has a solver of its own, as a closed loop over a horizon of steps would
-        c.restore()
+        # backward would come after it -- so each step has a solver of its own, as a closed loop over a horizon of steps would.  The
+        # two-step chain against its composition from the host entries (tests/test_gpu_torch_chain.py::compare_chain: the forward bit
+        # for bit, every gradient of both steps to the reference's own rounding scale)
+        import test_gpu_torch_chain as TC
+
         c2 = _Start(track, B)
-        tx0, tZ = _t(c.x0, True), _t(Z, True)
-        _, u1, _, _, _ = rti_solve_soft(s, tx0, _t(c.yref), _t(c.yref_e), None, None, _t(z), tZ, _t(az), _t(aZ), zero_failed=True)
-        x1, _ = plant_step(s, tx0, u1[:, 0].contiguous(), model=0, M_sim=25)
-        x2, u2, _, _, _ = rti_solve_soft(c2.s, x1, _t(c.yref), _t(c.yref_e), None, None, _t(z), _t(Z), _t(az), _t(aZ), zero_failed=True)
-        loss = (x2[:, -1] ** 2).sum() + (u2 ** 2).sum()
-        gx0, gZ = torch.autograd.grad(loss, (tx0, tZ))
-        assert gx0.shape == (B, 8) and gZ.shape == (B, N + 1, 28)
-        assert torch.isfinite(gx0).all() and torch.isfinite(gZ).all()
-        assert gx0.abs().max() > 0.0
+        cs = [c, c2]
+        _, grads, _, worst = TC.compare_chain(cs, c.x0, TC.chain_inputs(c, 2), TC.chain_seeds(2), model=0, zero_failed=True)
+        print(f"CHAIN-HOST two steps: worst ratio {worst[0]:.3f} of 8 (step {worst[1]}, {worst[2]})")
+        assert grads[0]["x0"].shape == (B, 8) and grads[0]["soft_Z"].shape == (B, N + 1, 28)
+        assert np.isfinite(grads[0]["x0"]).all() and np.isfinite(grads[0]["soft_Z"]).all()          # (zero_failed)
+        assert np.abs(grads[0]["x0"]).max() > 0.0 and np.abs(grads[0]["soft_Z"]).max() > 0.0
         return c2
 
     c2 = body()
     _free(c2.s)
     _free(s)
+
+
+@pytest.mark.parametrize("subset", ["s", "sa", "u_sa"])
+def test_layer_seed_subsets_equal_the_host_entry_with_zeros_for_the_absent_seeds(track, subset):
+    """rti_solve_soft's backward with a loss on some of its outputs only (set_materialize_grads(False): an output the loss does not use
+    reaches backward as None -- no x / u seed at all, a slack seed alone) against the host entry given zeros for the absent seeds: the
+    bits on the solved rows, the NaN pattern on the failed one, B = 8."""
+    from ihm2_amd.torch_layer import rti_solve_soft
+
+    c = _Start(track, B, fail0=True)
+    s = c.s
+
+    def body():
+        rng = np.random.default_rng(23)
+        z, Z, az, aZ = _penalties(s)
+        seeds = dict(x=None, u=rng.standard_normal((B, N, 2)), s=rng.standard_normal((B, N + 1, 28)), sa=rng.standard_normal((B, N + 1, 2)))
+        used = {"s": ("s",), "sa": ("sa",), "u_sa": ("u", "sa")}[subset]
+        ins = [_t(a, grad=True) for a in (c.x0, c.yref, c.yref_e, None, None, z, Z, az, aZ) if a is not None]
+        c.restore()
+        x, u, sl, sa, status = rti_solve_soft(s, *ins[:3], None, None, *ins[3:])
+        out = dict(x=x, u=u, s=sl, sa=sa)
+        loss = sum((_t(seeds[k]) * out[k]).sum() for k in used)
+        grads = [g.cpu().numpy() for g in torch.autograd.grad(loss, ins)]
+        st = status.cpu().numpy()
+        zeros = dict(x=np.zeros((B, N + 1, 8)), u=np.zeros((B, N, 2)), s=np.zeros((B, N + 1, 28)), sa=np.zeros((B, N + 1, 2)))
+        host = s.eval_adjoint_penalty_sensitivities(*[seeds[k] if k in used else zeros[k] for k in ("x", "u", "s", "sa")])
+        return grads, st, host
+
+    grads, st, host = body()
+    _free(s)
+    ok = (st == 0) | (st == 2)
+    assert not ok[0] and ok.mean() > 0.7, st
+    layer = dict(zip(("x0", "yref", "yref_e", "soft_z", "soft_Z", "alat_z", "alat_Z"), grads))
+    for k in ("x0", "yref", "yref_e", "soft_z", "soft_Z"):
+        bitcmp.assert_same_bits(f"seeds on {subset}: gradient in {k}", layer[k], host[k], nan_equal=True)
+        bitcmp.assert_same_bits(f"seeds on {subset}: gradient in {k}, solved instances", layer[k], host[k], rows=ok)
+        assert np.isnan(layer[k][~ok]).all() and np.isfinite(layer[k][ok]).all(), k
+    assert any(np.abs(layer[k][ok]).max() > 0.0 for k in ("soft_z", "soft_Z"))
+    for k, hk in (("alat_z", "alat_soft_z"), ("alat_Z", "alat_soft_Z")):     # the sum over the stages: test_layer_gradients_equal_the_host_entrys_bits' rule
+        want, mag = host[hk][ok].sum(1), np.abs(host[hk][ok]).sum(1)
+        assert (np.abs(layer[k][ok] - want) <= 8 * np.finfo(float).eps * mag).all(), k
+        assert np.isnan(layer[k][~ok]).all()
 
 
 # ---- 9. workspace poison ----
