@@ -63,6 +63,11 @@ namespace {
 #define SWEEP_RING 4
 #endif
 #define SWEEP_DL ((SWEEP_RING >= 8) ? 4 : 2)       // stages the LDS operands are fetched ahead
+// QP_RG_RESIDENT: in the full slot form the followed stationarity residual stays in its lane's registers from one update (S:17) to the next
+// instead of going through HBM (0: the text of the general form, for a build that measures the difference).
+#ifndef QP_RG_RESIDENT
+#define QP_RG_RESIDENT 1
+#endif
 
 __device__ __forceinline__ bool fin(double v) { return fabs(v) < INF_BOUND; }
 // A value the compiler takes as new wherever it is asked for: what is computed from it stays where it is used.  (The fields unpacked from a
@@ -605,6 +610,10 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
     bool exact_mode = false;     // residuals from the problem data in every iteration (set when followed residuals failed their check)
     double res_g = 0, res_b = 0, res_d = 0, res_m = 0, mu = 0;
     double fol_g = 0.0, fol_b = 0.0;        // this lane's share of max |r_g|, max |r_b| of the followed residuals (formed where the update writes them)
+    // FULL: this lane's elements of the followed stationarity residual, kept from one update (S:17) to the next
+    constexpr bool RG_RESIDENT = FULL != 0 && QP_RG_RESIDENT != 0;
+    constexpr int NRG = RG_RESIDENT ? ((NF + 1) * 10 + NT - 1) / NT : 1;
+    double rg_own[NRG];
     double rd_l[NSLOT], rd_u[NSLOT], dlam_l[NSLOT], dlam_u[NSLOT], dt_l[NSLOT], dt_u[NSLOT];
     double pa_l[NSLOT], pa_u[NSLOT];      // dlam * dt of the predictor (only the products enter the corrector): 2 registers per slot less than the factors
     for (it = 0;; it++) {
@@ -1043,6 +1052,7 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                 // adjacent -- four 16-byte loads per entry, those of three entries in flight before the first is used
                 const int n = NS * 8;
                 for (int base = 0; base < n; base += 3 * NT) {
+                    /*@S:16*/
                     double2 pr[3][4];
 #pragma unroll
                     for (int q = 0; q < 3; q++) {
@@ -1053,10 +1063,12 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
 #pragma unroll
                     for (int q = 0; q < 3; q++) {
                         const int e = base + NT * q + tid, ec = min(e, n - 1), k = ec >> 3;
+                        if (q == 0) { /*@S:18*/ }
                         double acc = pv[ec];
 #pragma unroll
                         for (int l = 0; l < 4; l++) { acc = fma(pr[q][l].x, dz[k * 10 + l], acc); acc = fma(pr[q][l].y, dz[k * 10 + l + 4], acc); }
                         if (e < n) pv[e] = acc;        // dpi_k = P_k dx_k + p_k
+                        if (q == 0) { /*@S:19*/ }
                     }
                 }
             }
@@ -1211,7 +1223,51 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
             const double cd = 1.0 - alpha_d, cp = alpha - alpha_d, cb = 1.0 - alpha;
             const int n10 = NS * 10;
             fol_g = 0.0; fol_b = 0.0;
+            if constexpr (RG_RESIDENT) {
+                // element e = NT q + tid belongs to this lane in every iteration: with the Hessians' sparse rows r_g stays in rg_own between two
+                // updates.  rgb is read where this iteration formed the residual from the data (S:3 stored it there: the first iteration) and
+                // never written -- nobody else reads it.  The lanes past the end follow a copy of the last element, which is never stored.
+                if (!(HL && h_sparse)) {
+                    // Hessians with full rows (no benchmarked table): element by element through rgb, as the general form does, in a loop that
+                    // is not unrolled -- the kernel's loop fills the instruction cache (40 instructions more cost what a round trip saves), and
+                    // the rows' ten products seven times over are not worth their place in it
+                    for (int e = tid; e < n10; e += NT) {
+                        const int k = e / 10, j = e % 10;
+                        double hdz = 0.0;
+#pragma unroll
+                        for (int l = 0; l < 10; l++) hdz = fma(HS(k, j, l), dz[k * 10 + l], hdz);
+                        const bool masked = (k == 0 && j < 8) || (k == N && j >= 8);
+                        const double v = masked ? 0.0 : fma(cp, hdz, cd * rgb[e]);
+                        rgb[e] = v; gt[e] = v; fol_g = nanmax(fol_g, fabs(v));
+                    }
+                } else {
+                if (exact) {
+#pragma unroll
+                    for (int q = 0; q < NRG; q++) rg_own[q] = rgb[min(NT * q + here(tid), n10 - 1)];
+                }
+#pragma unroll
+                for (int q = 0; q < NRG; q++) {
+                    const int e = NT * q + here(tid), ec = min(e, n10 - 1), k = ec / 10, j = ec % 10;
+                    const int row = ((k == N) ? 10 : 0) + j;
+                    double hdz = 0.0;
+#pragma unroll
+                    for (int l = 0; l < 3; l++) hdz = fma(spv[row * 3 + l], dz[k * 10 + spc[row * 3 + l]], hdz);
+                    const bool masked = (k == 0 && j < 8) || (k == N && j >= 8);
+                    if (q == 0) { /*@S:20*/ }
+                    rg_own[q] = masked ? 0.0 : fma(cp, hdz, cd * rg_own[q]);
+                    if (q == 0) { /*@S:21*/ }
+                }
+                // the stores behind the last read: a store to gt would keep the next element's reads of dz behind it (the compiler cannot tell
+                // the arrays of the block apart), one element's LDS round trips after the other's
+#pragma unroll
+                for (int q = 0; q < NRG; q++) {
+                    const int e = NT * q + here(tid);
+                    if (e < n10) { gt[e] = rg_own[q]; fol_g = nanmax(fol_g, fabs(rg_own[q])); }
+                }
+                }
+            } else
             for (int base = 0; base < n10; base += 4 * NT) {
+                /*@S:17*/
                 double ro[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) ro[q] = rgb[min(base + NT * q + tid, n10 - 1)];
@@ -1228,10 +1284,13 @@ __device__ __forceinline__ void qp_wave_body(const QpArgs &a, const int b, doubl
                         for (int l = 0; l < 10; l++) hdz = fma(HS(k, j, l), dz[k * 10 + l], hdz);
                     }
                     const bool masked = (k == 0 && j < 8) || (k == N && j >= 8);
+                    if (q == 0) { /*@S:20*/ }
                     const double v = masked ? 0.0 : fma(cp, hdz, cd * ro[q]);
                     if (e < n10) { rgb[e] = v; gt[e] = v; if (LEAN != 0) fol_g = nanmax(fol_g, fabs(v)); }
+                    if (q == 0) { /*@S:21*/ }
                 }
             }
+/*@S:22*/
             for (int e = tid; e < N * 8; e += NT) {
                 const double v = cb * rb[e];
                 rb[e] = v;

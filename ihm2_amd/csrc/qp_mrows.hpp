@@ -70,4 +70,22 @@ QP_MROWS_FN int qm_pair_odd_delta(int N, int g, int j) { return qm_pair_write(N,
 QP_MROWS_FN int qm_pair_row4_step(int N, bool odd) { return qm_pair_write(N, odd ? 1 : 0, 4, 0) - qm_pair_write(N, odd ? 1 : 0, 0, 0); }
 static_assert(qm_pair_row4_step(40, false) == 512 && qm_pair_row4_step(40, true) == 64, "rows g and g + 4 of a column: 32 lanes or 4 lanes apart");
 
+// The store schedule of the factor sweep (riccati_mfma.hpp, PLAIN, NF > 0): at stage k its lane (g, j) = (lane >> 4, lane & 15), j < 8, stores
+// 8 bytes at qm_pair_write(N, k, g, j) and 8 bytes at qm_pair_write(N, k, g + 4, j) -- at an odd stage the second halves of the sweeps' slots
+// j * 8 + g and j * 8 + g + 4, one stage later, at the even stage of the pair, the first halves of the slots g * 8 + j and (g + 4) * 8 + j.
+// The two halves of a slot are therefore formed in DIFFERENT lanes of the factor sweep unless the slot lies on the diagonal: one 16-byte store
+// per slot would take the odd stage's values across lanes (the 8 x 8 transpose the layout was made to avoid), not just one stage further.
+QP_MROWS_FN int qm_factor_lane(int row, int col) { return (row & 3) * 16 + col; }                 // the lane that forms M_k[row][col] (in S[2] for row < 4, S[3] else)
+QP_MROWS_FN int qm_pair_half_holder(int slot_lane, int half)                                      // half 0: the even stage's M[g][w], half 1: the odd stage's M[w][g]
+{
+    return half ? qm_factor_lane(slot_lane & 7, slot_lane >> 3) : qm_factor_lane(slot_lane >> 3, slot_lane & 7);
+}
+QP_MROWS_FN int qm_pair_slots_formed_in_one_lane()
+{
+    int n = 0;
+    for (int lane = 0; lane < 64; lane++) n += qm_pair_half_holder(lane, 0) == qm_pair_half_holder(lane, 1);
+    return n;
+}
+static_assert(qm_pair_slots_formed_in_one_lane() == 8, "only the diagonal slots have both halves in one lane of the factor sweep");
+
 }  // namespace ihm2

@@ -2,6 +2,9 @@
 //   * the writer's bytes: every (k, row, col) lands on its own 8 bytes of the instance's block, the block is covered exactly once, and what
 //     the factor sweep's lane (g, j) forms from its running stage-major offset (riccati_mfma.hpp: gofs, + the lane's constant at odd stages,
 //     + the row-4 step) are those bytes;
+//   * the factor sweep's store schedule replayed (two 8-byte stores per lane and stage, k = N - 1 .. 0): every byte of the block written exactly
+//     once by the end of the sweep, none outside it, each half by the lane qm_pair_half_holder names -- and only the 8 diagonal slots have both
+//     halves in one lane (why a 16-byte store per slot is not "hold the odd stage's values for one stage");
 //   * the readers: lane (g, w) of the forward sweep gets M_k[g][w] at even k and M_k[w][g] at odd k; the backward sweep gets M_k[w][g] on its
 //     even steps and M_k[g][w] on its odd steps (step = N - 1 - k); both from the lane's one 16-byte slot of the pair;
 //   * a replay of stream_rows' paired fetch sequence (prologue of `ring` pair rows, then one refill per pair of every pass) touches exactly
@@ -49,6 +52,33 @@ int main()
                     const int at = qm_stage_byte(k, g, j) + (odd ? qm_pair_odd_delta(N, g, j) : 0);
                     CHECK(at == qm_pair_write(N, k, g, j) && at + qm_pair_row4_step(N, odd) == qm_pair_write(N, k, g + 4, j), "N %d k %d lane (%d, %d)", N, k, g, j);
                 }
+        // ---- the store schedule replayed: the sweep runs k = N - 1 .. 0, every lane (g, j), j < 8, stores its two 8-byte halves per stage; every
+        // byte of the block is written exactly once, all of it by the end of the sweep (the caller's barrier stands behind it), nothing outside;
+        // and the lane that stores a half is the lane qm_pair_half_holder names for the slot the half belongs to ----
+        {
+            std::vector<int> written(N * QM_STAGE_BYTES, 0);
+            int outside = 0, wrong_holder = 0, whole = 0;
+            for (int k = N - 1; k >= 0; k--)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int g = lane >> 4, j = lane & 15;
+                    if (j >= 8) continue;
+                    const bool odd = (k & 1) != 0;
+                    const int at0 = qm_stage_byte(k, g, j) + (odd ? qm_pair_odd_delta(N, g, j) : 0), at[2] = {at0, at0 + qm_pair_row4_step(N, odd)};
+                    for (int h = 0; h < 2; h++) {
+                        if (at[h] < 0 || at[h] + 8 > N * QM_STAGE_BYTES) { outside++; continue; }
+                        for (int b = 0; b < 8; b++) written[at[h] + b]++;
+                        const int slot = (at[h] % QM_PAIR_BYTES) / 16, half = (at[h] % 16) / 8;
+                        CHECK(half == (k & 1) && at[h] / QM_PAIR_BYTES == (k >> 1), "N %d k %d lane %d: half %d of pair %d", N, k, lane, half, at[h] / QM_PAIR_BYTES);
+                        if (qm_pair_half_holder(slot, half) != lane) wrong_holder++;
+                    }
+                }
+            CHECK(outside == 0, "N %d: %d stores outside the block", N, outside);
+            CHECK(std::count(written.begin(), written.end(), 1) == N * QM_STAGE_BYTES, "N %d: a byte written twice or not at all", N);
+            CHECK(wrong_holder == 0, "N %d: %d halves stored by another lane than qm_pair_half_holder names", N, wrong_holder);
+            for (int slot = 0; slot < 64; slot++) whole += qm_pair_half_holder(slot, 0) == qm_pair_half_holder(slot, 1);
+            CHECK(whole == 8 && whole == qm_pair_slots_formed_in_one_lane(), "slots with both halves in one lane: %d", whole);
+            if (N == 40) std::printf("N 40 writer: %d bytes written once, %d of 64 slots have both halves in one lane of the factor sweep\n", N * QM_STAGE_BYTES, whole);
+        }
         // ---- readers ----
         for (int k = 0; k < N; k++)
             for (int lane = 0; lane < 64; lane++) {

@@ -9,8 +9,9 @@ import sys
 
 NAMES = {31: "QP data, NLP residuals, slot load", 0: "initial point", 1: "slack residuals, complementarity", 14: "exact residual (i)", 2: "dyn_residual (ii)",
          3: "norms, convergence test", 4: "slot_coeffs + add_coeffs", 5: "factor sweep", 6: "corrector: p base", 7: "vector sweep", 8: "kff, c_k",
-         9: "forward sweep (both passes)", 10: "du", 16: "dpi", 11: "slack / multiplier steps", 15: "step length reductions, mu_aff, sigma", 12: "step test",
-         17: "update: followed residuals, z, pi, slots", 13: "RTI update, outputs"}
+         9: "forward sweep (both passes)", 10: "du", 16: "dpi: addresses, loads issued", 18: "dpi: first chain (the wait for P_k)", 19: "dpi: the other chains", 11: "slack / multiplier steps", 15: "step length reductions, mu_aff, sigma", 12: "step test",
+         17: "update: r_g loads issued, H dz of the first element", 20: "update: first r_g used (the wait for it)", 21: "update: the other r_g",
+         22: "update: r_b, z, pi, slots", 13: "RTI update, outputs"}
 SWEEPS_PER_ITER = {7: 1, 9: 2}
 
 
